@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- train-step throughput of the SZN pixel-embedding path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--precision bf16|fp32] [--size 512] [--classes 59]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--precision bf16|fp32] [--size 512] [--classes 59] [--dump-outputs DIR]
     (N > 1: `python bench.py --gpus N` re-executes itself under torch.distributed.run, one rank per GPU; the driver's own
      `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` form works as well)
 
@@ -72,9 +72,15 @@ def parse():
                     help="N > 1: wire format of the gradient exchange.  auto = bf16 written by the weight-gradient kernels themselves on "
                          "the 16-bit paths (271 MB per step instead of 542), fp32 on the fp32 path; bf16-sharded = reduce-scatter + "
                          "rank-sharded Adam + all-gather of the weight image; the `comm` record times the alternatives beside it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (loss, class map) and a fixed sample of the "
+                         "updated parameters as DIR/<name>.npy (float32 / float64, rank 0) for output-to-output comparison of builds")
     ap.add_argument("--sub-record", choices=["fp32", "b1", "comm", "c1_fcn8s", "c4_768"], default=None,
                     help="(internal) measure one sub-record and print it as JSON; run by the main process as a child")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ---- algorithmic work of one C-ABI call (what `achieved` is computed from; formulas in DESIGN.md section 4) -------------
@@ -245,6 +251,31 @@ def projection_report(L, torch, step_frac, iters=10):
             "note": "true = what score_fr executes (17x17 map, before the x32 upsampling); nominal = a full-resolution "
                     "H*W x 4096 x 300 projection the path never runs (proj_gemm_stream: the 2.1 GB activation operand is read "
                     "once from HBM, AI = 300 FLOP/B; operands relu(randn) like fc7's output, randn beside it)"}
+
+
+DUMP_PARAM_SAMPLE = 65536          # elements per parameter tensor in --dump-outputs (all of them when the tensor is smaller)
+DUMP_MAX_PRED = 8 << 20            # class-map elements written in full; a larger map is sampled (<= 32 MB as float32)
+
+
+def _sample(flat, n, seed):
+    """a fixed, seeded subset of the 1-d tensor `flat` (all of it when it has at most n elements), as a float32 numpy array"""
+    import torch
+    if flat.numel() <= n:
+        return flat.float().cpu().numpy()
+    idx = np.sort(np.random.RandomState(seed).choice(flat.numel(), n, replace=False))
+    return flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+
+
+def dump_outputs(d, loss, pred, model):
+    """what the timed path handed back in its last step: loss (float64 scalar), the (B,H,W) class map (float32; a seeded sample when it
+    is larger than DUMP_MAX_PRED) and a seeded sample of every parameter tensor after that step's update (float32, name order)"""
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "loss.npy"), np.asarray(float(loss.item()), dtype=np.float64))
+    p = pred.detach().reshape(-1)
+    np.save(os.path.join(d, "pred.npy"), pred.detach().float().cpu().numpy() if p.numel() <= DUMP_MAX_PRED
+            else _sample(p, DUMP_MAX_PRED, 1))
+    for i, (name, t) in enumerate(sorted(model.named_parameters())):
+        np.save(os.path.join(d, "param.%s.npy" % name), _sample(t.detach().contiguous().reshape(-1), DUMP_PARAM_SAMPLE, 1000 + i))
 
 
 def _workload(args, torch, rank=0):
@@ -858,6 +889,8 @@ def main():
     if not np.isfinite(lossv):
         raise SystemExit("loss is not finite: %r" % lossv)
     timed_events, events = events, []
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, pred, model)     # before anything else runs a step: loss and class map are reused buffers
 
     out = None
     if rank == 0:

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -44,6 +45,30 @@ def test_bench_line_phase1_with_cpu_baseline():
 def test_bench_line_phase2():
     d = run("--phase", "seenmask", "--no-cpu-baseline")
     assert KEYS <= set(d) and d["value"] > 0 and "configs[2]" in d["config"]["workload"]
+
+
+def test_bench_dump_outputs_repeat_from_run_to_run(tmp_path):
+    """--dump-outputs DIR: the last timed step's loss and class map plus a fixed sample of the updated parameters as .npy (float32 /
+    float64, 64 MB at most); --steps sets the timed step count; two runs with the same arguments write the same outputs"""
+    dumps = []
+    for i in range(2):
+        d = str(tmp_path / ("run%d" % i))
+        r = run("--steps", "3", "--no-extras", "--no-cpu-baseline", "--dump-outputs", d)
+        assert r["steps"] == 3 and r["ms_per_step"] > 0
+        files = sorted(os.listdir(d))
+        assert "loss.npy" in files and "pred.npy" in files and any(f.startswith("param.") for f in files), files
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in files) <= 64 << 20
+        arrs = {f: np.load(os.path.join(d, f)) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrs.values())
+        assert abs(float(arrs["loss.npy"]) - r["config"]["final_loss"]) < 1e-4
+        pred = arrs["pred.npy"]
+        assert pred.shape == (1, 96, 96) and np.array_equal(pred, np.round(pred)) and 0 <= pred.min() and pred.max() < 59
+        dumps.append(arrs)
+    a, b = dumps
+    assert sorted(a) == sorted(b)
+    assert a["loss.npy"] == b["loss.npy"] and np.array_equal(a["pred.npy"], b["pred.npy"])
+    for f in a:
+        assert a[f].shape == b[f].shape and np.allclose(a[f], b[f], rtol=1e-4, atol=1e-6), f
 
 
 @pytest.mark.parametrize("arch", ["fcn32s", "fcn8s"])
