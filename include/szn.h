@@ -358,8 +358,9 @@ int szn_deconv64s32_wgrad(int B, int h, int w, int C, int ldc, int c0, int H, in
  * (anything else is ignored, cross_entropy2d's mask).  Outputs: loss[1]; stats[2] = {sum of terms, valid pixels}
  * (may be NULL); conf[4] int64 += confusion counts [target][prediction] (may be NULL; the running train metrics,
  * trainer_seenmask.py:87); pred int64 (B,H,W) (may be NULL); dscore2 f32 [B*h*w][2] = d loss / d coarse (compact) and
- * dweight (2,2,64,64) = d loss / d weight -- both NULL for a forward-only call.  Bit-reproducible (fixed-order slabs,
- * no atomics).  workspace: szn_seenmask_head_workspace_bytes.                                                      */
+ * dweight (2,2,64,64) = d loss / d weight -- both NULL for a forward-only call.  target and loss both NULL: a pred-only call
+ * (the seen-mask group of szn_fused_head_grouped; stats, conf, dscore2, dweight NULL, pred not).  Bit-reproducible (fixed-order
+ * slabs, no atomics).  workspace: szn_seenmask_head_workspace_bytes.                                               */
 size_t szn_seenmask_head_workspace_bytes(int B, int h, int w, int H, int W, int crop);
 int szn_seenmask_head(int B, int h, int w, int ldc, int c0, int H, int W, int crop, const float* coarse,
                       const float* weight, const int64_t* target, int n_class, uint64_t seen_bits, float* loss,
@@ -461,6 +462,25 @@ int szn_fused_head_prepare(int E, int K, const float* embed, void* workspace, sz
 int szn_fused_head_prepared(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
                             const float* coarse, const float* embed, const int64_t* target, float* loss, float* stats,
                             int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace, szn_stream_t stream);
+/* The same head with the class assignment of the full SZN network (train.py -m test_all, trainer_fcn.py:123-147) or of forced-unseen
+ * runs (trainer_fcn.py:110-112): the prediction of szn_embed_argmax_k mode 1 (utils.py:188-204) without the (B,E,H,W) score.  A pixel
+ * competes among its group's classes; every class outside the group scores 0 / (||s|| * 1) -- the zeroed row of the seen-only /
+ * unseen-only matrix (trainer_fcn.py:56-64), which still competes (a zero-norm pixel gives NaN and class 0) -- first index on ties.
+ * A pixel takes the unseen group (classes in `unseen`, NULL = the empty set) when
+ *   group_mode 1: group_map[pix] == 0 -- group_map int64 (B,H,W) = the seen-mask prediction (szn_seenmask_head's pred: s1 > s0),
+ *   group_mode 2: target[pix] is in `unseen` (np.in1d(target, unseen)); negative labels (-1, padding -2) take the seen group.
+ * group_mode 0 is szn_fused_head_strided bit for bit.  Loss, stats and dcoarse do not depend on the group: they are those of the
+ * full matrix, bit for bit.  NULL rules as szn_fused_head_strided, and: modes 1 and 2 need pred; mode 1 needs group_map, mode 2
+ * target (so also loss and stats); a class in `unseen` >= K is an error.  _prepared: the workspace holds szn_fused_head_prepare. */
+int szn_fused_head_grouped(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                           const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
+                           int group_mode, const int64_t* group_map, float* loss, float* stats, int64_t* pred,
+                           int dcoarse_dtype, void* dcoarse, void* workspace, szn_stream_t stream);
+int szn_fused_head_grouped_prepared(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                                    const float* coarse, const float* embed, const int64_t* target,
+                                    const szn_class_set* unseen, int group_mode, const int64_t* group_map, float* loss,
+                                    float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
+                                    szn_stream_t stream);
 
 /* ---- optimizers (train.py:126-133,174-175; torch.optim.Adam / SGD semantics) ----------------------
  * One launch per flat fp32 parameter buffer.  grad_scale multiplies the gradient first (1/world

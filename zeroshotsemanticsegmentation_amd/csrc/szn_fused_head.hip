@@ -28,7 +28,35 @@ struct FhArgs {
     const float* coarse; const float* embed; const int64_t* target;
     int64_t* pred; float* ws_f; double* part;
     int B, h, w, E, ldc, c0, H, W, crop, K, KP;
+    const int64_t* gmap; int gmode; ClassBits unseen;      // grouped class assignment (gmode 1 | 2), see fh_grouped_argmax
 };
+
+// Grouped class assignment (szn_fused_head_grouped; trainer_fcn.py:123-147, utils.py:188-204): the pixel competes among the classes
+// of ITS group only -- the unseen classes when it takes the unseen group, the others otherwise -- and every class outside that group
+// scores 0 / (sn * 1), exactly what a zeroed row of the seen-only / unseen-only matrix scores (trainer_fcn.py:56-64): it still
+// competes, and a zero-norm pixel gives NaN for every class like szn_embed_argmax_k mode 1.  Ascending classes, strictly larger
+// replaces: the first index wins.  The group bits stay in the kernel arguments: k is wave-uniform, so the word select and the bit
+// test are scalar instructions next to the per-class loop, no LDS read.
+template <int KP>
+__device__ __forceinline__ int fh_grouped_argmax(const FhArgs& a, const float (&wt)[4], const float* G, float sn,
+                                                 const float* __restrict__ en, size_t pix, long lbl) {
+    const bool take_unseen = (a.gmode == 1) ? (a.gmap[pix] == 0) : in_set(a.unseen, lbl);
+    const float zero_sim = 0.f / (sn * 1.f);
+    int best = 0;
+    float bv = 0.f;
+    for (int k = 0; k < a.K; ++k) {
+        const bool un = (class_word(a.unseen, k >> 6) >> (k & 63)) & 1ull;
+        float sim = zero_sim;
+        if (un == take_unseen) {
+            float d = 0.f;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) d = fmaf(wt[t], G[t * KP + k], d);
+            sim = d / (sn * en[k]);
+        }
+        if (k == 0 || sim > bv) { bv = sim; best = k; }
+    }
+    return best;
+}
 
 // workspace (floats): embT [E][KP] | en [KP] (0 -> 1, for the argmax) | ent [KP] (raw norms, for the loss)
 //                     | per cell: A [4][KP] , Bm [16]
@@ -70,7 +98,7 @@ __global__ __launch_bounds__(256) void fh_prep_kernel(const float* __restrict__ 
     }
 }
 
-template <int KP, int S>
+template <int KP, int S, bool GROUPED>
 __global__ __launch_bounds__(256) void fh_cell_kernel(FhArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* Ct = sm;                       // [4][E]
@@ -158,7 +186,9 @@ __global__ __launch_bounds__(256) void fh_cell_kernel(FhArgs a) {
             const float sn = sqrtf(ss);
             const size_t pix = ((size_t)b * a.H + y) * a.W + x;
             lbl = a.target ? a.target[pix] : -1;
-            if (a.pred) {
+            if (GROUPED) {
+                a.pred[pix] = fh_grouped_argmax<KP>(a, wt, G, sn, en, pix, lbl);
+            } else if (a.pred) {
                 int best = 0;
                 float bv = 0.f;
                 for (int k = 0; k < a.K; ++k) {
@@ -260,7 +290,7 @@ __global__ __launch_bounds__(256) void fh_tables_kernel(FhArgs a, float* __restr
 }
 
 // one wave per cell (S * S <= 64 pixels), four cells per block; same per-pixel arithmetic and the same outputs as fh_cell_kernel
-template <int KP, int S>
+template <int KP, int S, bool GROUPED>
 __global__ __launch_bounds__(256) void fh_cell_tab_kernel(FhArgs a, const float* __restrict__ D, const float* __restrict__ N) {
     static_assert(S * S <= 64, "one wave per cell");
     __shared__ float Gs[4][4 * KP];
@@ -326,7 +356,9 @@ __global__ __launch_bounds__(256) void fh_cell_tab_kernel(FhArgs a, const float*
             const float sn = sqrtf(ss);
             const size_t pix = ((size_t)b * a.H + y) * a.W + x;
             lbl = a.target ? a.target[pix] : -1;
-            if (a.pred) {
+            if (GROUPED) {
+                a.pred[pix] = fh_grouped_argmax<KP>(a, wt, G, sn, en, pix, lbl);
+            } else if (a.pred) {
                 int best = 0;
                 float bv = 0.f;
                 for (int k = 0; k < a.K; ++k) {
@@ -477,7 +509,8 @@ extern "C" size_t szn_fused_head_workspace_bytes(int B, int h, int w, int E, int
 static int fused_head_impl(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
                            const float* coarse, const float* embed, const int64_t* target, float* loss,
                            float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
-                           szn_stream_t stream, bool prep);
+                           szn_stream_t stream, bool prep, const szn_class_set* unseen = nullptr, int group_mode = 0,
+                           const int64_t* group_map = nullptr);
 
 extern "C" int szn_fused_head_strided(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
                                       const float* coarse, const float* embed, const int64_t* target, float* loss,
@@ -512,7 +545,8 @@ extern "C" int szn_fused_head_prepared(int stride, int B, int h, int w, int E, i
 static int fused_head_impl(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
                            const float* coarse, const float* embed, const int64_t* target, float* loss,
                            float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
-                           szn_stream_t stream, bool prep) {
+                           szn_stream_t stream, bool prep, const szn_class_set* unseen, int group_mode,
+                           const int64_t* group_map) {
     if (stride != 32 && stride != 8) SZN_FAIL(SZN_ERR_UNSUPPORTED, "fused_head: stride %d (32 and 8 are built)", stride);
     if (!coarse || !embed || !workspace || B <= 0 || h <= 0 || w <= 0 || E <= 0 || c0 < 0 || ldc < c0 + E || H <= 0 ||
         W <= 0 || crop < 0 || K <= 0)
@@ -523,6 +557,13 @@ static int fused_head_impl(int stride, int B, int h, int w, int E, int ldc, int 
     if ((target == nullptr) != (loss == nullptr) || (loss && !stats)) SZN_FAIL(SZN_ERR_ARG, "fused_head: target/loss/stats go together");
     if (dcoarse && !target) SZN_FAIL(SZN_ERR_ARG, "fused_head: dcoarse needs target");
     if (((uintptr_t)workspace) & 15) SZN_FAIL(SZN_ERR_ARG, "fused_head: workspace must be 16-B aligned");
+    const ClassBits ubits = class_bits(unseen);
+    if (group_mode < 0 || group_mode > 2) SZN_FAIL(SZN_ERR_ARG, "fused_head_grouped: bad group mode %d", group_mode);
+    if (group_mode != 0 && !pred) SZN_FAIL(SZN_ERR_ARG, "fused_head_grouped: group mode %d needs pred", group_mode);
+    if (group_mode == 1 && !group_map) SZN_FAIL(SZN_ERR_ARG, "fused_head_grouped: group mode 1 needs group_map");
+    if (group_mode == 2 && !target) SZN_FAIL(SZN_ERR_ARG, "fused_head_grouped: group mode 2 needs target");
+    if (!class_bits_fit(ubits, K)) SZN_FAIL(SZN_ERR_ARG, "fused_head_grouped: the unseen set names a class >= K = %d", K);
+    const bool grouped = group_mode != 0;
     hipStream_t st = (hipStream_t)stream;
     const int KP = kp_of(K);
     const int cells = (h + 1) * (w + 1);
@@ -540,23 +581,29 @@ static int fused_head_impl(int stride, int B, int h, int w, int E, int ldc, int 
     FhArgs a;
     a.coarse = coarse; a.embed = embed; a.target = target; a.pred = pred; a.ws_f = ws_f; a.part = part;
     a.B = B; a.h = h; a.w = w; a.E = E; a.ldc = ldc; a.c0 = c0; a.H = H; a.W = W; a.crop = crop; a.K = K; a.KP = KP;
+    a.gmap = group_map; a.gmode = group_mode; a.unseen = ubits;
     // LDS floats: Ct 4E | G 4KP | Q 16 | Aw 16KP | red 64 | dred 8 doubles; 4E + 20KP + 80 must be even for the doubles
     size_t lfl = (size_t)4 * E + 20 * KP + 16 + 64;
     const size_t lds = lfl * sizeof(float) + 8 * sizeof(double);
     if (lds > 150 * 1024) SZN_FAIL(SZN_ERR_UNSUPPORTED, "fused_head: E=%d too large for LDS", E);
-#define SZN_FH_LAUNCH(KPV)                                                                                           \
+#define SZN_FH_LAUNCH_G(KPV, GR)                                                                                     \
     do {                                                                                                             \
         if (stride == 8) {                                                                                           \
             hipLaunchKernelGGL(fh_tables_kernel<KPV>, dim3((unsigned)(((long)B * h * w + 3) / 4)), dim3(256),        \
                                (size_t)4 * E * sizeof(float), st, a, tabD, tabN);                                    \
-            hipLaunchKernelGGL((fh_cell_tab_kernel<KPV, 8>), dim3((unsigned)(((long)B * cells + 3) / 4)), dim3(256), 0, st, a,  \
+            hipLaunchKernelGGL((fh_cell_tab_kernel<KPV, 8, GR>), dim3((unsigned)(((long)B * cells + 3) / 4)), dim3(256), 0, st, a, \
                                (const float*)tabD, (const float*)tabN);                                              \
         } else {                                                                                                     \
-            auto kern = fh_cell_kernel<KPV, 32>;                                                                     \
+            auto kern = fh_cell_kernel<KPV, 32, GR>;                                                                 \
             if (lds > 48 * 1024)                                                                                     \
                 (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);  \
             hipLaunchKernelGGL(kern, dim3(B * cells), dim3(256), lds, st, a);                                        \
         }                                                                                                            \
+    } while (0)
+#define SZN_FH_LAUNCH(KPV)                                                                                           \
+    do {                                                                                                             \
+        if (grouped) SZN_FH_LAUNCH_G(KPV, true);                                                                     \
+        else SZN_FH_LAUNCH_G(KPV, false);                                                                            \
     } while (0)
     if (KP == 24) SZN_FH_LAUNCH(24);
     else if (KP == 40) SZN_FH_LAUNCH(40);
@@ -565,6 +612,7 @@ static int fused_head_impl(int stride, int B, int h, int w, int E, int ldc, int 
     else if (KP == 192) SZN_FH_LAUNCH(192);
     else SZN_FH_LAUNCH(256);
 #undef SZN_FH_LAUNCH
+#undef SZN_FH_LAUNCH_G
     SZN_CHECK_LAUNCH("fh_cell_kernel");
     if (loss) {
         hipLaunchKernelGGL(fh_image_sums_kernel, dim3(B), dim3(256), 0, st, (const double*)part, cells, stats, sums);
@@ -593,4 +641,23 @@ extern "C" int szn_fused_head(int B, int h, int w, int E, int ldc, int c0, int H
                               int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace, szn_stream_t stream) {
     return szn_fused_head_strided(32, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype,
                                   dcoarse, workspace, stream);
+}
+
+// group mode 0: szn_fused_head_strided / _prepared bit for bit.  1: a pixel takes the unseen group where group_map == 0 (the seen-mask
+// prediction, szn_seenmask_head: s1 > s0 ? 1 : 0).  2: where its target label is in `unseen` (negative labels -> seen group).
+extern "C" int szn_fused_head_grouped(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                                      const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
+                                      int group_mode, const int64_t* group_map, float* loss, float* stats, int64_t* pred,
+                                      int dcoarse_dtype, void* dcoarse, void* workspace, szn_stream_t stream) {
+    return fused_head_impl(stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype, dcoarse,
+                           workspace, stream, true, unseen, group_mode, group_map);
+}
+
+extern "C" int szn_fused_head_grouped_prepared(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                                               const float* coarse, const float* embed, const int64_t* target,
+                                               const szn_class_set* unseen, int group_mode, const int64_t* group_map, float* loss,
+                                               float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
+                                               szn_stream_t stream) {
+    return fused_head_impl(stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype, dcoarse,
+                           workspace, stream, false, unseen, group_mode, group_map);
 }

@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void smh_cell_kernel(const float* __restrict__
             const long pix = ((long)b * g.H + y) * g.W + x;
             const int am = s1 > s0 ? 1 : 0;                  // first maximum on ties (torch max / ce_fwd_kernel)
             if (pred) pred[pix] = am;
-            const long lbl = target[pix];
+            const long lbl = target ? target[pix] : -2;        // no target (pred-only call): nothing counts
             int tb;
             bool valid = true;
             // labels below -1 are batch PADDING (datasets.pad_collate writes -2): not a pixel of any image, so it is neither a
@@ -322,7 +322,10 @@ int seenmask_head_impl(int B, int h, int w, int ldc, int c0, int H, int W, int c
                        const int64_t* target, int n_class, const ClassBits& seen_bits, float* loss, float* stats, int64_t* conf,
                        int64_t* pred, float* dscore2, float* dweight, void* workspace, szn_stream_t stream) {
     if (B < 1 || h < 1 || w < 1 || H < 1 || W < 1 || crop < 0) SZN_FAIL(SZN_ERR_ARG, "szn_seenmask_head: bad geometry");
-    if (!coarse || !weight || !target || !loss || !workspace) SZN_FAIL(SZN_ERR_ARG, "szn_seenmask_head: null pointer");
+    if (!coarse || !weight || !workspace) SZN_FAIL(SZN_ERR_ARG, "szn_seenmask_head: null pointer");
+    // target and loss go together; without them the call is pred-only (no stats, confusion counts or gradients)
+    if ((target == nullptr) != (loss == nullptr)) SZN_FAIL(SZN_ERR_ARG, "szn_seenmask_head: target and loss go together");
+    if (!target && (!pred || stats || conf || dscore2 || dweight)) SZN_FAIL(SZN_ERR_ARG, "szn_seenmask_head: a call without target writes pred only");
     if (n_class < 0 || n_class > SZN_MAX_CLASSES) SZN_FAIL(SZN_ERR_UNSUPPORTED, "szn_seenmask_head: n_class %d > %d", n_class, SZN_MAX_CLASSES);
     if ((dscore2 == nullptr) != (dweight == nullptr)) SZN_FAIL(SZN_ERR_ARG, "szn_seenmask_head: dscore2 and dweight go together");
     // every tap of a pixel must exist or be outside the map on the low side only when crop says so: (Y>>5) <= h
@@ -340,6 +343,7 @@ int seenmask_head_impl(int B, int h, int w, int ldc, int c0, int H, int W, int c
     if (grad) smh_cell_kernel<true><<<G, 256, 0, st>>>(coarse, weight, target, n_class, seen_bits, pred, part, cellpart, slab, g);
     else smh_cell_kernel<false><<<G, 256, 0, st>>>(coarse, weight, target, n_class, seen_bits, pred, part, cellpart, slab, g);
     SZN_CHECK_LAUNCH("smh_cell_kernel");
+    if (!loss) return SZN_OK;
     const int fblocks = grad ? kTaps / 64 + szn_div_up((long)B * h * w * 2, 256) : 1;
     smh_finalize_kernel<<<fblocks, 256, 0, st>>>(part, G, cellpart, slab, loss, stats, conf, grad ? dscore2 : nullptr,
                                                                grad ? dweight : nullptr, g);

@@ -380,13 +380,16 @@ class TrainStep(object):
                  train_metrics=True, betas=(0.9, 0.999), eps=1e-8, bias_lr=None, bias_weight_decay=0.0,
                  adam_weight_decay=0.0, grad_comm_dtype=None, loss_scale=None, dynamic_loss_scale=None,
                  scale_growth=2.0, scale_backoff=0.5, scale_growth_interval=2000, force_comm=None, reserved_cus=None,
-                 fused_adam=None, keep_grads=True, exchange=None, direct_wire=None, sharded=None):
+                 fused_adam=None, keep_grads=True, exchange=None, direct_wire=None, sharded=None, forced_unseen=None):
         """Data-parallel knobs (the reference is single-GPU): grad_comm_dtype (SZN_GRAD_COMM = fp32 | bf16) = the
         wire format of the gradient buckets; exchange=False (SZN_GRAD_COMM=off) = no exchange at all (bench.py's comm-off timing);
         direct_wire (default: on for a 16-bit wire with keep_grads=False; SZN_WIRE_DIRECT=0 turns it off) = the weight-gradient
         kernels write the 16-bit wire image themselves and the optimizer kernel reads it (no staging copies; `.grad` of the
         weights is then None); sharded (SZN_SHARDED_OPT=1) = reduce-scatter + rank-sharded optimizer + all-gather of the weight
-        image instead of all-reduce + replicated optimizer."""
+        image instead of all-reduce + replicated optimizer.
+        forced_unseen (a list of class indices, trainer_fcn.py:110-112): the returned prediction is the forced-unseen one -- a pixel
+        whose label is one of these classes is assigned among them, any other among the rest (szn_fused_head_grouped, group mode 2;
+        the fused_head=False path: szn_embed_argmax_k mode 1 with the target).  Loss, gradients and updates do not change."""
         if loss not in ("cos", "mse") or (fused_head and loss != "cos"):
             raise L.SznError("TrainStep: fused head supports the cosine loss; use fused_head=False for mse")
         self.model = model
@@ -423,6 +426,10 @@ class TrainStep(object):
         self._want_direct = bool(direct_wire) and grad_comm_dtype != torch.float32
         self._want_sharded = (os.environ.get("SZN_SHARDED_OPT", "0") == "1") if sharded is None else bool(sharded)
         self.fused_head, self.loss_kind = fused_head, loss
+        self.forced_unseen = None if forced_unseen is None else [int(k) for k in forced_unseen]
+        if self.forced_unseen is not None and any(not 0 <= k < self.K for k in self.forced_unseen):
+            raise L.SznError("TrainStep: forced_unseen names a class outside [0, %d)" % self.K)
+        self._unseen_cs = L.class_set(self.forced_unseen) if self.forced_unseen is not None else None
         # static loss scaling for the fp16 path: gradients below 6e-8 vanish in IEEE half, so d(loss)/d(coarse) is multiplied
         # by loss_scale in fp32 before it enters the 16-bit backward pass and the optimizer kernel divides it out again
         # (grad_scale).  The .grad views then hold loss_scale x gradient.  bf16 / fp32 need none.
@@ -472,6 +479,7 @@ class TrainStep(object):
         self.gather_wait_log = []    # (tests) (layer that asked, bucket start, bucket end) in the order the waits were issued
         self.keep_ctx = False        # tests: keep the forward state of the last step (activations stay alive one step longer)
         self.last_ctx = None
+        self.last_fuse3 = None           # (FCN8s, keep_ctx) the 1/8 fused map of the last step
 
     # the class-embedding matrix: assigning a new tensor (or calling invalidate_head_prep() after writing into it behind torch's back --
     # a raw kernel does not bump _version, and a new tensor may reuse the address of the old one) makes the fused head rebuild its tables
@@ -683,8 +691,13 @@ class TrainStep(object):
             if self._ws_prep != prep:
                 L.call("szn_fused_head_prepare", E, K, L.ptr(self.emb), L.ptr(self._ws), st)
                 self._ws_prep = prep
-            L.call("szn_fused_head_prepared", 32, B, ctx.h, ctx.w, E, CP, 0, H, W, CROP, K, L.ptr(ctx.coarse), L.ptr(self.emb),
-                   L.ptr(target), L.ptr(self.loss), L.ptr(stats), L.ptr(pred), code, L.ptr(dcoarse), L.ptr(self._ws), st)
+            if self.forced_unseen is None:
+                L.call("szn_fused_head_prepared", 32, B, ctx.h, ctx.w, E, CP, 0, H, W, CROP, K, L.ptr(ctx.coarse), L.ptr(self.emb),
+                       L.ptr(target), L.ptr(self.loss), L.ptr(stats), L.ptr(pred), code, L.ptr(dcoarse), L.ptr(self._ws), st)
+            else:
+                L.call("szn_fused_head_grouped_prepared", 32, B, ctx.h, ctx.w, E, CP, 0, H, W, CROP, K, L.ptr(ctx.coarse),
+                       L.ptr(self.emb), L.ptr(target), self._unseen_cs, 2, None, L.ptr(self.loss), L.ptr(stats), L.ptr(pred), code,
+                       L.ptr(dcoarse), L.ptr(self._ws), st)
         else:
             f = eng.upscore(ctx)
             ws = torch.empty(L.load().szn_loss_workspace_bytes(B, H, W), dtype=torch.uint8, device=self.dev)
@@ -692,7 +705,11 @@ class TrainStep(object):
             bwd = "szn_cosine_loss_bwd" if self.loss_kind == "cos" else "szn_mse_loss_bwd"
             L.call(fwd, B, E, H, W, K, L.ptr(f), L.ptr(target), L.ptr(self.emb), None, L.ptr(self.loss), L.ptr(stats),
                    L.ptr(ws), st)
-            L.call("szn_embed_argmax_k", B, E, H, W, K, L.ptr(f), L.ptr(self.emb), 0, None, None, None, L.ptr(pred), st)
+            if self.forced_unseen is None:
+                L.call("szn_embed_argmax_k", B, E, H, W, K, L.ptr(f), L.ptr(self.emb), 0, None, None, None, L.ptr(pred), st)
+            else:
+                L.call("szn_embed_argmax_k", B, E, H, W, K, L.ptr(f), L.ptr(self.emb), 1, self._unseen_cs, None, L.ptr(target),
+                       L.ptr(pred), st)
             df = torch.empty_like(f)
             L.call(bwd, B, E, H, W, K, L.ptr(f), L.ptr(target), L.ptr(self.emb), None, L.ptr(stats), None, L.ptr(df), st)
             dc32, _ = eng.head_backward(ctx, df=df)
@@ -757,6 +774,7 @@ class TrainStep(object):
         sp3 = eng._conv(pool3, None, 0, relu=False, out_f32=True, w=s3["w"], b=s3["b"])
         n3, m3 = up4.shape[1:3]
         fuse3 = (up4 + sp3[:, CROP_POOL3:CROP_POOL3 + n3, CROP_POOL3:CROP_POOL3 + m3]).contiguous()
+        self.last_fuse3 = fuse3 if self.keep_ctx else None      # tests: the 1/8 map the head read
         # fused head over 8x8 cells: loss, prediction, d(fuse3)
         pred = torch.empty(B, H, W, dtype=torch.int64, device=self.dev)
         stats = torch.empty(B, 2, device=self.dev)
@@ -769,8 +787,13 @@ class TrainStep(object):
         if self._ws_prep != prep:
             L.call("szn_fused_head_prepare", E, K, L.ptr(self.emb), L.ptr(self._ws), st)
             self._ws_prep = prep
-        L.call("szn_fused_head_prepared", 8, B, n3, m3, E, CP, 0, H, W, CROP_UP8, K, L.ptr(fuse3), L.ptr(self.emb), L.ptr(target),
-               L.ptr(self.loss), L.ptr(stats), L.ptr(pred), L.SZN_F32, L.ptr(dfuse3), L.ptr(self._ws), st)
+        if self.forced_unseen is None:
+            L.call("szn_fused_head_prepared", 8, B, n3, m3, E, CP, 0, H, W, CROP_UP8, K, L.ptr(fuse3), L.ptr(self.emb), L.ptr(target),
+                   L.ptr(self.loss), L.ptr(stats), L.ptr(pred), L.SZN_F32, L.ptr(dfuse3), L.ptr(self._ws), st)
+        else:
+            L.call("szn_fused_head_grouped_prepared", 8, B, n3, m3, E, CP, 0, H, W, CROP_UP8, K, L.ptr(fuse3), L.ptr(self.emb),
+                   L.ptr(target), self._unseen_cs, 2, None, L.ptr(self.loss), L.ptr(stats), L.ptr(pred), L.SZN_F32, L.ptr(dfuse3),
+                   L.ptr(self._ws), st)
         self.stats = stats
         if self.dynamic:
             dfuse3 = dfuse3 * self.scale_state[0]

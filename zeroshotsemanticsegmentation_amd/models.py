@@ -1309,6 +1309,7 @@ class FCN32s(nn.Module):
         object.__setattr__(self, "_engine", _Engine(self))
         object.__setattr__(self, "_last_ctx", None)
         object.__setattr__(self, "_last_pred", None)
+        object.__setattr__(self, "_last_group", None)         # the seen-mask group map of the last szn_predict
 
     def _initialize_weights(self):
         # only the transposed convolutions are (re)initialised -- bilinear kernels (models.py:102-112)
@@ -1395,6 +1396,62 @@ class FCN32s(nn.Module):
                 loss, stats = torch.empty(1, device=dev), torch.empty(B, 2, device=dev)
             L.call("szn_fused_head", B, ctx.h, ctx.w, E, self.head_width, 0, H, W, CROP, K, L.ptr(ctx.coarse), L.ptr(emb),
                    L.ptr(tgt), L.ptr(loss), L.ptr(stats), L.ptr(pred), L.SZN_F32, None, L.ptr(ws), L.stream_ptr())
+        return (loss.reshape(()) if loss is not None else None), pred
+
+    def _seenmask_group(self, ctx):
+        """the seen-mask prediction (1 = seen) of the x32 seen-mask head on the 1/32 map (channels [n_class, n_class + 2)): a
+        pred-only szn_seenmask_head_k call (no target, no loss) -> (B,H,W) int64, the group map of szn_fused_head_grouped mode 1"""
+        dev = ctx.coarse.device
+        gmap = torch.empty(ctx.B, ctx.H, ctx.W, dtype=torch.int64, device=dev)
+        ws = torch.empty(L.load().szn_seenmask_head_workspace_bytes(ctx.B, ctx.h, ctx.w, ctx.H, ctx.W, CROP), dtype=torch.uint8,
+                         device=dev)
+        L.call("szn_seenmask_head_k", ctx.B, ctx.h, ctx.w, self.head_width, self.n_class, ctx.H, ctx.W, CROP, L.ptr(ctx.coarse),
+               L.ptr(self._engine._images["up.w"]), None, 0, None, None, None, None, L.ptr(gmap), None, None, L.ptr(ws),
+               L.stream_ptr())
+        self._last_group = gmap
+        return gmap
+
+    @staticmethod
+    def _szn_group(group, target):
+        if group not in ('seenmask', 'target'):
+            raise L.SznError("szn_predict: group must be 'seenmask' or 'target', got %r" % (group,))
+        if group == 'target' and target is None:
+            raise L.SznError("szn_predict: group='target' (forced unseen) needs the target")
+        return 1 if group == 'seenmask' else 2
+
+    def szn_predict(self, x, embeddings, unseen, target=None, group='seenmask'):
+        """forward pass + the full SZN network's class assignment (+ cosine loss when `target` is given) WITHOUT the (B,E,H,W)
+        embedding score or the (B,2,H,W) seen-mask score: the seen-mask head runs pred-only on the same 1/32 map
+        (szn_seenmask_head_k) and the grouped fused head (szn_fused_head_grouped, group mode 1) classifies each pixel among the
+        unseen classes where the seen mask says 'unseen' and among the seen ones elsewhere (trainer_fcn.py:123-147, utils.py:188-204,
+        train.py -m test_all).  group='target' (forced unseen, trainer_fcn.py:110-112): the group comes from the target label
+        (mode 2), no seen-mask head.  -> (loss 0-dim tensor or None, pred (B,H,W) int64 device tensor); the seen-mask prediction
+        is left in self._last_group (None for group='target').  Same numbers as forward(mode='both') + utils.infer_lbl_device(
+        mode=1) up to rounding order (class assignment differs only on pixels whose top-2 cosine margin in the group is < 1e-5;
+        the seen-mask decision is bit-identical).  Used by Trainer.validate."""
+        mode = self._szn_group(group, target)
+        eng = self._engine
+        with torch.no_grad():
+            ctx = eng.forward(x.detach(), train=False, keep=False)
+            emb = torch.as_tensor(embeddings).to(ctx.coarse.device, torch.float32).contiguous()
+            K, E = emb.shape
+            if E != self.n_class:
+                raise L.SznError("embedding dimension %d != model n_class %d" % (E, self.n_class))
+            if K > L.MAX_CLASSES:
+                raise L.SznError("szn_predict: at most %d classes (szn_class_set), got %d" % (L.MAX_CLASSES, K))
+            B, H, W = ctx.B, ctx.H, ctx.W
+            dev = ctx.coarse.device
+            self._last_group = None
+            gmap = self._seenmask_group(ctx) if mode == 1 else None
+            pred = torch.empty(B, H, W, dtype=torch.int64, device=dev)
+            ws = torch.empty(L.load().szn_fused_head_workspace_bytes(B, ctx.h, ctx.w, E, K), dtype=torch.uint8, device=dev)
+            loss = stats = tgt = None
+            if target is not None:
+                tgt = target.to(device=dev, dtype=torch.int64).contiguous()
+                loss, stats = torch.empty(1, device=dev), torch.empty(B, 2, device=dev)
+            L.call("szn_fused_head_grouped", 32, B, ctx.h, ctx.w, E, self.head_width, 0, H, W, CROP, K, L.ptr(ctx.coarse),
+                   L.ptr(emb), L.ptr(tgt), L.class_set(unseen), mode, L.ptr(gmap), L.ptr(loss), L.ptr(stats), L.ptr(pred),
+                   L.SZN_F32, None, L.ptr(ws), L.stream_ptr())
         return (loss.reshape(()) if loss is not None else None), pred
 
     def seenmask_predict(self, x, target, n_class, unseen):
@@ -1664,6 +1721,33 @@ class FCN8s(FCN32s):
             tgt = None if target is None else target.to(device=x.device, dtype=torch.int64).contiguous()
             loss = _FusedHead8.apply(self, fuse3, emb, tgt, x.shape[2], x.shape[3], False)
             return (loss if target is not None else None), self._last_pred
+
+    def szn_predict(self, x, embeddings, unseen, target=None, group='seenmask'):
+        """the full SZN network's class assignment on the skip head -> (loss 0-dim tensor or None, pred (B,H,W) int64); see
+        FCN32s.szn_predict.  The seen-mask head keeps its x32 geometry on the backbone's 1/32 map (as forward(mode='both')); the
+        grouped head runs over the 8x8 cells of the 1/8 fused map (szn_fused_head_grouped, stride 8)."""
+        mode = self._szn_group(group, target)
+        with torch.no_grad():
+            emb = self._emb(embeddings, x.device)
+            _, fuse3 = self._fuse(x.detach(), False, None)
+            ctx = self._last_ctx
+            self._last_group = None
+            gmap = self._seenmask_group(ctx) if mode == 1 else None
+            fuse3 = fuse3.contiguous()
+            B, h, w, ld = fuse3.shape
+            K, E = emb.shape
+            H, W = x.shape[2], x.shape[3]
+            dev = fuse3.device
+            pred = torch.empty(B, H, W, dtype=torch.int64, device=dev)
+            ws = torch.empty(L.load().szn_fused_head_workspace_bytes(B, h, w, E, K), dtype=torch.uint8, device=dev)
+            loss = stats = tgt = None
+            if target is not None:
+                tgt = target.to(device=dev, dtype=torch.int64).contiguous()
+                loss, stats = torch.empty(1, device=dev), torch.empty(B, 2, device=dev)
+            L.call("szn_fused_head_grouped", 8, B, h, w, E, ld, 0, H, W, CROP_UP8, K, L.ptr(fuse3), L.ptr(emb), L.ptr(tgt),
+                   L.class_set(unseen), mode, L.ptr(gmap), L.ptr(loss), L.ptr(stats), L.ptr(pred), L.SZN_F32, None, L.ptr(ws),
+                   L.stream_ptr())
+        return (loss.reshape(()) if loss is not None else None), pred
 
 
 def VGG16(pretrained=False, data_dir='data'):

@@ -181,11 +181,10 @@ def main(argv=None):
     cfg = update_cfg_with_args(configurations[args.config], args)
     validate_cfg(cfg)
     if args.precision == 'fp16' and cfg['mode'] == 'train' and cfg['fcn_epochs'] > 0 and \
-            (cfg['fcn_loss'] != 'cos' or not cfg['embed_dim'] or cfg['forced_unseen']):
+            (cfg['fcn_loss'] != 'cos' or not cfg['embed_dim']):
         # loss scaling lives in the fused steps only (engine.TrainStep / SeenmaskStep); see trainer_fcn.Trainer.train_epoch
-        raise Exception("--precision fp16 needs the fused training step: embedding configuration with fcn_loss 'cos' and no "
-                        "forced_unseen (got loss %r, embed_dim %r, forced_unseen %r); use bf16 or fp32"
-                        % (cfg['fcn_loss'], cfg['embed_dim'], cfg['forced_unseen']))
+        raise Exception("--precision fp16 needs the fused training step: embedding configuration with fcn_loss 'cos' "
+                        "(got loss %r, embed_dim %r); use bf16 or fp32" % (cfg['fcn_loss'], cfg['embed_dim']))
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", str(args.gpu)))

@@ -160,13 +160,11 @@ class Trainer(object):
 
     # ---- training --------------------------------------------------------------------------------------------
     def _fast_step(self):
-        """engine.TrainStep when the configuration allows it: embedding cosine loss, no forced_unseen train metrics, and an
-        optimizer with exactly the reference's two parameter groups (train.py:126-133: all Conv2d weights | all Conv2d
-        biases).  Hyper-parameters are read per group from the optimizer object; any other wiring keeps the autograd path."""
+        """engine.TrainStep when the configuration allows it: embedding cosine loss (forced_unseen: the step's prediction is the
+        forced-unseen one, trainer_fcn.py:110-112) and an optimizer with exactly the reference's two parameter groups
+        (train.py:126-133: all Conv2d weights | all Conv2d biases).  Hyper-parameters are read per group from the optimizer object; any other wiring keeps the autograd path."""
         if self._step is not None or not (self._fused_step and self.pixel_embeddings and self.loss_func == "cos"):
             return self._step
-        if self.forced_unseen:
-            return None
         from .optim import FusedAdam, FusedSGD
         from .models import opt_layers
         _OPT_LAYERS = opt_layers(self.model)
@@ -189,7 +187,8 @@ class Trainer(object):
             return None
         self._step = _engine.TrainStep(self.model, self.embeddings, lr=gw['lr'], bias_lr=gb['lr'],
                                        bias_weight_decay=gb.get('weight_decay', 0.0), precision=self.precision,
-                                       fused_head=True, keep_grads=os.environ.get("SZN_KEEP_GRADS", "0") == "1", **kw)
+                                       fused_head=True, keep_grads=os.environ.get("SZN_KEEP_GRADS", "0") == "1",
+                                       forced_unseen=self.unseen if self.forced_unseen else None, **kw)
         # keep_grads=False (default; SZN_KEEP_GRADS=1 restores the reference's "`.grad` valid until zero_grad()"): the loop
         # calls zero_grad() next (train.py:170-175) and nothing reads the weight gradients in between, so the layers whose Adam
         # step rides in their weight-gradient kernel do not store theirs -- those `.grad`s are None, not stale
@@ -201,10 +200,10 @@ class Trainer(object):
         step = self._fast_step()
         if step is None and self.model._engine.dtype == torch.float16:
             # IEEE-half gradients need loss scaling, which only engine.TrainStep applies (d(coarse) is multiplied in fp32 before
-            # it enters the 16-bit backward pass); the autograd paths (mse / cross_entropy losses, forced_unseen, non-reference
-            # optimizer wiring) would push ~1e-7-sized activation gradients through fp16 unscaled and lose them silently
+            # it enters the 16-bit backward pass); the autograd paths (mse / cross_entropy losses, non-reference optimizer
+            # wiring) would push ~1e-7-sized activation gradients through fp16 unscaled and lose them silently
             raise RuntimeError("precision fp16 is only supported on the fused training step (embedding cosine loss, reference "
-                               "optimizer wiring, no forced_unseen); use bf16 or fp32 for this configuration")
+                               "optimizer wiring); use bf16 or fp32 for this configuration")
         for batch_idx, (data, target) in enumerate(self.train_loader):
             if step is not None:
                 data, target, _ = self._unpack(data, target)
@@ -264,6 +263,13 @@ class Trainer(object):
                 and not self.verbose_val and self.embeddings.shape[0] <= 256):
             # plain embedding inference: loss + class assignment straight from the 1/32 map (no (n,E,h,w) score in HBM)
             loss, pred = self.model.embed_predict(data, self.embeddings, target)
+            return None, loss, pred, target
+        if (self.pixel_embeddings and self.loss_func == "cos" and (szn or self.forced_unseen) and target_embed is None
+                and not self.verbose_val and self.embeddings.shape[0] <= 256):
+            # full SZN network (seen-mask-stitched) or forced-unseen inference, same route: the seen-mask group (or the target's)
+            # picks the class subset per pixel inside the fused head -- neither (n,E,h,w) nor (n,2,h,w) score in HBM
+            loss, pred = self.model.szn_predict(data, self.embeddings, self.unseen, target,
+                                                group='seenmask' if szn else 'target')
             return None, loss, pred, target
         if szn:
             score, seen_mask_score = self.model(data, mode='both')
