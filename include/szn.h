@@ -28,7 +28,18 @@ extern "C" {
 typedef void* szn_stream_t; /* hipStream_t */
 
 enum { SZN_OK = 0, SZN_ERR_ARG = -1, SZN_ERR_LAUNCH = -2, SZN_ERR_UNSUPPORTED = -3 };
-enum { SZN_F32 = 0, SZN_BF16 = 1, SZN_F16 = 2 };   /* SZN_F16: IEEE half activations / weight images (BASELINE configs[4]) */
+enum { SZN_F32 = 0, SZN_BF16 = 1, SZN_F16 = 2, SZN_BF16X3 = 3 };   /* SZN_F16: IEEE half activations / weight images (BASELINE configs[4]) */
+/* SZN_BF16X3: fp32-accurate GEMMs on the bf16 matrix cores.  Tensors are fp32 exactly as for SZN_F32 (same layouts, strides, sizes,
+ * workspaces); only the products inside the conv GEMMs change.  Arithmetic contract:
+ *   hi = bf16_rne(x), lo = bf16_rne(x - float(hi))   (the subtraction is exact in fp32), for every operand element x;
+ *   each product a.b is computed as a_hi.b_hi + a_hi.b_lo + a_lo.b_hi (lo.lo dropped), accumulated in fp32 by the bf16 MFMA;
+ *   every epilogue (bias, ReLU, gate, Dropout2d factor, split-K slabs, column sums) is the SZN_F32 one, unchanged.
+ * Error per product <= ~3 * 2^-18 relative (about 1e-5), against ~4e-3 for plain bf16 operands.  A non-finite input may give NaN where
+ * fp32 gives +-Inf (x - hi = Inf - Inf).
+ * Taken by szn_conv2d_fwd / _dgrad / _wgrad, szn_conv2d_dgrad_gemm and szn_gemm_proj_*; the helpers the fp32 path calls around
+ * them (szn_pack_weight_dgrad, szn_conv2d_dgrad_gemm_native_supported, szn_conv2d_wgrad_adam_supported, szn_conv2d_dgrad_border_region,
+ * szn_conv2d_wgrad_cb_region) treat it as SZN_F32.  Every other entry point rejects it (SZN_ERR_ARG).  szn_last_kernel() names the
+ * split variants with a "+bf16x3" suffix (e.g. "conv_igemm_v2+bf16x3").                                                            */
 
 /* a set of class indices below SZN_MAX_CLASSES: bit (k % 64) of w[k / 64] = class k.  Passed by HOST pointer, read during the
  * call (NULL = the empty set); used by the *_k entry points (more than 64 classes).                                                                                        */
@@ -82,7 +93,7 @@ typedef struct szn_call_result {
 } szn_call_result_t;
 
 typedef struct {
-    int dtype;        /* SZN_F32 | SZN_BF16: element type of in / w / gate / out                 */
+    int dtype;        /* SZN_F32 | SZN_BF16 | SZN_F16 | SZN_BF16X3 (fp32 tensors): element type of in / w / gate / out */
     int B, Hi, Wi, Ci; /* input  [B][Hi][Wi][Ci], pixel stride ldi >= Ci elements                 */
     int Ho, Wo, Co;   /* output [B][Ho][Wo][Co], pixel stride ldo >= Co; Ho = Hi + 2*pad - KH + 1 */
     int KH, KW, pad;

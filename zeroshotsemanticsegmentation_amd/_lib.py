@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SZN_LIB_PATH") or os.path.join(_HERE, "lib", "libszn_hip.so")   # (override: A/B builds in tools/)
 
 SZN_F32, SZN_BF16, SZN_F16 = 0, 1, 2
+SZN_BF16X3 = 3          # fp32 tensors, split-bf16 conv GEMMs (include/szn.h)
 
 
 class SznError(RuntimeError):

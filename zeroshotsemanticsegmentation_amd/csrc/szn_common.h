@@ -10,6 +10,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <math.h>
+#include <type_traits>
 #include "../../include/szn.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
@@ -142,7 +143,38 @@ template <> __device__ __forceinline__ f32x4_t mfma16<f16_raw>(szn_u32x4_t a, sz
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
 }
 static inline bool szn_is16(int dtype) { return dtype == SZN_BF16 || dtype == SZN_F16; }
-static inline size_t szn_esize(int dtype) { return dtype == SZN_F32 ? 4 : 2; }
+// fp32 storage: SZN_F32, and SZN_BF16X3 (fp32 tensors, split-bf16 products inside the conv GEMMs; include/szn.h)
+static inline bool szn_store_f32(int dtype) { return dtype == SZN_F32 || dtype == SZN_BF16X3; }
+static inline size_t szn_esize(int dtype) { return szn_store_f32(dtype) ? 4 : 2; }
+
+// ---- bf16x3 (SZN_BF16X3): the GEMM kernels' fp32 instantiations, with x = hi + lo split into two RNE bf16 values ----------------
+// f32x3_t is the storage tag of those instantiations: 4 bytes, loaded and stored as float, so every fp32 address / byte computation
+// and every epilogue is the fp32 one.  Only the fragment -> MFMA step differs.
+struct f32x3_t { float v; };
+template <> struct elem<f32x3_t> {
+    static constexpr int kPer16B = 4;
+    __device__ static __forceinline__ float ld(const f32x3_t* p) { return p->v; }
+    __device__ static __forceinline__ void st(f32x3_t* p, float v) { p->v = v; }
+};
+// four fp32 K values of one lane -> [hi0 hi1 hi2 hi3 | lo0 lo1 lo2 lo3] as bf16 pairs; hi = rne(x), lo = rne(x - hi) (the
+// subtraction is exact).  Done once per fragment, right after its LDS read.
+__device__ __forceinline__ szn_u32x4_t x3_split(float x0, float x1, float x2, float x3) {
+    const uint32_t h01 = pack2<bf16_raw>(x0, x1), h23 = pack2<bf16_raw>(x2, x3);
+    const uint32_t l01 = pack2<bf16_raw>(x0 - __uint_as_float(h01 << 16), x1 - __uint_as_float(h01 & 0xffff0000u));
+    const uint32_t l23 = pack2<bf16_raw>(x2 - __uint_as_float(h23 << 16), x3 - __uint_as_float(h23 & 0xffff0000u));
+    return szn_u32x4_t{h01, h23, l01, l23};
+}
+__device__ __forceinline__ szn_u32x4_t x3_split(szn_u32x4_t f) {
+    return x3_split(__uint_as_float(f.x), __uint_as_float(f.y), __uint_as_float(f.z), __uint_as_float(f.w));
+}
+// acc += A.B over the 4 K values of split fragments a = [a_hi | a_lo], b = [b_hi | b_lo] (same lane -> K mapping on both sides):
+//   [a_hi | a_lo] . [b_hi | b_hi] = hi.hi + lo.hi,   [a_hi | a_lo] . [b_lo | 0] = hi.lo      (lo.lo dropped)
+__device__ __forceinline__ f32x4_t x3_mma(szn_u32x4_t a, szn_u32x4_t b, f32x4_t c) {
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a),
+                                                __builtin_bit_cast(bf16x8_t, (szn_u32x4_t{b.x, b.y, b.x, b.y})), c, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a),
+                                                   __builtin_bit_cast(bf16x8_t, (szn_u32x4_t{b.z, b.w, 0u, 0u})), c, 0, 0, 0);
+}
 
 // ---- wave helpers (wave = 64 lanes) ---------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {

@@ -32,6 +32,7 @@ namespace {
 // ------------------------------------------------------------------------------------------------
 template <typename T> struct Mma;
 template <> struct Mma<bf16_raw> {
+    static __device__ __forceinline__ u32x4_t frag(const u32x4_t& f) { return f; }
     // one 16x16x32 step: lane (r = lane&15, g = lane>>4) holds k = 8*g .. 8*g+7 of row r
     static __device__ __forceinline__ void run(f32x4_t& acc, const u32x4_t& a, const u32x4_t& b) {
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a),
@@ -39,9 +40,11 @@ template <> struct Mma<bf16_raw> {
     }
 };
 template <> struct Mma<f16_raw> {
+    static __device__ __forceinline__ u32x4_t frag(const u32x4_t& f) { return f; }
     static __device__ __forceinline__ void run(f32x4_t& acc, const u32x4_t& a, const u32x4_t& b) { acc = mfma16<f16_raw>(a, b, acc); }
 };
 template <> struct Mma<float> {
+    static __device__ __forceinline__ u32x4_t frag(const u32x4_t& f) { return f; }
     // four 16x16x4 steps; step e uses element e of every lane's 16-B chunk (k = 4*g + e)
     static __device__ __forceinline__ void run(f32x4_t& acc, const u32x4_t& a, const u32x4_t& b) {
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.x), __uint_as_float(b.x), acc, 0, 0, 0);
@@ -49,6 +52,11 @@ template <> struct Mma<float> {
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.z), __uint_as_float(b.z), acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.w), __uint_as_float(b.w), acc, 0, 0, 0);
     }
+};
+
+template <> struct Mma<f32x3_t> {     // bf16x3: [hi | lo] fragments (split once after the LDS read), two bf16 MFMAs (szn_common.h)
+    static __device__ __forceinline__ u32x4_t frag(const u32x4_t& f) { return x3_split(f); }
+    static __device__ __forceinline__ void run(f32x4_t& acc, const u32x4_t& a, const u32x4_t& b) { acc = x3_mma(a, b, acc); }
 };
 
 struct ConvArgs {
@@ -155,9 +163,9 @@ __global__ __launch_bounds__(256, 2) void conv_igemm(ConvArgs a) {
             const int off = (((s * 4 + g) ^ (r16 & 7)) << 4);
             u32x4_t wf[4], pf[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) wf[i] = *(const u32x4_t*)(sw + i * 16 * ROWB + off);
+            for (int i = 0; i < 4; ++i) wf[i] = Mma<T>::frag(*(const u32x4_t*)(sw + i * 16 * ROWB + off));
 #pragma unroll
-            for (int j = 0; j < 4; ++j) pf[j] = *(const u32x4_t*)(sp + j * 16 * ROWB + off);
+            for (int j = 0; j < 4; ++j) pf[j] = Mma<T>::frag(*(const u32x4_t*)(sp + j * 16 * ROWB + off));
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -320,6 +328,7 @@ template <typename T> struct WgTraits;
 template <> struct WgTraits<bf16_raw> { static constexpr int KP = 32; static constexpr int TRS = 256 + 32; };
 template <> struct WgTraits<f16_raw> { static constexpr int KP = 32; static constexpr int TRS = 256 + 32; };
 template <> struct WgTraits<float>    { static constexpr int KP = 16; static constexpr int TRS = 512 + 64; };
+template <> struct WgTraits<f32x3_t> { static constexpr int KP = 16; static constexpr int TRS = 512 + 64; };
 
 template <typename T>
 __global__ __launch_bounds__(256, 2) void conv_wgrad(WgradArgs a) {
@@ -425,6 +434,24 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad(WgradArgs a) {
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) Mma<T>::run(acc[i][j], df[i], xf[j]);
+        } else if constexpr (std::is_same<T, f32x3_t>::value) {
+            // bf16x3: the four steps' elements [k = 4*s + g][ch r16] (s = 0..3) of a fragment as one 4-vector, split once
+            u32x4_t df[4], xf[4];
+            const int ro = g * TRS + r16 * 4;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const char* p = sd + ro + (wm * 64 + i * 16) * 4;
+                df[i] = x3_split(*(const float*)p, *(const float*)(p + 4 * TRS), *(const float*)(p + 8 * TRS), *(const float*)(p + 12 * TRS));
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const char* p = si + ro + (wn * 64 + j * 16) * 4;
+                xf[j] = x3_split(*(const float*)p, *(const float*)(p + 4 * TRS), *(const float*)(p + 8 * TRS), *(const float*)(p + 12 * TRS));
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] = x3_mma(df[i], xf[j], acc[i][j]);
         } else {
             // f32: one element per lane per 16x16x4 step: lane (r16, g) reads [k = 4*s + g][ch r16]
 #pragma unroll
@@ -518,13 +545,13 @@ int launch_conv(const ConvArgs& a, hipStream_t st) {
         attr_done = true;
     }
     hipLaunchKernelGGL(conv_igemm<T>, dim3(a.mtiles * a.ntiles), dim3(256), lds, st, a);
-    SZN_CHECK_LAUNCH("conv_igemm");
+    SZN_CHECK_LAUNCH((std::is_same<T, f32x3_t>::value ? "conv_igemm+bf16x3" : "conv_igemm"));
     return SZN_OK;
 }
 
 int check_desc(const szn_conv_desc_t* d) {
     if (!d) SZN_FAIL(SZN_ERR_ARG, "conv: null descriptor");
-    if (d->dtype != SZN_F32 && !szn_is16(d->dtype)) SZN_FAIL(SZN_ERR_ARG, "conv: bad dtype %d", d->dtype);
+    if (!szn_store_f32(d->dtype) && !szn_is16(d->dtype)) SZN_FAIL(SZN_ERR_ARG, "conv: bad dtype %d", d->dtype);
     if (d->B <= 0 || d->Hi <= 0 || d->Wi <= 0 || d->Ci <= 0 || d->Co <= 0 || d->KH <= 0 || d->KW <= 0 || d->pad < 0)
         SZN_FAIL(SZN_ERR_ARG, "conv: non-positive dimension");
     if (d->Ho != d->Hi + 2 * d->pad - d->KH + 1 || d->Wo != d->Wi + 2 * d->pad - d->KW + 1 || d->Ho <= 0 || d->Wo <= 0)
@@ -557,10 +584,12 @@ int szn_conv2d_fwd_v1(const szn_conv_desc_t* d, const void* in, const void* w, c
     a.M = d->B * d->Ho * d->Wo; a.HoWo = d->Ho * d->Wo;
     a.mtiles = szn_div_up(a.M, TILE); a.ntiles = szn_div_up(a.Co, TILE);
     rc = d->dtype == SZN_BF16 ? launch_conv<bf16_raw>(a, (hipStream_t)stream)
-       : d->dtype == SZN_F16 ? launch_conv<f16_raw>(a, (hipStream_t)stream) : launch_conv<float>(a, (hipStream_t)stream);
+       : d->dtype == SZN_F16 ? launch_conv<f16_raw>(a, (hipStream_t)stream)
+       : d->dtype == SZN_BF16X3 ? launch_conv<f32x3_t>(a, (hipStream_t)stream) : launch_conv<float>(a, (hipStream_t)stream);
     if (rc || !d->colsum) return rc;
     if (d->out_f32 && szn_is16(d->dtype)) SZN_FAIL(SZN_ERR_UNSUPPORTED, "conv2d_fwd(v1): colsum with out_f32 is unsupported");
-    return szn_bias_grad_slab(d->dtype, a.M, d->Co, d->ldo, out, d->colsum, 1, d->colsum_slab, d->colsum_slab_rows, nullptr, stream);   // fallback path: separate pass
+    return szn_bias_grad_slab(szn_store_f32(d->dtype) ? SZN_F32 : d->dtype, a.M, d->Co, d->ldo, out, d->colsum, 1, d->colsum_slab,
+                              d->colsum_slab_rows, nullptr, stream);   // fallback path: separate pass
 }
 
 extern "C" int szn_pack_weight_dgrad(int dtype, int Co, int KH, int KW, int Ci, const void* w, void* wT,
@@ -576,7 +605,7 @@ extern "C" int szn_pack_weight_dgrad(int dtype, int Co, int KH, int KW, int Ci, 
     if (szn_is16(dtype))
         hipLaunchKernelGGL(pack_dgrad_kernel<uint16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)w,
                            (uint16_t*)wT, Co, KH, KW, Ci);
-    else if (dtype == SZN_F32)
+    else if (szn_store_f32(dtype))
         hipLaunchKernelGGL(pack_dgrad_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)w, (float*)wT,
                            Co, KH, KW, Ci);
     else
@@ -839,9 +868,11 @@ int szn_conv2d_wgrad_v1(const szn_conv_desc_t* d, const void* in, const void* do
         hipLaunchKernelGGL(conv_wgrad<bf16_raw>, dim3((unsigned)blocks), dim3(256), 0, st, a);
     else if (d->dtype == SZN_F16)
         hipLaunchKernelGGL(conv_wgrad<f16_raw>, dim3((unsigned)blocks), dim3(256), 0, st, a);
+    else if (d->dtype == SZN_BF16X3)
+        hipLaunchKernelGGL(conv_wgrad<f32x3_t>, dim3((unsigned)blocks), dim3(256), 0, st, a);
     else
         hipLaunchKernelGGL(conv_wgrad<float>, dim3((unsigned)blocks), dim3(256), 0, st, a);
-    SZN_CHECK_LAUNCH("conv_wgrad");
+    SZN_CHECK_LAUNCH(d->dtype == SZN_BF16X3 ? "conv_wgrad+bf16x3" : "conv_wgrad");
     return SZN_OK;
 }
 

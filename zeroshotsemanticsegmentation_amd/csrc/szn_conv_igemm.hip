@@ -41,22 +41,31 @@ int szn_conv_regw_try(const szn_conv_desc_t* d, const void* in, const void* w, c
 namespace {
 
 template <typename T> struct Mma2;
+// frag(): what a fragment becomes right after its LDS read (identity, or the hi / lo split of bf16x3), reused by every MFMA it feeds
 template <> struct Mma2<bf16_raw> {
+    static __device__ __forceinline__ u32x4_t frag(const u32x4_t& f) { return f; }
     static __device__ __forceinline__ void run(f32x4_t& acc, const u32x4_t& a, const u32x4_t& b) {
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc,
                                                       0, 0, 0);
     }
 };
 template <> struct Mma2<f16_raw> {
+    static __device__ __forceinline__ u32x4_t frag(const u32x4_t& f) { return f; }
     static __device__ __forceinline__ void run(f32x4_t& acc, const u32x4_t& a, const u32x4_t& b) { acc = mfma16<f16_raw>(a, b, acc); }
 };
 template <> struct Mma2<float> {
+    static __device__ __forceinline__ u32x4_t frag(const u32x4_t& f) { return f; }
     static __device__ __forceinline__ void run(f32x4_t& acc, const u32x4_t& a, const u32x4_t& b) {
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.x), __uint_as_float(b.x), acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.y), __uint_as_float(b.y), acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.z), __uint_as_float(b.z), acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.w), __uint_as_float(b.w), acc, 0, 0, 0);
     }
+};
+
+template <> struct Mma2<f32x3_t> {      // bf16x3: 4 fp32 K values per lane -> [hi | lo], two bf16 MFMAs (szn_common.h)
+    static __device__ __forceinline__ u32x4_t frag(const u32x4_t& f) { return x3_split(f); }
+    static __device__ __forceinline__ void run(f32x4_t& acc, const u32x4_t& a, const u32x4_t& b) { acc = x3_mma(a, b, acc); }
 };
 
 struct Conv2Args {
@@ -193,18 +202,18 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_v2(Conv2Args a) {
             const char* sp = smem + (wm * 64 + r16) * 128;
             const char* sw = smem + BM * 128 + (wn * (BN / 2) + r16) * 128;
 #pragma unroll
-            for (int i = 0; i < WNF; ++i) wfA[i] = *(const u32x4_t*)(sw + i * 16 * 128 + offs0);
+            for (int i = 0; i < WNF; ++i) wfA[i] = Mma2<T>::frag(*(const u32x4_t*)(sw + i * 16 * 128 + offs0));
 #pragma unroll
-            for (int j = 0; j < 4; ++j) pfA[j] = *(const u32x4_t*)(sp + j * 16 * 128 + offs0);
+            for (int j = 0; j < 4; ++j) pfA[j] = Mma2<T>::frag(*(const u32x4_t*)(sp + j * 16 * 128 + offs0));
         }
         for (int kc = 0; kc < nK; ++kc) {
             const char* sp = smem + stage * STAGE + (wm * 64 + r16) * 128;
             const char* sw = smem + stage * STAGE + BM * 128 + (wn * (BN / 2) + r16) * 128;
             // ---- half 1: fetch the second-half fragments, multiply the first-half ones ----
 #pragma unroll
-            for (int i = 0; i < WNF; ++i) wfB[i] = *(const u32x4_t*)(sw + i * 16 * 128 + offs1);
+            for (int i = 0; i < WNF; ++i) wfB[i] = Mma2<T>::frag(*(const u32x4_t*)(sw + i * 16 * 128 + offs1));
 #pragma unroll
-            for (int j = 0; j < 4; ++j) pfB[j] = *(const u32x4_t*)(sp + j * 16 * 128 + offs1);
+            for (int j = 0; j < 4; ++j) pfB[j] = Mma2<T>::frag(*(const u32x4_t*)(sp + j * 16 * 128 + offs1));
 #pragma unroll
             for (int i = 0; i < WNF; ++i)
 #pragma unroll
@@ -223,9 +232,9 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_v2(Conv2Args a) {
                 const char* sp2 = smem + nstage * STAGE + (wm * 64 + r16) * 128;
                 const char* sw2 = smem + nstage * STAGE + BM * 128 + (wn * (BN / 2) + r16) * 128;
 #pragma unroll
-                for (int i = 0; i < WNF; ++i) wfA[i] = *(const u32x4_t*)(sw2 + i * 16 * 128 + offs0);
+                for (int i = 0; i < WNF; ++i) wfA[i] = Mma2<T>::frag(*(const u32x4_t*)(sw2 + i * 16 * 128 + offs0));
 #pragma unroll
-                for (int j = 0; j < 4; ++j) pfA[j] = *(const u32x4_t*)(sp2 + j * 16 * 128 + offs0);
+                for (int j = 0; j < 4; ++j) pfA[j] = Mma2<T>::frag(*(const u32x4_t*)(sp2 + j * 16 * 128 + offs0));
             }
 #pragma unroll
             for (int i = 0; i < WNF; ++i)
@@ -255,9 +264,9 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_v2(Conv2Args a) {
             const int off = s ? offs1 : offs0;
             u32x4_t wf[WNF], pf[4];
 #pragma unroll
-            for (int i = 0; i < WNF; ++i) wf[i] = *(const u32x4_t*)(sw + i * 16 * 128 + off);
+            for (int i = 0; i < WNF; ++i) wf[i] = Mma2<T>::frag(*(const u32x4_t*)(sw + i * 16 * 128 + off));
 #pragma unroll
-            for (int j = 0; j < 4; ++j) pf[j] = *(const u32x4_t*)(sp + j * 16 * 128 + off);
+            for (int j = 0; j < 4; ++j) pf[j] = Mma2<T>::frag(*(const u32x4_t*)(sp + j * 16 * 128 + off));
 #pragma unroll
             for (int i = 0; i < WNF; ++i) {
                 if (s * WNF + i > 0 && s * WNF + i < 4 && fill && turn == s * WNF + i) issue(stage >= 1 ? stage - 1 : 2);
@@ -581,7 +590,7 @@ int launch_v2(const Conv2Args& a, hipStream_t st) {
         return SZN_OK;
     }
     hipLaunchKernelGGL((conv_igemm_v2<T, WNF>), dim3(a.mtiles * a.ntiles, a.nsplit), dim3(512), lds, st, a);
-    SZN_CHECK_LAUNCH("conv_igemm_v2");
+    SZN_CHECK_LAUNCH((std::is_same<T, f32x3_t>::value ? "conv_igemm_v2+bf16x3" : "conv_igemm_v2"));
     return SZN_OK;
 }
 
@@ -614,7 +623,7 @@ static int conv2d_fwd_entry(const szn_conv_desc_t* d, const void* in, const void
     const int rc = conv2d_fwd_dispatch(d, in, w, bias, gate, chan_scale, out, stream, &pooled);
     if (rc || !d->pool_out || pooled) return rc;
     // the kernel that ran has no fused pooling: pool the tensor it wrote (and write the winner codes when asked for)
-    return szn_maxpool2x2_ceil_fwd_code((d->out_f32 || d->dtype == SZN_F32) ? SZN_F32 : d->dtype, d->B, d->Ho, d->Wo, d->Co, out,
+    return szn_maxpool2x2_ceil_fwd_code((d->out_f32 || szn_store_f32(d->dtype)) ? SZN_F32 : d->dtype, d->B, d->Ho, d->Wo, d->Co, out,
                                         d->pool_out, d->pool_code, stream);
 }
 
@@ -624,7 +633,7 @@ static int conv2d_fwd_dispatch(const szn_conv_desc_t* d, const void* in, const v
     const size_t in_bytes = (size_t)d->B * d->Hi * d->Wi * d->ldi * es;
     const size_t w_bytes = (size_t)d->Co * d->KH * d->KW * d->Ci * es;
     const int bke = (int)(128 / es);
-    const bool v2_ok = (szn_is16(d->dtype) || d->dtype == SZN_F32) && d->Ci > 0 && (d->Ci % bke) == 0 &&
+    const bool v2_ok = (szn_is16(d->dtype) || szn_store_f32(d->dtype)) && d->Ci > 0 && (d->Ci % bke) == 0 &&
                        in_bytes < 0x7fff0000ul && w_bytes < 0x7fff0000ul && d->Hi < 32000 && d->Wi < 32000 && d->pad < 16000 &&
                        ((size_t)d->ldi * es) % 16 == 0;
     {   // the pixel projection at full-resolution sizes (>= 256 pixel tiles x one 320-wide cout tile): HBM-streaming kernel
@@ -682,7 +691,7 @@ static int conv2d_fwd_dispatch(const szn_conv_desc_t* d, const void* in, const v
     // efficiency + slab traffic.
     bool use_wide = false;                            // split-K on the 256 x 256 tile kernel (szn_conv_wide.hip)
     // column sums under split-K: splitk_epilogue_cs (its conditions are checked here; the slab must hold its row count)
-    const bool out32_ = d->out_f32 || d->dtype == SZN_F32;
+    const bool out32_ = d->out_f32 || szn_store_f32(d->dtype);
     const int cs_rpb = 32;
     const long cs_rows = ((long)a.M + cs_rpb - 1) / cs_rpb;
     const int cs_split = 1; /* (was SZN_SPLITK_COLSUM) */
@@ -739,6 +748,7 @@ static int conv2d_fwd_dispatch(const szn_conv_desc_t* d, const void* in, const v
     if (rc != 0) {                                    // (rc == 0: the wide / 8-phase kernel ran, or wrote the slabs)
         if (d->dtype == SZN_BF16) rc = narrow ? launch_v2<bf16_raw, 2>(a, st) : launch_v2<bf16_raw, 4>(a, st);
         else if (d->dtype == SZN_F16) rc = narrow ? launch_v2<f16_raw, 2>(a, st) : launch_v2<f16_raw, 4>(a, st);
+        else if (d->dtype == SZN_BF16X3) rc = narrow ? launch_v2<f32x3_t, 2>(a, st) : launch_v2<f32x3_t, 4>(a, st);
         else rc = narrow ? launch_v2<float, 2>(a, st) : launch_v2<float, 4>(a, st);
         if (rc) return rc;
     }

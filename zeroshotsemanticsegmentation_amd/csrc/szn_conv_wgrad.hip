@@ -201,6 +201,23 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_v2(Wg2Args a) {
 #pragma unroll
                 for (int j = 0; j < FB; ++j)
                     acc[i][j] = mfma16<T>(df[i], xf[j], acc[i][j]);
+        } else if constexpr (std::is_same<T, f32x3_t>::value) {
+            // bf16x3: the four rows 4s + g (s = 0..3) of a fragment gathered into one 4-vector, split once, two bf16 MFMAs per pair
+            u32x4_t df[FA], xf[FB];
+#pragma unroll
+            for (int i = 0; i < FA; ++i) {
+                const char* p = sb + offA[i];
+                df[i] = x3_split(*(const float*)p, *(const float*)(p + 4 * RBA), *(const float*)(p + 8 * RBA), *(const float*)(p + 12 * RBA));
+            }
+#pragma unroll
+            for (int j = 0; j < FB; ++j) {
+                const char* p = sb + offB[j];
+                xf[j] = x3_split(*(const float*)p, *(const float*)(p + 4 * RBB), *(const float*)(p + 8 * RBB), *(const float*)(p + 12 * RBB));
+            }
+#pragma unroll
+            for (int i = 0; i < FA; ++i)
+#pragma unroll
+                for (int j = 0; j < FB; ++j) acc[i][j] = x3_mma(df[i], xf[j], acc[i][j]);
         } else {
 #pragma unroll
             for (int s = 0; s < 4; ++s) {       // rows 4s + g; the swizzle depends on (row & 1) == (g & 1) only
@@ -375,7 +392,7 @@ static int wgrad_dispatch(const szn_conv_desc_t* d, const void* in, const void* 
     const int ch = (int)(16 / es);
     const size_t in_bytes = (size_t)d->B * d->Hi * d->Wi * d->ldi * es;
     const size_t dout_bytes = (size_t)d->B * d->Ho * d->Wo * d->ldo * es;
-    const bool ok = (szn_is16(d->dtype) || d->dtype == SZN_F32) && in && dout && dw && d->B > 0 && d->Hi > 0 && d->Wi > 0 &&
+    const bool ok = (szn_is16(d->dtype) || szn_store_f32(d->dtype)) && in && dout && dw && d->B > 0 && d->Hi > 0 && d->Wi > 0 &&
                     d->Ci > 0 && d->Co > 0 && d->KH > 0 && d->KW > 0 && d->pad >= 0 &&
                     d->Ho == d->Hi + 2 * d->pad - d->KH + 1 && d->Wo == d->Wi + 2 * d->pad - d->KW + 1 && d->Ho > 0 && d->Wo > 0 &&
                     (d->Ci % ch) == 0 && (d->ldi % ch) == 0 && (d->ldo % ch) == 0 && in_bytes < 0x7fff0000ul &&
@@ -444,13 +461,18 @@ static int wgrad_dispatch(const szn_conv_desc_t* d, const void* in, const void* 
         else if (FA == 4) launch_wg2<f16_raw, 4, 2>(a, blocks, st);
         else if (FB == 4) launch_wg2<f16_raw, 2, 4>(a, blocks, st);
         else launch_wg2<f16_raw, 2, 2>(a, blocks, st);
+    } else if (d->dtype == SZN_BF16X3) {
+        if (FA == 4 && FB == 4) launch_wg2<f32x3_t, 4, 4>(a, blocks, st);
+        else if (FA == 4) launch_wg2<f32x3_t, 4, 2>(a, blocks, st);
+        else if (FB == 4) launch_wg2<f32x3_t, 2, 4>(a, blocks, st);
+        else launch_wg2<f32x3_t, 2, 2>(a, blocks, st);
     } else {
         if (FA == 4 && FB == 4) launch_wg2<float, 4, 4>(a, blocks, st);
         else if (FA == 4) launch_wg2<float, 4, 2>(a, blocks, st);
         else if (FB == 4) launch_wg2<float, 2, 4>(a, blocks, st);
         else launch_wg2<float, 2, 2>(a, blocks, st);
     }
-    SZN_CHECK_LAUNCH("conv_wgrad_v2");
+    SZN_CHECK_LAUNCH(d->dtype == SZN_BF16X3 ? "conv_wgrad_v2+bf16x3" : "conv_wgrad_v2");
     if (a.slab) {
         const long n4 = nw / 4;                        // (the slab form requires nw % 4 == 0, see above)
         // many splits of a small gradient: sixteen split lanes per group; else four

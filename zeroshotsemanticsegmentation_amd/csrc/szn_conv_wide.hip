@@ -213,6 +213,7 @@ template <typename T, int WNF, int ABL = 0>       // WNF = 16-cout fragments per
 __global__ __launch_bounds__(512, 2) void conv_igemm_wide(WideArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int ES = sizeof(T);
+    constexpr bool kX3 = std::is_same<T, f32x3_t>::value;
     constexpr int BKE = 128 / ES;
     constexpr int BM = 256, BN = 32 * WNF;
     constexpr int NBW = BN / 64;                  // weight LDS-DMA instructions per wave per chunk (3 / 4 / 5)
@@ -317,6 +318,12 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_wide(WideArgs a) {
             for (int j = 0; j < 4; ++j) pf[j] = *(const u32x4_t*)(sp + j * 16 * 128 + off);
 #pragma unroll
             for (int i = 0; i < WNF; ++i) wf[i] = *(const u32x4_t*)(sw + i * 16 * 128 + off);
+            if constexpr (kX3) {                  // bf16x3: every fragment split once, here (szn_common.h)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) pf[j] = x3_split(pf[j]);
+#pragma unroll
+                for (int i = 0; i < WNF; ++i) wf[i] = x3_split(wf[i]);
+            }
 #pragma unroll
             for (int i = 0; i < WNF; ++i) {
                 if (s == 0 && i > 0 && i < 8 && fill && turn == i) issue(stage ^ 1);
@@ -324,6 +331,8 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_wide(WideArgs a) {
                 for (int j = 0; j < 4; ++j) {
                     if constexpr (ES == 2) {
                         acc[i][j] = mfma16<T>(wf[i], pf[j], acc[i][j]);
+                    } else if constexpr (kX3) {
+                        acc[i][j] = x3_mma(wf[i], pf[j], acc[i][j]);
                     } else {
                         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wf[i].x), __uint_as_float(pf[j].x), acc[i][j], 0, 0, 0);
                         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(wf[i].y), __uint_as_float(pf[j].y), acc[i][j], 0, 0, 0);
@@ -716,7 +725,7 @@ int launch_wide(const WideArgs& a, hipStream_t st) {
         return SZN_OK;
     }
     hipLaunchKernelGGL((conv_igemm_wide<T, WNF>), dim3(a.mtiles * a.ntiles, a.nsplit), dim3(512), lds, st, a);
-    SZN_CHECK_LAUNCH("conv_igemm_wide");
+    SZN_CHECK_LAUNCH((std::is_same<T, f32x3_t>::value ? "conv_igemm_wide+bf16x3" : "conv_igemm_wide"));
     return SZN_OK;
 }
 
@@ -795,6 +804,7 @@ int szn_conv_wide_try(const szn_conv_desc_t* d, const void* in, const void* w, c
     if (bn == 320)
         return d->dtype == SZN_F16 ? launch_wide<f16_raw, 10>(a, (hipStream_t)stream) : launch_wide<bf16_raw, 10>(a, (hipStream_t)stream);
     if (d->dtype == SZN_F16) return launch_wide<f16_raw, 8>(a, (hipStream_t)stream);
+    if (d->dtype == SZN_BF16X3) return launch_wide<f32x3_t, 8>(a, (hipStream_t)stream);
     return d->dtype == SZN_BF16 ? launch_wide<bf16_raw, 8>(a, (hipStream_t)stream) : launch_wide<float, 8>(a, (hipStream_t)stream);
 }
 

@@ -95,6 +95,10 @@ def _cb_pool(reg, n):
 # then run without the constant-border hint, which skipped 30 % of the forward tiles and none of the dgrad tiles) and, on the fp32 path
 # -- whose kernels take no hints at all -- for conv1_2 (710 -> 526 rows / columns, -45 %).  On the 16-bit paths conv1_2 keeps its hints:
 # cropping conv1_1's 516 MB output would cost what it saves.
+# precision "bf16x3": the conv GEMMs of these layers take SZN_BF16X3 (fp32 tensors, split-bf16 products: include/szn.h); conv1_1, the
+# projection head, the skip heads, pools, band remap and the optimizer stay exact fp32
+_X3_LAYERS = frozenset(["conv1_2", "conv2_1", "conv2_2", "conv3_1", "conv3_2", "conv3_3", "conv4_1", "conv4_2", "conv4_3", "conv5_1",
+                        "conv5_2", "conv5_3", "fc6", "fc7"])
 _BAND_CROP = os.environ.get("SZN_BAND_CROP", "1") != "0"
 _BAND_BLOCKS = {"conv1_2": ("conv1_2",), "conv2_1": ("conv2_1", "conv2_2"), "conv3_1": ("conv3_1", "conv3_2", "conv3_3")}   # first layer -> block
 # (module constants, not environment knobs since round 6: tools/diag_band.py and the tests patch them)
@@ -269,6 +273,7 @@ class _Engine(object):
     def __init__(self, model):
         self.model = model
         self.dtype = torch.float32
+        self.bf16x3 = False           # precision "bf16x3": storage as float32, the _X3_LAYERS' conv GEMMs on split-bf16 MFMA
         self._versions = None
         self._images = {}
         self._layer_versions = {}     # layer -> parameter versions its images were built from
@@ -318,12 +323,26 @@ class _Engine(object):
 
     # ---- weights ---------------------------------------------------------------------------------
     def set_precision(self, dtype):
-        if dtype not in (torch.float32, torch.bfloat16, torch.float16):
-            raise L.SznError("compute dtype must be float32, bfloat16 or float16")
+        x3 = isinstance(dtype, str) and dtype == "bf16x3"
+        if x3:
+            dtype = torch.float32
+        if isinstance(dtype, str) or dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise L.SznError("compute dtype must be float32, bfloat16, float16 or 'bf16x3'")
+        self.bf16x3 = x3
         if dtype != self.dtype:
             self.dtype = dtype
             self._versions = None
             self._layer_versions = {}
+
+    @property
+    def precision(self):
+        """what set_precision was given: the torch dtype, or 'bf16x3'"""
+        return "bf16x3" if self.bf16x3 else self.dtype
+
+    def _gemm_code(self, name):
+        """dtype code of the conv descriptors of layer `name` (forward, dgrad, wgrad): SZN_BF16X3 for the _X3_LAYERS under precision
+        'bf16x3', else the storage dtype's"""
+        return L.SZN_BF16X3 if (self.bf16x3 and name in _X3_LAYERS) else L.dtype_code(self.dtype)
 
     def mark_dirty(self):
         """parameters were rewritten behind torch's back (the optimizer kernel of TrainStep works on the flat buffers): every
@@ -550,7 +569,7 @@ class _Engine(object):
         k = w.shape[1] if k is None else k
         Ho, Wo = Hi + 2 * pad - k + 1, Wi + 2 * pad - k + 1
         out = torch.empty(B, Ho, Wo, co, device=x.device, dtype=torch.float32 if out_f32 else self.dtype)
-        d = L.ConvDesc(L.dtype_code(self.dtype), B, Hi, Wi, Ci, Ho, Wo, co, k, k, pad, Ci, co, 0, int(relu), int(out_f32))
+        d = L.ConvDesc(self._gemm_code(name), B, Hi, Wi, Ci, Ho, Wo, co, k, k, pad, Ci, co, 0, int(relu), int(out_f32))
         self._workspace(d, B * Ho * Wo * co * 4, x.device)
         pooled = code = None
         if pool:
@@ -852,14 +871,13 @@ class _Engine(object):
             raise L.SznError("szn_conv1_1_wgrad_reads failed (%d)" % sub)
         return ((ry[0], ry[1], rx[0], rx[1]), tuple(reads))
 
-    def _wgrad_desc(self, x, dout_shape, ci, co, k, pad, ldo=None, cb=None):
+    def _wgrad_desc(self, x, dout_shape, ci, co, k, pad, ldo=None, cb=None, name=None):
         """the descriptor of one layer's szn_conv2d_wgrad call (with the slab workspace and, on the 16-bit paths, the constant-border
         hint of the layer's INPUT x: cb = its per-axis regions)"""
         B, Hi, Wi, _ = x.shape
         Ho, Wo = dout_shape[1:3]
         ldo = dout_shape[3] if ldo is None else ldo
-        code = L.dtype_code(self.dtype)
-        d = L.ConvDesc(code, B, Hi, Wi, ci, Ho, Wo, co, k, k, pad, ci, ldo, 0, 0, 0)
+        d = L.ConvDesc(self._gemm_code(name), B, Hi, Wi, ci, Ho, Wo, co, k, k, pad, ci, ldo, 0, 0, 0)
         d.reserved_cus = self.reserved_cus
         # slab workspace of the weight-gradient kernels: the all-taps kernel (szn_conv_wgrad_taps.hip: <= 256 blocks x 64*9*64
         # fp32, room for SZN_WGT_OVERSUB=2) and the pixel splits of conv_wgrad_v2 (head / skip layers, every f32 layer: fixed-order
@@ -875,7 +893,7 @@ class _Engine(object):
             d.cb_const[0], d.cb_const[1], d.cb_const[2], d.cb_const[3] = ry[2], ry[3], rx[2], rx[3]
         return d
 
-    def _wgrad(self, x, dout, dw, db, ci, co, k, pad, ldo=None, after=None, fuse=None, cb=None, csum=None, dw_lp=None):
+    def _wgrad(self, x, dout, dw, db, ci, co, k, pad, ldo=None, after=None, fuse=None, cb=None, csum=None, dw_lp=None, name=None):
         """dw (OHWI f32) = wgrad of one layer, on the wgrad stream; `after` (e.g. the DDP bucket hook) runs there too.  fuse: layer
         name under which self.fused_opt may hold the Adam step to apply in the kernel's epilogue.  cb / csum: constant-border regions
         of x and, optionally, the column sums of dout over the tiles the hint skips (from the producer of dout).  dw_lp: deliver the
@@ -883,7 +901,7 @@ class _Engine(object):
         B, Hi, Wi, _ = x.shape
         Ho, Wo = dout.shape[1:3]
         code = L.dtype_code(self.dtype)
-        d = self._wgrad_desc(x, dout.shape, ci, co, k, pad, ldo=ldo, cb=cb)
+        d = self._wgrad_desc(x, dout.shape, ci, co, k, pad, ldo=ldo, cb=cb, name=name)
         ldo = d.ldo
         if dw_lp is not None:
             d.dw_lp, d.dw_lp_dtype = dw_lp.data_ptr(), L.dtype_code(dw_lp.dtype)
@@ -922,7 +940,7 @@ class _Engine(object):
             wf = img[name + ".w"]                                  # forward image [Co][k][k][Ci]
             k = wf.shape[1]
             code = L.dtype_code(self.dtype)
-            d = L.ConvDesc(code, B, Hi, Wi, Ci, Ho, Wo, Co, k, k, pad, Ci, Co, 0, 0, 0)
+            d = L.ConvDesc(self._gemm_code(name), B, Hi, Wi, Ci, Ho, Wo, Co, k, k, pad, Ci, Co, 0, 0, 0)
             lib = L.load()
             native = _FC6_NATIVE and dout.is_contiguous() and lib.szn_conv2d_dgrad_gemm_native_supported(C.byref(d)) == 1
             nb = (lib.szn_conv2d_dgrad_gemm_native_workspace_bytes if native else lib.szn_conv2d_dgrad_gemm_workspace_bytes)(C.byref(d))
@@ -941,7 +959,7 @@ class _Engine(object):
             return din
         wT = self._images[name + ".wT"] if wT is None else wT
         k = wT.shape[1]
-        d = L.ConvDesc(L.dtype_code(self.dtype), B, Hi, Wi, Ci, Ho, Wo, Co, k, k, pad, Ci, Co, Ci, 0, 0)
+        d = L.ConvDesc(self._gemm_code(name), B, Hi, Wi, Ci, Ho, Wo, Co, k, k, pad, Ci, Co, Ci, 0, 0)
         d.reserved_cus = self.reserved_cus
         slab = None
         M = B * Hi * Wi
@@ -1026,16 +1044,16 @@ class _Engine(object):
             d = self._head_dgrad_fp8(dc, feat, s7, grads["fc7"][1])
         else:
             d = self._dgrad(dc, "head", feat.shape, 0, gate=feat, scale=s7, colsum=grads["fc7"][1])
-        self._wgrad(ctx.relu6, d, grads["fc7"][0], None, F, F, 1, 0, after=lambda: done("fc7"), fuse="fc7", dw_lp=lp.get("fc7"))
+        self._wgrad(ctx.relu6, d, grads["fc7"][0], None, F, F, 1, 0, after=lambda: done("fc7"), fuse="fc7", dw_lp=lp.get("fc7"), name="fc7")
         d = self._dgrad(d, "fc7", ctx.relu6.shape, 0, gate=ctx.relu6, scale=s6, colsum=grads["fc6"][1])
         pool5 = ctx.pools[4][1]
         if self.fused_opt and "fc6" in self.fused_opt:
             # the fused update rewrites fc6's 16-bit weight image, which fc6's dgrad reads in place: dgrad first
             d6 = d
             d = self._dgrad(d6, "fc6", pool5.shape, 0)
-            self._wgrad(pool5, d6, grads["fc6"][0], None, pool5.shape[3], F, 7, 0, after=lambda: done("fc6"), fuse="fc6")
+            self._wgrad(pool5, d6, grads["fc6"][0], None, pool5.shape[3], F, 7, 0, after=lambda: done("fc6"), fuse="fc6", name="fc6")
         else:
-            self._wgrad(pool5, d, grads["fc6"][0], None, pool5.shape[3], F, 7, 0, after=lambda: done("fc6"), dw_lp=lp.get("fc6"))
+            self._wgrad(pool5, d, grads["fc6"][0], None, pool5.shape[3], F, 7, 0, after=lambda: done("fc6"), dw_lp=lp.get("fc6"), name="fc6")
             d = self._dgrad(d, "fc6", pool5.shape, 0)
         pi = 4
         prev_out = None
@@ -1150,7 +1168,7 @@ class _Engine(object):
             layer = getattr(m, name)
             self._wgrad(xin, d, grads[name][0], None, layer.in_channels, layer.out_channels, 3, pad,
                         after=lambda name=name: done(name), cb=(getattr(ctx, "cb_in", None) or {}).get(name),
-                        csum=cb_sums.pop(name, None), dw_lp=lp.get(name))
+                        csum=cb_sums.pop(name, None), dw_lp=lp.get(name), name=name)
             # next d: wrt this conv's input; gate by the ReLU of the producing conv unless a pool sits in between
             if prev == "P":
                 d = self._dgrad(d, name, xin.shape, pad)
@@ -1321,7 +1339,9 @@ class FCN32s(nn.Module):
     # ---- precision / synthetic init ----------------------------------------------------------------
     def set_precision(self, dtype):
         """compute dtype of the HIP path: torch.float32 (parity), torch.bfloat16 (throughput) or torch.float16 (IEEE half
-        activations / weight images, BASELINE configs[4]; training needs TrainStep's loss scaling)"""
+        activations / weight images, BASELINE configs[4]; training needs TrainStep's loss scaling); or the string 'bf16x3': float32
+        tensors throughout, the conv GEMMs of conv1_2 .. fc7 on the bf16 matrix cores with each operand split into hi + lo
+        (fp32-accurate to ~1e-5 relative per product; include/szn.h)"""
         self._engine.set_precision(dtype)
         return self
 

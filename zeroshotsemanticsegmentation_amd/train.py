@@ -9,7 +9,7 @@ Added for this implementation (none change the reference flags):
   --synthetic N H W    deterministic synthetic dataset (no PASCAL data / network here); without it the PASCAL-VOC /
                        PASCAL-Context readers of datasets.py load <data_dir> in the reference's layout
   --batch-size B       images per GPU per step (reference: 1)
-  --precision fp32|bf16
+  --precision fp32|bf16|fp16|bf16x3 (bf16x3: fp32 tensors, conv GEMMs on split-bf16 matrix cores, fp32-accurate)
   --init synthetic|vgg path handling: without the caffe VGG16 file the backbone starts from synth weights
   torchrun: RANK / LOCAL_RANK / WORLD_SIZE are honoured (one process per GPU, RCCL gradient all-reduce).
 """
@@ -56,7 +56,7 @@ def build_parser():
     # additions
     p.add_argument('--synthetic', type=int, nargs=3, metavar=('N', 'H', 'W'), help='synthetic dataset: N images of HxW')
     p.add_argument('--batch-size', type=int, default=1)
-    p.add_argument('--precision', choices=['fp32', 'bf16', 'fp16'], default='fp32')
+    p.add_argument('--precision', choices=['fp32', 'bf16', 'fp16', 'bf16x3'], default='fp32')
     p.add_argument('--arch', choices=['fcn32s', 'fcn8s'], default='fcn32s',
                    help="fcn32s = the reference's only backbone (train.py:103,105); fcn8s = the public FCN8s skip head "
                         "(not in the reference: BASELINE north_star wording, parity unpinned)")
@@ -280,7 +280,7 @@ def main(argv=None):
             print("%s -> deterministic synthetic initialisation" % e)
             model.load_synthetic(1337)
     model = model.to(device)
-    precision = {'bf16': torch.bfloat16, 'fp16': torch.float16, 'fp32': torch.float32}[args.precision]
+    precision = {'bf16': torch.bfloat16, 'fp16': torch.float16, 'fp32': torch.float32, 'bf16x3': 'bf16x3'}[args.precision]
     model.set_precision(precision)
     model._engine.dropout_seed = 1337 + 7919 * rank       # data-parallel ranks draw different Dropout2d masks
 
