@@ -493,6 +493,31 @@ int szn_fused_head_grouped_prepared(int stride, int B, int h, int w, int E, int 
                                     float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
                                     szn_stream_t stream);
 
+/* ---- fused softmax cross-entropy head: coarse -> (loss, stats, prediction, dcoarse) without the (B,C,H,W) score ---------
+ * Equivalent to szn_bilinear_up_crop_fwd(stride) -> szn_ce2d_fwd (pred = channel argmax) -> szn_ce2d_bwd (gout NULL) ->
+ * szn_bilinear_up_crop_bwd(stride) (models.py:94,146-147 upscore + crop, utils.py:19-48 cross_entropy2d, trainer_fcn.py:117
+ * score.max(1)[1]).  stride 32: FCN32s' upscore (crop 19); stride 8: the FCN8s upscore8 stage (crop 31).  coarse: NHWC f32
+ * [B][h][w] with pixel stride ldc, the C class channels at [c0, c0+C); 1 <= C <= SZN_MAX_CLASSES.
+ * Bit identity (-ffp-contract=off): a pixel's logits are those of the materialised score element (bilinear weights formed as
+ * double products rounded to float, fmaf chain over taps (I-1,J-1), (I-1,J), (I,J-1), (I,J)); max, first-index argmax, sum of
+ * exps, logf, the per-pixel term and the class-weight product are ce_fwd_kernel's operations in its order, so pred and every
+ * per-pixel term equal the chain's bit for bit.  The per-pixel gradient is ce_bwd_kernel's g * (softmax_c - [c == label]).
+ * Labels: a pixel counts when 0 <= label < C; -1 (unlabelled), -2 (batch padding) and labels >= C are ignored.  Every pixel
+ * gets a prediction.  weight: optional f32 [C] class weights (NULL = 1).  loss[1]: the sum of the terms, or the sum divided by
+ * the number of valid pixels of the batch (size_average); stats f32 [B][2] = {sum of terms, valid pixels} (may be NULL).
+ * pred int64 (B,H,W) (may be NULL).  dcoarse (may be NULL): d loss / d coarse in dcoarse_dtype (SZN_F32 | SZN_BF16 | SZN_F16),
+ * written to channels [c0, c0+C) of pixel stride ldc only -- padding channels are left untouched.  target and loss both NULL:
+ * a pred-only call (stats and dcoarse NULL, pred not).  Reductions: loss partials in double per pixel cell, fixed-order
+ * finalize; dcoarse is the per-cell table A[t][c] = sum_px w_t * d_c gathered over the <= 4 cells that use each coarse
+ * position -- no atomics, two calls give bitwise-equal outputs.  Bad arguments return SZN_ERR_ARG (geometry, NULL rules, crop
+ * window larger than the deconv output) or SZN_ERR_UNSUPPORTED (stride not 32 or 8, C > SZN_MAX_CLASSES) before any launch.
+ * workspace: szn_fused_ce_head_workspace_bytes of the map's own stride, B, h, w, C.                                      */
+size_t szn_fused_ce_head_workspace_bytes(int stride, int B, int h, int w, int C);
+int szn_fused_ce_head(int stride, int B, int h, int w, int C, int ldc, int c0, int H, int W, int crop,
+                      const float* coarse, const int64_t* target, const float* weight, int size_average,
+                      float* loss, float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse,
+                      void* workspace, szn_stream_t stream);
+
 /* ---- optimizers (train.py:126-133,174-175; torch.optim.Adam / SGD semantics) ----------------------
  * One launch per flat fp32 parameter buffer.  grad_scale multiplies the gradient first (1/world
  * after a sum all-reduce; 1/(world * loss_scale) on the fp16 path).  If w_lp != NULL the updated weight is

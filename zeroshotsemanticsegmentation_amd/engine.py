@@ -375,12 +375,13 @@ class SeenmaskStep(object):
 
 
 class TrainStep(object):
-    def __init__(self, model, embeddings, optimizer="adam", lr=1e-5, momentum=0.99, weight_decay=0.0005,
+    def __init__(self, model, embeddings=None, optimizer="adam", lr=1e-5, momentum=0.99, weight_decay=0.0005,
                  precision=torch.bfloat16, fused_head=True, loss="cos", process_group=None, bucket_mb=25,
                  train_metrics=True, betas=(0.9, 0.999), eps=1e-8, bias_lr=None, bias_weight_decay=0.0,
                  adam_weight_decay=0.0, grad_comm_dtype=None, loss_scale=None, dynamic_loss_scale=None,
                  scale_growth=2.0, scale_backoff=0.5, scale_growth_interval=2000, force_comm=None, reserved_cus=None,
-                 fused_adam=None, keep_grads=True, exchange=None, direct_wire=None, sharded=None, forced_unseen=None):
+                 fused_adam=None, keep_grads=True, exchange=None, direct_wire=None, sharded=None, forced_unseen=None,
+                 class_weight=None, size_average=False):
         """Data-parallel knobs (the reference is single-GPU): grad_comm_dtype (SZN_GRAD_COMM = fp32 | bf16) = the
         wire format of the gradient buckets; exchange=False (SZN_GRAD_COMM=off) = no exchange at all (bench.py's comm-off timing);
         direct_wire (default: on for a 16-bit wire with keep_grads=False; SZN_WIRE_DIRECT=0 turns it off) = the weight-gradient
@@ -389,9 +390,18 @@ class TrainStep(object):
         image instead of all-reduce + replicated optimizer.
         forced_unseen (a list of class indices, trainer_fcn.py:110-112): the returned prediction is the forced-unseen one -- a pixel
         whose label is one of these classes is assigned among them, any other among the rest (szn_fused_head_grouped, group mode 2;
-        the fused_head=False path: szn_embed_argmax_k mode 1 with the target).  Loss, gradients and updates do not change."""
-        if loss not in ("cos", "mse") or (fused_head and loss != "cos"):
-            raise L.SznError("TrainStep: fused head supports the cosine loss; use fused_head=False for mse")
+        the fused_head=False path: szn_embed_argmax_k mode 1 with the target).  Loss, gradients and updates do not change.
+        loss="cross_entropy" (embeddings=None; the softmax FCN of train.py -c 1, utils.py:19-48 with trainer_fcn.py:133's
+        size_average=False): K = C = model.n_class classes, the head is szn_fused_ce_head (fused_head=False: upscore -> szn_ce2d_fwd
+        -> szn_ce2d_bwd -> head_backward), the prediction is the channel argmax; class_weight = optional [C] class weights.  Under
+        data parallelism the update uses the mean of the rank gradients, as allreduce_param_grads gives the autograd route."""
+        if loss not in ("cos", "mse", "cross_entropy") or (fused_head and loss == "mse"):
+            raise L.SznError("TrainStep: fused head supports the cosine and cross-entropy losses; use fused_head=False for mse")
+        self.ce = loss == "cross_entropy"
+        if self.ce and (embeddings is not None or forced_unseen is not None):
+            raise L.SznError("TrainStep: the cross-entropy head takes no embeddings and no forced_unseen classes")
+        if not self.ce and embeddings is None:
+            raise L.SznError("TrainStep: the %s loss needs the class embeddings" % loss)
         self.model = model
         self.eng = model._engine
         # FCN8s (models.FCN8s: public skip head, not in the reference): two more Conv2d layers in the flat buffers and the head
@@ -405,10 +415,22 @@ class TrainStep(object):
         if self.dev.type != "cuda":
             raise L.SznError("TrainStep needs the model on the GPU")
         self._ws_prep = None             # what the head of the fused head's workspace was prepared for (szn_fused_head_prepare)
-        self.emb = torch.as_tensor(embeddings).to(self.dev, torch.float32).contiguous()
-        self.K, self.E = self.emb.shape
-        if self.E != model.n_class:
-            raise L.SznError("embedding dimension %d != model n_class %d" % (self.E, model.n_class))
+        if self.ce:
+            self.emb = None
+            self.K = self.E = model.n_class
+            if self.K > L.MAX_CLASSES:
+                raise L.SznError("TrainStep: the cross-entropy head holds at most %d classes, got %d" % (L.MAX_CLASSES, self.K))
+            self.class_weight = None
+            if class_weight is not None:
+                self.class_weight = torch.as_tensor(class_weight).to(self.dev, torch.float32).contiguous()
+                if self.class_weight.numel() != self.K:
+                    raise L.SznError("TrainStep: class_weight has %d entries for %d classes" % (self.class_weight.numel(), self.K))
+            self.size_average = bool(size_average)
+        else:
+            self.emb = torch.as_tensor(embeddings).to(self.dev, torch.float32).contiguous()
+            self.K, self.E = self.emb.shape
+            if self.E != model.n_class:
+                raise L.SznError("embedding dimension %d != model n_class %d" % (self.E, model.n_class))
         self.opt, self.lr, self.momentum, self.wd = optimizer, lr, momentum, weight_decay
         # the reference wiring (train.py:126-133): biases at 2 x lr without weight decay; Adam has no weight decay at all
         self.betas, self.eps = betas, eps
@@ -433,16 +455,25 @@ class TrainStep(object):
         # static loss scaling for the fp16 path: gradients below 6e-8 vanish in IEEE half, so d(loss)/d(coarse) is multiplied
         # by loss_scale in fp32 before it enters the 16-bit backward pass and the optimizer kernel divides it out again
         # (grad_scale).  The .grad views then hold loss_scale x gradient.  bf16 / fp32 need none.
-        self._loss_scale0 = float(loss_scale) if loss_scale is not None else (4096.0 if precision == torch.float16 else 1.0)
+        # The cross-entropy head's loss is a SUM over pixels (trainer_fcn.py:133): each coarse position of d(coarse) collects the
+        # gradients (|d| <= 1 per class) of the up to (2 S)^2 pixels its taps reach -- ~1e3 at stride 32, 2^18 x B times the
+        # 1/(B N)-scaled cosine gradient.  4096 x that overflows IEEE half (65504) at the head already, so the CE step starts at
+        # scale 1 (its gradients are far above fp16's subnormal range) and may back off below 1 (floor 2^-8) if a batch overflows.
+        fp16_scale0 = 1.0 if self.ce else 4096.0
+        self._loss_scale0 = float(loss_scale) if loss_scale is not None else (fp16_scale0 if precision == torch.float16 else 1.0)
         # dynamic loss scaling (default for fp16): the scale, the overflow flag and the count of APPLIED optimizer steps live
         # on the device (include/szn.h, szn_grad_check_finite / szn_*_step_scaled / szn_loss_scale_update); a step whose
         # gradients contain inf / NaN leaves masters, moments and weight images untouched and halves the scale -- no host
         # synchronisation, identical decisions on every data-parallel rank (the flag is read from the all-reduced gradient)
         self.dynamic = (precision == torch.float16) if dynamic_loss_scale is None else bool(dynamic_loss_scale)
-        self.scale_cfg = (float(scale_growth), float(scale_backoff), int(scale_growth_interval), 1.0, 2.0 ** 32)
+        self.scale_cfg = (float(scale_growth), float(scale_backoff), int(scale_growth_interval), 2.0 ** -8 if self.ce else 1.0,
+                          2.0 ** 32)
         self.scale_state = None
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
+        if self.ce and self.size_average and self.world > 1:
+            # the mean over the valid pixels of the whole data-parallel batch would need the pixel count all-reduced first
+            raise L.SznError("TrainStep: size_average=True cross entropy is single-process only")
         self.force_comm = force_comm
         self.train_metrics = train_metrics
         self.nstep = 0
@@ -667,6 +698,8 @@ class TrainStep(object):
         self.last_ctx = ctx if self.keep_ctx else None
         if self.is8:
             return self._step8(ctx, target, B, H, W)
+        if self.ce:
+            return self._step_ce(ctx, target, B, H, W)
         CP, E, K = m.head_width, self.E, self.K
         code = L.dtype_code(eng.dtype)
         pred = torch.empty(B, H, W, dtype=torch.int64, device=self.dev)
@@ -729,6 +762,58 @@ class TrainStep(object):
             L.call("szn_confusion_hist_k", target.numel(), K, L.ptr(target), L.ptr(pred), None, L.ptr(self.hist), st)
         return self.loss.reshape(()), pred
 
+    def _ce_head(self, stride, fmap, target, H, W, crop, stats, pred, dcoarse):
+        """szn_fused_ce_head on the NHWC map `fmap` (the C class channels first): loss, stats, pred, d(fmap)"""
+        B, h, w, ld = fmap.shape
+        nbytes = L.load().szn_fused_ce_head_workspace_bytes(stride, B, h, w, self.K)
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+        L.call("szn_fused_ce_head", stride, B, h, w, self.K, ld, 0, H, W, crop, L.ptr(fmap), L.ptr(target), L.ptr(self.class_weight),
+               int(self.size_average), L.ptr(self.loss), L.ptr(stats), L.ptr(pred), L.dtype_code(dcoarse.dtype), L.ptr(dcoarse),
+               L.ptr(self._ws), L.stream_ptr())
+
+    def _step_ce(self, ctx, target, B, H, W):
+        """FCN32s + softmax cross entropy: the fused CE head (fused_head=False: the materialised chain, the in-step referee) ->
+        backward -> exchange -> optimizer, as _step"""
+        m, eng = self.model, self.eng
+        st = L.stream_ptr()
+        CP, C = m.head_width, self.K
+        pred = torch.empty(B, H, W, dtype=torch.int64, device=self.dev)
+        stats = torch.empty(B, 2, device=self.dev)
+        scaled = self.dynamic or self._loss_scale0 != 1.0
+        if self.fused_head:
+            # channels [0, C) are written by every call and the padding channels stay zero: the buffer is reused (see _step)
+            key = (B, ctx.h, ctx.w, CP, torch.float32 if scaled else eng.dtype)
+            if getattr(self, "_dcoarse_key", None) == key:
+                dcoarse = self._dcoarse
+            else:
+                dcoarse = torch.zeros(B, ctx.h, ctx.w, CP, device=self.dev, dtype=key[4])
+                self._dcoarse, self._dcoarse_key = dcoarse, key
+            self._ce_head(32, ctx.coarse, target, H, W, CROP, stats, pred, dcoarse)
+        else:
+            f = eng.upscore(ctx)
+            ws = torch.empty(L.load().szn_loss_workspace_bytes(B, H, W), dtype=torch.uint8, device=self.dev)
+            sa = int(self.size_average)
+            L.call("szn_ce2d_fwd", B, C, H, W, L.ptr(f), L.ptr(target), L.ptr(self.class_weight), sa, L.ptr(self.loss), L.ptr(stats),
+                   L.ptr(pred), L.ptr(ws), st)
+            df = torch.empty_like(f)
+            L.call("szn_ce2d_bwd", B, C, H, W, L.ptr(f), L.ptr(target), L.ptr(self.class_weight), sa, L.ptr(stats), None, L.ptr(df), st)
+            dcoarse, _ = eng.head_backward(ctx, df=df)
+        if scaled:
+            dcoarse = self._scale(dcoarse)
+        self.stats = stats
+        self._fused_begin()
+        try:
+            self.buckets.begin_step()
+            self._backward(ctx, dcoarse, self._layer_done_hook(B * H * W))
+            self.buckets.finish()
+            self._optimizer_step()
+        finally:                         # an error in between must not leave the engine armed with this step's Adam arguments
+            eng.fused_opt, eng.fused_done = None, set()
+        if self.train_metrics:
+            L.call("szn_confusion_hist_k", target.numel(), C, L.ptr(target), L.ptr(pred), None, L.ptr(self.hist), st)
+        return self.loss.reshape(()), pred
+
     # ---- FCN8s head chain (forward and backward by hand: no autograd objects on the step path) ----------------------------
     def _skip_images(self):
         """padded [CP][Ci] images of score_pool3 / score_pool4 (rows >= E stay zero) + their dgrad transposes, from the flat
@@ -759,9 +844,7 @@ class TrainStep(object):
 
     def _step8(self, ctx, target, B, H, W):
         m, eng = self.model, self.eng
-        st = L.stream_ptr()
-        CP, E, K = m.head_width, self.E, self.K
-        dt = eng.dtype
+        CP = m.head_width
         self._skip_images()
         pool3, pool4 = ctx.pools[2][1], ctx.pools[3][1]
         s3, s4 = self.skip["score_pool3"], self.skip["score_pool4"]
@@ -779,6 +862,22 @@ class TrainStep(object):
         pred = torch.empty(B, H, W, dtype=torch.int64, device=self.dev)
         stats = torch.empty(B, 2, device=self.dev)
         dfuse3 = torch.zeros(B, n3, m3, CP, device=self.dev, dtype=torch.float32)
+        if self.ce:
+            self._ce_head(8, fuse3, target, H, W, CROP_UP8, stats, pred, dfuse3)
+        else:
+            self._head8_embed(fuse3, target, H, W, stats, pred, dfuse3)
+        self.stats = stats
+        if self.dynamic:
+            dfuse3 = dfuse3 * self.scale_state[0]
+        elif self._loss_scale0 != 1.0:
+            dfuse3 = dfuse3 * self._loss_scale0
+        return self._step8_backward(ctx, target, pred, fuse4, pool3, pool4, s3, s4, dfuse3)
+
+    def _head8_embed(self, fuse3, target, H, W, stats, pred, dfuse3):
+        """the cosine head over the 8x8 cells of the 1/8 fused map: loss, prediction, d(fuse3)"""
+        st = L.stream_ptr()
+        E, K = self.E, self.K
+        B, n3, m3, CP = fuse3.shape
         nbytes = L.load().szn_fused_head_workspace_bytes(B, n3, m3, E, K)
         if self._ws is None or self._ws.numel() < nbytes:
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
@@ -794,11 +893,12 @@ class TrainStep(object):
             L.call("szn_fused_head_grouped_prepared", 8, B, n3, m3, E, CP, 0, H, W, CROP_UP8, K, L.ptr(fuse3), L.ptr(self.emb),
                    L.ptr(target), self._unseen_cs, 2, None, L.ptr(self.loss), L.ptr(stats), L.ptr(pred), L.SZN_F32, L.ptr(dfuse3),
                    L.ptr(self._ws), st)
-        self.stats = stats
-        if self.dynamic:
-            dfuse3 = dfuse3 * self.scale_state[0]
-        elif self._loss_scale0 != 1.0:
-            dfuse3 = dfuse3 * self._loss_scale0
+
+    def _step8_backward(self, ctx, target, pred, fuse4, pool3, pool4, s3, s4, dfuse3):
+        m, eng = self.model, self.eng
+        st = L.stream_ptr()
+        CP, E, K = m.head_width, self.E, self.K
+        dt = eng.dtype
         # backward of the head chain; the skip gradients join the backbone chain at the pool3 / pool4 outputs
         skips = {}
         dmap = dfuse3

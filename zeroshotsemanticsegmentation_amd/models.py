@@ -1418,6 +1418,38 @@ class FCN32s(nn.Module):
                    L.ptr(tgt), L.ptr(loss), L.ptr(stats), L.ptr(pred), L.SZN_F32, None, L.ptr(ws), L.stream_ptr())
         return (loss.reshape(()) if loss is not None else None), pred
 
+    def _ce_predict(self, stride, fmap, crop, H, W, target, weight):
+        """szn_fused_ce_head forward-only (or pred-only without target) on the NHWC map `fmap` -> (loss 0-dim or None, pred)"""
+        C = self.n_class
+        if C > L.MAX_CLASSES:
+            raise L.SznError("softmax_predict: the fused head holds at most %d classes, got %d" % (L.MAX_CLASSES, C))
+        fmap = fmap.contiguous()
+        B, h, w, ld = fmap.shape
+        dev = fmap.device
+        pred = torch.empty(B, H, W, dtype=torch.int64, device=dev)
+        ws = torch.empty(L.load().szn_fused_ce_head_workspace_bytes(stride, B, h, w, C), dtype=torch.uint8, device=dev)
+        loss = tgt = wt = None
+        if target is not None:
+            tgt = target.to(device=dev, dtype=torch.int64).contiguous()
+            loss = torch.empty(1, device=dev)
+            if weight is not None:
+                wt = torch.as_tensor(weight).to(dev, torch.float32).contiguous()
+                if wt.numel() != C:
+                    raise L.SznError("softmax_predict: weight has %d entries for %d classes" % (wt.numel(), C))
+        L.call("szn_fused_ce_head", stride, B, h, w, C, ld, 0, H, W, crop, L.ptr(fmap), L.ptr(tgt), L.ptr(wt), 0, L.ptr(loss), None,
+               L.ptr(pred), L.SZN_F32, None, L.ptr(ws), L.stream_ptr())
+        return (loss.reshape(()) if loss is not None else None), pred
+
+    def softmax_predict(self, x, target=None, weight=None):
+        """forward pass + channel-argmax prediction (+ the summed cross entropy, utils.cross_entropy2d(size_average=False) with
+        optional class weights, when `target` is given) WITHOUT the (B,C,H,W) score: szn_fused_ce_head evaluates upscore + crop
+        (models.py:146-147), the loss (utils.py:19-48) and score.max(1)[1] (trainer_fcn.py:117) per 32x32 cell of the 1/32 map.
+        -> (loss 0-dim tensor or None, pred (B,H,W) int64 device tensor).  The prediction and every per-pixel loss term are
+        bit-identical to forward() + utils; the loss differs by summation order only.  Used by Trainer.validate (train.py -c 1)."""
+        with torch.no_grad():
+            ctx = self._engine.forward(x.detach(), train=False, keep=False)
+            return self._ce_predict(32, ctx.coarse, CROP, ctx.H, ctx.W, target, weight)
+
     def _seenmask_group(self, ctx):
         """the seen-mask prediction (1 = seen) of the x32 seen-mask head on the 1/32 map (channels [n_class, n_class + 2)): a
         pred-only szn_seenmask_head_k call (no target, no loss) -> (B,H,W) int64, the group map of szn_fused_head_grouped mode 1"""
@@ -1741,6 +1773,13 @@ class FCN8s(FCN32s):
             tgt = None if target is None else target.to(device=x.device, dtype=torch.int64).contiguous()
             loss = _FusedHead8.apply(self, fuse3, emb, tgt, x.shape[2], x.shape[3], False)
             return (loss if target is not None else None), self._last_pred
+
+    def softmax_predict(self, x, target=None, weight=None):
+        """inference-time softmax head over the 8x8 cells of the 1/8 fused map (szn_fused_ce_head, stride 8) -> (loss 0-dim tensor
+        or None, pred (B,H,W) int64); see FCN32s.softmax_predict"""
+        with torch.no_grad():
+            _, fuse3 = self._fuse(x.detach(), False, None)
+            return self._ce_predict(8, fuse3, CROP_UP8, x.shape[2], x.shape[3], target, weight)
 
     def szn_predict(self, x, embeddings, unseen, target=None, group='seenmask'):
         """the full SZN network's class assignment on the skip head -> (loss 0-dim tensor or None, pred (B,H,W) int64); see

@@ -180,11 +180,12 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     cfg = update_cfg_with_args(configurations[args.config], args)
     validate_cfg(cfg)
-    if args.precision == 'fp16' and cfg['mode'] == 'train' and cfg['fcn_epochs'] > 0 and \
-            (cfg['fcn_loss'] != 'cos' or not cfg['embed_dim']):
+    fused_cfg = (cfg['fcn_loss'] == 'cos' and cfg['embed_dim']) or (cfg['fcn_loss'] == 'cross_entropy' and not cfg['embed_dim'])
+    if args.precision == 'fp16' and cfg['mode'] == 'train' and cfg['fcn_epochs'] > 0 and not fused_cfg:
         # loss scaling lives in the fused steps only (engine.TrainStep / SeenmaskStep); see trainer_fcn.Trainer.train_epoch
-        raise Exception("--precision fp16 needs the fused training step: embedding configuration with fcn_loss 'cos' "
-                        "(got loss %r, embed_dim %r); use bf16 or fp32" % (cfg['fcn_loss'], cfg['embed_dim']))
+        raise Exception("--precision fp16 needs the fused training step: embedding configuration with fcn_loss 'cos' or the "
+                        "softmax configuration (fcn_loss 'cross_entropy', no embedding) (got loss %r, embed_dim %r); use bf16 "
+                        "or fp32" % (cfg['fcn_loss'], cfg['embed_dim']))
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", str(args.gpu)))

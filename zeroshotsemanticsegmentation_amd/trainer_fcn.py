@@ -2,8 +2,8 @@
 
 Same constructor / method surface and return contracts as /root/reference/trainer_fcn.py (Trainer.__init__ :21-81,
 forward :83-120, forward_szn :123-147, train_epoch :149-180, validate :182-292, train :294-306), on top of the
-HIP path: with an embedding loss 'cos' the hot loop runs engine.TrainStep (fused head, flat-buffer optimizer,
-RCCL gradient all-reduce); other losses compose the same kernels through autograd.  Logging (CSV, optional
+HIP path: with an embedding loss 'cos' or the softmax cross entropy (train.py -c 1) the hot loop runs engine.TrainStep
+(fused head, flat-buffer optimizer, RCCL gradient all-reduce); other losses compose the same kernels through autograd.  Logging (CSV, optional
 tensorboard writer, checkpoints with the reference's dict keys) is host-side and kept format-compatible;
 JPEG tile visualisations (third-party `fcn` package in the reference) are out of scope and skipped.
 """
@@ -159,11 +159,19 @@ class Trainer(object):
         return fcn_score, loss, lbl_pred, target.detach().cpu()
 
     # ---- training --------------------------------------------------------------------------------------------
+    def _cos_cfg(self):
+        return bool(self.pixel_embeddings) and self.loss_func == "cos"
+
+    def _ce_cfg(self):
+        """the softmax configuration (train.py -c 1): cross entropy over the model's own n_class channels, at most 256 classes"""
+        return (not self.pixel_embeddings and self.loss_func == "cross_entropy" and self.n_class <= 256
+                and self.model.n_class == self.n_class)
+
     def _fast_step(self):
         """engine.TrainStep when the configuration allows it: embedding cosine loss (forced_unseen: the step's prediction is the
-        forced-unseen one, trainer_fcn.py:110-112) and an optimizer with exactly the reference's two parameter groups
+        forced-unseen one, trainer_fcn.py:110-112) or the softmax cross entropy (_ce_cfg), and an optimizer with exactly the reference's two parameter groups
         (train.py:126-133: all Conv2d weights | all Conv2d biases).  Hyper-parameters are read per group from the optimizer object; any other wiring keeps the autograd path."""
-        if self._step is not None or not (self._fused_step and self.pixel_embeddings and self.loss_func == "cos"):
+        if self._step is not None or not (self._fused_step and (self._cos_cfg() or self._ce_cfg())):
             return self._step
         from .optim import FusedAdam, FusedSGD
         from .models import opt_layers
@@ -185,10 +193,14 @@ class Trainer(object):
             kw = dict(optimizer="sgd", momentum=gw.get('momentum', 0), weight_decay=gw.get('weight_decay', 0.0))
         else:
             return None
-        self._step = _engine.TrainStep(self.model, self.embeddings, lr=gw['lr'], bias_lr=gb['lr'],
+        if self._ce_cfg():
+            # the softmax FCN (train.py -c 1): fused cross-entropy head, summed loss (self._loss), channel-argmax prediction
+            kw.update(loss="cross_entropy", size_average=False)
+        else:
+            kw.update(embeddings=self.embeddings, forced_unseen=self.unseen if self.forced_unseen else None)
+        self._step = _engine.TrainStep(self.model, lr=gw['lr'], bias_lr=gb['lr'],
                                        bias_weight_decay=gb.get('weight_decay', 0.0), precision=self.precision,
-                                       fused_head=True, keep_grads=os.environ.get("SZN_KEEP_GRADS", "0") == "1",
-                                       forced_unseen=self.unseen if self.forced_unseen else None, **kw)
+                                       fused_head=True, keep_grads=os.environ.get("SZN_KEEP_GRADS", "0") == "1", **kw)
         # keep_grads=False (default; SZN_KEEP_GRADS=1 restores the reference's "`.grad` valid until zero_grad()"): the loop
         # calls zero_grad() next (train.py:170-175) and nothing reads the weight gradients in between, so the layers whose Adam
         # step rides in their weight-gradient kernel do not store theirs -- those `.grad`s are None, not stale
@@ -270,6 +282,10 @@ class Trainer(object):
             # picks the class subset per pixel inside the fused head -- neither (n,E,h,w) nor (n,2,h,w) score in HBM
             loss, pred = self.model.szn_predict(data, self.embeddings, self.unseen, target,
                                                 group='seenmask' if szn else 'target')
+            return None, loss, pred, target
+        if self._ce_cfg() and self._fused_step and not szn and not self.verbose_val:
+            # softmax inference: summed cross entropy + channel argmax straight from the coarse map (no (n,C,h,w) score in HBM)
+            loss, pred = self.model.softmax_predict(data, target)
             return None, loss, pred, target
         if szn:
             score, seen_mask_score = self.model(data, mode='both')
