@@ -15,9 +15,9 @@ import torch
 import torch.distributed as dist
 
 from . import _lib as L
-from . import synth
+from . import heads, synth
 from . import models as _models
-from .models import CROP, CROP_POOL3, CROP_POOL4, CROP_UP8, opt_layers
+from .models import CROP_POOL3, CROP_POOL4, opt_layers, up2_nhwc, up2_nhwc_bwd
 
 
 def init_process_group(backend="nccl", device=None, **kw):
@@ -255,8 +255,7 @@ class SeenmaskStep(object):
                  process_group=None):
         """n_class / unseen: the binary target of a pixel is "its label is one of the n_class classes and not in `unseen`"
         (trainer_seenmask.py:53-56); n_class = 0: step() is handed {0,1} targets already (other values are ignored)"""
-        if n_class > L.MAX_CLASSES:
-            raise L.SznError("SeenmaskStep: at most %d classes (szn_class_set), got %d" % (L.MAX_CLASSES, n_class))
+        self.seen = heads.seen_set("SeenmaskStep", int(n_class), unseen)
         self.model, self.eng = model, model._engine
         if precision is not None:
             model.set_precision(precision)
@@ -264,7 +263,6 @@ class SeenmaskStep(object):
         if self.dev.type != "cuda":
             raise L.SznError("SeenmaskStep needs the model on the GPU")
         self.n_class = int(n_class)
-        self.seen = L.class_set(k for k in range(self.n_class) if k not in set(unseen))
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
@@ -296,7 +294,8 @@ class SeenmaskStep(object):
         self.loss = torch.zeros(1, device=self.dev)
         self.stats = torch.zeros(2, device=self.dev)
         self.conf = torch.zeros(4, dtype=torch.int64, device=self.dev)     # [target][prediction] counts since the last reset
-        self._ws = self._ws2 = None
+        self.head_ws = heads.Workspace(self.dev)
+        self._ws2 = None
 
     def _head_images(self):
         """(rows E, E+1 of the fused head's weight image in the compute dtype, the same slice of its bias vector)"""
@@ -311,22 +310,17 @@ class SeenmaskStep(object):
         B, _, H, W = x.shape
         st = L.stream_ptr()
         ctx = eng.forward(x, train=m.training, masks=dropout_masks, keep=False)
-        E, CP, F = m.n_class, m.head_width, self.F
-        lib = L.load()
-        nb = lib.szn_seenmask_head_workspace_bytes(B, ctx.h, ctx.w, H, W, CROP)
-        if self._ws is None or self._ws.numel() < nb:
-            self._ws = torch.empty(nb, dtype=torch.uint8, device=self.dev)
+        E, F = m.n_class, self.F
         M = B * ctx.h * ctx.w
-        nb2 = lib.szn_seenmask_score_wgrad_workspace_bytes(M, F)
+        nb2 = L.load().szn_seenmask_score_wgrad_workspace_bytes(M, F)
         if self._ws2 is None or self._ws2.numel() < nb2 + M * 8:
             self._ws2 = torch.empty(nb2 + M * 8, dtype=torch.uint8, device=self.dev)
         dsc = self._ws2[nb2:nb2 + M * 8].view(torch.float32)
         pred = torch.empty(B, H, W, dtype=torch.int64, device=self.dev)
         (ow, nw), (ou, nu), (ob, nbias) = self.seg["score_w"], self.seg["up_w"], self.seg["score_b"]
         g = self.flat_g
-        L.call("szn_seenmask_head_k", B, ctx.h, ctx.w, CP, E, H, W, CROP, L.ptr(ctx.coarse), L.ptr(self.flat_p[ou:ou + nu]),
-               L.ptr(target), self.n_class, self.seen, L.ptr(self.loss), L.ptr(self.stats), L.ptr(self.conf), L.ptr(pred),
-               L.ptr(dsc), L.ptr(g[ou:ou + nu]), L.ptr(self._ws), st)
+        heads.seenmask(ctx.coarse, E, self.flat_p[ou:ou + nu], pred, target, self.n_class, self.seen, self.loss, self.stats, self.conf,
+                       dsc, g[ou:ou + nu], ws=self.head_ws, stream=st)
         feat = ctx.relu7
         L.call("szn_seenmask_score_wgrad", L.dtype_code(feat.dtype), M, F, F, L.ptr(feat), L.ptr(dsc), L.ptr(g[ow:ow + nw]),
                L.ptr(g[ob:ob + nbias]), L.ptr(self._ws2), st)
@@ -414,7 +408,7 @@ class TrainStep(object):
         self.dev = model.conv1_1.weight.device
         if self.dev.type != "cuda":
             raise L.SznError("TrainStep needs the model on the GPU")
-        self._ws_prep = None             # what the head of the fused head's workspace was prepared for (szn_fused_head_prepare)
+        self.head_ws = heads.Workspace(self.dev)        # the fused head's scratch and prepared embedding tables, kept across steps
         if self.ce:
             self.emb = None
             self.K = self.E = model.n_class
@@ -427,10 +421,8 @@ class TrainStep(object):
                     raise L.SznError("TrainStep: class_weight has %d entries for %d classes" % (self.class_weight.numel(), self.K))
             self.size_average = bool(size_average)
         else:
-            self.emb = torch.as_tensor(embeddings).to(self.dev, torch.float32).contiguous()
+            self.emb = heads.embeddings(embeddings, model.n_class, self.dev, fused=fused_head)
             self.K, self.E = self.emb.shape
-            if self.E != model.n_class:
-                raise L.SznError("embedding dimension %d != model n_class %d" % (self.E, model.n_class))
         self.opt, self.lr, self.momentum, self.wd = optimizer, lr, momentum, weight_decay
         # the reference wiring (train.py:126-133): biases at 2 x lr without weight decay; Adam has no weight decay at all
         self.betas, self.eps = betas, eps
@@ -452,6 +444,7 @@ class TrainStep(object):
         if self.forced_unseen is not None and any(not 0 <= k < self.K for k in self.forced_unseen):
             raise L.SznError("TrainStep: forced_unseen names a class outside [0, %d)" % self.K)
         self._unseen_cs = L.class_set(self.forced_unseen) if self.forced_unseen is not None else None
+        self._group = 0 if self.forced_unseen is None else 2          # heads.cosine group mode: plain / forced unseen
         # static loss scaling for the fp16 path: gradients below 6e-8 vanish in IEEE half, so d(loss)/d(coarse) is multiplied
         # by loss_scale in fp32 before it enters the 16-bit backward pass and the optimizer kernel divides it out again
         # (grad_scale).  The .grad views then hold loss_scale x gradient.  bf16 / fp32 need none.
@@ -469,6 +462,7 @@ class TrainStep(object):
         self.scale_cfg = (float(scale_growth), float(scale_backoff), int(scale_growth_interval), 2.0 ** -8 if self.ce else 1.0,
                           2.0 ** 32)
         self.scale_state = None
+        self._scaled = self.dynamic or self._loss_scale0 != 1.0
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
         if self.ce and self.size_average and self.world > 1:
@@ -489,7 +483,10 @@ class TrainStep(object):
         self.hist = torch.zeros(3, self.K, self.K, dtype=torch.int64, device=self.dev)
         self.loss = torch.zeros(1, device=self.dev)
         self.stats = None
-        self._ws = None
+        # fused stride-32 head: d(loss)/d(coarse), reused across steps of one shape and dtype (_dcoarse_buffer)
+        self._dcoarse = self._dcoarse_key = None
+        # the head layers' report to the gradient buckets, last-to-first: the flat order ends (..., score_pool3, score_pool4, score_fr)
+        self._head_layers = ("score_fr", "score_pool4", "score_pool3") if self.is8 else ("score_fr",)
         # Adam for fc6 / fc7 (89 % of the weights) applied in the epilogue of their weight-gradient kernels (szn_conv2d_wgrad_adam):
         # only where a gradient is final when its kernel ends -- one rank (no exchange), no dynamic loss scale -- and on the 16-bit
         # paths (the kernel with that epilogue is a 16-bit MFMA kernel).  SZN_FUSED_ADAM=0 / fused_adam=False: the separate pass.
@@ -524,19 +521,16 @@ class TrainStep(object):
         self.invalidate_head_prep()
 
     def invalidate_head_prep(self):
-        self._emb_serial = getattr(self, "_emb_serial", 0) + 1
-        self._ws_prep = None
+        self.head_ws.invalidate()
 
     @property
     def loss_scale(self):
         """the factor the .grad views currently carry (dynamic scaling: read back from the device -- a host sync; tests only)"""
         return float(self.scale_state[0].item()) if self.dynamic else self._loss_scale0
 
-    def _scale(self, t):
-        """t (fp32 d loss / d head input) x loss scale, as the compute dtype"""
-        if self.dynamic:
-            return (t.float() * self.scale_state[0]).to(self.eng.dtype)
-        return (t.float() * self._loss_scale0).to(self.eng.dtype)
+    def _scale(self, t, dtype):
+        """t (fp32 d loss / d head input) x loss scale in fp32, as `dtype`"""
+        return (t.float() * (self.scale_state[0] if self.dynamic else self._loss_scale0)).to(dtype)
 
     @property
     def applied_steps(self):
@@ -690,135 +684,100 @@ class TrainStep(object):
         return self._own_stream
 
     def _step(self, x, target):
+        """forward -> the head map (the 1/32 map, or FCN8s' 1/8 fused map) -> head (fused, or the materialised referee) -> loss
+        scale -> backward -> exchange -> optimizer -> confusion histogram"""
         m, eng = self.model, self.eng
         B, _, H, W = x.shape
         st = L.stream_ptr()
         eng.keep_prepool = bool(self.keep_ctx)          # tests that read the forward state need the un-pooled tensors too
         ctx = eng.forward(x, train=m.training)
         self.last_ctx = ctx if self.keep_ctx else None
+        pred = torch.empty(B, H, W, dtype=torch.int64, device=self.dev)
+        stats = torch.empty(B, 2, device=self.dev)
+        skips = None
         if self.is8:
-            return self._step8(ctx, target, B, H, W)
+            fuse4, fuse3 = self._chain8(ctx)
+            dmap = torch.zeros(B, fuse3.shape[1], fuse3.shape[2], m.head_width, device=self.dev, dtype=torch.float32)
+            self._head(8, fuse3, target, H, W, stats, pred, dmap, st)
+            if self._scaled:                            # d(fuse3) is scaled in fp32; the chain's backward converts
+                dmap = self._scale(dmap, torch.float32)
+            dcoarse, skips = self._chain8_backward(ctx, fuse4, dmap)
+        else:
+            if self.fused_head:
+                dcoarse = self._dcoarse_buffer(ctx)
+                self._head(32, ctx.coarse, target, H, W, stats, pred, dcoarse, st)
+            else:
+                dcoarse = self._referee(ctx, target, stats, pred, st)
+            if self._scaled:
+                dcoarse = self._scale(dcoarse, eng.dtype)
+        self.stats = stats
+        done = self._layer_done_hook(B * H * W)
+        self._fused_begin()
+        try:
+            self.buckets.begin_step()
+            # rows [0,E) of the fused head gradient ARE score_fr's slot of the flat gradient (seenmask_score is frozen in phase 1):
+            # nothing to copy, the first bucket can go as soon as the head wgrad has been queued
+            eng.backward(ctx, dcoarse, self.grads, backbone=True, layer_done=done,
+                         head_first=lambda: [done(n) for n in self._head_layers], skips=skips)
+            # FCN8s: the skip layers' bias gradients live in the flat bias buffer the engine zeroes first: re-apply them
+            for n, s in self.skip.items():
+                bo, bc = self.boff[n]
+                self.flat_gb[bo:bo + bc].copy_(s["gb"][:self.E])
+            self.buckets.finish()
+            self._optimizer_step()
+        finally:                         # an error in between must not leave the engine armed with this step's Adam arguments
+            eng.fused_opt, eng.fused_done = None, set()
+        if self.train_metrics:
+            L.call("szn_confusion_hist_k", target.numel(), self.K, L.ptr(target), L.ptr(pred), None, L.ptr(self.hist), st)
+        return self.loss.reshape(()), pred
+
+    # ---- the head: fused (heads.py) or materialised --------------------------------------------------------------------------
+    def _head(self, stride, fmap, target, H, W, stats, pred, dmap, st):
+        """the fused head on the NHWC map `fmap`: loss, stats, pred, d(fmap) into the zero-padded `dmap`"""
         if self.ce:
-            return self._step_ce(ctx, target, B, H, W)
-        CP, E, K = m.head_width, self.E, self.K
-        code = L.dtype_code(eng.dtype)
-        pred = torch.empty(B, H, W, dtype=torch.int64, device=self.dev)
-        stats = torch.empty(B, 2, device=self.dev)
-        scaled = self.dynamic or self._loss_scale0 != 1.0
-        # d(loss)/d(coarse): the fused head writes channels [0, E) and the padding channels stay zero, so the buffer of the previous
-        # step is reused without a fill (everything that read it was queued on this stream -- or joined -- before this step)
-        key = (B, ctx.h, ctx.w, CP, torch.float32 if scaled else eng.dtype)
-        if self.fused_head and getattr(self, "_dcoarse_key", None) == key:
-            dcoarse = self._dcoarse
+            heads.ce(stride, fmap, self.K, H, W, pred, target, self.class_weight, self.size_average, self.loss, stats, dmap,
+                     ws=self.head_ws, stream=st)
         else:
-            dcoarse = torch.zeros(B, ctx.h, ctx.w, CP, device=self.dev, dtype=key[4])
-            self._dcoarse, self._dcoarse_key = (dcoarse, key) if self.fused_head else (None, None)
-        code = L.dtype_code(dcoarse.dtype)
-        if self.fused_head:
-            nbytes = L.load().szn_fused_head_workspace_bytes(B, ctx.h, ctx.w, E, K)
-            if self._ws is None or self._ws.numel() < nbytes:
-                self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
-            # the embeddings are constants of a run: their transpose + norms (fh_prep_kernel: 23 us of dependent loads) are written to the head of
-            # the workspace once -- again whenever the workspace or the embedding tensor (an in-place edit bumps _version) changes
-            prep = (self._ws.data_ptr(), self.emb.data_ptr(), self.emb._version, self._emb_serial, E, K)
-            if self._ws_prep != prep:
-                L.call("szn_fused_head_prepare", E, K, L.ptr(self.emb), L.ptr(self._ws), st)
-                self._ws_prep = prep
-            if self.forced_unseen is None:
-                L.call("szn_fused_head_prepared", 32, B, ctx.h, ctx.w, E, CP, 0, H, W, CROP, K, L.ptr(ctx.coarse), L.ptr(self.emb),
-                       L.ptr(target), L.ptr(self.loss), L.ptr(stats), L.ptr(pred), code, L.ptr(dcoarse), L.ptr(self._ws), st)
-            else:
-                L.call("szn_fused_head_grouped_prepared", 32, B, ctx.h, ctx.w, E, CP, 0, H, W, CROP, K, L.ptr(ctx.coarse),
-                       L.ptr(self.emb), L.ptr(target), self._unseen_cs, 2, None, L.ptr(self.loss), L.ptr(stats), L.ptr(pred), code,
-                       L.ptr(dcoarse), L.ptr(self._ws), st)
-        else:
-            f = eng.upscore(ctx)
-            ws = torch.empty(L.load().szn_loss_workspace_bytes(B, H, W), dtype=torch.uint8, device=self.dev)
-            fwd = "szn_cosine_loss_fwd" if self.loss_kind == "cos" else "szn_mse_loss_fwd"
-            bwd = "szn_cosine_loss_bwd" if self.loss_kind == "cos" else "szn_mse_loss_bwd"
-            L.call(fwd, B, E, H, W, K, L.ptr(f), L.ptr(target), L.ptr(self.emb), None, L.ptr(self.loss), L.ptr(stats),
+            heads.cosine(stride, fmap, self.emb, H, W, pred, target, self.loss, stats, dmap, self._group, self._unseen_cs,
+                         ws=self.head_ws, stream=st)
+
+    def _dcoarse_buffer(self, ctx):
+        """d(loss)/d(coarse) of the fused head: it writes channels [0, E) and the padding channels stay zero, so the buffer of the
+        previous step is reused without a fill (everything that read it was queued on this stream -- or joined -- before this step)"""
+        key = (ctx.B, ctx.h, ctx.w, self.model.head_width, torch.float32 if self._scaled else self.eng.dtype)
+        if self._dcoarse_key != key:
+            self._dcoarse, self._dcoarse_key = torch.zeros(key[:4], device=self.dev, dtype=key[4]), key
+        return self._dcoarse
+
+    def _referee(self, ctx, target, stats, pred, st):
+        """fused_head=False (stride 32): the materialised head as the in-step referee -- upscore -> loss forward and prediction ->
+        loss backward -> head_backward; cosine / mse with szn_embed_argmax_k, cross entropy with szn_ce2d_*.  -> fp32 d(coarse)"""
+        eng = self.eng
+        B, H, W, K = ctx.B, ctx.H, ctx.W, self.K
+        f = eng.upscore(ctx)
+        ws = torch.empty(L.load().szn_loss_workspace_bytes(B, H, W), dtype=torch.uint8, device=self.dev)
+        df = torch.empty_like(f)
+        if self.ce:                      # szn_ce2d_fwd writes the channel-argmax prediction too
+            cw, sa = L.ptr(self.class_weight), int(self.size_average)
+            L.call("szn_ce2d_fwd", B, K, H, W, L.ptr(f), L.ptr(target), cw, sa, L.ptr(self.loss), L.ptr(stats), L.ptr(pred),
                    L.ptr(ws), st)
-            if self.forced_unseen is None:
-                L.call("szn_embed_argmax_k", B, E, H, W, K, L.ptr(f), L.ptr(self.emb), 0, None, None, None, L.ptr(pred), st)
-            else:
-                L.call("szn_embed_argmax_k", B, E, H, W, K, L.ptr(f), L.ptr(self.emb), 1, self._unseen_cs, None, L.ptr(target),
-                       L.ptr(pred), st)
-            df = torch.empty_like(f)
-            L.call(bwd, B, E, H, W, K, L.ptr(f), L.ptr(target), L.ptr(self.emb), None, L.ptr(stats), None, L.ptr(df), st)
-            dc32, _ = eng.head_backward(ctx, df=df)
-            dcoarse = dc32
-        if scaled:
-            dcoarse = self._scale(dcoarse)
-        self.stats = stats
-        self._fused_begin()
-        try:
-            self.buckets.begin_step()
-            self._backward(ctx, dcoarse, self._layer_done_hook(B * H * W))
-            self.buckets.finish()
-            self._optimizer_step()
-        finally:                         # an error in between must not leave the engine armed with this step's Adam arguments
-            eng.fused_opt, eng.fused_done = None, set()
-        if self.train_metrics:
-            L.call("szn_confusion_hist_k", target.numel(), K, L.ptr(target), L.ptr(pred), None, L.ptr(self.hist), st)
-        return self.loss.reshape(()), pred
-
-    def _ce_head(self, stride, fmap, target, H, W, crop, stats, pred, dcoarse):
-        """szn_fused_ce_head on the NHWC map `fmap` (the C class channels first): loss, stats, pred, d(fmap)"""
-        B, h, w, ld = fmap.shape
-        nbytes = L.load().szn_fused_ce_head_workspace_bytes(stride, B, h, w, self.K)
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
-        L.call("szn_fused_ce_head", stride, B, h, w, self.K, ld, 0, H, W, crop, L.ptr(fmap), L.ptr(target), L.ptr(self.class_weight),
-               int(self.size_average), L.ptr(self.loss), L.ptr(stats), L.ptr(pred), L.dtype_code(dcoarse.dtype), L.ptr(dcoarse),
-               L.ptr(self._ws), L.stream_ptr())
-
-    def _step_ce(self, ctx, target, B, H, W):
-        """FCN32s + softmax cross entropy: the fused CE head (fused_head=False: the materialised chain, the in-step referee) ->
-        backward -> exchange -> optimizer, as _step"""
-        m, eng = self.model, self.eng
-        st = L.stream_ptr()
-        CP, C = m.head_width, self.K
-        pred = torch.empty(B, H, W, dtype=torch.int64, device=self.dev)
-        stats = torch.empty(B, 2, device=self.dev)
-        scaled = self.dynamic or self._loss_scale0 != 1.0
-        if self.fused_head:
-            # channels [0, C) are written by every call and the padding channels stay zero: the buffer is reused (see _step)
-            key = (B, ctx.h, ctx.w, CP, torch.float32 if scaled else eng.dtype)
-            if getattr(self, "_dcoarse_key", None) == key:
-                dcoarse = self._dcoarse
-            else:
-                dcoarse = torch.zeros(B, ctx.h, ctx.w, CP, device=self.dev, dtype=key[4])
-                self._dcoarse, self._dcoarse_key = dcoarse, key
-            self._ce_head(32, ctx.coarse, target, H, W, CROP, stats, pred, dcoarse)
+            L.call("szn_ce2d_bwd", B, K, H, W, L.ptr(f), L.ptr(target), cw, sa, L.ptr(stats), None, L.ptr(df), st)
         else:
-            f = eng.upscore(ctx)
-            ws = torch.empty(L.load().szn_loss_workspace_bytes(B, H, W), dtype=torch.uint8, device=self.dev)
-            sa = int(self.size_average)
-            L.call("szn_ce2d_fwd", B, C, H, W, L.ptr(f), L.ptr(target), L.ptr(self.class_weight), sa, L.ptr(self.loss), L.ptr(stats),
-                   L.ptr(pred), L.ptr(ws), st)
-            df = torch.empty_like(f)
-            L.call("szn_ce2d_bwd", B, C, H, W, L.ptr(f), L.ptr(target), L.ptr(self.class_weight), sa, L.ptr(stats), None, L.ptr(df), st)
-            dcoarse, _ = eng.head_backward(ctx, df=df)
-        if scaled:
-            dcoarse = self._scale(dcoarse)
-        self.stats = stats
-        self._fused_begin()
-        try:
-            self.buckets.begin_step()
-            self._backward(ctx, dcoarse, self._layer_done_hook(B * H * W))
-            self.buckets.finish()
-            self._optimizer_step()
-        finally:                         # an error in between must not leave the engine armed with this step's Adam arguments
-            eng.fused_opt, eng.fused_done = None, set()
-        if self.train_metrics:
-            L.call("szn_confusion_hist_k", target.numel(), C, L.ptr(target), L.ptr(pred), None, L.ptr(self.hist), st)
-        return self.loss.reshape(()), pred
+            E, emb = self.E, L.ptr(self.emb)
+            kind = "cosine" if self.loss_kind == "cos" else "mse"
+            L.call("szn_%s_loss_fwd" % kind, B, E, H, W, K, L.ptr(f), L.ptr(target), emb, None, L.ptr(self.loss), L.ptr(stats),
+                   L.ptr(ws), st)
+            grouped = self.forced_unseen is not None          # forced unseen: mode 1, the group from the target
+            L.call("szn_embed_argmax_k", B, E, H, W, K, L.ptr(f), emb, int(grouped), self._unseen_cs, None,
+                   L.ptr(target) if grouped else None, L.ptr(pred), st)
+            L.call("szn_%s_loss_bwd" % kind, B, E, H, W, K, L.ptr(f), L.ptr(target), emb, None, L.ptr(stats), None, L.ptr(df), st)
+        return eng.head_backward(ctx, df=df)[0]
 
     # ---- FCN8s head chain (forward and backward by hand: no autograd objects on the step path) ----------------------------
     def _skip_images(self):
         """padded [CP][Ci] images of score_pool3 / score_pool4 (rows >= E stay zero) + their dgrad transposes, from the flat
         masters the optimizer kernel just wrote"""
-        m, E = self.model, self.E
+        E = self.E
         code = L.dtype_code(self.eng.dtype)
         for n, s in self.skip.items():
             o, cnt = self.woff[n]
@@ -829,81 +788,32 @@ class TrainStep(object):
             s["b"][:E].copy_(self.flat_b[bo:bo + bc])
             L.call("szn_pack_weight_dgrad", code, s["w"].shape[0], 1, 1, ci, L.ptr(s["w"]), L.ptr(s["wT"]), L.stream_ptr())
 
-    @staticmethod
-    def _up2(x, fwd=True, shape=None):
-        x = x.contiguous()
-        if fwd:
-            B, h, w, ld = x.shape
-            out = torch.empty(B, 2 * h + 2, 2 * w + 2, ld, device=x.device, dtype=torch.float32)
-            L.call("szn_bilinear_up2_nhwc_fwd", B, h, w, ld, ld, L.ptr(x), L.ptr(out), L.stream_ptr())
-            return out
-        B, h, w, ld = shape
-        out = torch.empty(B, h, w, ld, device=x.device, dtype=torch.float32)
-        L.call("szn_bilinear_up2_nhwc_bwd", B, h, w, ld, ld, L.ptr(x), L.ptr(out), L.stream_ptr())
-        return out
-
-    def _step8(self, ctx, target, B, H, W):
-        m, eng = self.model, self.eng
-        CP = m.head_width
+    def _chain8(self, ctx):
+        """upscore2(score_fr) + score_pool4c -> upscore_pool4 -> + score_pool3c: -> (fuse4, fuse3), fp32 NHWC at 1/16 and 1/8"""
+        eng = self.eng
         self._skip_images()
-        pool3, pool4 = ctx.pools[2][1], ctx.pools[3][1]
         s3, s4 = self.skip["score_pool3"], self.skip["score_pool4"]
-        # forward: upscore2(score_fr) + score_pool4c -> upscore_pool4 -> + score_pool3c
-        up2 = self._up2(ctx.coarse)
-        sp4 = eng._conv(pool4, None, 0, relu=False, out_f32=True, w=s4["w"], b=s4["b"])
+        up2 = up2_nhwc(ctx.coarse)
+        sp4 = eng._conv(ctx.pools[3][1], None, 0, relu=False, out_f32=True, w=s4["w"], b=s4["b"])
         n4, m4 = up2.shape[1:3]
         fuse4 = up2 + sp4[:, CROP_POOL4:CROP_POOL4 + n4, CROP_POOL4:CROP_POOL4 + m4]
-        up4 = self._up2(fuse4)
-        sp3 = eng._conv(pool3, None, 0, relu=False, out_f32=True, w=s3["w"], b=s3["b"])
+        up4 = up2_nhwc(fuse4)
+        sp3 = eng._conv(ctx.pools[2][1], None, 0, relu=False, out_f32=True, w=s3["w"], b=s3["b"])
         n3, m3 = up4.shape[1:3]
         fuse3 = (up4 + sp3[:, CROP_POOL3:CROP_POOL3 + n3, CROP_POOL3:CROP_POOL3 + m3]).contiguous()
         self.last_fuse3 = fuse3 if self.keep_ctx else None      # tests: the 1/8 map the head read
-        # fused head over 8x8 cells: loss, prediction, d(fuse3)
-        pred = torch.empty(B, H, W, dtype=torch.int64, device=self.dev)
-        stats = torch.empty(B, 2, device=self.dev)
-        dfuse3 = torch.zeros(B, n3, m3, CP, device=self.dev, dtype=torch.float32)
-        if self.ce:
-            self._ce_head(8, fuse3, target, H, W, CROP_UP8, stats, pred, dfuse3)
-        else:
-            self._head8_embed(fuse3, target, H, W, stats, pred, dfuse3)
-        self.stats = stats
-        if self.dynamic:
-            dfuse3 = dfuse3 * self.scale_state[0]
-        elif self._loss_scale0 != 1.0:
-            dfuse3 = dfuse3 * self._loss_scale0
-        return self._step8_backward(ctx, target, pred, fuse4, pool3, pool4, s3, s4, dfuse3)
+        return fuse4, fuse3
 
-    def _head8_embed(self, fuse3, target, H, W, stats, pred, dfuse3):
-        """the cosine head over the 8x8 cells of the 1/8 fused map: loss, prediction, d(fuse3)"""
-        st = L.stream_ptr()
-        E, K = self.E, self.K
-        B, n3, m3, CP = fuse3.shape
-        nbytes = L.load().szn_fused_head_workspace_bytes(B, n3, m3, E, K)
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
-        # (the embedding tables at the head of the workspace are prepared once per workspace / embedding tensor, as in _step)
-        prep = (self._ws.data_ptr(), self.emb.data_ptr(), self.emb._version, self._emb_serial, E, K)
-        if self._ws_prep != prep:
-            L.call("szn_fused_head_prepare", E, K, L.ptr(self.emb), L.ptr(self._ws), st)
-            self._ws_prep = prep
-        if self.forced_unseen is None:
-            L.call("szn_fused_head_prepared", 8, B, n3, m3, E, CP, 0, H, W, CROP_UP8, K, L.ptr(fuse3), L.ptr(self.emb), L.ptr(target),
-                   L.ptr(self.loss), L.ptr(stats), L.ptr(pred), L.SZN_F32, L.ptr(dfuse3), L.ptr(self._ws), st)
-        else:
-            L.call("szn_fused_head_grouped_prepared", 8, B, n3, m3, E, CP, 0, H, W, CROP_UP8, K, L.ptr(fuse3), L.ptr(self.emb),
-                   L.ptr(target), self._unseen_cs, 2, None, L.ptr(self.loss), L.ptr(stats), L.ptr(pred), L.SZN_F32, L.ptr(dfuse3),
-                   L.ptr(self._ws), st)
-
-    def _step8_backward(self, ctx, target, pred, fuse4, pool3, pool4, s3, s4, dfuse3):
-        m, eng = self.model, self.eng
-        st = L.stream_ptr()
-        CP, E, K = m.head_width, self.E, self.K
+    def _chain8_backward(self, ctx, fuse4, dfuse3):
+        """backward of the skip chain from the (scaled) fp32 d(fuse3): the skip layers' weight / bias gradients, their input
+        gradients (which join the backbone chain at the pool3 / pool4 outputs) -> (d(coarse) in the compute dtype, skips)"""
+        eng, CP, E = self.eng, self.model.head_width, self.E
         dt = eng.dtype
-        # backward of the head chain; the skip gradients join the backbone chain at the pool3 / pool4 outputs
         skips = {}
         dmap = dfuse3
-        for (name, s, pool, crop, pi, up_shape) in (("score_pool3", s3, pool3, CROP_POOL3, 2, fuse4.shape),
-                                                    ("score_pool4", s4, pool4, CROP_POOL4, 3, ctx.coarse.shape)):
+        for (name, pool, crop, pi, up_shape) in (("score_pool3", ctx.pools[2][1], CROP_POOL3, 2, fuse4.shape),
+                                                 ("score_pool4", ctx.pools[3][1], CROP_POOL4, 3, ctx.coarse.shape)):
+            s = self.skip[name]
             Bp, hp, wp, ci = pool.shape
             nn, mm = dmap.shape[1:3]
             dsp = torch.zeros(Bp, hp, wp, CP, device=self.dev, dtype=dt)
@@ -914,37 +824,9 @@ class TrainStep(object):
             eng._wgrad(pool, dsp, s["gw"], s["gb"], ci, CP, 1, 0,
                        after=lambda o=o, cnt=cnt, s=s, ci=ci: self.flat_gw[o:o + cnt].view(E, 1, 1, ci).copy_(s["gw"][:E]))
             skips[pi] = eng._dgrad(dsp, None, pool.shape, 0, wT=s["wT"])
-            dmap = self._up2(dmap, fwd=False, shape=tuple(up_shape))
+            dmap = up2_nhwc_bwd(dmap, tuple(up_shape))
         eng._join_wgrad()
-        dcoarse = dmap if dmap.dtype == dt else dmap.to(dt)
-        done = self.buckets.layer_done
-
-        def head_first():                 # flat order is (..., score_pool3, score_pool4, score_fr): report them last-to-first
-            done("score_fr"); done("score_pool4"); done("score_pool3")
-        # the bias gradients of the skip layers live in the flat bias buffer the engine zeroes first: re-apply them after
-        saved = [(self.boff[n], self.skip[n]["gb"]) for n in ("score_pool3", "score_pool4")]
-        self._fused_begin()
-        try:
-            self.buckets.begin_step()
-            eng.backward(ctx, dcoarse, self.grads, backbone=True, layer_done=done, head_first=head_first, skips=skips)
-            for (bo, bc), gb in saved:
-                self.flat_gb[bo:bo + bc].copy_(gb[:E])
-            self.buckets.finish()
-            self._optimizer_step()
-        finally:
-            eng.fused_opt, eng.fused_done = None, set()
-        if self.train_metrics:
-            L.call("szn_confusion_hist_k", target.numel(), K, L.ptr(target), L.ptr(pred), None, L.ptr(self.hist), st)
-        return self.loss.reshape(()), pred
-
-    def _backward(self, ctx, dcoarse, layer_done):
-        eng, m = self.eng, self.model
-        eng.backward(ctx, dcoarse, self.grads, backbone=True, layer_done=layer_done, head_first=self._head_copy(layer_done))
-
-    def _head_copy(self, layer_done):
-        # rows [0,E) of the fused head gradient ARE score_fr's slot of the flat gradient (seenmask_score is frozen in
-        # phase 1): nothing to copy, the first bucket can go as soon as the head wgrad has been queued
-        return lambda: layer_done("score_fr")
+        return (dmap if dmap.dtype == dt else dmap.to(dt)), skips
 
     # ---- optimizer --------------------------------------------------------------------------------------
     def _layer_done_hook(self, pixels):

@@ -1,0 +1,159 @@
+"""heads.py -- the host side of the fused heads: every call into szn_fused_head_grouped[_prepared], szn_fused_ce_head and
+szn_seenmask_head_k goes through here (models.FCN32s / FCN8s predict methods, engine.TrainStep, engine.SeenmaskStep).
+
+  cosine    loss, stats, nearest-embedding prediction and d(map) from an NHWC map: stride 32 on the 1/32 map, stride 8 on FCN8s'
+            1/8 fused map (fp32).  Group mode 0 = plain (szn_fused_head_grouped launches exactly what szn_fused_head_strided
+            launches, bit for bit), 1 = seen / unseen group from the seen-mask prediction, 2 = forced unseen (group from the target).
+  ce        the softmax cross-entropy head, stride 32 or 8.
+  seenmask  the x32 seen-mask head on the 1/32 map: training, predict and pred-only (group map) calls.
+
+The crop belongs to the stride (32: CROP, reference models.py:147; 8: CROP_UP8, FCN8s' upscore8).  A call without a `Workspace`
+allocates its scratch and builds the embedding tables itself (the predict methods); TrainStep keeps one `Workspace` across steps.
+"""
+import torch
+
+from . import _lib as L
+
+CROP = 19            # models.py:147
+CROP_UP8 = 31        # FCN8s upscore8 (public pytorch-fcn definition)
+_CROP = {32: CROP, 8: CROP_UP8}
+
+
+class Workspace(object):
+    """a head workspace kept across calls, plus the embedding tables szn_fused_head_prepare wrote to its head.  The tables are
+    rebuilt for a new buffer, a new embedding tensor or an in-place torch write into it (_version), and after invalidate() (a raw
+    kernel writing into the tensor does not bump _version, and a new tensor may reuse the old one's address)."""
+
+    def __init__(self, device):
+        self.device, self.buf, self.prep = device, None, None
+
+    def get(self, nbytes):
+        if self.buf is None or self.buf.numel() < nbytes:
+            self.buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return self.buf
+
+    def invalidate(self):
+        self.prep = None
+
+    def prepared(self, nbytes, emb, K, E, stream):
+        ws = self.get(nbytes)
+        key = (ws.data_ptr(), emb.data_ptr(), emb._version, K, E)
+        if self.prep != key:
+            L.call("szn_fused_head_prepare", E, K, L.ptr(emb), L.ptr(ws), stream)
+            self.prep = key
+        return ws
+
+
+def _scratch(nbytes, device):
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def embeddings(emb, n_class, device, fused=True):
+    """the K x E class-embedding matrix as a contiguous fp32 tensor on `device`; E must be the model's n_class and, for the fused
+    head (fused=True), K <= MAX_CLASSES"""
+    emb = torch.as_tensor(emb).to(device, torch.float32).contiguous()
+    K, E = emb.shape
+    if E != n_class:
+        raise L.SznError("embedding dimension %d != model n_class %d" % (E, n_class))
+    if fused and K > L.MAX_CLASSES:
+        raise L.SznError("the fused head holds at most %d classes, got %d: use forward() + utils" % (L.MAX_CLASSES, K))
+    return emb
+
+
+def seen_set(who, n_class, unseen):
+    """the class set `label is one of the n_class classes and not in unseen` (trainer_seenmask.py:53-56)"""
+    if n_class > L.MAX_CLASSES:
+        raise L.SznError("%s: at most %d classes (szn_class_set), got %d" % (who, L.MAX_CLASSES, n_class))
+    return L.class_set(k for k in range(n_class) if k not in set(unseen))
+
+
+def _outputs(B, H, W, device, target):
+    """(pred, target as int64, loss) of a forward-only call: target and loss are None without a target"""
+    pred = torch.empty(B, H, W, dtype=torch.int64, device=device)
+    if target is None:
+        return pred, None, None
+    return pred, target.to(device=device, dtype=torch.int64).contiguous(), torch.empty(1, device=device)
+
+
+# ---- cosine head ----------------------------------------------------------------------------------------------------------
+def cosine(stride, fmap, emb, H, W, pred, target=None, loss=None, stats=None, dmap=None, mode=0, classes=None, gmap=None,
+           ws=None, stream=None):
+    """szn_fused_head_grouped on the contiguous NHWC map `fmap` (the E embedding channels first).  target / loss / stats go
+    together; dmap (zero-padded, [E, ld) stays untouched) receives d loss / d fmap in its dtype.  classes = the unseen class set
+    (L.class_set) of modes 1 / 2, gmap the group map of mode 1.  ws: a Workspace (its embedding tables are reused) or None."""
+    B, h, w, ld = fmap.shape
+    K, E = emb.shape
+    st = L.stream_ptr() if stream is None else stream
+    nbytes = L.load().szn_fused_head_workspace_bytes(B, h, w, E, K)
+    if ws is None:
+        fn, buf = "szn_fused_head_grouped", _scratch(nbytes, fmap.device)
+    else:
+        fn, buf = "szn_fused_head_grouped_prepared", ws.prepared(nbytes, emb, K, E, st)
+    code = L.dtype_code(dmap.dtype) if dmap is not None else L.SZN_F32
+    L.call(fn, stride, B, h, w, E, ld, 0, H, W, _CROP[stride], K, L.ptr(fmap), L.ptr(emb), L.ptr(target), classes, mode,
+           L.ptr(gmap), L.ptr(loss), L.ptr(stats), L.ptr(pred), code, L.ptr(dmap), L.ptr(buf), st)
+
+
+def cosine_predict(stride, fmap, emb, H, W, target=None, mode=0, unseen=None, gmap=None):
+    """forward-only cosine head -> (loss 0-dim tensor or None, pred (B,H,W) int64)"""
+    B = fmap.shape[0]
+    pred, tgt, loss = _outputs(B, H, W, fmap.device, target)
+    stats = None if loss is None else torch.empty(B, 2, device=fmap.device)
+    cosine(stride, fmap, emb, H, W, pred, tgt, loss, stats, mode=mode, classes=L.class_set(unseen), gmap=gmap)
+    return (loss.reshape(()) if loss is not None else None), pred
+
+
+# ---- softmax cross-entropy head -------------------------------------------------------------------------------------------
+def ce(stride, fmap, C, H, W, pred, target=None, weight=None, size_average=False, loss=None, stats=None, dmap=None, ws=None,
+       stream=None):
+    """szn_fused_ce_head on the contiguous NHWC map `fmap` (the C class channels first); arguments as in cosine()"""
+    B, h, w, ld = fmap.shape
+    nbytes = L.load().szn_fused_ce_head_workspace_bytes(stride, B, h, w, C)
+    buf = _scratch(nbytes, fmap.device) if ws is None else ws.get(nbytes)
+    code = L.dtype_code(dmap.dtype) if dmap is not None else L.SZN_F32
+    L.call("szn_fused_ce_head", stride, B, h, w, C, ld, 0, H, W, _CROP[stride], L.ptr(fmap), L.ptr(target), L.ptr(weight),
+           int(size_average), L.ptr(loss), L.ptr(stats), L.ptr(pred), code, L.ptr(dmap), L.ptr(buf),
+           L.stream_ptr() if stream is None else stream)
+
+
+def ce_predict(stride, fmap, C, H, W, target=None, weight=None):
+    """forward-only softmax head (summed cross entropy, optional class weights) -> (loss 0-dim tensor or None, pred)"""
+    if C > L.MAX_CLASSES:
+        raise L.SznError("softmax_predict: the fused head holds at most %d classes, got %d" % (L.MAX_CLASSES, C))
+    pred, tgt, loss = _outputs(fmap.shape[0], H, W, fmap.device, target)
+    wt = None
+    if target is not None and weight is not None:
+        wt = torch.as_tensor(weight).to(fmap.device, torch.float32).contiguous()
+        if wt.numel() != C:
+            raise L.SznError("softmax_predict: weight has %d entries for %d classes" % (wt.numel(), C))
+    ce(stride, fmap, C, H, W, pred, tgt, wt, loss=loss)
+    return (loss.reshape(()) if loss is not None else None), pred
+
+
+# ---- x32 seen-mask head ---------------------------------------------------------------------------------------------------
+def seenmask(coarse, E, up_w, pred, target=None, n_class=0, seen=None, loss=None, stats=None, conf=None, dscore=None, dup_w=None,
+             ws=None, stream=None):
+    """szn_seenmask_head_k on the 1/32 map `coarse` (B,h,w,CP) (the two seen-mask channels at [E, E + 2)) with the learned deconv
+    weight `up_w`: pred (B,H,W) always; loss / stats / confusion counts / d(score) / d(up_w) where given.  ws: a Workspace or None."""
+    B, h, w, CP = coarse.shape
+    _, H, W = pred.shape
+    nbytes = L.load().szn_seenmask_head_workspace_bytes(B, h, w, H, W, CROP)
+    buf = _scratch(nbytes, coarse.device) if ws is None else ws.get(nbytes)
+    L.call("szn_seenmask_head_k", B, h, w, CP, E, H, W, CROP, L.ptr(coarse), L.ptr(up_w), L.ptr(target), n_class, seen, L.ptr(loss),
+           L.ptr(stats), L.ptr(conf), L.ptr(pred), L.ptr(dscore), L.ptr(dup_w), L.ptr(buf),
+           L.stream_ptr() if stream is None else stream)
+
+
+def seenmask_predict(coarse, E, up_w, H, W, target, n_class, seen):
+    """forward-only seen-mask head (2-class cross entropy, size_average; seen = seen_set(...)) -> (loss 0-dim tensor, pred (B,H,W)
+    int64, 1 = seen)"""
+    pred, tgt, loss = _outputs(coarse.shape[0], H, W, coarse.device, target)
+    seenmask(coarse, E, up_w, pred, tgt, n_class, seen, loss)
+    return loss.reshape(()), pred
+
+
+def seenmask_group(coarse, E, up_w, H, W):
+    """the seen-mask prediction alone (no target, no loss) -> (B,H,W) int64, the group map of cosine() mode 1"""
+    gmap = torch.empty(coarse.shape[0], H, W, dtype=torch.int64, device=coarse.device)
+    seenmask(coarse, E, up_w, gmap)
+    return gmap

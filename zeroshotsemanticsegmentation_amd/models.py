@@ -26,9 +26,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from . import synth
-
-CROP = 19            # models.py:147
+from . import heads, synth
+from .heads import CROP, CROP_UP8
 PAD1 = 100           # models.py:43
 
 
@@ -1393,75 +1392,35 @@ class FCN32s(nn.Module):
             return s
         return f, s
 
+    # ---- inference on the fused heads (heads.py): no (B,E,H,W), (B,C,H,W) or (B,2,H,W) score -----------------------------
+    def _head_map(self, x):
+        """inference forward -> (the backbone pass's ctx, stride, the contiguous NHWC map the class head reads): the 1/32 map"""
+        ctx = self._engine.forward(x.detach() if isinstance(x, torch.Tensor) else x, train=False, keep=False)
+        return ctx, 32, ctx.coarse
+
     def embed_predict(self, x, embeddings, target=None):
         """forward pass + nearest-class-embedding prediction (+ cosine loss when `target` is given) WITHOUT materialising the
         (B,E,H,W) score: the fused-from-coarse head (szn_fused_head) evaluates upscore + crop (models.py:146-147), cosine_loss
-        (utils.py:75-102) and infer_lbl (utils.py:159-185) per 32x32 cell of the 1/32 map.  -> (loss 0-dim tensor or None,
-        pred (B,H,W) int64 device tensor).  Same numbers as `forward` + utils up to rounding order (class assignment differs only
-        on pixels whose top-2 cosine margin is < 1e-5).  Used by Trainer.validate."""
-        eng = self._engine
+        (utils.py:75-102) and infer_lbl (utils.py:159-185) per 32x32 cell of the 1/32 map (FCN8s: per 8x8 cell of the 1/8
+        fused map).  -> (loss 0-dim tensor or None, pred (B,H,W) int64 device tensor), the prediction also in self._last_pred.
+        Same numbers as `forward` + utils up to rounding order (class assignment differs only on pixels whose top-2 cosine margin
+        is < 1e-5).  Used by Trainer.validate."""
         with torch.no_grad():
-            ctx = eng.forward(x.detach() if isinstance(x, torch.Tensor) else x, train=False, keep=False)
-            emb = torch.as_tensor(embeddings).to(ctx.coarse.device, torch.float32).contiguous()
-            K, E = emb.shape
-            if E != self.n_class:
-                raise L.SznError("embedding dimension %d != model n_class %d" % (E, self.n_class))
-            B, H, W = ctx.B, ctx.H, ctx.W
-            dev = ctx.coarse.device
-            pred = torch.empty(B, H, W, dtype=torch.int64, device=dev)
-            ws = torch.empty(L.load().szn_fused_head_workspace_bytes(B, ctx.h, ctx.w, E, K), dtype=torch.uint8, device=dev)
-            loss = stats = tgt = None
-            if target is not None:
-                tgt = target.to(device=dev, dtype=torch.int64).contiguous()
-                loss, stats = torch.empty(1, device=dev), torch.empty(B, 2, device=dev)
-            L.call("szn_fused_head", B, ctx.h, ctx.w, E, self.head_width, 0, H, W, CROP, K, L.ptr(ctx.coarse), L.ptr(emb),
-                   L.ptr(tgt), L.ptr(loss), L.ptr(stats), L.ptr(pred), L.SZN_F32, None, L.ptr(ws), L.stream_ptr())
-        return (loss.reshape(()) if loss is not None else None), pred
-
-    def _ce_predict(self, stride, fmap, crop, H, W, target, weight):
-        """szn_fused_ce_head forward-only (or pred-only without target) on the NHWC map `fmap` -> (loss 0-dim or None, pred)"""
-        C = self.n_class
-        if C > L.MAX_CLASSES:
-            raise L.SznError("softmax_predict: the fused head holds at most %d classes, got %d" % (L.MAX_CLASSES, C))
-        fmap = fmap.contiguous()
-        B, h, w, ld = fmap.shape
-        dev = fmap.device
-        pred = torch.empty(B, H, W, dtype=torch.int64, device=dev)
-        ws = torch.empty(L.load().szn_fused_ce_head_workspace_bytes(stride, B, h, w, C), dtype=torch.uint8, device=dev)
-        loss = tgt = wt = None
-        if target is not None:
-            tgt = target.to(device=dev, dtype=torch.int64).contiguous()
-            loss = torch.empty(1, device=dev)
-            if weight is not None:
-                wt = torch.as_tensor(weight).to(dev, torch.float32).contiguous()
-                if wt.numel() != C:
-                    raise L.SznError("softmax_predict: weight has %d entries for %d classes" % (wt.numel(), C))
-        L.call("szn_fused_ce_head", stride, B, h, w, C, ld, 0, H, W, crop, L.ptr(fmap), L.ptr(tgt), L.ptr(wt), 0, L.ptr(loss), None,
-               L.ptr(pred), L.SZN_F32, None, L.ptr(ws), L.stream_ptr())
-        return (loss.reshape(()) if loss is not None else None), pred
+            ctx, stride, fmap = self._head_map(x)
+            emb = heads.embeddings(embeddings, self.n_class, fmap.device)
+            loss, self._last_pred = heads.cosine_predict(stride, fmap, emb, ctx.H, ctx.W, target)
+        return loss, self._last_pred
 
     def softmax_predict(self, x, target=None, weight=None):
         """forward pass + channel-argmax prediction (+ the summed cross entropy, utils.cross_entropy2d(size_average=False) with
         optional class weights, when `target` is given) WITHOUT the (B,C,H,W) score: szn_fused_ce_head evaluates upscore + crop
-        (models.py:146-147), the loss (utils.py:19-48) and score.max(1)[1] (trainer_fcn.py:117) per 32x32 cell of the 1/32 map.
-        -> (loss 0-dim tensor or None, pred (B,H,W) int64 device tensor).  The prediction and every per-pixel loss term are
-        bit-identical to forward() + utils; the loss differs by summation order only.  Used by Trainer.validate (train.py -c 1)."""
+        (models.py:146-147), the loss (utils.py:19-48) and score.max(1)[1] (trainer_fcn.py:117) per 32x32 cell of the 1/32 map
+        (FCN8s: per 8x8 cell of the 1/8 fused map).  -> (loss 0-dim tensor or None, pred (B,H,W) int64 device tensor).  The
+        prediction and every per-pixel loss term are bit-identical to forward() + utils; the loss differs by summation order
+        only.  Used by Trainer.validate (train.py -c 1)."""
         with torch.no_grad():
-            ctx = self._engine.forward(x.detach(), train=False, keep=False)
-            return self._ce_predict(32, ctx.coarse, CROP, ctx.H, ctx.W, target, weight)
-
-    def _seenmask_group(self, ctx):
-        """the seen-mask prediction (1 = seen) of the x32 seen-mask head on the 1/32 map (channels [n_class, n_class + 2)): a
-        pred-only szn_seenmask_head_k call (no target, no loss) -> (B,H,W) int64, the group map of szn_fused_head_grouped mode 1"""
-        dev = ctx.coarse.device
-        gmap = torch.empty(ctx.B, ctx.H, ctx.W, dtype=torch.int64, device=dev)
-        ws = torch.empty(L.load().szn_seenmask_head_workspace_bytes(ctx.B, ctx.h, ctx.w, ctx.H, ctx.W, CROP), dtype=torch.uint8,
-                         device=dev)
-        L.call("szn_seenmask_head_k", ctx.B, ctx.h, ctx.w, self.head_width, self.n_class, ctx.H, ctx.W, CROP, L.ptr(ctx.coarse),
-               L.ptr(self._engine._images["up.w"]), None, 0, None, None, None, None, L.ptr(gmap), None, None, L.ptr(ws),
-               L.stream_ptr())
-        self._last_group = gmap
-        return gmap
+            ctx, stride, fmap = self._head_map(x)
+            return heads.ce_predict(stride, fmap, self.n_class, ctx.H, ctx.W, target, weight)
 
     @staticmethod
     def _szn_group(group, target):
@@ -1480,31 +1439,16 @@ class FCN32s(nn.Module):
         (mode 2), no seen-mask head.  -> (loss 0-dim tensor or None, pred (B,H,W) int64 device tensor); the seen-mask prediction
         is left in self._last_group (None for group='target').  Same numbers as forward(mode='both') + utils.infer_lbl_device(
         mode=1) up to rounding order (class assignment differs only on pixels whose top-2 cosine margin in the group is < 1e-5;
-        the seen-mask decision is bit-identical).  Used by Trainer.validate."""
+        the seen-mask decision is bit-identical).  FCN8s: the seen-mask head keeps its x32 geometry on the backbone's 1/32 map
+        (as forward(mode='both')), the grouped head runs over the 8x8 cells of the 1/8 fused map.  Used by Trainer.validate."""
         mode = self._szn_group(group, target)
-        eng = self._engine
         with torch.no_grad():
-            ctx = eng.forward(x.detach(), train=False, keep=False)
-            emb = torch.as_tensor(embeddings).to(ctx.coarse.device, torch.float32).contiguous()
-            K, E = emb.shape
-            if E != self.n_class:
-                raise L.SznError("embedding dimension %d != model n_class %d" % (E, self.n_class))
-            if K > L.MAX_CLASSES:
-                raise L.SznError("szn_predict: at most %d classes (szn_class_set), got %d" % (L.MAX_CLASSES, K))
-            B, H, W = ctx.B, ctx.H, ctx.W
-            dev = ctx.coarse.device
+            ctx, stride, fmap = self._head_map(x)
+            emb = heads.embeddings(embeddings, self.n_class, fmap.device)
             self._last_group = None
-            gmap = self._seenmask_group(ctx) if mode == 1 else None
-            pred = torch.empty(B, H, W, dtype=torch.int64, device=dev)
-            ws = torch.empty(L.load().szn_fused_head_workspace_bytes(B, ctx.h, ctx.w, E, K), dtype=torch.uint8, device=dev)
-            loss = stats = tgt = None
-            if target is not None:
-                tgt = target.to(device=dev, dtype=torch.int64).contiguous()
-                loss, stats = torch.empty(1, device=dev), torch.empty(B, 2, device=dev)
-            L.call("szn_fused_head_grouped", 32, B, ctx.h, ctx.w, E, self.head_width, 0, H, W, CROP, K, L.ptr(ctx.coarse),
-                   L.ptr(emb), L.ptr(tgt), L.class_set(unseen), mode, L.ptr(gmap), L.ptr(loss), L.ptr(stats), L.ptr(pred),
-                   L.SZN_F32, None, L.ptr(ws), L.stream_ptr())
-        return (loss.reshape(()) if loss is not None else None), pred
+            if mode == 1:
+                self._last_group = heads.seenmask_group(ctx.coarse, self.n_class, self._engine._images["up.w"], ctx.H, ctx.W)
+            return heads.cosine_predict(stride, fmap, emb, ctx.H, ctx.W, target, mode, unseen, self._last_group)
 
     def seenmask_predict(self, x, target, n_class, unseen):
         """forward pass + seen-mask loss and prediction WITHOUT the (B,2,H,W) score: szn_seenmask_head evaluates the learned
@@ -1513,22 +1457,11 @@ class FCN32s(nn.Module):
         int64 class labels.  -> (loss 0-dim tensor, pred (B,H,W) int64 device tensor).
         Same numbers as forward(mode='seenmask') + utils.cross_entropy2d / channel_argmax (bit-identical score arithmetic).
         Used by trainer_seenmask.Trainer.validate."""
-        if n_class > L.MAX_CLASSES:
-            raise L.SznError("seenmask_predict: at most %d classes (szn_class_set), got %d" % (L.MAX_CLASSES, n_class))
+        seen = heads.seen_set("seenmask_predict", n_class, unseen)
         eng = self._engine
         with torch.no_grad():
             ctx = eng.forward(x.detach(), train=False, keep=False)
-            dev = ctx.coarse.device
-            B, H, W = ctx.B, ctx.H, ctx.W
-            tgt = target.to(device=dev, dtype=torch.int64).contiguous()
-            seen = L.class_set(k for k in range(n_class) if k not in set(unseen))
-            pred = torch.empty(B, H, W, dtype=torch.int64, device=dev)
-            loss = torch.empty(1, device=dev)
-            ws = torch.empty(L.load().szn_seenmask_head_workspace_bytes(B, ctx.h, ctx.w, H, W, CROP), dtype=torch.uint8, device=dev)
-            L.call("szn_seenmask_head_k", B, ctx.h, ctx.w, self.head_width, self.n_class, H, W, CROP, L.ptr(ctx.coarse),
-                   L.ptr(eng._images["up.w"]), L.ptr(tgt), n_class, seen, L.ptr(loss), None, None, L.ptr(pred), None, None,
-                   L.ptr(ws), L.stream_ptr())
-        return loss.reshape(()), pred
+            return heads.seenmask_predict(ctx.coarse, self.n_class, eng._images["up.w"], ctx.H, ctx.W, target, n_class, seen)
 
     def copy_params_from_vgg16(self, vgg16):
         """reference models.py:162-193: zip vgg16.features with our conv list; fc6/fc7 from classifier[0], [3]"""
@@ -1558,7 +1491,7 @@ class FCN32s(nn.Module):
 # upscore8 ConvTranspose2d(E,E,16,stride 8), all transposed convolutions bias-free with the fixed bilinear kernel
 # (models.py:11-24,109-112 initialise them that way and train.py:324-327 never updates them), crops 5 / 9 / 31.  PARITY UNPINNED:
 # the checker the tests use is a torch-CPU restatement of that public definition (FCN8sTorch), not reference output.
-CROP_POOL4, CROP_POOL3, CROP_UP8 = 5, 9, 31
+CROP_POOL4, CROP_POOL3 = 5, 9             # (upscore8: heads.CROP_UP8 = 31)
 
 
 class _Backbone8(torch.autograd.Function):
@@ -1609,25 +1542,35 @@ class _SkipScore(torch.autograd.Function):
         return None, dx, dw[:E].permute(0, 3, 1, 2), db[:E]
 
 
+def up2_nhwc(x):
+    """upscore2 / upscore_pool4 (fixed bilinear x2) of an NHWC fp32 map (B,h,w,ld) -> (B,2h+2,2w+2,ld) fp32"""
+    x = x.contiguous()
+    B, h, w, ld = x.shape
+    out = torch.empty(B, 2 * h + 2, 2 * w + 2, ld, device=x.device, dtype=torch.float32)
+    L.call("szn_bilinear_up2_nhwc_fwd", B, h, w, ld, ld, L.ptr(x), L.ptr(out), L.stream_ptr())
+    return out
+
+
+def up2_nhwc_bwd(dout, shape):
+    """d(input) (B,h,w,ld) = shape, fp32, of up2_nhwc from the fp32 d(output)"""
+    dout = dout.contiguous()
+    B, h, w, ld = shape
+    din = torch.empty(B, h, w, ld, device=dout.device, dtype=torch.float32)
+    L.call("szn_bilinear_up2_nhwc_bwd", B, h, w, ld, ld, L.ptr(dout), L.ptr(din), L.stream_ptr())
+    return din
+
+
 class _Up2(torch.autograd.Function):
-    """upscore2 / upscore_pool4 (fixed bilinear x2) between NHWC fp32 maps"""
+    """up2_nhwc under autograd"""
 
     @staticmethod
     def forward(ctx, x):
-        x = x.contiguous()
-        B, h, w, ld = x.shape
-        ctx.shape = (B, h, w, ld)
-        out = torch.empty(B, 2 * h + 2, 2 * w + 2, ld, device=x.device, dtype=torch.float32)
-        L.call("szn_bilinear_up2_nhwc_fwd", B, h, w, ld, ld, L.ptr(x), L.ptr(out), L.stream_ptr())
-        return out
+        ctx.shape = tuple(x.shape)
+        return up2_nhwc(x)
 
     @staticmethod
     def backward(ctx, dout):
-        B, h, w, ld = ctx.shape
-        dout = dout.contiguous().float()
-        din = torch.empty(B, h, w, ld, device=dout.device, dtype=torch.float32)
-        L.call("szn_bilinear_up2_nhwc_bwd", B, h, w, ld, ld, L.ptr(dout), L.ptr(din), L.stream_ptr())
-        return din
+        return up2_nhwc_bwd(dout.float(), ctx.shape)
 
 
 class _Up8Crop(torch.autograd.Function):
@@ -1652,7 +1595,7 @@ class _Up8Crop(torch.autograd.Function):
 
 
 class _FusedHead8(torch.autograd.Function):
-    """upscore8 + crop + cosine loss + nearest-embedding prediction straight from the 1/8 fused map (szn_fused_head_strided,
+    """upscore8 + crop + cosine loss + nearest-embedding prediction straight from the 1/8 fused map (heads.cosine at stride 8,
     8x8 cells): the (B,E,H,W) score and its gradient never exist in HBM.  forward -> loss (0-dim); the prediction is left in
     model._last_pred; backward hands back d loss / d map, which the kernel produced in the same pass."""
 
@@ -1660,20 +1603,15 @@ class _FusedHead8(torch.autograd.Function):
     def forward(ctx, model, x, emb, target, H, W, want_grad):
         x = x.contiguous()
         B, h, w, ld = x.shape
-        K, E = emb.shape
         dev = x.device
         pred = torch.empty(B, H, W, dtype=torch.int64, device=dev)
-        ws = torch.empty(L.load().szn_fused_head_workspace_bytes(B, h, w, E, K), dtype=torch.uint8, device=dev)
-        loss = stats = dx = None
-        if target is not None:
-            loss, stats = torch.empty(1, device=dev), torch.empty(B, 2, device=dev)
-            if want_grad:
-                dx = torch.zeros(B, h, w, ld, device=dev, dtype=torch.float32)
-        L.call("szn_fused_head_strided", 8, B, h, w, E, ld, 0, H, W, CROP_UP8, K, L.ptr(x), L.ptr(emb), L.ptr(target), L.ptr(loss),
-               L.ptr(stats), L.ptr(pred), L.SZN_F32, L.ptr(dx), L.ptr(ws), L.stream_ptr())
+        loss = torch.empty(1, device=dev)
+        stats = torch.empty(B, 2, device=dev)
+        dx = torch.zeros(B, h, w, ld, device=dev, dtype=torch.float32) if want_grad else None
+        heads.cosine(8, x, emb, H, W, pred, target, loss, stats, dx)
         ctx.dx = dx
         model._last_pred = pred
-        return loss.reshape(()) if loss is not None else x.new_zeros(())
+        return loss.reshape(())
 
     @staticmethod
     def backward(ctx, g):
@@ -1747,66 +1685,25 @@ class FCN8s(FCN32s):
         f, s = self._run(x, mode, self.training, dropout_masks)
         return f if mode == 'fcn' else (s if mode == 'seenmask' else (f, s))
 
-    def _emb(self, embeddings, dev):
-        emb = torch.as_tensor(embeddings).to(dev, torch.float32).contiguous()
-        if emb.shape[1] != self.n_class:
-            raise L.SznError("embedding dimension %d != model n_class %d" % (emb.shape[1], self.n_class))
-        if emb.shape[0] > L.MAX_CLASSES:
-            raise L.SznError("the fused head holds at most %d classes, got %d: use forward() + utils" % (L.MAX_CLASSES, emb.shape[0]))
-        return emb
+    def _head_map(self, x):
+        """inference forward -> (the backbone pass's ctx, stride 8, the 1/8 fused map)"""
+        _, fuse3 = self._fuse(x.detach(), False, None)
+        return self._last_ctx, 8, fuse3.contiguous()
+
+    def softmax_predict(self, x, target=None, weight=None):
+        """inference-time softmax head over the 8x8 cells of the 1/8 fused map (szn_fused_ce_head, stride 8) -> (loss 0-dim tensor
+        or None, pred (B,H,W) int64); see FCN32s.softmax_predict"""
+        return super(FCN8s, self).softmax_predict(x, target, weight)
 
     def embed_loss(self, x, embeddings, target, dropout_masks=None):
         """training-time fused head: -> (cosine loss with autograd history, pred (B,H,W) int64).  Same numbers as
         utils.cosine_loss(self(x), target, embeddings) / utils.infer_lbl_device up to rounding order, without the
         (B,E,H,W) score or its gradient in HBM."""
-        emb = self._emb(embeddings, x.device)
+        emb = heads.embeddings(embeddings, self.n_class, x.device)
         _, fuse3 = self._fuse(x, self.training, dropout_masks)
         tgt = target.to(device=x.device, dtype=torch.int64).contiguous()
         loss = _FusedHead8.apply(self, fuse3, emb, tgt, x.shape[2], x.shape[3], torch.is_grad_enabled())
         return loss, self._last_pred
-
-    def embed_predict(self, x, embeddings, target=None):
-        """inference-time fused head -> (loss 0-dim tensor or None, pred (B,H,W) int64 device tensor); see FCN32s.embed_predict"""
-        with torch.no_grad():
-            emb = self._emb(embeddings, x.device)
-            _, fuse3 = self._fuse(x.detach(), False, None)
-            tgt = None if target is None else target.to(device=x.device, dtype=torch.int64).contiguous()
-            loss = _FusedHead8.apply(self, fuse3, emb, tgt, x.shape[2], x.shape[3], False)
-            return (loss if target is not None else None), self._last_pred
-
-    def softmax_predict(self, x, target=None, weight=None):
-        """inference-time softmax head over the 8x8 cells of the 1/8 fused map (szn_fused_ce_head, stride 8) -> (loss 0-dim tensor
-        or None, pred (B,H,W) int64); see FCN32s.softmax_predict"""
-        with torch.no_grad():
-            _, fuse3 = self._fuse(x.detach(), False, None)
-            return self._ce_predict(8, fuse3, CROP_UP8, x.shape[2], x.shape[3], target, weight)
-
-    def szn_predict(self, x, embeddings, unseen, target=None, group='seenmask'):
-        """the full SZN network's class assignment on the skip head -> (loss 0-dim tensor or None, pred (B,H,W) int64); see
-        FCN32s.szn_predict.  The seen-mask head keeps its x32 geometry on the backbone's 1/32 map (as forward(mode='both')); the
-        grouped head runs over the 8x8 cells of the 1/8 fused map (szn_fused_head_grouped, stride 8)."""
-        mode = self._szn_group(group, target)
-        with torch.no_grad():
-            emb = self._emb(embeddings, x.device)
-            _, fuse3 = self._fuse(x.detach(), False, None)
-            ctx = self._last_ctx
-            self._last_group = None
-            gmap = self._seenmask_group(ctx) if mode == 1 else None
-            fuse3 = fuse3.contiguous()
-            B, h, w, ld = fuse3.shape
-            K, E = emb.shape
-            H, W = x.shape[2], x.shape[3]
-            dev = fuse3.device
-            pred = torch.empty(B, H, W, dtype=torch.int64, device=dev)
-            ws = torch.empty(L.load().szn_fused_head_workspace_bytes(B, h, w, E, K), dtype=torch.uint8, device=dev)
-            loss = stats = tgt = None
-            if target is not None:
-                tgt = target.to(device=dev, dtype=torch.int64).contiguous()
-                loss, stats = torch.empty(1, device=dev), torch.empty(B, 2, device=dev)
-            L.call("szn_fused_head_grouped", 8, B, h, w, E, ld, 0, H, W, CROP_UP8, K, L.ptr(fuse3), L.ptr(emb), L.ptr(tgt),
-                   L.class_set(unseen), mode, L.ptr(gmap), L.ptr(loss), L.ptr(stats), L.ptr(pred), L.SZN_F32, None, L.ptr(ws),
-                   L.stream_ptr())
-        return (loss.reshape(()) if loss is not None else None), pred
 
 
 def VGG16(pretrained=False, data_dir='data'):
