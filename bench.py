@@ -2,6 +2,7 @@
 """bench.py -- train-step throughput of the SZN pixel-embedding path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--precision bf16|fp32] [--size 512] [--classes 59] [--dump-outputs DIR]
+                    [--full]
     (N > 1: `python bench.py --gpus N` re-executes itself under torch.distributed.run, one rank per GPU; the driver's own
      `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` form works as well)
 
@@ -17,6 +18,8 @@ Prints ONE JSON line: metric train_Mpixels_per_sec (whole job) plus
   roofline      the dominant kernel (conv_igemm_8ph: conv3_x / conv4_x forward + dgrad, fc6 forward): algorithmic FLOPs of
                 its launches / their HIP-event-measured duration INSIDE the timed region, against the dense MFMA peak;
                 `traffic` = HBM bytes per launch from the committed PMC passes (source file named; null if none matches)
+A plain run stops there: it sets up, warms up, times the steps, writes --dump-outputs and prints the line.  With --full the
+line also carries what takes steps, processes or host time of its own after the headline:
   kernels       per kernel family, MFMA-class and HBM-class, from 3 extra instrumented steps after the timed region
                 (HIP events around every C-ABI call): ms per step, algorithmic FLOPs or bytes, fraction of the peak
   projection    the three labelled MFMA numbers SURVEY 8-d asks for (true shape, step aggregate, nominal shape)
@@ -29,6 +32,7 @@ Prints ONE JSON line: metric train_Mpixels_per_sec (whole job) plus
   fp32, b1      measured in a child process after the headline (a crash there cannot lose the line): the same step at the
                 reference's arithmetic (fp32, B = 8, against the 157.3 TF fp32 MFMA peak) and at the reference's batch size
                 (B = 1, bf16 and fp32, eager and replayed from a captured hipGraph)
+  c1_fcn8s, c4_768  BASELINE configs[1] (FCN8s, K = 21) and configs[4] (768x768, fp16 + fp8 head), one child process each
   cpu_baseline  the same train step on this host's cores (rank 0, N = 1 only): torch-CPU restatement (what the reference
                 executes; primary) and the C + OpenMP oracle beside it; one 512x512 image each.
 """
@@ -47,7 +51,7 @@ PEAK_BF16, PEAK_F32, PEAK_HBM = 2500.0, 157.3, 8000.0       # TFLOP/s dense MFMA
 STEP_MFLOP_PER_PX = {512: 4.342, 768: 3.678}                # SURVEY 8-d, E = 300, phase-1 train step
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -65,9 +69,13 @@ def parse():
                          "per-tensor fused Adam) -- a secondary line, the default stays the reference's FCN32s")
     ap.add_argument("--phase", choices=["fcn", "seenmask"], default="fcn",
                     help="fcn = phase 1 (headline; phase 2 is reported as a sub-record); seenmask = phase 2 as the headline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the kernels / projection / phase2 / comm / fp32 / b1 / c1_fcn8s / c4_768 "
+                         "sub-records and the CPU baseline (off: the line carries the headline and its roofline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-kernel-events", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the kernels / projection / phase2 / fp32 / b1 sub-records")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the kernels / projection / phase2 / comm / fp32 / b1 / "
+                                                             "c1_fcn8s / c4_768 sub-records")
     ap.add_argument("--grad-comm", choices=["auto", "fp32", "bf16", "bf16-sharded", "off"], default="auto",
                     help="N > 1: wire format of the gradient exchange.  auto = bf16 written by the weight-gradient kernels themselves on "
                          "the 16-bit paths (271 MB per step instead of 542), fp32 on the fp32 path; bf16-sharded = reduce-scatter + "
@@ -77,7 +85,7 @@ def parse():
                          "updated parameters as DIR/<name>.npy (float32 / float64, rank 0) for output-to-output comparison of builds")
     ap.add_argument("--sub-record", choices=["fp32", "b1", "comm", "c1_fcn8s", "c4_768"], default=None,
                     help="(internal) measure one sub-record and print it as JSON; run by the main process as a child")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
     return args
@@ -955,11 +963,14 @@ def main():
                 out["roofline"]["step_gflop_executed"] = round(step_fl / 1e9, 1)
                 out["roofline"]["step_gflop_skipped_constant_border"] = round(skipped[0] / 1e9, 1)   # hints + the band removed from conv3_x
 
-    if world > 1 and args.phase == "fcn" and args.arch == "fcn32s" and not args.unfused_head and not args.no_extras:
-        if out is not None:
-            out["config"]["grad_wire"] = wire
-            if wire_note:
-                out["config"]["grad_wire_note"] = wire_note[:300]
+    if world > 1 and args.phase == "fcn" and args.arch == "fcn32s" and not args.unfused_head and out is not None:
+        out["config"]["grad_wire"] = wire
+        if wire_note:
+            out["config"]["grad_wire_note"] = wire_note[:300]
+
+    # ---- --full only: sub-records measured after the headline, on steps and processes of their own ----
+    extras = args.full and not args.no_extras
+    if world > 1 and args.phase == "fcn" and args.arch == "fcn32s" and not args.unfused_head and extras:
         L.call = orig_call
         for mod in (models, engine):
             mod.L.call = orig_call
@@ -973,7 +984,7 @@ def main():
             out["comm"] = rec
 
     # ---- instrumented pass: every C-ABI call of 3 more steps (same state, not part of `value`) ----
-    if not args.no_kernel_events and not args.no_extras and world == 1:
+    if not args.no_kernel_events and extras and world == 1:
         NI = 3
         mode[0] = "all"
         torch.cuda.synchronize()
@@ -1008,7 +1019,7 @@ def main():
                           "rows": rows}
         events = []
 
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and extras:
         if dtype != torch.float32:
             try:
                 out["projection"] = projection_report(L, torch, out.get("roofline", {}).get("step_mfma_frac"))
@@ -1074,7 +1085,7 @@ def main():
             if dtype == torch.bfloat16:
                 out["comm"] = run_sub_record("comm", args)
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(E, K, H, emb_np, args.arch)
             except Exception as ex:      # the baseline is a reported extra: never lose the measured line

@@ -24,7 +24,7 @@ def run(*extra):
 
 
 def test_bench_line_phase1_with_cpu_baseline():
-    d = run()
+    d = run("--full")
     assert KEYS <= set(d) and "cpu_baseline" in d
     assert d["metric"] == "train_Mpixels_per_sec" and d["unit"] == "Mpixels/s" and d["n_gpus"] == 1 and d["steps"] == 2
     assert d["higher_is_better"] is True and d["scaling"] == "weak" and d["vs_baseline"] is None and d["dtype"] == "bf16"
@@ -40,6 +40,16 @@ def test_bench_line_phase1_with_cpu_baseline():
     assert all(abs(x["frac"] - x["achieved"] / (r["peak"] if x["bound"] == "mfma" else 8000.0)) < 1e-3 for x in rows if "frac" in x)
     assert len(d["projection"]["true_shape"]) == 3 and d["projection"]["nominal_shape"]["M"] == 262144
     assert d["phase2"]["value"] > 0 and "configs[2]" in d["phase2"]["workload"]
+
+
+def test_bench_plain_line_is_the_headline_only():
+    """without --full the line carries the headline and its roofline (events inside the timed region), none of the sub-records
+    that take steps, processes or host time of their own"""
+    d = run()
+    assert KEYS <= set(d) and d["value"] > 0 and d["steps"] == 2 and d["warmup"] == 1 and d["dtype"] == "bf16"
+    assert abs(d["value"] - 96 * 96 * 1e-6 / (d["ms_per_step"] * 1e-3)) < 0.02 * d["value"]
+    assert d["roofline"]["bound"] == "mfma" and d["roofline"]["achieved"] > 0
+    assert not {"kernels", "projection", "phase2", "comm", "fp32", "b1", "c1_fcn8s", "c4_768", "cpu_baseline"} & set(d), sorted(d)
 
 
 def test_bench_line_phase2():
@@ -98,7 +108,7 @@ def test_bench_plain_gpus2_relaunches_itself_under_torchrun():
     env = dict(os.environ, SZN_TEST_ONE_GPU="1")
     env.pop("WORLD_SIZE", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "1",
-                          "--size", "96"], capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
+                          "--size", "96", "--full"], capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]

@@ -328,3 +328,11 @@ def test_gather_form_of_a_transposed_band_map():
         got = np.array([[d[ys, xs] if (yc and xc) else 0 for xs, xc in t1x] for ys, yc in t1y])
         assert np.array_equal(got, want)
         assert max(c for _, c in ty) > 1 and max(c for _, c in tx) > 1
+
+
+def test_bench_extras_only_with_full():
+    """bench.py: a plain run measures the headline alone; --full (off by default) adds the sub-records and the CPU baseline"""
+    import bench
+    plain, full = bench.parse(["--gpus", "1", "--steps", "5", "--warmup", "2"]), bench.parse(["--full"])
+    assert not plain.full and full.full
+    assert (plain.steps, plain.warmup, plain.no_extras, plain.no_cpu_baseline) == (5, 2, False, False)

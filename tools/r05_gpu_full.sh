@@ -8,10 +8,10 @@ timeout 2400 python -m pytest tests -m gpu -q -x > gpurun_out/full_${T}_tests.lo
 echo "tests rc $?" >> gpurun_out/full_${T}_tests.log
 tail -6 gpurun_out/full_${T}_tests.log
 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/full_${T}_smoke.log 2>&1; tail -2 gpurun_out/full_${T}_smoke.log
-timeout 1200 python bench.py --steps 20 --warmup 3 > gpurun_out/full_${T}_bench.json 2> gpurun_out/full_${T}_bench.err
-python - <<PY
-import json
-d=json.load(open("gpurun_out/full_${T}_bench.json"))
+BENCH_LINE=$(timeout 1200 python bench.py --full --steps 20 --warmup 3); echo "$BENCH_LINE"
+BENCH_LINE="$BENCH_LINE" python - <<PY
+import json, os
+d=json.loads([l for l in os.environ["BENCH_LINE"].splitlines() if l.startswith("{")][-1])
 r=d["roofline"]
 print("bench", d["value"], d["ms_per_step"], r["kernel"], r["frac"], r.get("step_mfma_frac"))
 print("phase2", d["phase2"].get("ms_per_step"), "fp32", d["fp32"].get("ms_per_step"), "b1", d["b1"].get("bf16",{}).get("ms_per_step"))
