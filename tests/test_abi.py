@@ -93,12 +93,12 @@ def test_every_knob_has_a_case():
             found |= set(re.findall(r'environ[^\n]*?"(SZN_[A-Z0-9_]+)"', open(os.path.join(pkg, fn)).read()))
     assert found == PY_KNOBS, (sorted(found - PY_KNOBS), sorted(PY_KNOBS - found))
     assert PY_KNOBS - ELSEWHERE <= covered, sorted(PY_KNOBS - ELSEWHERE - covered)
-    # and no C source reads the environment behind szn_knob's back (the ablation switches exist in `make ABLATE=1` builds only)
+    # and no C source reads the environment behind szn_knob's back
     src = os.path.join(pkg, "csrc")
     for fn in os.listdir(src):
         if fn.endswith((".hip", ".h")):
             for ln in open(os.path.join(src, fn)).read().splitlines():
                 if "getenv(" in ln:
-                    assert fn == "szn_elementwise.hip" and "getenv(name)" in ln or fn == "szn_common.h", (fn, ln.strip())
+                    assert fn == "szn_elementwise.hip" and "getenv(name)" in ln, (fn, ln.strip())
 
 

@@ -1,6 +1,5 @@
 #!/usr/bin/env python
-"""conv1_1 weight gradient at the bench shape (B = 8, 512 x 512, pad 100): ms per call, alone on the device
-(SZN_C11_WGRAD_GATHER=1: the round-2 form whose taps are gathered straight from memory)"""
+"""conv1_1 weight gradient at the bench shape (B = 8, 512 x 512, pad 100): ms per call, alone on the device"""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -59,7 +59,7 @@ __device__ __forceinline__ void tile_epilogue_single(const Args& a, f32x4_t (&ac
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int m = mb + 16 * j + r16;
-        if (m >= a.M || a.abl_ep) continue;
+        if (m >= a.M) continue;
         f32x4_t v = acc[j] + bv;
         v[0] = fmaxf(v[0], lo); v[1] = fmaxf(v[1], lo); v[2] = fmaxf(v[2], lo); v[3] = fmaxf(v[3], lo);
         if (a.out_f32) *(f32x4_t*)((float*)a.out + (long)m * a.ldo + n) = v;
@@ -434,8 +434,8 @@ int launch_8ph_v(const WideArgs& a, hipStream_t st) {
 
 template <typename T, int NF0, int NF1>
 int launch_8ph(const WideArgs& a, hipStream_t st) {
-    // SZN_8PH_MODE: 2 (default) = two phases of 32 MFMA per K tile; 0 = four phases of 16 (the template's form: 2-4 % slower per kernel,
-    // profiles/r04_ablations.txt section 8); 1 = four phases with the second LDS-DMA load issued among the MFMAs (6-8 % slower, section 6)
+    // mode 2: two phases of 32 MFMA per K tile.  Four phases of 16 (the template's form) measured 2-4 % slower per kernel
+    // (profiles/r04_ablations.txt section 8), four phases with the second LDS-DMA load issued among the MFMAs 6-8 % slower (section 6)
     return launch_8ph_v<T, NF0, NF1, 2>(a, st);
 }
 

@@ -77,10 +77,7 @@ struct Conv2Args {
     int B, Hi, Wi, Ci, Ho, Wo, Co, KH, KW, pad;
     int ldi, ldo, ldg, relu, out_f32;
     int M, HoWo, mtiles, ntiles, nsplit, chunks_per_split;
-    int nmajor;                // tile order: 1 = pixel tile fastest (weights larger than activations)
-    int stagger;               // 1: wave pairs take turns issuing a chunk's LDS-DMA loads (SZN_IGEMM_STAGGER=0: all at once)
     int direct_ep;             // 1: epilogue straight from the accumulator registers (szn_epilogue.h)
-    int abl_ep;                // always 0 here (the accounting switch of the wide kernels)
 };
 
 __device__ __forceinline__ int xcd_remap2(int bid, int nwg) {
@@ -90,9 +87,7 @@ __device__ __forceinline__ int xcd_remap2(int bid, int nwg) {
 
 constexpr unsigned kOOB = 0x80000000u;   // any offset >= num_records reads as zero
 
-// ABL (debug ablation, env SZN_ABLATE, results are then WRONG): 1 = no LDS-DMA issue in the loop, 2 = no waits/barrier,
-// 3 = fragments read once (no ds_read in the loop), 4 = no MFMA
-template <typename T, int WNF, int ABL = 0>   // WNF = 16-cout fragments per wave: 4 -> BN = 128, 2 -> BN = 64
+template <typename T, int WNF>   // WNF = 16-cout fragments per wave: 4 -> BN = 128, 2 -> BN = 64
 __global__ __launch_bounds__(512, 2) void conv_igemm_v2(Conv2Args a) {
 #if defined(__HIP_DEVICE_COMPILE__)   // the buffer-resource type does not exist in the host pass
     constexpr int ES = sizeof(T);
@@ -110,9 +105,8 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_v2(Conv2Args a) {
 
     const int nwg = a.mtiles * a.ntiles;
     const int lid = xcd_remap2(blockIdx.x, nwg);
-    // consecutive ids (= one XCD) walk the cout tiles of a pixel tile, or -- when the filter bank is the larger operand
-    // (fc6, fc7) -- the pixel tiles of a cout tile, so that the big operand is fetched by one L2 only
-    const int nt = a.nmajor ? lid / a.mtiles : lid % a.ntiles, mt = a.nmajor ? lid % a.mtiles : lid / a.ntiles;
+    // consecutive ids (= one XCD) walk the cout tiles of a pixel tile (pixel-tile-fastest order measured slower on fc6 / fc7)
+    const int nt = lid % a.ntiles, mt = lid / a.ntiles;
     const int m0 = mt * BM, n0 = nt * BN;
     const int split = blockIdx.y;
 
@@ -187,78 +181,19 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_v2(Conv2Args a) {
     if (nK > 1) issue(1);
     const int offs0 = ((g ^ (r16 & 7)) << 4), offs1 = (((4 + g) ^ (r16 & 7)) << 4);
     int stage = 0;
-    if constexpr (ABL == 5) {
-        // Software-pipelined loop: the LDS fragment reads of the NEXT half chunk are issued before the MFMAs of the
-        // current one (two fragment register sets), also across the chunk boundary, so the LDS pipe and the matrix pipe
-        // overlap instead of alternating; three chunks of LDS-DMA in flight; the per-chunk barrier sits between the two
-        // MFMA halves, after this wave's reads of the stage that is recycled behind it have retired.
-        if (nK > 2) issue(2);
-        if (nK > 2) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(2 * LPC) : "memory");
-        else if (nK > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(LPC) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        u32x4_t wfA[WNF], pfA[4], wfB[WNF], pfB[4];
-        {
-            const char* sp = smem + (wm * 64 + r16) * 128;
-            const char* sw = smem + BM * 128 + (wn * (BN / 2) + r16) * 128;
-#pragma unroll
-            for (int i = 0; i < WNF; ++i) wfA[i] = Mma2<T>::frag(*(const u32x4_t*)(sw + i * 16 * 128 + offs0));
-#pragma unroll
-            for (int j = 0; j < 4; ++j) pfA[j] = Mma2<T>::frag(*(const u32x4_t*)(sp + j * 16 * 128 + offs0));
-        }
-        for (int kc = 0; kc < nK; ++kc) {
-            const char* sp = smem + stage * STAGE + (wm * 64 + r16) * 128;
-            const char* sw = smem + stage * STAGE + BM * 128 + (wn * (BN / 2) + r16) * 128;
-            // ---- half 1: fetch the second-half fragments, multiply the first-half ones ----
-#pragma unroll
-            for (int i = 0; i < WNF; ++i) wfB[i] = Mma2<T>::frag(*(const u32x4_t*)(sw + i * 16 * 128 + offs1));
-#pragma unroll
-            for (int j = 0; j < 4; ++j) pfB[j] = Mma2<T>::frag(*(const u32x4_t*)(sp + j * 16 * 128 + offs1));
-#pragma unroll
-            for (int i = 0; i < WNF; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) Mma2<T>::run(acc[i][j], wfA[i], pfA[j]);
-            // ---- chunk kc+1 visible to everyone; everyone done reading this stage ----
-            if (kc + 1 < nK) {
-                if (kc + 2 < nK) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(LPC) : "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            if (kc + 3 < nK) issue(stage);                          // chunk kc+3 recycles the stage just drained
-            const int nstage = (stage == 2) ? 0 : stage + 1;
-            // ---- half 2: fetch the next chunk's first-half fragments, multiply the second-half ones ----
-            if (kc + 1 < nK) {
-                const char* sp2 = smem + nstage * STAGE + (wm * 64 + r16) * 128;
-                const char* sw2 = smem + nstage * STAGE + BM * 128 + (wn * (BN / 2) + r16) * 128;
-#pragma unroll
-                for (int i = 0; i < WNF; ++i) wfA[i] = Mma2<T>::frag(*(const u32x4_t*)(sw2 + i * 16 * 128 + offs0));
-#pragma unroll
-                for (int j = 0; j < 4; ++j) pfA[j] = Mma2<T>::frag(*(const u32x4_t*)(sp2 + j * 16 * 128 + offs0));
-            }
-#pragma unroll
-            for (int i = 0; i < WNF; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) Mma2<T>::run(acc[i][j], wfB[i], pfB[j]);
-            stage = nstage;
-        }
-    } else
     for (int kc = 0; kc < nK; ++kc) {
         // chunk kc has landed once at most the next chunk's loads are still outstanding
-        if (ABL != 2) {
-            if (kc + 1 < nK) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(LPC) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-        }
+        if (kc + 1 < nK) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(LPC) : "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
         // (stage + 2) % 3 was last read in iteration kc - 1.  Wave pair k issues its LDS-DMA loads behind its k-th weight
         // fragment: all eight waves stalled at VMEM issue at once (a CU ingests ~64 B of LDS-DMA per clock) would idle the
         // MFMA pipe for most of a chunk's fill time
-        const bool fill = ABL != 1 && kc + 2 < nK;
-        const int turn = a.stagger ? (w >> 1) : 0;
+        const bool fill = kc + 2 < nK;
+        const int turn = w >> 1;
         if (fill && turn == 0) issue(stage >= 1 ? stage - 1 : 2);
-        const int rstage = (ABL == 3) ? 0 : stage;
-        const char* sp = smem + rstage * STAGE + (wm * 64 + r16) * 128;
-        const char* sw = smem + rstage * STAGE + BM * 128 + (wn * (BN / 2) + r16) * 128;
+        const char* sp = smem + stage * STAGE + (wm * 64 + r16) * 128;
+        const char* sw = smem + stage * STAGE + BM * 128 + (wn * (BN / 2) + r16) * 128;
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             const int off = s ? offs1 : offs0;
@@ -271,10 +206,7 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_v2(Conv2Args a) {
             for (int i = 0; i < WNF; ++i) {
                 if (s * WNF + i > 0 && s * WNF + i < 4 && fill && turn == s * WNF + i) issue(stage >= 1 ? stage - 1 : 2);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if (ABL == 4) { acc[i][j][0] += __uint_as_float(wf[i].x ^ pf[j].x); }
-                    else Mma2<T>::run(acc[i][j], wf[i], pf[j]);
-                }
+                for (int j = 0; j < 4; ++j) Mma2<T>::run(acc[i][j], wf[i], pf[j]);
             }
         }
         if (++stage == 3) stage = 0;
@@ -299,15 +231,6 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_v2(Conv2Args a) {
                 }
             }
         }
-        return;
-    }
-    if (ABL == 6) {                                   // ablation: no output stores
-        float keep = 0.f;
-#pragma unroll
-        for (int i = 0; i < WNF; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) keep += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
-        if (keep == 123.456f) ((float*)a.out)[0] = keep;
         return;
     }
     // ---- epilogue from registers (16-bit operands, aligned rows: szn_epilogue.h); the staged one below is the general path ----
@@ -562,12 +485,6 @@ __global__ __launch_bounds__(256) void splitk_epilogue_cs(const float* __restric
     }
 }
 
-template <typename T, int WNF, int ABL>
-void launch_abl(const Conv2Args& a, size_t lds, hipStream_t st) {
-    (void)hipFuncSetAttribute((const void*)conv_igemm_v2<T, WNF, ABL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((conv_igemm_v2<T, WNF, ABL>), dim3(a.mtiles * a.ntiles, a.nsplit), dim3(512), lds, st, a);
-}
-
 template <typename T, int WNF>
 int launch_v2(const Conv2Args& a, hipStream_t st) {
     constexpr int BN = 32 * WNF;
@@ -576,18 +493,6 @@ int launch_v2(const Conv2Args& a, hipStream_t st) {
     if (!attr_done) {
         (void)hipFuncSetAttribute((const void*)conv_igemm_v2<T, WNF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_done = true;
-    }
-    static int abl = -1;
-    if (abl < 0) { abl = szn_ablate_env("SZN_ABLATE"); }
-    if (abl && sizeof(T) == 2) {                      // debug ablations of the bf16 kernels (wrong results)
-        if (abl == 1) launch_abl<T, WNF, 1>(a, lds, st);
-        else if (abl == 2) launch_abl<T, WNF, 2>(a, lds, st);
-        else if (abl == 3) launch_abl<T, WNF, 3>(a, lds, st);
-        else if (abl == 5) launch_abl<T, WNF, 5>(a, lds, st);
-        else if (abl == 6) launch_abl<T, WNF, 6>(a, lds, st);
-        else launch_abl<T, WNF, 4>(a, lds, st);
-        SZN_CHECK_LAUNCH("conv_igemm_v2(ablation)");
-        return SZN_OK;
     }
     hipLaunchKernelGGL((conv_igemm_v2<T, WNF>), dim3(a.mtiles * a.ntiles, a.nsplit), dim3(512), lds, st, a);
     SZN_CHECK_LAUNCH((std::is_same<T, f32x3_t>::value ? "conv_igemm_v2+bf16x3" : "conv_igemm_v2"));
@@ -665,7 +570,6 @@ static int conv2d_fwd_dispatch(const szn_conv_desc_t* d, const void* in, const v
     a.KH = d->KH; a.KW = d->KW; a.pad = d->pad; a.ldi = d->ldi; a.ldo = d->ldo; a.ldg = d->ldg;
     a.relu = d->relu; a.out_f32 = d->out_f32;
     a.M = d->B * d->Ho * d->Wo; a.HoWo = d->Ho * d->Wo;
-    { const int stg = 1; /* (was SZN_IGEMM_STAGGER) */ a.stagger = stg; }
     {
         // epilogue from registers (szn_epilogue.h): whole 16-B pieces of 8 couts, so rows and bases have to be 16-B aligned
         static const int de = szn_knob("SZN_IGEMM_DIRECT", 1);
@@ -673,9 +577,7 @@ static int conv2d_fwd_dispatch(const szn_conv_desc_t* d, const void* in, const v
         const uintptr_t al = (uintptr_t)out | (uintptr_t)gate | (uintptr_t)bias | (uintptr_t)chan_scale;
         a.direct_ep = de && szn_is16(d->dtype) && (d->Co % 8) == 0 && (((size_t)d->ldo * oes) & 15) == 0 && (al & 15) == 0 &&
                       (!gate || (((size_t)d->ldg * 2) & 15) == 0);
-        a.abl_ep = 0;
     }
-    { const int nm = 0; /* (was SZN_NMAJOR) */ a.nmajor = (nm && w_bytes > in_bytes) ? 1 : 0; }   // measured slower on fc6/fc7: off
     const bool narrow = d->Co <= 64;
     const int BN = narrow ? 64 : 128;
     a.mtiles = szn_div_up(a.M, 256); a.ntiles = szn_div_up(a.Co, BN);
@@ -694,8 +596,7 @@ static int conv2d_fwd_dispatch(const szn_conv_desc_t* d, const void* in, const v
     const bool out32_ = d->out_f32 || szn_store_f32(d->dtype);
     const int cs_rpb = 32;
     const long cs_rows = ((long)a.M + cs_rpb - 1) / cs_rpb;
-    const int cs_split = 1; /* (was SZN_SPLITK_COLSUM) */
-    const bool cs_ok = d->colsum && cs_split && !(d->Co & 3) && (d->Co >> 2) <= 256 && 256 % (d->Co >> 2) == 0 && !(d->ldo & 3) &&
+    const bool cs_ok = d->colsum && !(d->Co & 3) && (d->Co >> 2) <= 256 && 256 % (d->Co >> 2) == 0 && !(d->ldo & 3) &&
                        (!gate || !(d->ldg & 3)) && !((uintptr_t)d->workspace & 15) && !((uintptr_t)bias & 15) && !((uintptr_t)chan_scale & 15) &&
                        !((uintptr_t)out & (out32_ ? 15 : 7)) && (!d->colsum_slab || d->colsum_slab_rows >= cs_rows) &&
                        (long)a.mtiles * a.ntiles < 128;
@@ -725,9 +626,6 @@ static int conv2d_fwd_dispatch(const szn_conv_desc_t* d, const void* in, const v
                 if ((cand == 0 && ns == 1) || t < best_t * 0.97) { best = ns; best_t = t; best_wide = cand != 0; }
             }
         }
-        const int force_ns = 0; /* (was SZN_SPLITK_NS) */                   // tuning knob: SZN_SPLITK_NS=n forces the split count (0 = model)
-
-        if (force_ns > 0 && force_ns <= nK / 8 && (size_t)force_ns * a.M * a.Co * sizeof(float) <= d->workspace_bytes) best = force_ns;
         if (best > 1) {
             a.chunks_per_split = (int)((nK + best - 1) / best);
             a.nsplit = szn_div_up(nK, a.chunks_per_split);

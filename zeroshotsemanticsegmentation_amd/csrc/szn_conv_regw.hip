@@ -47,14 +47,7 @@ struct RwArgs {
     int B, Hi, Wi, Ho, Wo, pad;
     int ldi, ldo, ldg, relu;
     int tiles_x, tiles_y, ntiles;      // ntiles = B * tiles_y * tiles_x
-    int ablate;                        // SZN_REGW_ABLATE (make ABLATE=1 only; WRONG results): 1 no MFMA phase, 2 no global stores, 4 no patch DMA
-    int shift;                         // 1: phase-shifted wave groups (CIG = 1 kernels; SZN_REGW_SHIFT=0 restores the lockstep order)
 };
-#ifdef SZN_ABLATE_BUILD
-#define RW_ABL(bit) (a.ablate & (bit))
-#else
-#define RW_ABL(bit) 0
-#endif
 
 constexpr unsigned kOOBr = 0x80000000u;
 constexpr unsigned kOOBst = 0xfffffff0u;                // store offset beyond any output this kernel takes (out_bytes, pool_bytes < 0xffff0000)
@@ -216,7 +209,7 @@ __global__ __launch_bounds__(512) void conv3x3_regw(RwArgs a) {
     __syncthreads();
 
     // Phase shift (CIG = 1).  The two waves of a SIMD (w, w + 4) used to run the same phase at the same time -- MFMA phase, then
-    // epilogue (permlane / bias / ReLU / pack / stores) -- and the phases simply added up (SZN_REGW_ABLATE accounting of conv1_2
+    // epilogue (permlane / bias / ReLU / pack / stores) -- and the phases simply added up (profiles/r02_ablations.txt 11, conv1_2
     // forward: 0.42 ms = 0.14 epilogue + barriers, + 0.19 MFMA phase, + 0.05 stores, + 0.09 patch DMA).  Waves 4 .. 7 (group B) now take
     // the per-tile block barrier BETWEEN their MFMA phase and their epilogue, waves 0 .. 3 (group A) behind the epilogue as before:
     //     A:  MFMA(t) epi(t) | MFMA(t+1) epi(t+1) | ...          B:  MFMA(t) | epi(t) MFMA(t+1) | epi(t+1) MFMA(t+2) | ...
@@ -224,7 +217,7 @@ __global__ __launch_bounds__(512) void conv3x3_regw(RwArgs a) {
     // (after barrier k everyone has finished the MFMAs of tile first + k - 1, whose patch buffer is the one refilled next, and has
     // waited for its own pieces of patch first + k), no extra registers.  CIG = 2 keeps the lockstep order: its mid-tile partner
     // exchange needs a block barrier that both groups reach at the same point.
-    const bool grpB = CIG == 1 && a.shift && w >= 4;
+    const bool grpB = CIG == 1 && w >= 4;
     // column sums (bias gradient of the producer layer): each lane keeps running sums of its 8 couts over all the tiles of the
     // block; they are combined once, in a fixed order, behind the tile loop (no LDS atomics: bit-reproducible)
     float cst[8];
@@ -232,18 +225,7 @@ __global__ __launch_bounds__(512) void conv3x3_regw(RwArgs a) {
     for (int e = 0; e < 8; ++e) cst[e] = 0.f;
     const float relu_lo = a.relu ? 0.f : -__builtin_inff();
     int buf = 0;
-#ifdef SZN_ABLATE_BUILD
-    // SZN_REGW_ABLATE bit 8 (tools/probe_regw_cycles.py): clock64 split of the tile loop per wave -- top (gate / patch DMA issue), MFMA phase,
-    // counted wait, group B's barrier, epilogue, group A's barrier -- written over the first bytes of `out` (which is garbage then)
-    long long pc[6] = {0, 0, 0, 0, 0, 0}, pk0 = 0;
-#define RW_PROBE(i) do { if (a.ablate & 8) { const long long now_ = clock64(); pc[i] += now_ - pk0; pk0 = now_; } } while (0)
-#else
-#define RW_PROBE(i) do { } while (0)
-#endif
     for (int t = first; t < last; ++t) {
-#ifdef SZN_ABLATE_BUILD
-        if (a.ablate & 8) pk0 = clock64();
-#endif
         const bool more = t + NBUF - 1 < last;
         const int b = cb_b, ty = cb_ty, tx = cb_tx;
         step(cb_b, cb_ty, cb_tx);
@@ -268,8 +250,7 @@ __global__ __launch_bounds__(512) void conv3x3_regw(RwArgs a) {
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rsG, (ldsptr_t)(smem + G_::OFF_GATE + (w * NJ + jj) * 1024), 16, v, 0, 0, 0);
             }
         }
-        if (more && !RW_ABL(4)) issue((buf + NBUF - 1) % NBUF);
-        RW_PROBE(0);
+        if (more) issue((buf + NBUF - 1) % NBUF);
 
         f32x4_t acc[2][4];
 #pragma unroll
@@ -291,7 +272,6 @@ __global__ __launch_bounds__(512) void conv3x3_regw(RwArgs a) {
             dst[1] = *(const u32x4_t*)(rowp + (((cig * 8 + 4 + g) ^ sw) << 4));
         };
         ldP(0, P[0]);
-        if (!RW_ABL(1))
 #pragma unroll
         for (int step = 0; step < 18; ++step) {
             const int pr = step / 3, kw = step - pr * 3;
@@ -343,16 +323,13 @@ __global__ __launch_bounds__(512) void conv3x3_regw(RwArgs a) {
         float bv[8];
         *(f32x4_t*)&bv[0] = *(const f32x4_t*)(smem + G_::OFF_BIAS + cstart * 4);
         *(f32x4_t*)&bv[4] = *(const f32x4_t*)(smem + G_::OFF_BIAS + cstart * 4 + 16);
-        RW_PROBE(1);
         // retire the gate pieces of t, the patch pieces of t + 1 and the stores of t - 1
         if (NBUF == 3 && more) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(SLOTS) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        RW_PROBE(2);
         if (grpB) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
         }
-        RW_PROBE(3);
         float pm[8];                                                       // pooling: the even row of the current row pair
         u32x4_t pkm = {0u, 0u, 0u, 0u};
 #pragma unroll
@@ -385,7 +362,7 @@ __global__ __launch_bounds__(512) void conv3x3_regw(RwArgs a) {
             pk.y = pack2<T>(v[2], v[3]);
             pk.z = pack2<T>(v[4], v[5]);
             pk.w = pack2<T>(v[6], v[7]);
-            if (!RW_ABL(2) && !a.skip_x && !nostore)             // (wave-uniform conditions)
+            if (!a.skip_x && !nostore)             // (wave-uniform conditions)
                 __builtin_amdgcn_raw_buffer_store_b128(pk, rsO, ok ? ((m0 + j * a.Wo) * a.ldo + cstart) * 2u : kOOBst, 0, 0);
             if constexpr (!GATED) {
                 if (a.pool && a.pcode) {
@@ -415,15 +392,13 @@ __global__ __launch_bounds__(512) void conv3x3_regw(RwArgs a) {
                             Co4[i] = code;
                         }
                         const int poh = (oh0 + j) >> 1, pw = ow >> 1;
-                        if (!RW_ABL(2)) {
-                            const bool pst = (r16 & 1) == 0 && okw && poh < a.Hp;
-                            const unsigned pe = (unsigned)((b * a.Hp + poh) * a.Wp + pw) * (32 * COG) + cstart;
-                            __builtin_amdgcn_raw_buffer_store_b128(Mo, rsPo, pst ? pe * 2u : kOOBst, 0, 0);
-                            u32x2_t cb;
-                            cb.x = __builtin_amdgcn_perm(Co4[1], Co4[0], 0x06040200u);
-                            cb.y = __builtin_amdgcn_perm(Co4[3], Co4[2], 0x06040200u);
-                            __builtin_amdgcn_raw_buffer_store_b64(cb, rsPc, pst ? pe : kOOBst, 0, 0);
-                        }
+                        const bool pst = (r16 & 1) == 0 && okw && poh < a.Hp;
+                        const unsigned pe = (unsigned)((b * a.Hp + poh) * a.Wp + pw) * (32 * COG) + cstart;
+                        __builtin_amdgcn_raw_buffer_store_b128(Mo, rsPo, pst ? pe * 2u : kOOBst, 0, 0);
+                        u32x2_t cb;
+                        cb.x = __builtin_amdgcn_perm(Co4[1], Co4[0], 0x06040200u);
+                        cb.y = __builtin_amdgcn_perm(Co4[3], Co4[2], 0x06040200u);
+                        __builtin_amdgcn_raw_buffer_store_b64(cb, rsPc, pst ? pe : kOOBst, 0, 0);
                     }
                 } else
                 // fused MaxPool2d(2,2,ceil): rows (j, j + 1) pair up in this lane (oh0 is even), columns (ow, ow ^ 1) in
@@ -441,7 +416,7 @@ __global__ __launch_bounds__(512) void conv3x3_regw(RwArgs a) {
                             mx[e] = fmaxf(m2, nb);                         // quad_perm [1,0,3,2]: the lane of column ow ^ 1
                         }
                         const int poh = (oh0 + j) >> 1, pw = ow >> 1;
-                        if ((r16 & 1) == 0 && okw && poh < a.Hp && !RW_ABL(2)) {
+                        if ((r16 & 1) == 0 && okw && poh < a.Hp) {
                             u32x4_t pq;
                             pq.x = pack2<T>(mx[0], mx[1]);
                             pq.y = pack2<T>(mx[2], mx[3]);
@@ -453,23 +428,12 @@ __global__ __launch_bounds__(512) void conv3x3_regw(RwArgs a) {
                 }
             }
         }
-        RW_PROBE(4);
         if (!grpB) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
         }
-        RW_PROBE(5);
         buf = (buf == NBUF - 1) ? 0 : buf + 1;
     }
-#ifdef SZN_ABLATE_BUILD
-    if ((a.ablate & 8) && lane == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        float* pr = (float*)a.out + ((size_t)blockIdx.x * 8 + w) * 8;
-        for (int i = 0; i < 6; ++i) pr[i] = (float)pc[i];
-        pr[6] = (float)(last - first);
-        pr[7] = 1.f;
-    }
-#endif
     if constexpr (COLSUM) {
         // lane (g, r16 == 0) of wave w holds, after the row sum, the 8 couts cstart .. cstart + 7 of its wave: 8 waves x 4 rows x 8
         // values go to LDS (the patch buffers are free behind the barrier) and thread c adds the waves that own cout c in
@@ -660,8 +624,6 @@ int szn_conv_regw_try(const szn_conv_desc_t* d, const void* in, const void* w, c
             }
         }
     }
-    { static int abl = -1; if (abl < 0) abl = szn_ablate_env("SZN_REGW_ABLATE"); a.ablate = abl; }
-    { const int sh = 1; /* (was SZN_REGW_SHIFT) */ a.shift = sh; }
     static int ncu = 0;
     if (!ncu) {
         int dev = 0; hipDeviceProp_t p;

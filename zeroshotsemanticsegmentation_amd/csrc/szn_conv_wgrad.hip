@@ -41,7 +41,6 @@ struct Wg2Args {
     int plain_store;           // single split and no accumulation: write the tile instead of atomically adding it
     float* slab;               // pixel splits > 1 with a workspace: split s stores its partial into slab[s][Co*KH*KW*Ci] (plain
                                // stores; wgrad_slab_reduce adds the splits in a fixed order: deterministic, no atomics / memset)
-    int ablate;                // debug (env SZN_WG_ABLATE=1): skip the output epilogue (wrong results)
 };
 
 constexpr unsigned kOOBw = 0x80000000u;
@@ -236,15 +235,6 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_v2(Wg2Args a) {
         if (++stage == 3) stage = 0;
     }
 
-    if (a.ablate) {
-        float keep = 0.f;
-#pragma unroll
-        for (int i = 0; i < FA; ++i)
-#pragma unroll
-            for (int j = 0; j < FB; ++j) keep += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
-        if (keep == 123.456f) a.dw[0] = keep;
-        return;
-    }
     // ---- epilogue: D[co][ci] (lane: rows co = g*4+e, column ci = r16) staged through LDS in two co halves so that
     // every atomic / store instruction covers whole rows of the OHWI gradient (64 consecutive cins = 256 B per wave
     // instead of 4 x 64 B): the atomic tail was up to half of the kernel time on the 512-channel layers.
@@ -423,8 +413,7 @@ static int wgrad_dispatch(const szn_conv_desc_t* d, const void* in, const void* 
     a.cotiles = szn_div_up(d->Co, 32 * FA); a.citiles = szn_div_up(d->Ci, 32 * FB);
     const long tiles = (long)a.cotiles * a.citiles * d->KH * d->KW;
     // ~3 blocks per CU x 256 CUs x a few waves of blocks; each split covers a multiple of 64 pixels, at least 1024
-    const int wg_target = 3072; /* (was SZN_WG_BLOCKS) */
-    long want = (wg_target + tiles - 1) / tiles;
+    long want = (3072 + tiles - 1) / tiles;
     if (want < 1) want = 1;
     long span = (a.M + want - 1) / want;
     if (span < 1024) span = 1024;
@@ -444,9 +433,6 @@ static int wgrad_dispatch(const szn_conv_desc_t* d, const void* in, const void* 
     const long blocks = tiles * a.nsplit;
     if (blocks >= (1L << 31)) SZN_FAIL(SZN_ERR_UNSUPPORTED, "conv2d_wgrad: grid too large");
     a.plain_store = (a.nsplit == 1 && !accumulate) ? 1 : 0;      // fc6: 411 MB written once instead of memset + atomics
-    static int wg_abl = -1;
-    if (wg_abl < 0) { wg_abl = szn_ablate_env("SZN_WG_ABLATE"); }
-    a.ablate = wg_abl;
     if (!accumulate && !a.plain_store && !a.slab) {
         hipError_t e = hipMemsetAsync(dw, 0, nw * sizeof(float), st);
         if (e != hipSuccess) SZN_FAIL(SZN_ERR_LAUNCH, "conv2d_wgrad memset: %s", hipGetErrorString(e));

@@ -36,8 +36,6 @@ struct WtArgs {
     int cotiles, citiles, nsplit;
     int accumulate;
     int xcd_mode;              // block -> (split, combo) mapping, see the kernel
-    int ablate;                // debug (env SZN_WGT_ABLATE, wrong results): 1 = no LDS-DMA in the loop, 2 = no reads / MFMA
-    int fill_mode;             // who issues the fill of the next tile when: 0 = wave pair p at K step p (p < 4), 1 = wave group g (waves 4 g .. 4 g + 3) at K step g
     // constant-border hint (szn_conv_desc_t.cb_on for szn_conv2d_wgrad): the tiles whose whole 18 x 18 input patch holds ONE value per
     // channel are not run (cb numbers the others; ntiles = B * cb.per_image).  Their share of dW is a rank-one term, the same for
     // all nine taps:  dW[co][tap][ci] += (sum of dout[px][co] over their pixels) * x_const[ci]  -- csum [Co] comes from
@@ -163,7 +161,6 @@ __global__ __launch_bounds__(512) void conv_wgrad_taps(WtArgs a) {
     }
     const int smem_lds = (int)(uintptr_t)(__attribute__((address_space(3))) char*)smem;      // LDS byte address of the dynamic segment
     int stage = 0;
-    long long tw = 0, ti = 0, tc = 0, c0 = 0, c1 = 0, c2 = 0;   // SZN_WGT_ABLATE=9: cycles in wait+barrier / issue / compute
     // Fragment addresses = per-lane base + compile-time offset (the ds_read offset field), and reads issued ONE K step ahead.
     // A patch read of row R at column shift kw touches flattened patch pixel q = s + kk with s = 18 R + kw known at compile
     // time; its row swizzle ((q >> 1) & 3) is ((kk + (s & 1)) >> 1) + (s >> 1) mod 4, so eight per-lane bases Xb[s & 1][(s >> 1) & 3]
@@ -186,7 +183,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_taps(WtArgs a) {
     // read from LDS straight into its own register quadruple (two ds_read_b64_tr_b16 each, 12 + 4 reads per step instead of
     // 6 + 4) -- until round 4 a patch row was read once and the nine groups of a step were assembled from row PAIRS with ~12
     // v_mov per step, each in front of the MFMA that consumed it (VALU write -> MFMA read hazard on the critical path of an
-    // in-order wave; compute-only form of the loop, SZN_WGT_ABLATE=1: 0.56 of the matrix peak).  LDS traffic 1.6 x, ~100 B/clk.
+    // in-order wave; compute-only form of the loop: 0.56 of the matrix peak, profiles/r05_ablations.txt).  LDS traffic 1.6 x, ~100 B/clk.
     u32x4_t U[3][3];
     u32x4_t Af[2][2];
     // Round 5: the K steps run on ACROSS tile boundaries.  Until round 4 a tile began with vmcnt(0) + barrier, then all eight
@@ -218,16 +215,14 @@ __global__ __launch_bounds__(512) void conv_wgrad_taps(WtArgs a) {
                        "+v"(U[2][0]), "+v"(U[2][1]), "+v"(U[2][2]), "+v"(Af[0][0]), "+v"(Af[0][1]));
     }
     for (int t = first; t < last; ++t) {
-        if (a.ablate == 9) c0 = clock64();
-        const bool fill = t + 1 < last && a.ablate != 1;
+        const bool fill = t + 1 < last;
         const int sdo = smem_lds + stage * STAGEt, sdn = smem_lds + (stage ^ 1) * STAGEt;
-        if (a.ablate != 2)
 #pragma unroll
         for (int p = 0; p < 8; ++p) {
             // The fill of tile t + 1 is issued by wave pair p at K step p (p < 4): ten 1-KiB LDS-DMA loads stall their wave
-            // at VMEM issue for a few hundred cycles (SZN_WGT_ABLATE=9), so the waves take turns and the other waves of the
+            // at VMEM issue for a few hundred cycles (profiles/r01_ablations.txt), so the waves take turns and the other waves of the
             // CU -- in particular the SIMD partner w +- 4 -- keep the MFMA pipe busy meanwhile.
-            if (p < 4 && fill && (a.fill_mode ? (p < 2 && (w >> 2) == p) : (w >> 1) == p)) {
+            if (p < 4 && fill && (w >> 1) == p) {
                 prepare(t + 1);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) fireA(q, stage ^ 1);
@@ -236,7 +231,6 @@ __global__ __launch_bounds__(512) void conv_wgrad_taps(WtArgs a) {
             }
             // the groups and dout fragments of the NEXT step, fetched while this step's 18 MFMAs run
             u32x4_t N[3][3], An[2];
-            const bool nxt = p < 7 || fill;
             if (p < 7) {
 #pragma unroll
                 for (int kh = 1; kh < 3; ++kh)
@@ -249,10 +243,8 @@ __global__ __launch_bounds__(512) void conv_wgrad_taps(WtArgs a) {
                 }
             } else if (fill) {
                 // every wave's share of tile t + 1 has landed and nobody reads this stage any more (see above)
-                if (a.ablate == 9) c1 = clock64();
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
-                if (a.ablate == 9) tw += clock64() - c1;
 #pragma unroll
                 for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
@@ -284,12 +276,9 @@ __global__ __launch_bounds__(512) void conv_wgrad_taps(WtArgs a) {
                     for (int kw = 0; kw < 3; ++kw) U[kh][kw] = N[kh][kw];
                 Af[0][0] = An[0]; Af[0][1] = An[1];
             }
-            (void)nxt;
         }
-        if (a.ablate == 9) tc += clock64() - c0;
         stage ^= 1;
     }
-    (void)ti; (void)c2;
 
     // ---- partial -> slab [wave][fragment f = 9 i + tap][e][lane], 256 contiguous bytes per store instruction ----
     float* slab = a.ws + (size_t)slab_id * SLAB + (size_t)w * (18 * 256) + lane;
@@ -299,10 +288,6 @@ __global__ __launch_bounds__(512) void conv_wgrad_taps(WtArgs a) {
         for (int k = 0; k < 9; ++k)
 #pragma unroll
             for (int e = 0; e < 4; ++e) slab[((i * 9 + k) * 4 + e) * 64] = acc[i][k][e];
-    if (a.ablate == 9 && tid == 0) {                  // debug: the block's cycle split replaces the head of its slab
-        float* dbg = a.ws + (size_t)slab_id * SLAB;
-        dbg[0] = (float)tw; dbg[1] = (float)ti; dbg[2] = (float)tc; dbg[3] = (float)(last - first);
-    }
 #endif
 }
 
@@ -526,21 +511,15 @@ int szn_conv_wgrad_taps_try(const szn_conv_desc_t* d, const void* in, const void
     a.ntiles = (int)nt;
     // pixel splits: one block per CU at most, at least min_tiles_per_block tiles each (the slab write + reduction
     // must amortise), slabs must fit the workspace; too little parallelism left -> conv_wgrad_v2
-    // SZN_WGT_OVERSUB = k (default 1): k blocks per CU instead of one.  One block per CU is fastest on an idle GPU but its
-    // static partition has a full-kernel tail whenever another queue (an RCCL all-reduce running under the backward
-    // pass) holds CUs; k = 2 halves the late blocks.  Measured with a 32-CU stand-in hog (profiles/r01_ablations.txt): 12.2 vs 12.3
-    // ms/step under contention, 11.7 vs 11.9 without -- no net gain, so nothing sets it by default.
-    const int oversub = 1; /* (was SZN_WGT_OVERSUB) */
+    // (two blocks per CU measured no net gain, with or without a co-running queue: profiles/r01_ablations.txt)
     // reserved_cus: CUs left to another queue (the RCCL all-reduce under the backward pass), see szn_conv_desc_t
     const int cus = (d->reserved_cus > 0 && ncu - d->reserved_cus >= ncombo) ? ncu - d->reserved_cus : ncu;
-    long ns = (long)cus * oversub / ncombo;
+    long ns = (long)cus / ncombo;
     if (min_tiles_per_block < 1) min_tiles_per_block = 1;
     if (ns > nt / min_tiles_per_block) {
         // few tiles (conv5_x of ONE image: 9 tiles, 64 combos): the min_tiles rule would leave three quarters of the chip idle while 64
         // blocks walk 9 tiles each; down to two tiles per block the extra slabs cost less than the idle CUs (round 5, B = 1)
-        const int small = 1; /* (was SZN_WGT_SMALLSPLIT) */
-        const long relaxed = small ? std::max<long>(nt / min_tiles_per_block, std::min<long>(ns, nt / 2)) : nt / min_tiles_per_block;
-        ns = relaxed;
+        ns = std::max<long>(nt / min_tiles_per_block, std::min<long>(ns, nt / 2));
     }
     const size_t slab_bytes = (size_t)ncombo * SLAB * sizeof(float);
     int cb_rows = 0, cb_per = 1, cb_units = 0;
@@ -554,21 +533,17 @@ int szn_conv_wgrad_taps_try(const szn_conv_desc_t* d, const void* in, const void
     const size_t cb_bytes = a.cb.on ? ((size_t)cb_rows + 1) * d->Co * sizeof(float) : 0;
     if (cb_bytes + slab_bytes > d->workspace_bytes) return 1;
     if (ns > (long)((d->workspace_bytes - cb_bytes) / slab_bytes)) ns = (long)((d->workspace_bytes - cb_bytes) / slab_bytes);
-    const int minblk = 32; /* (was SZN_WGT_MINBLOCKS) */
-    if (ns < 1 || ns * ncombo < minblk) return 1;
+    if (ns < 1 || ns * ncombo < 32) return 1;
     a.nsplit = (int)ns;
     const bool own_sum = a.cb.on && !d->colsum;        // d->colsum: the producer of dout already summed the skipped tiles (include/szn.h)
     if (a.cb.on) {                                     // behind the slabs
         a.crow = (float*)d->workspace + (size_t)ns * ncombo * SLAB;
         a.csum = own_sum ? a.crow + (size_t)cb_rows * d->Co : (float*)d->colsum;
     }
-    {
-        const int xm = 1; /* (was SZN_WGT_XCD) */
-        a.xcd_mode = 0;
-        if (xm && ncombo >= 4) {        // (two combos: measured 3 % slower than launch order, conv2_1)
-            if (ns % 8 == 0) a.xcd_mode = 1;
-            else if (ns <= 8 && 8 % ns == 0 && ncombo % (8 / ns) == 0) a.xcd_mode = 2;
-        }
+    a.xcd_mode = 0;
+    if (ncombo >= 4) {                  // (two combos: measured 3 % slower than launch order, conv2_1)
+        if (ns % 8 == 0) a.xcd_mode = 1;
+        else if (ns <= 8 && 8 % ns == 0 && ncombo % (8 / ns) == 0) a.xcd_mode = 2;
     }
     a.dout = (const char*)dout; a.in = (const char*)in; a.dw = dw; a.ws = (float*)d->workspace;
     a.dw_lp = accumulate ? nullptr : (uint16_t*)d->dw_lp; a.lp_f16 = d->dw_lp_dtype == SZN_F16;
@@ -576,8 +551,6 @@ int szn_conv_wgrad_taps_try(const szn_conv_desc_t* d, const void* in, const void
     a.in_bytes = (unsigned)((size_t)d->B * d->Hi * d->Wi * d->ldi * 2);
     a.B = d->B; a.Hi = d->Hi; a.Wi = d->Wi; a.Ci = d->Ci; a.Ho = d->Ho; a.Wo = d->Wo; a.Co = d->Co; a.pad = d->pad;
     a.ldi = d->ldi; a.ldd = d->ldo; a.accumulate = accumulate;
-    { static int abl = -1; if (abl < 0) { abl = szn_ablate_env("SZN_WGT_ABLATE"); } a.ablate = abl; }
-    { const int fm = 0; /* (was SZN_WGT_FILL) */ a.fill_mode = fm; }
     hipStream_t st = (hipStream_t)stream;
     static bool attr_done = false;
     if (!attr_done) {

@@ -39,9 +39,7 @@ struct WgwArgs {
     int M;
     int cotiles, citiles;
     int accumulate;
-    int ablate;                // debug (env SZN_WGW_ABLATE, wrong results): 1 = no LDS-DMA in the loop, 2 = no reads / MFMA
     int use_tab;               // 1: pixel -> input-offset table of this block's tap in LDS behind the ring (M <= kTabMax)
-    int shift;                 // 1: phase-shifted wave groups (SZN_WGW_SHIFT=0: lockstep)
     int xcd_order;             // 1: an XCD takes a contiguous share of the tiles, cout tile fastest (the B operand is the large one)
     // conv_wgrad_wide<T, true> (szn_conv2d_wgrad_adam): the Adam step of this layer's weights in the epilogue -- fp32 master, both
     // moments and the 16-bit weight image, all in the gradient's OHWI order; dw may then be NULL (gradient not stored)
@@ -194,12 +192,6 @@ __global__ __launch_bounds__(512) void conv_wgrad_wide(WgwArgs a) {
         const int phase = (blockIdx.x >> 3) & 7;
         for (int i = 0; i < phase * a.stagger; ++i) __builtin_amdgcn_s_sleep(127);
     }
-#ifdef SZN_ABLATE_BUILD
-    long long pt[12];                                 // SZN_WGW_ABLATE=9: clock64 at the phase boundaries of the tile (tools/probe_wgw_cycles.py)
-#pragma unroll
-    for (int i = 0; i < 12; ++i) pt[i] = 0;
-    if (a.ablate == 9) pt[0] = clock64();
-#endif
     prepare(); fire(0);
     prepare(); if (nK > 1) fire(1);
     prepare(); if (nK > 2) fire(2);
@@ -212,7 +204,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_wide(WgwArgs a) {
     //   * W at the top of step k waits for the wave's own pieces of stage k + 1 (B reads stage k + 1 behind barrier k), so two
     //     stages stay in flight instead of three; a prologue barrier covers stage 0;
     //   * a wave fires stage k + 3 (the buffer of step k - 1) only behind barrier k, when everybody has finished reading step k - 1.
-    const bool grpB = a.shift && w >= 4;
+    const bool grpB = w >= 4;
     // stage 0 has landed for every wave before group B reads it (the prologue fired min(nK, 3) stages of four loads each)
     if (nK > 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     else if (nK > 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
@@ -224,60 +216,54 @@ __global__ __launch_bounds__(512) void conv_wgrad_wide(WgwArgs a) {
         if (kc + 2 < nK) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (!grpB) __builtin_amdgcn_s_barrier();
-        if (!grpB && kc + 3 < nK && a.ablate != 1) fire((stage + 3) & 3);       // the stage drained in step kc - 1
+        if (!grpB && kc + 3 < nK) fire((stage + 3) & 3);       // the stage drained in step kc - 1
         prepare_issue();                              // offsets of step kc + 4 (table reads go out in front of the fragment reads)
         // Transpose reads as inline asm with explicit waits: behind the `buffer_load ... lds` of fire() the compiler puts
         // s_waitcnt vmcnt(0) in front of the next LDS read it knows about (the DMA might alias it) -- every K step then waited for
         // the stage it had JUST issued, i.e. the ring never had anything in flight (0.32 of peak).  The fill goes to another stage;
         // the counted vmcnt above is the only wait on it.
         const int sbo = smem_lds + stage * STAGEg;
-        if (a.ablate != 2) {
-            auto rd_tr = [&](int addr, int off) -> u32x2_t {
-                u32x2_t v;
-                asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(off));
-                return v;
-            };
-            u32x2_t dl[8], dh[8], xl[4], xh[4];
+        auto rd_tr = [&](int addr, int off) -> u32x2_t {
+            u32x2_t v;
+            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(off));
+            return v;
+        };
+        u32x2_t dl[8], dh[8], xl[4], xh[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { xl[j] = rd_tr(sbo + offB[j], 0); xh[j] = rd_tr(sbo + offB[j], 16 * 512); }
+        for (int j = 0; j < 4; ++j) { xl[j] = rd_tr(sbo + offB[j], 0); xh[j] = rd_tr(sbo + offB[j], 16 * 512); }
 #pragma unroll
-            for (int i = 0; i < 4; ++i) { dl[i] = rd_tr(sbo + offA[i], 0); dh[i] = rd_tr(sbo + offA[i], 16 * 512); }
+        for (int i = 0; i < 4; ++i) { dl[i] = rd_tr(sbo + offA[i], 0); dh[i] = rd_tr(sbo + offA[i], 16 * 512); }
 #pragma unroll
-            for (int i = 4; i < 8; ++i) { dl[i] = rd_tr(sbo + offA[i], 0); dh[i] = rd_tr(sbo + offA[i], 16 * 512); }
-            // first half: the pixel fragments and dout fragments 0 .. 3 have landed (8 reads may still be in flight)
-            asm volatile("s_waitcnt lgkmcnt(8)"
-                         : "+v"(tb[0]), "+v"(tb[1]), "+v"(xl[0]), "+v"(xh[0]), "+v"(xl[1]), "+v"(xh[1]), "+v"(xl[2]), "+v"(xh[2]), "+v"(xl[3]), "+v"(xh[3]),
-                           "+v"(dl[0]), "+v"(dh[0]), "+v"(dl[1]), "+v"(dh[1]), "+v"(dl[2]), "+v"(dh[2]), "+v"(dl[3]), "+v"(dh[3]));
-            if (grpB) __builtin_amdgcn_s_barrier();
-            u32x4_t xf[4];
+        for (int i = 4; i < 8; ++i) { dl[i] = rd_tr(sbo + offA[i], 0); dh[i] = rd_tr(sbo + offA[i], 16 * 512); }
+        // first half: the pixel fragments and dout fragments 0 .. 3 have landed (8 reads may still be in flight)
+        asm volatile("s_waitcnt lgkmcnt(8)"
+                     : "+v"(tb[0]), "+v"(tb[1]), "+v"(xl[0]), "+v"(xh[0]), "+v"(xl[1]), "+v"(xh[1]), "+v"(xl[2]), "+v"(xh[2]), "+v"(xl[3]), "+v"(xh[3]),
+                       "+v"(dl[0]), "+v"(dh[0]), "+v"(dl[1]), "+v"(dh[1]), "+v"(dl[2]), "+v"(dh[2]), "+v"(dl[3]), "+v"(dh[3]));
+        if (grpB) __builtin_amdgcn_s_barrier();
+        u32x4_t xf[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) xf[j] = u32x4_t{xl[j].x, xl[j].y, xh[j].x, xh[j].y};
+        for (int j = 0; j < 4; ++j) xf[j] = u32x4_t{xl[j].x, xl[j].y, xh[j].x, xh[j].y};
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const u32x4_t df = u32x4_t{dl[i].x, dl[i].y, dh[i].x, dh[i].y};
+        for (int i = 0; i < 4; ++i) {
+            const u32x4_t df = u32x4_t{dl[i].x, dl[i].y, dh[i].x, dh[i].y};
 #pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = mfma16<T>(df, xf[j], acc[i][j]);
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)"
-                         : "+v"(dl[4]), "+v"(dh[4]), "+v"(dl[5]), "+v"(dh[5]), "+v"(dl[6]), "+v"(dh[6]), "+v"(dl[7]), "+v"(dh[7]),
-                           "+v"(acc[3][3]));            // (behind the 16 MFMAs of the first half)
+            for (int j = 0; j < 4; ++j) acc[i][j] = mfma16<T>(df, xf[j], acc[i][j]);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)"
+                     : "+v"(dl[4]), "+v"(dh[4]), "+v"(dl[5]), "+v"(dh[5]), "+v"(dl[6]), "+v"(dh[6]), "+v"(dl[7]), "+v"(dh[7]),
+                       "+v"(acc[3][3]));            // (behind the 16 MFMAs of the first half)
 #pragma unroll
-            for (int i = 4; i < 8; ++i) {
-                const u32x4_t df = u32x4_t{dl[i].x, dl[i].y, dh[i].x, dh[i].y};
+        for (int i = 4; i < 8; ++i) {
+            const u32x4_t df = u32x4_t{dl[i].x, dl[i].y, dh[i].x, dh[i].y};
 #pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = mfma16<T>(df, xf[j], acc[i][j]);
-            }
+            for (int j = 0; j < 4; ++j) acc[i][j] = mfma16<T>(df, xf[j], acc[i][j]);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(tb[0]), "+v"(tb[1]) : : "memory");
-        if (grpB && a.ablate == 2) __builtin_amdgcn_s_barrier();
-        if (grpB && kc + 3 < nK && a.ablate != 1) fire((stage + 3) & 3);        // (behind B's barrier)
+        if (grpB && kc + 3 < nK) fire((stage + 3) & 3);        // (behind B's barrier)
         prepare_finish();
         stage = (stage + 1) & 3;
     }
 
-#ifdef SZN_ABLATE_BUILD
-    if (a.ablate == 9) pt[1] = clock64();
-#endif
     // ---- epilogue: D[co][ci] (lane: rows co = 4 g + e, column ci = r16) staged through LDS in four 64-row passes so that
     //      every store instruction covers whole 1-KiB rows of the OHWI gradient ----
     constexpr int PT = 256 + 4;
@@ -310,13 +296,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_wide(WgwArgs a) {
                 vq[it] = __builtin_amdgcn_raw_buffer_load_b128(rsV, off, 0, SZN_WGW_ADAM_AUX);
             }
         }
-#ifdef SZN_ABLATE_BUILD
-        if (a.ablate == 9 && pass == 1) pt[2] = clock64();            // pass 1: loads issued
-#endif
         __syncthreads();
-#ifdef SZN_ABLATE_BUILD
-        if (a.ablate == 9 && pass == 1) pt[3] = clock64();            // ... first barrier passed
-#endif
         if (wm == (pass >> 1)) {
 #pragma unroll
             for (int ii = 0; ii < 4; ++ii)
@@ -327,16 +307,9 @@ __global__ __launch_bounds__(512) void conv_wgrad_wide(WgwArgs a) {
                         tile[(ii * 16 + g * 4 + e) * PT + wn * 64 + j * 16 + r16] = acc[(pass & 1) * 4 + ii][j][e];
         }
         __syncthreads();
-#ifdef SZN_ABLATE_BUILD
-        if (a.ablate == 9 && pass == 1) pt[4] = clock64();            // ... gradient tile staged
-#endif
         if (ADAM) {
 #pragma unroll
             for (int it = 0; it < 8; ++it) {
-#ifdef SZN_ABLATE_BUILD
-                if (a.ablate == 9 && pass == 1 && it == 1) pt[5] = clock64();     // ... first group updated and stored (its loads had landed)
-                if (a.ablate == 9 && pass == 1 && it == 7) pt[6] = clock64();
-#endif
                 if (eo[it] < 0) continue;
                 const int idx = tid + it * 512;
                 const int r = idx >> 6, c4 = (idx & 63) * 4;
@@ -363,16 +336,6 @@ __global__ __launch_bounds__(512) void conv_wgrad_wide(WgwArgs a) {
                     __builtin_amdgcn_raw_buffer_store_b128(go, rsG, off, 0, 0);
                 }
             }
-#ifdef SZN_ABLATE_BUILD
-            if (a.ablate == 9 && pass == 1) pt[7] = clock64();        // pass 1 done (stores issued)
-            if (a.ablate == 9 && pass == 3 && tid == 0 && a.dw_lp) {  // the block's split: cycles in {prologue + K loop, pass 0, pass 1 parts, passes 2-3}
-                pt[8] = clock64();
-                float* dbg = (float*)a.dw_lp + (size_t)blockIdx.x * 16;   // (probe runs hand a scratch buffer over in szn_conv_desc_t.dw_lp)
-                dbg[0] = (float)(pt[1] - pt[0]); dbg[1] = (float)(pt[2] - pt[1]); dbg[2] = (float)(pt[3] - pt[2]); dbg[3] = (float)(pt[4] - pt[3]);
-                dbg[4] = (float)(pt[5] - pt[4]); dbg[5] = (float)(pt[6] - pt[5]); dbg[6] = (float)(pt[7] - pt[6]); dbg[7] = (float)(pt[8] - pt[7]);
-                dbg[8] = (float)(pt[8] - pt[0]);
-            }
-#endif
             continue;
         }
         for (int idx = tid; idx < 64 * 64; idx += 512) {              // 64 rows x 64 float4
@@ -698,10 +661,7 @@ int szn_conv_wgrad_wide_try(const szn_conv_desc_t* d, const void* in, const void
     a.KH = d->KH; a.KW = d->KW; a.pad = d->pad; a.ldi = d->ldi; a.ldd = d->ldo;
     a.M = d->B * d->Ho * d->Wo;
     a.accumulate = accumulate;
-    { static int abl = -1; if (abl < 0) { abl = szn_ablate_env("SZN_WGW_ABLATE"); } a.ablate = abl; }
-    if (a.ablate == 9 && opt) a.dw_lp = (uint16_t*)d->dw_lp;      // (ablation build: the cycle probe's output buffer, >= 64 B per tile)
-    { const int tab = 1; /* (was SZN_WGW_TAB) */ a.use_tab = (tab && a.M <= kTabMax) ? 1 : 0; }
-    { const int sh = 1; /* (was SZN_WGW_SHIFT) */ a.shift = sh; }
+    a.use_tab = a.M <= kTabMax ? 1 : 0;
     a.stagger = 0;
     {
         static int ncu = 0;

@@ -30,8 +30,7 @@ __device__ __forceinline__ void wide_epilogue(const WideArgs& a, f32x4_t (&acc)[
     constexpr int RG = 512 / CPR;                      // row groups (16 / 12; threads >= RG * CPR idle in the epilogue)
     constexpr int NIT = (64 + RG - 1) / RG;
     float* tile = (float*)smem;
-    if (a.abl_ep == 2) return;
-    const T* __restrict__ gate = a.abl_ep ? nullptr : (const T*)a.gate;
+    const T* __restrict__ gate = (const T*)a.gate;
     const bool out32 = a.out_f32 || sizeof(T) == 4;
     const int oes = out32 ? 4 : 2;
     const bool fast_o = (((long)a.ldo * oes) & 15) == 0;
@@ -44,10 +43,10 @@ __device__ __forceinline__ void wide_epilogue(const WideArgs& a, f32x4_t (&acc)[
     for (int e = 0; e < 8; ++e) { bv[e] = (a.bias && n + e < a.Co) ? a.bias[n + e] : 0.f; cs[e] = 0.f; }
     // ReLU-gate rows (dgrad: 16 B of the forward activation per 8 outputs) are fetched ONE PASS AHEAD: issued in front of the two
     // barriers and the LDS staging of the pass before, so their latency is no longer paid NIT times per pass in the store loop
-    // (dgrad ran ~10 % behind the forward pass of the same layer).  16-bit gates with 16-B rows only; SZN_WIDE_GATEPF=0: off.
+    // (dgrad ran ~10 % behind the forward pass of the same layer).  16-bit gates with 16-B rows only.
     // (the 320-wide tile keeps 160 accumulator registers and is never gated: no prefetch registers there)
     constexpr int NG = (ES == 2 && WNF <= 8) ? NIT : 1;
-    const bool gpf = ES == 2 && WNF <= 8 && fast_g && full && a.gate_prefetch && !a.ws;
+    const bool gpf = ES == 2 && WNF <= 8 && fast_g && full && !a.ws;
     u32x4_t gcur[NG], gnext[NG];
     auto load_gates = [&](int pass, u32x4_t (&dst)[NG]) {
 #pragma unroll
@@ -134,8 +133,7 @@ __device__ __forceinline__ void wide_epilogue(const WideArgs& a, f32x4_t (&acc)[
                         v[e] = x;
                         cs[e] += x;
                     }
-                    if (a.abl_ep) { if (v[0] == 1.2345e-33f) ((float*)a.out)[0] = v[1]; }
-                    else if (out32) {
+                    if (out32) {
                         float* o = (float*)a.out + (long)m * a.ldo + n;
                         if (full && fast_o) {
                             *(f32x4_t*)o = *(const f32x4_t*)&v[0];
@@ -208,8 +206,7 @@ __device__ __forceinline__ void wide_finish(const WideArgs& a, f32x4_t (&acc)[WN
     wide_epilogue<T, WNF>(a, acc, smem, tid, wm, wn, g, r16, m0, n0, split);
 }
 
-// ABL (debug, SZN_WIDE_ABLATE, wrong results): 1 = no LDS-DMA in the loop, 2 = no fragment reads / MFMA
-template <typename T, int WNF, int ABL = 0>       // WNF = 16-cout fragments per wave: 6 -> BN = 192, 8 -> 256, 10 -> 320
+template <typename T, int WNF>       // WNF = 16-cout fragments per wave: 6 -> BN = 192, 8 -> 256, 10 -> 320
 __global__ __launch_bounds__(512, 2) void conv_igemm_wide(WideArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int ES = sizeof(T);
@@ -301,15 +298,13 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_wide(WideArgs a) {
         // The eight LDS-DMA loads of a wave stall it at VMEM issue (a CU ingests ~64 B of LDS-DMA per clock: 64 KiB = ~1000
         // cycles per chunk, half of the chunk's MFMA time): wave pair k issues behind its k-th pair of weight fragments of
         // the first K half, so the eight waves are never all stalled at once and their SIMD partners keep the MFMA pipe busy.
-        const bool fill = ABL != 1 && kc + 1 < nK;
-        // turn = the weight-fragment index (of the first K half) behind which this wave issues: stagger 1 -> pairs at
-        // 0, 2, 4, 6; stagger 2 -> every wave its own slot
+        const bool fill = kc + 1 < nK;
+        // turn = the weight-fragment index (of the first K half) behind which this wave issues: pairs at 0, 2, 4, 6
         // (WNF < 8, the 192-wide tile: pairs at 0, 1, 2, 3 -- every slot has to be below WNF)
-        const int turn = WNF < 8 ? (a.stagger ? (w >> 1) : 0) : a.stagger == 2 ? w : (a.stagger ? 2 * (w >> 1) : 0);
+        const int turn = WNF < 8 ? (w >> 1) : 2 * (w >> 1);
         if (fill && turn == 0) issue(stage ^ 1);
         const char* sp = smem + stage * STAGE + (wm * 64 + r16) * 128;
         const char* sw = smem + stage * STAGE + BM * 128 + (wn * (BN / 2) + r16) * 128;
-        if constexpr (ABL == 2) { if (fill && turn != 0) issue(stage ^ 1); } else
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             const int off = s ? offs1 : offs0;
@@ -465,7 +460,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_rows(WideArgs a) {
     if (w == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (ldsptr_t)(sA + 256 * 128), 16, voffA[4], 0, 0, 0);
     issue(0);
 
-    const int turn = a.stagger == 2 ? w : (a.stagger ? 2 * (w >> 1) : 0);
+    const int turn = 2 * (w >> 1);                       // wave pairs issue behind weight fragments 0, 2, 4, 6 (as conv_igemm_wide)
     int ckw = 0, cgrp = 0, ctap_base = 0, cic = 0;       // the step being computed: tap = ctap_base + ckw
     for (int kc = 0; kc < nK; ++kc) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -521,18 +516,18 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_rows(WideArgs a) {
 // Co <= 304 (the 300-d projection): the 20th 16-cout fragment is pure padding.  Its filter rows are not loaded and the waves of the
 // upper cout half run 9 fragments; waves w and w + 4 share a SIMD, so (wm, wn) = (w & 3, w >> 2) gives every SIMD 40 + 36 MFMA per half
 // step instead of 80.
-// STAG (round 4, SZN_PROJ_STAG): the two wave groups (wn = 0 / 1: waves w and w + 4 share a SIMD) run one barrier apart, every half step
+// Staggered schedule (round 4): the two wave groups (wn = 0 / 1: waves w and w + 4 share a SIMD) run one barrier apart, every half step
 // becomes {fragment reads (inline asm) + this half step's LDS-DMA issue + counted vmcnt + lgkmcnt(0); barrier; 40 MFMA; barrier}: one wave of
 // every SIMD multiplies while its partner reads and issues (the schedule of szn_conv_8ph.hip).  Reads are retired before the barrier, so a
 // slot is re-staged in the half step after its last read (the 3-unit rings stay); a unit issued in half step p is waited for in p + 1 (filters:
 // read in p + 2) -- the activation units keep three half steps of flight instead of four.
-template <typename T, bool NT, bool NF19, bool STAG>
+template <typename T, bool NF19>
 __global__ __launch_bounds__(512, 2) void proj_gemm_stream(WideArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
     static_assert(sizeof(T) == 2, "16-bit storage only");
     constexpr int BM = 256, BN = 320, WNF = 10;
     constexpr int AUNIT = BM * 128, WUNIT = BN * 64;           // 32 KiB, 20 KiB
-    constexpr int AUXA = NT ? 2 : 0;
+    constexpr int AUXA = 2;                                     // nt: the activations are streamed once
     extern __shared__ __attribute__((aligned(16))) char smem[];     // activations [3][256 x 128 B] | filters [3][320 x 64 B]
     char* const sA = smem;
     char* const sW = smem + 3 * AUNIT;
@@ -546,7 +541,7 @@ __global__ __launch_bounds__(512, 2) void proj_gemm_stream(WideArgs a) {
 
     // the activation resource covers this block's rows only (base = row m0): no 2 GB limit on the matrix, rows >= M fall outside
     const int rows = min(BM, a.M - m0);
-    const size_t abase = a.proj_abl == 1 ? 0 : (size_t)m0 * a.ldi * 2;     // ablation 1: every block streams the rows of block 0 (L2 hits)
+    const size_t abase = (size_t)m0 * a.ldi * 2;
     const auto rsA = __builtin_amdgcn_make_buffer_rsrc((void*)(a.in + abase), 0, (int)((size_t)rows * a.ldi * 2), 0x00020000);
     const auto rsB = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, (int)a.w_bytes, 0x00020000);
 
@@ -595,65 +590,37 @@ __global__ __launch_bounds__(512, 2) void proj_gemm_stream(WideArgs a) {
     if (nU > 1) issueA(1);
     if (H > 1) issueW(1);
     const int offw = ((g ^ ((r16 >> 1) & 3)) << 4);
-    if constexpr (STAG) {
-        const int smem_lds = (int)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-        auto rd = [&](int addr) -> u32x4_t {
-            u32x4_t v;
-            asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr));
-            return v;
-        };
-        // everything the un-staggered prologue issued stays; its first wait happens in half step 0
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (A0, W0, A1, W1 of this wave landed: a one-off)
-        __builtin_amdgcn_s_barrier();
-        if (wn == 1) __builtin_amdgcn_s_barrier();            // group 1 runs one barrier behind group 0
-        for (int h = 0; h < H; ++h) {
-            const int base = smem_lds + (int)(sA - smem);
-            const int ap = base + ((h >> 1) % 3) * AUNIT + (wm * 64 + r16) * 128 + (((4 * (h & 1) + g) ^ (r16 & 7)) << 4);
-            const int wp = smem_lds + (int)(sW - smem) + (h % 3) * WUNIT + (wn * 160 + r16) * 64 + offw;
-            u32x4_t pf[4], wf[WNF];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) pf[j] = rd(ap + j * 16 * 128);
-#pragma unroll
-            for (int i = 0; i < WNF; ++i) wf[i] = rd(wp + i * 16 * 64);
-            if (h + 2 < H) issueW(h + 2);                     // into the slot of W[h - 1] (its reads were retired before the last barrier)
-            if (!(h & 1) && (h >> 1) + 2 < nU) issueA((h >> 1) + 2);
-            // W[h + 1] (issued in half step h - 1) has to have landed: behind it in issue order there are at most one activation unit and
-            // this half step's filter unit
-            if (h + 4 >= H) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the activation issue stops four half steps before the end)
-            else if (w < W3) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-            asm volatile("s_waitcnt lgkmcnt(0)"
-                         : "+v"(pf[0]), "+v"(pf[1]), "+v"(pf[2]), "+v"(pf[3]), "+v"(wf[0]), "+v"(wf[1]), "+v"(wf[2]), "+v"(wf[3]),
-                           "+v"(wf[4]), "+v"(wf[5]), "+v"(wf[6]), "+v"(wf[7]), "+v"(wf[8]), "+v"(wf[9]));
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < WNF - 1; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = mfma16<T>(wf[i], pf[j], acc[i][j]);
-            if (!NF19 || wn == 0) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[WNF - 1][j] = mfma16<T>(wf[WNF - 1], pf[j], acc[WNF - 1][j]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-        }
-        if (wn == 0) __builtin_amdgcn_s_barrier();            // group 0 waits for group 1's last half step
-    } else
+    const int smem_lds = (int)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+    auto rd = [&](int addr) -> u32x4_t {
+        u32x4_t v;
+        asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr));
+        return v;
+    };
+    // everything the un-staggered prologue issued stays; its first wait happens in half step 0
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (A0, W0, A1, W1 of this wave landed: a one-off)
+    __builtin_amdgcn_s_barrier();
+    if (wn == 1) __builtin_amdgcn_s_barrier();            // group 1 runs one barrier behind group 0
     for (int h = 0; h < H; ++h) {
-        if (h + 4 >= H) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (w < W3) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        __builtin_amdgcn_s_barrier();                 // (A[h/2], W[h]) landed for every wave; everyone left half step h - 1
-        if (h + 2 < H) issueW(h + 2);                 // into the slot of W[h - 1]
-        if (!(h & 1) && (h >> 1) + 2 < nU) issueA((h >> 1) + 2);     // into the slot of A[h/2 - 1]
-        const char* sp = sA + ((h >> 1) % 3) * AUNIT + (wm * 64 + r16) * 128 + (((4 * (h & 1) + g) ^ (r16 & 7)) << 4);
-        const char* sw = sW + (h % 3) * WUNIT + (wn * 160 + r16) * 64 + offw;
+        const int base = smem_lds + (int)(sA - smem);
+        const int ap = base + ((h >> 1) % 3) * AUNIT + (wm * 64 + r16) * 128 + (((4 * (h & 1) + g) ^ (r16 & 7)) << 4);
+        const int wp = smem_lds + (int)(sW - smem) + (h % 3) * WUNIT + (wn * 160 + r16) * 64 + offw;
         u32x4_t pf[4], wf[WNF];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) pf[j] = *(const u32x4_t*)(sp + j * 16 * 128);
+        for (int j = 0; j < 4; ++j) pf[j] = rd(ap + j * 16 * 128);
 #pragma unroll
-        for (int i = 0; i < WNF; ++i) wf[i] = *(const u32x4_t*)(sw + i * 16 * 64);
+        for (int i = 0; i < WNF; ++i) wf[i] = rd(wp + i * 16 * 64);
+        if (h + 2 < H) issueW(h + 2);                     // into the slot of W[h - 1] (its reads were retired before the last barrier)
+        if (!(h & 1) && (h >> 1) + 2 < nU) issueA((h >> 1) + 2);
+        // W[h + 1] (issued in half step h - 1) has to have landed: behind it in issue order there are at most one activation unit and
+        // this half step's filter unit
+        if (h + 4 >= H) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the activation issue stops four half steps before the end)
+        else if (w < W3) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        asm volatile("s_waitcnt lgkmcnt(0)"
+                     : "+v"(pf[0]), "+v"(pf[1]), "+v"(pf[2]), "+v"(pf[3]), "+v"(wf[0]), "+v"(wf[1]), "+v"(wf[2]), "+v"(wf[3]),
+                       "+v"(wf[4]), "+v"(wf[5]), "+v"(wf[6]), "+v"(wf[7]), "+v"(wf[8]), "+v"(wf[9]));
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int i = 0; i < WNF - 1; ++i)
 #pragma unroll
@@ -662,30 +629,25 @@ __global__ __launch_bounds__(512, 2) void proj_gemm_stream(WideArgs a) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[WNF - 1][j] = mfma16<T>(wf[WNF - 1], pf[j], acc[WNF - 1][j]);
         }
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
     }
+    if (wn == 0) __builtin_amdgcn_s_barrier();            // group 0 waits for group 1's last half step
     wide_finish<T, WNF>(a, acc, smem, tid, wm, wn, g, r16, m0, 0, 0);
 #endif
 }
 
-template <typename T, bool NT, bool NF19>
+template <typename T, bool NF19>
 void launch_proj_variant(const WideArgs& a, size_t lds, hipStream_t st) {
-    const int stag = 1; /* (was SZN_PROJ_STAG) */
-    if (stag) {
-        (void)hipFuncSetAttribute((const void*)proj_gemm_stream<T, NT, NF19, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((proj_gemm_stream<T, NT, NF19, true>), dim3(a.mtiles), dim3(512), lds, st, a);
-        return;
-    }
-    (void)hipFuncSetAttribute((const void*)proj_gemm_stream<T, NT, NF19, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((proj_gemm_stream<T, NT, NF19, false>), dim3(a.mtiles), dim3(512), lds, st, a);
+    (void)hipFuncSetAttribute((const void*)proj_gemm_stream<T, NF19>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((proj_gemm_stream<T, NF19>), dim3(a.mtiles), dim3(512), lds, st, a);
 }
 
 template <typename T>
 int launch_proj_stream(const WideArgs& a, hipStream_t st) {
     const size_t lds = 3 * 256 * 128 + 3 * 320 * 64;
-    const int nt = 1; /* (was SZN_PROJ_NT) */
-    const bool nf19 = a.Co <= 304;
-    if (nt) { if (nf19) launch_proj_variant<T, true, true>(a, lds, st); else launch_proj_variant<T, true, false>(a, lds, st); }
-    else { if (nf19) launch_proj_variant<T, false, true>(a, lds, st); else launch_proj_variant<T, false, false>(a, lds, st); }
+    if (a.Co <= 304) launch_proj_variant<T, true>(a, lds, st);
+    else launch_proj_variant<T, false>(a, lds, st);
     SZN_CHECK_LAUNCH("proj_gemm_stream");
     return SZN_OK;
 }
@@ -711,19 +673,6 @@ int launch_wide(const WideArgs& a, hipStream_t st) {
         (void)hipFuncSetAttribute((const void*)conv_igemm_wide<T, WNF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_done = true;
     }
-    static int abl = -1;
-    if (abl < 0) { abl = szn_ablate_env("SZN_WIDE_ABLATE"); }
-    if (abl && sizeof(T) == 2 && WNF == 8) {          // debug ablations of the bf16 256 x 256 kernel (wrong results)
-        if (abl == 1) {
-            (void)hipFuncSetAttribute((const void*)conv_igemm_wide<T, WNF, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL((conv_igemm_wide<T, WNF, 1>), dim3(a.mtiles * a.ntiles, a.nsplit), dim3(512), lds, st, a);
-        } else {
-            (void)hipFuncSetAttribute((const void*)conv_igemm_wide<T, WNF, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL((conv_igemm_wide<T, WNF, 2>), dim3(a.mtiles * a.ntiles, a.nsplit), dim3(512), lds, st, a);
-        }
-        SZN_CHECK_LAUNCH("conv_igemm_wide(ablation)");
-        return SZN_OK;
-    }
     hipLaunchKernelGGL((conv_igemm_wide<T, WNF>), dim3(a.mtiles * a.ntiles, a.nsplit), dim3(512), lds, st, a);
     SZN_CHECK_LAUNCH((std::is_same<T, f32x3_t>::value ? "conv_igemm_wide+bf16x3" : "conv_igemm_wide"));
     return SZN_OK;
@@ -739,11 +688,7 @@ int szn_conv_wide_try(const szn_conv_desc_t* d, const void* in, const void* w, c
                       float* ws, int nsplit, int chunks_per_split, szn_stream_t stream) {
     if (d->Co < 256) return 1;
     WideArgs a;
-    a.proj_abl = 0;
-    { static int ea = -1; if (ea < 0) ea = szn_ablate_env("SZN_WIDE_EPABL"); a.abl_ep = ea; }
     a.ws = nsplit > 1 ? ws : nullptr; a.nsplit = nsplit > 1 ? nsplit : 1;
-    { const int stg = 1; /* (was SZN_WIDE_STAGGER) */ a.stagger = stg; }
-    { const int gp = 1; /* (was SZN_WIDE_GATEPF) */ a.gate_prefetch = gp; }
     a.chunks_per_split = nsplit > 1 ? chunks_per_split : (1 << 30);
     a.M = d->B * d->Ho * d->Wo;
     // cout tile 256, or 320 (bf16) when that wastes fewer columns: the 300-d projection is one 320-wide tile
@@ -752,7 +697,7 @@ int szn_conv_wide_try(const szn_conv_desc_t* d, const void* in, const void* w, c
     a.mtiles = szn_div_up(a.M, 256); a.ntiles = szn_div_up(d->Co, bn);
     // tile order within an XCD's share of the grid: pixel tile fastest when the filter bank is the larger operand (fc6: 205 MB against a
     // 4 MB map), so that the blocks of one XCD share cout tiles and the bank crosses the fabric once, not once per XCD
-    { const int nm = 1; /* (was SZN_WIDE_NMAJOR) */ a.nmajor = (nm && w_bytes > in_bytes) ? 1 : 0; }
+    a.nmajor = w_bytes > in_bytes ? 1 : 0;
     if ((long)a.mtiles * a.ntiles * a.nsplit < min_tiles) {         // too few blocks to fill the chip: keep 256 x 128 ...
         // ... unless 256 x 192 tiles fit ONE round of the chip where the 256 x 128 tiles need two (fc7 at B = 8, 512 x 512:
         // 2,312 x 4096 is 10 x 32 = 320 narrow tiles = 1.25 rounds, but 10 x 22 = 220 tiles of 192 couts: 0.117 -> ~0.09 ms)
@@ -813,8 +758,7 @@ int szn_conv_wide_try(const szn_conv_desc_t* d, const void* in, const void* w, c
 // 2 GB operand check of the generic kernels: the activation resource is rebased per block.  Returns 1 when the shape does not fit.
 int szn_proj_stream_try(const szn_conv_desc_t* d, const void* in, const void* w, const float* bias, const void* gate,
                         const float* chan_scale, void* out, int min_tiles, szn_stream_t stream) {
-    const int proj = 1; /* (was SZN_PROJ_STREAM) */
-    if (!proj || !szn_is16(d->dtype) || d->KH != 1 || d->KW != 1 || d->pad != 0 || d->Co <= 256 || d->Co > 320 || d->Ci < 256 ||
+    if (!szn_is16(d->dtype) || d->KH != 1 || d->KW != 1 || d->pad != 0 || d->Co <= 256 || d->Co > 320 || d->Ci < 256 ||
         (d->Ci % 64) || gate || chan_scale || d->colsum || d->pool_out || d->relu)
         return 1;
     if (d->B <= 0 || d->Hi <= 0 || d->Wi <= 0 || d->Ho != d->Hi || d->Wo != d->Wi || d->ldi < d->Ci || d->ldo < d->Co || !in || !w ||
@@ -825,11 +769,8 @@ int szn_proj_stream_try(const szn_conv_desc_t* d, const void* in, const void* w,
     a.M = d->B * d->Ho * d->Wo;
     a.mtiles = szn_div_up(a.M, 256); a.ntiles = 1; a.nmajor = 0;
     if (a.mtiles < min_tiles) return 1;
-    a.ws = nullptr; a.nsplit = 1; a.chunks_per_split = 1 << 30; a.stagger = 0; a.gate_prefetch = 0;
+    a.ws = nullptr; a.nsplit = 1; a.chunks_per_split = 1 << 30;
     {
-        static int abl = -1;
-        if (abl < 0) abl = szn_ablate_env("SZN_PROJ_ABLATE");
-        a.proj_abl = abl; a.abl_ep = 0;
         static const int de = szn_knob("SZN_WIDE_DIRECT", 1);
         const size_t oes = d->out_f32 ? 4 : 2;
         a.direct_ep = de && (d->Co % 8) == 0 && (((size_t)d->ldo * oes) & 15) == 0 && (((uintptr_t)out | (uintptr_t)bias) & 15) == 0;

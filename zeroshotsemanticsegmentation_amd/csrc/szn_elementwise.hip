@@ -1160,8 +1160,7 @@ extern "C" int szn_maxpool2x2_ceil_bwd(int dtype, int B, int Hi, int Wi, int C, 
     if (colsum && (256 % (C / ch)) != 0) SZN_FAIL(SZN_ERR_UNSUPPORTED, "maxpool_bwd: colsum needs C/%d to divide 256", ch);
     // with column sums every block ends in C atomicAdds on the same C addresses: 4096 blocks spent more time there than streaming
     // (pool3 .. pool5); two blocks per CU stream at 5.3 TB/s (tools/bench sweep in profiles/r02_ablations.txt section 13)
-    const int capx = 512; /* (was SZN_POOLBWD_BLOCKS) */
-    const int grid = grid_for(total, 256, colsum ? capx : 65536);
+    const int grid = grid_for(total, 256, colsum ? 512 : 65536);
     float* cslab = colsum ? colsum_slab : nullptr;
     if (cslab && colsum_slab_rows < grid)
         SZN_FAIL(SZN_ERR_ARG, "maxpool_bwd: colsum_slab holds %d rows, %d needed", colsum_slab_rows, grid);
@@ -1201,8 +1200,7 @@ static int maxpool_bwd_code_impl(int dtype, int B, int Hi, int Wi, int C, const 
     if (skip_tiles)
         for (int i = 0; i < 8 * n_regions; ++i)
             if (skip_tiles[i] & 1) SZN_FAIL(SZN_ERR_ARG, "maxpool_bwd_code_cb: region bounds must be even (2 x 2 windows must not straddle them)");
-    const int capx = 512; /* (was SZN_POOLBWD_BLOCKS) */
-    const int grid = grid_for(total, 256, sums ? capx : 65536);
+    const int grid = grid_for(total, 256, sums ? 512 : 65536);      // (512: see szn_maxpool2x2_ceil_bwd)
     float* cslab = colsum ? colsum_slab : nullptr;
     if (cslab && colsum_slab_rows < grid)
         SZN_FAIL(SZN_ERR_ARG, "maxpool_bwd_code: colsum_slab holds %d rows, %d needed", colsum_slab_rows, grid);

@@ -19,7 +19,7 @@ __device__ __forceinline__ float row16_sum_w(float x) {                    // su
 }
 
 // ---- epilogue straight from the accumulator registers (16-bit operands, Co a multiple of 8, 16-B aligned rows) ----------------
-// The LDS-staged epilogue of the tile kernels costs 10-13 us per 256 x 256 tile (SZN_WIDE_EPABL accounting, profiles/r03_ablations.txt section 4:
+// The LDS-staged epilogue of the tile kernels costs 10-13 us per 256 x 256 tile (epilogue accounting, profiles/r03_ablations.txt section 4:
 // conv3_2 forward 0.305 ms, 0.299 without its global stores, 0.255 without the epilogue): four passes in which two of the eight
 // waves write 64 KiB into LDS while six wait at the barrier, then a branchy read-back loop.  Here nothing is staged: a lane of the
 // MFMA result holds 4 consecutive couts of one pixel for each cout fragment; v_permlane16_swap on a PAIR of fragments (the DPP rows
@@ -126,7 +126,7 @@ __device__ __forceinline__ void tile_epilogue_block(const Args& a, f32x4_t (&acc
 #pragma unroll
                 for (int e = 0; e < 8; ++e) cs[e] += ok ? v[e] : 0.f;
             }
-            if (RAGGED && ok && !a.abl_ep && n + 8 > a.Co) {   // ragged last piece: element by element
+            if (RAGGED && ok && n + 8 > a.Co) {   // ragged last piece: element by element
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     if (n + e < a.Co) {
@@ -134,7 +134,7 @@ __device__ __forceinline__ void tile_epilogue_block(const Args& a, f32x4_t (&acc
                         else ((uint16_t*)a.out)[(long)mrow[j] * a.ldo + n + e] = to_bits16<T>(v[e]);
                     }
                 }
-            } else if (ok && !a.abl_ep) {
+            } else if (ok) {
                 if (out32) {
                     float* o = (float*)a.out + (long)mrow[j] * a.ldo + n;
                     *(f32x4_t*)o = *(const f32x4_t*)&v[0];
@@ -209,7 +209,7 @@ __device__ __forceinline__ void tile_epilogue_raw(const Args& a, f32x4_t (&acc)[
                 v[c] = __uint_as_float(r[0]);
                 v[4 + c] = __uint_as_float(r[1]);
             }
-            if (m < a.M && n < a.Co && !a.abl_ep) {
+            if (m < a.M && n < a.Co) {
                 float* o = slab + (size_t)m * a.Co + n;
                 *(f32x4_t*)o = *(const f32x4_t*)&v[0];
                 *(f32x4_t*)(o + 4) = *(const f32x4_t*)&v[4];

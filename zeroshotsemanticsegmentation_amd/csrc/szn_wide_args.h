@@ -14,11 +14,7 @@ struct WideArgs {
     int M, HoWo, mtiles, ntiles, nmajor;
     float* ws;                 // split-K: fp32 slabs [nsplit][M][Co] (plain stores, no epilogue); nullptr = single pass
     int nsplit, chunks_per_split;
-    int stagger;               // 1: wave pairs take turns issuing the LDS-DMA loads of a chunk (SZN_WIDE_STAGGER=0: all at once)
-    int gate_prefetch;         // 1: the epilogue fetches the ReLU-gate rows one pass ahead (SZN_WIDE_GATEPF=0: inside the store loop)
     int direct_ep;             // 1: epilogue straight from the accumulator registers (wide_epilogue_direct)
-    int abl_ep;                // ablation builds only (SZN_WIDE_EPABL): 1 = epilogue without global stores / gate loads, 2 = no epilogue
-    int proj_abl;              // ablation builds only (SZN_PROJ_ABLATE): 1 = every block of proj_gemm_stream streams the rows of block 0
 };
 
 constexpr unsigned kOOBx = 0x80000000u;

@@ -46,10 +46,7 @@ _BACKBONE = [("conv1_1", PAD1), ("conv1_2", 1), "P", ("conv2_1", 1), ("conv2_2",
              ("conv5_1", 1), ("conv5_2", 1), ("conv5_3", 1), "P"]
 _TRUNK = [n for n, _, _, _ in synth.CONV_LAYERS]          # conv1_1 .. fc7
 _CONST_BORDER = os.environ.get("SZN_CONST_BORDER", "1") != "0"  # 0: no constant-border hint to the 710^2 / 355^2 forward convs
-_DGRAD_SPLIT = True         # few-tile dgrads may split their K range (the library decides; its split-K epilogue delivers the column sums)
-_WGRAD_CB_FUSED = True      # the pools' backward pass sums dn over the tiles the producer's weight gradient skips (False: that call sums them itself)
 _DGRAD_BORDER = os.environ.get("SZN_DGRAD_BORDER", "1") != "0"        # 0: conv1_2's dgrad runs the tiles nobody reads (for their column sums)
-_FC6_NATIVE = True          # fc6's dgrad GEMM on the forward weight image (False: on the packed transpose, rounds 1-2)
 _OPT_LAYERS = _TRUNK + ["score_fr"]                        # the layers train.get_parameters yields (train.py:302-331)
 _OPT_LAYERS8 = _TRUNK + ["score_pool3", "score_pool4", "score_fr"]       # ... for FCN8s (score_fr stays last: engine.TrainStep)
 
@@ -100,14 +97,11 @@ _X3_LAYERS = frozenset(["conv1_2", "conv2_1", "conv2_2", "conv3_1", "conv3_2", "
                         "conv5_2", "conv5_3", "fc6", "fc7"])
 _BAND_CROP = os.environ.get("SZN_BAND_CROP", "1") != "0"
 _BAND_BLOCKS = {"conv1_2": ("conv1_2",), "conv2_1": ("conv2_1", "conv2_2"), "conv3_1": ("conv3_1", "conv3_2", "conv3_3")}   # first layer -> block
-# (module constants, not environment knobs since round 6: tools/diag_band.py and the tests patch them)
+# (a module constant, not an environment knob since round 6: tools/diag_band.py patches it)
 _BAND_16BIT = ["conv2_1", "conv3_1"]      # blocks cropped through the generic szn_band_remap on the 16-bit paths (fp32: all three)
-_BAND_C11 = True       # 16-bit paths: conv1_1 writes its output cropped (szn_conv1_1_fwd_c) and conv1_2's block runs on it
-_BAND_FUSE = True      # adjacent cropped blocks hand over in one composed index map (False: copy the pooled rows back, crop again)
 # default of SZN_FC6_CUMASK (see _Engine._masked_stream): CUs of the stream fc6's weight gradient + Adam runs on in a small step.  Off:
 # measured on three boxes, "128:low" moved the one-image step by -0.13 / -0.04 ms for a caller on a non-blocking stream and by -0.05 / +0.02 ms
 # for a caller on the null stream (profiles/r05_ablations.txt 15) -- inside the box-to-box spread
-_POOL_GATHER = True   # the pools' backward pass applies the transposed band map while reading (szn_maxpool2x2_ceil_bwd_code_gather) instead of two szn_band_remap passes in front of it
 _FC6_CUMASK = "0"
 _SMALL_STEP_PX = 2 * 512 * 512
 
@@ -293,7 +287,6 @@ class _Engine(object):
         self.fused_opt = None
         self.fused_done = set()
         self.reserved_cus = 0         # CUs the persistent backward kernels leave to the RCCL queue (szn_conv_desc_t.reserved_cus; TrainStep)
-        self.pool_codes = True        # False (tests / A-B): the pools' backward pass reads the un-pooled tensors (rounds 1-2) instead of winner codes
         self.head_fp8 = False         # forward of the projection head on the fp8 matrix cores (set_head_precision)
         self.head_fp8_bwd = False     # ... and its dgrad / wgrad (e5m2 gradient x e4m3 operands)
         self._fp8_ws = None
@@ -529,7 +522,7 @@ class _Engine(object):
         pooled map stays as it is and the next block's entry maps it straight into its own cropped coordinates (_BandPlan.fused_with).
         -> (tensor, pending)"""
         nxt = items[i + 2][0] if (i + 2 < len(items) and items[i + 2] != "P") else None
-        if nxt in _BAND_BLOCKS and _BAND_FUSE and (self.dtype == torch.float32 or nxt in _BAND_16BIT):
+        if nxt in _BAND_BLOCKS and (self.dtype == torch.float32 or nxt in _BAND_16BIT):
             ny, nx = _cb_pool(regy, band.H), _cb_pool(regx, band.W)
             nplan = self._band_plan(ny, nx, band.Hp, band.Wp, a.device, len(_BAND_BLOCKS[nxt]))
             if nplan is not None:
@@ -622,7 +615,7 @@ class _Engine(object):
         # (the cropped pair has no fallback in the backward pass -- szn_conv1_1_wgrad_c is the fused kernel or nothing -- so the forward pass takes
         #  it only where that kernel's own admission rule holds: full-map gradient and image below 2 GiB, i.e. B < 34 at 512 x 512)
         c11_fits = B * H1 * W1 * 128 < 0x7fff0000 and B * 3 * H * W * 4 < 0x7fff0000
-        if _BAND_CROP and _BAND_C11 and c11_fits and self.dtype != torch.float32 and not self.keep_prepool and (self.pool_codes or not keep):
+        if _BAND_CROP and c11_fits and self.dtype != torch.float32 and not self.keep_prepool:
             # 16-bit paths: conv1_1 never stores the rows / columns of the constant band that conv1_2's block does without (92 per side
             # at 512 x 512: 526^2 instead of 710^2 pixels written here, read by conv1_2, pooled, and walked by the backward pass)
             c11 = self._band_plan(regy, regx, H1, W1, x.device, len(_BAND_BLOCKS["conv1_2"]))
@@ -646,7 +639,7 @@ class _Engine(object):
                 regy, regx = _cb_pool(regy, a_hw[0]), _cb_pool(regx, a_hw[1])
                 continue                                  # pooled by the conv in front of it (pool_out)
             name, pad = item
-            if name in _BAND_BLOCKS and _BAND_CROP and not self.keep_prepool and (self.pool_codes or not keep) and \
+            if name in _BAND_BLOCKS and _BAND_CROP and not self.keep_prepool and \
                     (self.dtype == torch.float32 or name in _BAND_16BIT or (i == 0 and c11 is not None)):
                 # the constant band inside a conv block: remove most of it (see _band_cut), put the pooled rows back behind the block's pool
                 blk = _BAND_BLOCKS[name]
@@ -672,19 +665,16 @@ class _Engine(object):
             regy, regx = _cb_conv3x3(regy, a_hw[0]), _cb_conv3x3(regx, a_hw[1])
             cb = (regy, regx) if band is None else None
             if i + 1 < len(items) and items[i + 1] == "P":
-                if keep and self.pool_codes:
+                if keep:
                     pin, a, code = self._conv(a, name, pad, pool=True, codes=True, pool_only=not self.keep_prepool, cb=cb)
                     acts[name] = pin if self.keep_prepool else None       # (may be unwritten: the backward pass takes the codes)
                     if band is not None:
                         a, pending = self._band_close(ctx, a, band, name, items, i, regy, regx)
                     pools.append((acts[name], a, code, tuple(pin.shape)))
-                else:
-                    pin, a = self._conv(a, name, pad, pool=True, pool_only=not keep, cb=cb)
+                else:                                     # (no state kept: the pooled map alone)
+                    pin, a = self._conv(a, name, pad, pool=True, pool_only=True, cb=cb)
                     if band is not None:
                         a, pending = self._band_close(ctx, a, band, name, items, i, regy, regx)
-                    if keep:
-                        acts[name] = pin
-                        pools.append((pin, a))
                 del pin
                 band = None
             else:
@@ -941,7 +931,7 @@ class _Engine(object):
             code = L.dtype_code(self.dtype)
             d = L.ConvDesc(self._gemm_code(name), B, Hi, Wi, Ci, Ho, Wo, Co, k, k, pad, Ci, Co, 0, 0, 0)
             lib = L.load()
-            native = _FC6_NATIVE and dout.is_contiguous() and lib.szn_conv2d_dgrad_gemm_native_supported(C.byref(d)) == 1
+            native = dout.is_contiguous() and lib.szn_conv2d_dgrad_gemm_native_supported(C.byref(d)) == 1
             nb = (lib.szn_conv2d_dgrad_gemm_native_workspace_bytes if native else lib.szn_conv2d_dgrad_gemm_workspace_bytes)(C.byref(d))
             if self._gemm_ws is None or self._gemm_ws.numel() < nb or self._gemm_ws.device != dout.device:
                 self._gemm_ws = torch.empty(nb, dtype=torch.uint8, device=dout.device)
@@ -971,7 +961,7 @@ class _Engine(object):
         # 256 x 128 on 256 CUs): the library may split the K range (deterministic slabs); since round 5 its split-K epilogue also
         # produces the column sums (= the producer layer's bias gradient) from the fp32 values (splitk_epilogue_cs), so the
         # scratch is handed over whether or not column sums are asked for and the decision is the library's alone
-        if colsum is None or (cb is None and _DGRAD_SPLIT):
+        if colsum is None or cb is None:
             self._workspace(d, M * Ci * 4, dout.device)
         if cb is not None and gate is not None and _CONST_BORDER and self.dtype != torch.float32:
             grect, srect = cb                                   # (r0, r1, c0, c1) each: where the gate varies / what the consumer reads
@@ -1069,7 +1059,7 @@ class _Engine(object):
                 gather = None          # (ytab, xtab): d is still in the consumer's coordinates, this pool's backward pass reads it through the map
                 if ctx.crop and ("out", producer) in ctx.crop and not ctx.crop.get(("fusedout", producer)):
                     band = ctx.crop[("out", producer)]         # the pooled rows that were copies: their gradients are summed
-                    if _POOL_GATHER and pcode is not None:
+                    if pcode is not None:
                         gather = band.gather_uncrop
                     else:
                         d = self._band_remap(d, band, "uncrop_bwd_y", band.Hpc, band.Wp)
@@ -1089,7 +1079,7 @@ class _Engine(object):
                 # that call is going to skip, instead of a second pass over them (szn_conv2d_wgrad_cb_tiles)
                 regions, want = [], []
                 cbp = (getattr(ctx, "cb_in", None) or {}).get(producer)
-                if pcode is not None and slab is not None and _WGRAD_CB_FUSED and idx >= 2 and self.dtype != torch.float32 and _CONST_BORDER:
+                if pcode is not None and slab is not None and idx >= 2 and self.dtype != torch.float32 and _CONST_BORDER:
                     prev2 = items[idx - 2]
                     xin2 = ctx.pools[pi][1] if prev2 == "P" else ctx.acts[prev2[0]]
                     lay = getattr(m, producer)
@@ -1177,7 +1167,7 @@ class _Engine(object):
                     if prev_band is not None:                  # ... straight into the previous block's pooled, cropped coordinates
                         ft = prev_band.fused_with(band)
                         two = [(ft["bwd_y"], prev_band.Hpc, band.Wc), (ft["bwd_x"], prev_band.Hpc, prev_band.Wpc)]
-                        if _POOL_GATHER and not (skips and skips.get(pi) is not None):
+                        if not (skips and skips.get(pi) is not None):
                             pending_gather = (ft["bwd_gather"], two, band)      # applied by the pool's backward pass while it reads d
                         else:
                             for tab, ho, wo in two:
