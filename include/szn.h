@@ -493,6 +493,27 @@ int szn_fused_head_grouped_prepared(int stride, int B, int h, int w, int E, int 
                                     float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
                                     szn_stream_t stream);
 
+/* ---- fused MSE embedding head (train.py -loss mse): coarse -> (loss, stats, prediction, dcoarse) without the (B,E,H,W) score -----
+ * Equivalent to szn_bilinear_up_crop_fwd(stride) -> szn_mse_loss_fwd (embedding gather) -> szn_embed_argmax_k ->
+ * szn_mse_loss_bwd (gout NULL) -> szn_bilinear_up_crop_bwd(stride) (models.py:146-147 upscore + crop; utils.py:50-73 mse_loss as
+ * trainer_fcn.py forward / forward_szn call it; utils.py:159-204 infer_lbl).  Arguments, strides (32 | 8), group modes, NULL rules
+ * (pred-only, loss-only, no dcoarse), error codes, workspace (szn_fused_head_workspace_bytes) and prepare step
+ * (szn_fused_head_prepare for _prepared) are those of szn_fused_head_grouped[_prepared].  pred is that head's pred bit for bit: the
+ * class assignment is the cosine argmax whatever the loss.  stats f32 [B][2] = {sum over valid px of |s - e_lbl|^2, number of valid
+ * px}; loss = mean_b S_b / N_b (labels >= K take row 0, negative labels are ignored: szn_mse_loss_fwd's contract); dcoarse =
+ * 2 (s - e_lbl) / (B N_b) carried back through the upsample, channels [c0, c0+E) only.  The per-pixel term is the quadratic form
+ * sum_{t,u} w_t w_u (C_t - e).(C_u - e) over the cell's four taps, never |s|^2 - 2 s.e + |e|^2 (which cancels near convergence).
+ * Fixed-order reductions, no atomics: two calls give bitwise-equal outputs.                                                        */
+int szn_fused_mse_head(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                       const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
+                       int group_mode, const int64_t* group_map, float* loss, float* stats, int64_t* pred,
+                       int dcoarse_dtype, void* dcoarse, void* workspace, szn_stream_t stream);
+int szn_fused_mse_head_prepared(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                                const float* coarse, const float* embed, const int64_t* target,
+                                const szn_class_set* unseen, int group_mode, const int64_t* group_map, float* loss,
+                                float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
+                                szn_stream_t stream);
+
 /* ---- fused softmax cross-entropy head: coarse -> (loss, stats, prediction, dcoarse) without the (B,C,H,W) score ---------
  * Equivalent to szn_bilinear_up_crop_fwd(stride) -> szn_ce2d_fwd (pred = channel argmax) -> szn_ce2d_bwd (gout NULL) ->
  * szn_bilinear_up_crop_bwd(stride) (models.py:94,146-147 upscore + crop, utils.py:19-48 cross_entropy2d, trainer_fcn.py:117

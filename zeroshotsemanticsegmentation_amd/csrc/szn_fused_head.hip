@@ -17,9 +17,37 @@
 //   the cell's loss partial, A and Bm.  All reductions are fixed-order (bit-reproducible).
 // Kernel 2: loss_finalize (per-image sums, fixed order).  Kernel 3 (gather): one block per coarse
 //   position sums the contributions of the <= 4 cells that use it as a tap and writes dcoarse.
+//
+// MSE variant (template flag MSE; szn_fused_mse_head, utils.py:50-73): L_b = sum_px |s - e_lbl|^2 / N_b.  Prediction, G, Q and the
+// grouped modes are the cosine head's, bit for bit.  The gradient has the same shape with per-pixel coefficients 1,
+//     dC_t = 2/(B N_b) ( sum_u Bm[t][u] C_u - sum_k A[t][k] e_k ),   A[t][k] = sum_{px: label k} w_t,  Bm[t][u] = sum_{valid px} w_t w_u,
+// so fh_gather_kernel serves both (numerator 2 instead of 1).  The per-pixel LOSS is not formed from G and Q as
+// |s|^2 - 2 s.e + |e|^2: that cancels once the net has learnt something (2e-2 of a cell's loss at C = e + 1e-3 |e| noise in fp32).
+// Layout chosen instead: the bilinear weights of a pixel sum to exactly 1 (multiples of 1/(2S)^2), so s - e_k = sum_t w_t (C_t - e_k) and
+//     |s - e_k|^2 = sum_{t,u} w_t w_u P_k[t][u],   P_k[t][u] = (C_t - e_k) . (C_u - e_k)      (10 distinct dot products of length E)
+// built from the vectors (differences first, then products: nothing large is subtracted) only for the classes that occur in the
+// cell; missing border taps are C_t = 0.  Stride 32: a first pass over the block's labels marks the classes present in
+// LDS, the four waves share the present classes round-robin and store P_k in LDS [KP][10] (each class built once per cell).
+// Stride 8: one wave owns the cell and already visits its labels class by class for A, so P_k lives in registers for the duration
+// of that class's turn, read from the coarse vectors themselves (the per-position tables D, N would only give the cancelling form).
 #include "szn_common.h"
 
 namespace {
+
+// index of the pair (t, u), t <= u, among the 10 distinct entries of a symmetric 4 x 4 matrix
+__device__ __forceinline__ constexpr int sym10(int t, int u) {
+    return t <= u ? (t * 4 - t * (t - 1) / 2) + (u - t) : (u * 4 - u * (u - 1) / 2) + (t - u);
+}
+
+// |s - e_k|^2 of one pixel from the cell's P_k (MSE variant): fixed-order chain over the 16 (t, u) pairs
+__device__ __forceinline__ float mse_px(const float (&wt)[4], const float* P) {
+    float l = 0.f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) l = fmaf(wt[t] * wt[u], P[sym10(t, u)], l);
+    return l;
+}
 
 template <int S>
 __device__ __forceinline__ double bil1d(int t) { return 1.0 - fabs((double)t - ((double)S - 0.5)) / (double)S; }
@@ -98,7 +126,7 @@ __global__ __launch_bounds__(256) void fh_prep_kernel(const float* __restrict__ 
     }
 }
 
-template <int KP, int S, bool GROUPED>
+template <int KP, int S, bool GROUPED, bool MSE>
 __global__ __launch_bounds__(256) void fh_cell_kernel(FhArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* Ct = sm;                       // [4][E]
@@ -107,6 +135,8 @@ __global__ __launch_bounds__(256) void fh_cell_kernel(FhArgs a) {
     float* Aw = Q + 16;                   // [4 waves][4][KP]
     float* red = Aw + 16 * KP;            // [4 waves][16]
     double* dred = (double*)(red + 64);   // [4 waves][2]   (offset is a multiple of 8 B: all terms are multiples of 4 floats... see host check)
+    float* Pk = (float*)(dred + 8);       // MSE only: [KP][10], rows of the classes present in this cell
+    int* present = (int*)(Pk + 10 * KP);  // MSE only: [KP]
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -128,7 +158,19 @@ __global__ __launch_bounds__(256) void fh_cell_kernel(FhArgs a) {
         Ct[i] = v;
     }
     for (int i = tid; i < 16 * KP; i += 256) Aw[i] = 0.f;
+    if (MSE)
+        for (int i = tid; i < KP; i += 256) present[i] = 0;
     __syncthreads();
+    // MSE: a first pass over the labels marks the classes of this cell for the P_k pass (the pixel loop reads them again from L2)
+    if (MSE && a.target) {
+        for (int q = tid; q < S * S; q += 256) {
+            const int y = S * I + q / S - a.crop, x = S * J + q % S - a.crop;
+            if (y >= 0 && y < a.H && x >= 0 && x < a.W) {
+                const long l = a.target[((size_t)b * a.H + y) * a.W + x];
+                if (l >= 0) present[l < a.K ? (int)l : 0] = 1;    // every writer stores the same value
+            }
+        }
+    }
     // G[t][k]: wave t, lane k (+ 64, + 128, + 192 when KP > 64)
     for (int k = lane; k < KP; k += 64) {
         float g = 0.f;
@@ -161,6 +203,34 @@ __global__ __launch_bounds__(256) void fh_cell_kernel(FhArgs a) {
         }
     }
     __syncthreads();
+    if (MSE) {
+        // P_k of the present classes, ascending k, dealt to the waves in turn: 64 strided partial chains + xor butterfly each
+        int n = 0;
+        for (int k = 0; k < a.K; ++k) {
+            if (!present[k]) continue;
+            if ((n++ & 3) != wave) continue;
+            float p[10];
+#pragma unroll
+            for (int v = 0; v < 10; ++v) p[v] = 0.f;
+            const float* ek = a.embed + (size_t)k * a.E;
+            for (int c = lane; c < a.E; c += 64) {
+                const float e = ek[c];
+                float d[4];
+#pragma unroll
+                for (int t = 0; t < 4; ++t) d[t] = Ct[t * a.E + c] - e;
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+#pragma unroll
+                    for (int u = t; u < 4; ++u) p[sym10(t, u)] = fmaf(d[t], d[u], p[sym10(t, u)]);
+            }
+#pragma unroll
+            for (int v = 0; v < 10; ++v) {
+                const float s = wave_sum(p[v]);
+                if (lane == 0) Pk[k * 10 + v] = s;
+            }
+        }
+        __syncthreads();
+    }
 
     // ---- pixels of this cell: Y in [S I, S I + S) x X in [S J, S J + S), image coords y = Y - crop ----
     float bm[16];
@@ -200,7 +270,16 @@ __global__ __launch_bounds__(256) void fh_cell_kernel(FhArgs a) {
                 }
                 a.pred[pix] = best;
             }
-            if (lbl >= 0) {
+            if (MSE && lbl >= 0) {
+                const int kl = lbl < a.K ? (int)lbl : 0;
+                cos_sum += (double)mse_px(wt, Pk + kl * 10);
+                cnt += 1.0;
+                aco = 1.f;
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) bm[t * 4 + u] += wt[t] * wt[u];
+            } else if (lbl >= 0) {
                 const int kl = lbl < a.K ? (int)lbl : 0;
                 float d = 0.f;
 #pragma unroll
@@ -290,7 +369,7 @@ __global__ __launch_bounds__(256) void fh_tables_kernel(FhArgs a, float* __restr
 }
 
 // one wave per cell (S * S <= 64 pixels), four cells per block; same per-pixel arithmetic and the same outputs as fh_cell_kernel
-template <int KP, int S, bool GROUPED>
+template <int KP, int S, bool GROUPED, bool MSE>
 __global__ __launch_bounds__(256) void fh_cell_tab_kernel(FhArgs a, const float* __restrict__ D, const float* __restrict__ N) {
     static_assert(S * S <= 64, "one wave per cell");
     __shared__ float Gs[4][4 * KP];
@@ -370,7 +449,14 @@ __global__ __launch_bounds__(256) void fh_cell_tab_kernel(FhArgs a, const float*
                 }
                 a.pred[pix] = best;
             }
-            if (lbl >= 0) {
+            if (MSE && lbl >= 0) {
+                cnt += 1.0;                 // the loss term follows in the class loop below, where P_k is at hand
+                aco = 1.f;
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) bm[t * 4 + u] += wt[t] * wt[u];
+            } else if (lbl >= 0) {
                 const int kl = lbl < a.K ? (int)lbl : 0;
                 float d = 0.f;
 #pragma unroll
@@ -392,6 +478,26 @@ __global__ __launch_bounds__(256) void fh_cell_tab_kernel(FhArgs a, const float*
             const int src = __ffsll((long long)todo) - 1;
             const int kl = (int)__shfl((int)(lbl < a.K ? lbl : 0), src, 64);
             const bool mine = (lbl >= 0) && ((int)(lbl < a.K ? lbl : 0) == kl);
+            if (MSE) {
+                // P_kl from the vectors (same chains as fh_cell_kernel: 64 strided partials + xor butterfly), kept in registers
+                float p[10];
+#pragma unroll
+                for (int v = 0; v < 10; ++v) p[v] = 0.f;
+                const float* ek = a.embed + (size_t)kl * a.E;
+                for (int c = lane; c < a.E; c += 64) {
+                    const float e = ek[c];
+                    float d[4];
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) d[t] = ((tp[t] >= 0) ? a.coarse[(size_t)tp[t] * a.ldc + a.c0 + c] : 0.f) - e;
+#pragma unroll
+                    for (int t = 0; t < 4; ++t)
+#pragma unroll
+                        for (int u = t; u < 4; ++u) p[sym10(t, u)] = fmaf(d[t], d[u], p[sym10(t, u)]);
+                }
+#pragma unroll
+                for (int v = 0; v < 10; ++v) p[v] = wave_sum(p[v]);
+                if (mine) cos_sum += (double)mse_px(wt, p);
+            }
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 const float s = wave_sum(mine ? wt[t] * aco : 0.f);
@@ -416,7 +522,7 @@ __global__ __launch_bounds__(256) void fh_cell_tab_kernel(FhArgs a, const float*
     }
 }
 
-// loss = mean_b (N_b - S_b)/N_b ; stats[b] = {S_b, N_b}.  One block per image sums its cells (fixed order: 256 strided double
+// loss = mean_b (N_b - S_b)/N_b (cosine) | mean_b S_b / N_b (mse); stats[b] = {S_b, N_b}.  One block per image sums its cells (fixed order: 256 strided double
 // chains, wave butterflies, then the four wave totals), a single wave combines the images.
 __global__ __launch_bounds__(256) void fh_image_sums_kernel(const double* __restrict__ part, int cells, float* __restrict__ stats,
                                                             double* __restrict__ sums) {
@@ -434,15 +540,15 @@ __global__ __launch_bounds__(256) void fh_image_sums_kernel(const double* __rest
     }
 }
 
-__global__ void fh_finalize_kernel(const double* __restrict__ sums, int B, float* __restrict__ loss) {
+__global__ void fh_finalize_kernel(const double* __restrict__ sums, int B, int mse, float* __restrict__ loss) {
     if (threadIdx.x == 0) {
         double acc = 0.0;
-        for (int b = 0; b < B; ++b) acc += (sums[2 * b + 1] - sums[2 * b]) / sums[2 * b + 1];
+        for (int b = 0; b < B; ++b) acc += mse ? sums[2 * b] / sums[2 * b + 1] : (sums[2 * b + 1] - sums[2 * b]) / sums[2 * b + 1];
         loss[0] = (float)(acc / B);
     }
 }
 
-template <typename T>
+template <typename T, bool MSE>
 __global__ __launch_bounds__(256) void fh_gather_kernel(const float* __restrict__ coarse, const float* __restrict__ embed,
                                                         const float* __restrict__ ws, const float* __restrict__ stats,
                                                         T* __restrict__ dcoarse, int B, int h, int w, int E, int ldc,
@@ -472,7 +578,7 @@ __global__ __launch_bounds__(256) void fh_gather_kernel(const float* __restrict_
     // the class term is linear in A: sum the four cells' rows first, one pass over the K embeddings instead of four
     Al[0][threadIdx.x] = (threadIdx.x < KP) ? (Al[0][threadIdx.x] + Al[1][threadIdx.x]) + (Al[2][threadIdx.x] + Al[3][threadIdx.x]) : 0.f;
     __syncthreads();
-    const float scale = 1.f / ((float)B * stats[2 * b + 1]);
+    const float scale = (MSE ? 2.f : 1.f) / ((float)B * stats[2 * b + 1]);
     for (int c = threadIdx.x; c < E; c += 256) {
         float acc = 0.f;
         for (int k = 0; k < K; ++k) acc = fmaf(-Al[0][k], embed[(size_t)k * E + c], acc);
@@ -488,7 +594,12 @@ __global__ __launch_bounds__(256) void fh_gather_kernel(const float* __restrict_
             }
             acc += bu;
         }
-        elem<T>::st(dcoarse + ((size_t)pos) * ldc + c0 + c, acc * scale);
+        float v = acc * scale;
+        // MSE: the 16-bit outputs are the rounding of the fp32 result.  Left alone, the compiler merges this product and the half
+        // conversion into one v_fma_mixlo_f16 (a single rounding) despite -ffp-contract=off; the cosine instantiations keep that
+        // form, their bits are pinned.
+        if (MSE) asm volatile("" : "+v"(v));
+        elem<T>::st(dcoarse + ((size_t)pos) * ldc + c0 + c, v);
     }
 }
 
@@ -510,7 +621,7 @@ static int fused_head_impl(int stride, int B, int h, int w, int E, int ldc, int 
                            const float* coarse, const float* embed, const int64_t* target, float* loss,
                            float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
                            szn_stream_t stream, bool prep, const szn_class_set* unseen = nullptr, int group_mode = 0,
-                           const int64_t* group_map = nullptr);
+                           const int64_t* group_map = nullptr, bool mse = false);
 
 extern "C" int szn_fused_head_strided(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
                                       const float* coarse, const float* embed, const int64_t* target, float* loss,
@@ -546,7 +657,7 @@ static int fused_head_impl(int stride, int B, int h, int w, int E, int ldc, int 
                            const float* coarse, const float* embed, const int64_t* target, float* loss,
                            float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
                            szn_stream_t stream, bool prep, const szn_class_set* unseen, int group_mode,
-                           const int64_t* group_map) {
+                           const int64_t* group_map, bool mse) {
     if (stride != 32 && stride != 8) SZN_FAIL(SZN_ERR_UNSUPPORTED, "fused_head: stride %d (32 and 8 are built)", stride);
     if (!coarse || !embed || !workspace || B <= 0 || h <= 0 || w <= 0 || E <= 0 || c0 < 0 || ldc < c0 + E || H <= 0 ||
         W <= 0 || crop < 0 || K <= 0)
@@ -583,22 +694,28 @@ static int fused_head_impl(int stride, int B, int h, int w, int E, int ldc, int 
     a.B = B; a.h = h; a.w = w; a.E = E; a.ldc = ldc; a.c0 = c0; a.H = H; a.W = W; a.crop = crop; a.K = K; a.KP = KP;
     a.gmap = group_map; a.gmode = group_mode; a.unseen = ubits;
     // LDS floats: Ct 4E | G 4KP | Q 16 | Aw 16KP | red 64 | dred 8 doubles; 4E + 20KP + 80 must be even for the doubles
+    // (+ the MSE variant's P [KP][10] and class marks [KP] behind the doubles)
     size_t lfl = (size_t)4 * E + 20 * KP + 16 + 64;
-    const size_t lds = lfl * sizeof(float) + 8 * sizeof(double);
+    const size_t lds = lfl * sizeof(float) + 8 * sizeof(double) + (mse ? (size_t)11 * KP * sizeof(float) : 0);
     if (lds > 150 * 1024) SZN_FAIL(SZN_ERR_UNSUPPORTED, "fused_head: E=%d too large for LDS", E);
-#define SZN_FH_LAUNCH_G(KPV, GR)                                                                                     \
+#define SZN_FH_LAUNCH_GM(KPV, GR, MS)                                                                                \
     do {                                                                                                             \
         if (stride == 8) {                                                                                           \
             hipLaunchKernelGGL(fh_tables_kernel<KPV>, dim3((unsigned)(((long)B * h * w + 3) / 4)), dim3(256),        \
                                (size_t)4 * E * sizeof(float), st, a, tabD, tabN);                                    \
-            hipLaunchKernelGGL((fh_cell_tab_kernel<KPV, 8, GR>), dim3((unsigned)(((long)B * cells + 3) / 4)), dim3(256), 0, st, a, \
+            hipLaunchKernelGGL((fh_cell_tab_kernel<KPV, 8, GR, MS>), dim3((unsigned)(((long)B * cells + 3) / 4)), dim3(256), 0, st, a, \
                                (const float*)tabD, (const float*)tabN);                                              \
         } else {                                                                                                     \
-            auto kern = fh_cell_kernel<KPV, 32, GR>;                                                                 \
+            auto kern = fh_cell_kernel<KPV, 32, GR, MS>;                                                             \
             if (lds > 48 * 1024)                                                                                     \
                 (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);  \
             hipLaunchKernelGGL(kern, dim3(B * cells), dim3(256), lds, st, a);                                        \
         }                                                                                                            \
+    } while (0)
+#define SZN_FH_LAUNCH_G(KPV, GR)                                                                                     \
+    do {                                                                                                             \
+        if (mse) SZN_FH_LAUNCH_GM(KPV, GR, true);                                                                    \
+        else SZN_FH_LAUNCH_GM(KPV, GR, false);                                                                       \
     } while (0)
 #define SZN_FH_LAUNCH(KPV)                                                                                           \
     do {                                                                                                             \
@@ -613,24 +730,29 @@ static int fused_head_impl(int stride, int B, int h, int w, int E, int ldc, int 
     else SZN_FH_LAUNCH(256);
 #undef SZN_FH_LAUNCH
 #undef SZN_FH_LAUNCH_G
+#undef SZN_FH_LAUNCH_GM
     SZN_CHECK_LAUNCH("fh_cell_kernel");
     if (loss) {
         hipLaunchKernelGGL(fh_image_sums_kernel, dim3(B), dim3(256), 0, st, (const double*)part, cells, stats, sums);
-        hipLaunchKernelGGL(fh_finalize_kernel, dim3(1), dim3(64), 0, st, (const double*)sums, B, loss);
+        hipLaunchKernelGGL(fh_finalize_kernel, dim3(1), dim3(64), 0, st, (const double*)sums, B, mse ? 1 : 0, loss);
         SZN_CHECK_LAUNCH("fh_finalize_kernel");
     }
     if (dcoarse) {
-        if (dcoarse_dtype == SZN_F32)
-            hipLaunchKernelGGL(fh_gather_kernel<float>, dim3(B * h * w), dim3(256), 0, st, coarse, embed, (const float*)ws_f,
-                               (const float*)stats, (float*)dcoarse, B, h, w, E, ldc, c0, K, KP);
-        else if (dcoarse_dtype == SZN_BF16)
-            hipLaunchKernelGGL(fh_gather_kernel<bf16_raw>, dim3(B * h * w), dim3(256), 0, st, coarse, embed,
-                               (const float*)ws_f, (const float*)stats, (bf16_raw*)dcoarse, B, h, w, E, ldc, c0, K, KP);
-        else if (dcoarse_dtype == SZN_F16)
-            hipLaunchKernelGGL(fh_gather_kernel<f16_raw>, dim3(B * h * w), dim3(256), 0, st, coarse, embed,
-                               (const float*)ws_f, (const float*)stats, (f16_raw*)dcoarse, B, h, w, E, ldc, c0, K, KP);
+#define SZN_FH_GATHER(T, MS)                                                                                         \
+    hipLaunchKernelGGL((fh_gather_kernel<T, MS>), dim3(B * h * w), dim3(256), 0, st, coarse, embed, (const float*)ws_f, \
+                       (const float*)stats, (T*)dcoarse, B, h, w, E, ldc, c0, K, KP)
+#define SZN_FH_GATHER_T(T)                                                                                           \
+    do {                                                                                                             \
+        if (mse) SZN_FH_GATHER(T, true);                                                                             \
+        else SZN_FH_GATHER(T, false);                                                                                \
+    } while (0)
+        if (dcoarse_dtype == SZN_F32) SZN_FH_GATHER_T(float);
+        else if (dcoarse_dtype == SZN_BF16) SZN_FH_GATHER_T(bf16_raw);
+        else if (dcoarse_dtype == SZN_F16) SZN_FH_GATHER_T(f16_raw);
         else
             SZN_FAIL(SZN_ERR_ARG, "fused_head: bad dcoarse_dtype %d", dcoarse_dtype);
+#undef SZN_FH_GATHER_T
+#undef SZN_FH_GATHER
         SZN_CHECK_LAUNCH("fh_gather_kernel");
     }
     return SZN_OK;
@@ -660,4 +782,25 @@ extern "C" int szn_fused_head_grouped_prepared(int stride, int B, int h, int w, 
                                                szn_stream_t stream) {
     return fused_head_impl(stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype, dcoarse,
                            workspace, stream, false, unseen, group_mode, group_map);
+}
+
+// The MSE embedding loss (train.py -loss mse; trainer_fcn.py forward / forward_szn -> utils.py:50-73 mse_loss) through the same head:
+// szn_bilinear_up_crop_fwd -> szn_mse_loss_fwd -> szn_embed_argmax_k -> szn_mse_loss_bwd -> szn_bilinear_up_crop_bwd without the score.
+// Arguments, NULL rules, error codes, workspace (szn_fused_head_workspace_bytes) and prepare step (szn_fused_head_prepare) of
+// szn_fused_head_grouped[_prepared]; pred is that head's pred bit for bit.
+extern "C" int szn_fused_mse_head(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                                  const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
+                                  int group_mode, const int64_t* group_map, float* loss, float* stats, int64_t* pred,
+                                  int dcoarse_dtype, void* dcoarse, void* workspace, szn_stream_t stream) {
+    return fused_head_impl(stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype, dcoarse,
+                           workspace, stream, true, unseen, group_mode, group_map, true);
+}
+
+extern "C" int szn_fused_mse_head_prepared(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                                           const float* coarse, const float* embed, const int64_t* target,
+                                           const szn_class_set* unseen, int group_mode, const int64_t* group_map, float* loss,
+                                           float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
+                                           szn_stream_t stream) {
+    return fused_head_impl(stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype, dcoarse,
+                           workspace, stream, false, unseen, group_mode, group_map, true);
 }

@@ -389,8 +389,8 @@ class TrainStep(object):
         size_average=False): K = C = model.n_class classes, the head is szn_fused_ce_head (fused_head=False: upscore -> szn_ce2d_fwd
         -> szn_ce2d_bwd -> head_backward), the prediction is the channel argmax; class_weight = optional [C] class weights.  Under
         data parallelism the update uses the mean of the rank gradients, as allreduce_param_grads gives the autograd route."""
-        if loss not in ("cos", "mse", "cross_entropy") or (fused_head and loss == "mse"):
-            raise L.SznError("TrainStep: fused head supports the cosine and cross-entropy losses; use fused_head=False for mse")
+        if loss not in ("cos", "mse", "cross_entropy"):
+            raise L.SznError("TrainStep: loss must be 'cos', 'mse' or 'cross_entropy', got %r" % (loss,))
         self.ce = loss == "cross_entropy"
         if self.ce and (embeddings is not None or forced_unseen is not None):
             raise L.SznError("TrainStep: the cross-entropy head takes no embeddings and no forced_unseen classes")
@@ -444,7 +444,7 @@ class TrainStep(object):
         if self.forced_unseen is not None and any(not 0 <= k < self.K for k in self.forced_unseen):
             raise L.SznError("TrainStep: forced_unseen names a class outside [0, %d)" % self.K)
         self._unseen_cs = L.class_set(self.forced_unseen) if self.forced_unseen is not None else None
-        self._group = 0 if self.forced_unseen is None else 2          # heads.cosine group mode: plain / forced unseen
+        self._group = 0 if self.forced_unseen is None else 2          # heads.embed group mode: plain / forced unseen
         # static loss scaling for the fp16 path: gradients below 6e-8 vanish in IEEE half, so d(loss)/d(coarse) is multiplied
         # by loss_scale in fp32 before it enters the 16-bit backward pass and the optimizer kernel divides it out again
         # (grad_scale).  The .grad views then hold loss_scale x gradient.  bf16 / fp32 need none.
@@ -452,7 +452,14 @@ class TrainStep(object):
         # gradients (|d| <= 1 per class) of the up to (2 S)^2 pixels its taps reach -- ~1e3 at stride 32, 2^18 x B times the
         # 1/(B N)-scaled cosine gradient.  4096 x that overflows IEEE half (65504) at the head already, so the CE step starts at
         # scale 1 (its gradients are far above fp16's subnormal range) and may back off below 1 (floor 2^-8) if a batch overflows.
-        fp16_scale0 = 1.0 if self.ce else 4096.0
+        # The MSE head's gradient is 2 (s - e) x the same geometric factor S^2 / (B N_b): linear in the residual and not bounded by
+        # 1 / |s| as the cosine's is.  A trained net's residual is below 1 (cosine-sized gradients); a freshly initialised head
+        # emits scores of order 1e3.  The worst case for overflow is a SMALL batch of small images, where S^2 / (B N_b) is largest:
+        # at B N_b / S^2 = 18 (two 96 x 96 images) 512 is the largest power of two that keeps the scaled head gradient under 65504
+        # for per-channel residuals up to 2^10.  At the product shape (eight 512 x 512 images) the factor is ~450 x smaller, 512 is
+        # merely conservative there and the dynamic scale grows (x2 per 2000 clean steps); too high a start costs skipped steps
+        # at once, too low a start only resolution that growth wins back.
+        fp16_scale0 = 1.0 if self.ce else (512.0 if loss == "mse" else 4096.0)
         self._loss_scale0 = float(loss_scale) if loss_scale is not None else (fp16_scale0 if precision == torch.float16 else 1.0)
         # dynamic loss scaling (default for fp16): the scale, the overflow flag and the count of APPLIED optimizer steps live
         # on the device (include/szn.h, szn_grad_check_finite / szn_*_step_scaled / szn_loss_scale_update); a step whose
@@ -738,8 +745,8 @@ class TrainStep(object):
             heads.ce(stride, fmap, self.K, H, W, pred, target, self.class_weight, self.size_average, self.loss, stats, dmap,
                      ws=self.head_ws, stream=st)
         else:
-            heads.cosine(stride, fmap, self.emb, H, W, pred, target, self.loss, stats, dmap, self._group, self._unseen_cs,
-                         ws=self.head_ws, stream=st)
+            heads.embed(self.loss_kind, stride, fmap, self.emb, H, W, pred, target, self.loss, stats, dmap, self._group,
+                        self._unseen_cs, ws=self.head_ws, stream=st)
 
     def _dcoarse_buffer(self, ctx):
         """d(loss)/d(coarse) of the fused head: it writes channels [0, E) and the padding channels stay zero, so the buffer of the

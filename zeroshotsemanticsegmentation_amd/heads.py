@@ -1,9 +1,12 @@
-"""heads.py -- the host side of the fused heads: every call into szn_fused_head_grouped[_prepared], szn_fused_ce_head and
-szn_seenmask_head_k goes through here (models.FCN32s / FCN8s predict methods, engine.TrainStep, engine.SeenmaskStep).
+"""heads.py -- the host side of the fused heads: every call into szn_fused_head_grouped[_prepared], szn_fused_mse_head[_prepared],
+szn_fused_ce_head and szn_seenmask_head_k goes through here (models.FCN32s / FCN8s predict methods, engine.TrainStep, engine.SeenmaskStep).
 
+  embed     the embedding head, kind "cos" | "mse" (wrappers cosine / cosine_predict, mse / mse_predict):
   cosine    loss, stats, nearest-embedding prediction and d(map) from an NHWC map: stride 32 on the 1/32 map, stride 8 on FCN8s'
             1/8 fused map (fp32).  Group mode 0 = plain (szn_fused_head_grouped launches exactly what szn_fused_head_strided
             launches, bit for bit), 1 = seen / unseen group from the seen-mask prediction, 2 = forced unseen (group from the target).
+  mse       the same head with the MSE embedding loss (szn_fused_mse_head): same arguments, same prediction bit for bit, same
+            Workspace tables; loss, stats and d(map) are those of sum |s - e_label|^2 / N_b.
   ce        the softmax cross-entropy head, stride 32 or 8.
   seenmask  the x32 seen-mask head on the 1/32 map: training, predict and pred-only (group map) calls.
 
@@ -75,32 +78,62 @@ def _outputs(B, H, W, device, target):
     return pred, target.to(device=device, dtype=torch.int64).contiguous(), torch.empty(1, device=device)
 
 
-# ---- cosine head ----------------------------------------------------------------------------------------------------------
-def cosine(stride, fmap, emb, H, W, pred, target=None, loss=None, stats=None, dmap=None, mode=0, classes=None, gmap=None,
-           ws=None, stream=None):
-    """szn_fused_head_grouped on the contiguous NHWC map `fmap` (the E embedding channels first).  target / loss / stats go
-    together; dmap (zero-padded, [E, ld) stays untouched) receives d loss / d fmap in its dtype.  classes = the unseen class set
-    (L.class_set) of modes 1 / 2, gmap the group map of mode 1.  ws: a Workspace (its embedding tables are reused) or None."""
+# ---- embedding heads (cosine | mse) -----------------------------------------------------------------------------------------
+_EMBED_ENTRY = {"cos": "szn_fused_head_grouped", "mse": "szn_fused_mse_head"}      # both share workspace and prepare step
+
+
+def embed_kind(loss):
+    """the embedding heads' loss argument checked: "cos" | "mse" """
+    if loss not in _EMBED_ENTRY:
+        raise L.SznError("embedding head: loss must be 'cos' or 'mse', got %r" % (loss,))
+    return loss
+
+
+def embed(kind, stride, fmap, emb, H, W, pred, target=None, loss=None, stats=None, dmap=None, mode=0, classes=None, gmap=None,
+          ws=None, stream=None):
+    """szn_fused_head_grouped (kind "cos") / szn_fused_mse_head (kind "mse") on the contiguous NHWC map `fmap` (the E embedding
+    channels first).  target / loss / stats go together; dmap (zero-padded, [E, ld) stays untouched) receives d loss / d fmap in its
+    dtype.  classes = the unseen class set (L.class_set) of modes 1 / 2, gmap the group map of mode 1.  ws: a Workspace (its
+    embedding tables are reused, whichever kind wrote them) or None."""
     B, h, w, ld = fmap.shape
     K, E = emb.shape
     st = L.stream_ptr() if stream is None else stream
     nbytes = L.load().szn_fused_head_workspace_bytes(B, h, w, E, K)
+    fn = _EMBED_ENTRY[kind]
     if ws is None:
-        fn, buf = "szn_fused_head_grouped", _scratch(nbytes, fmap.device)
+        buf = _scratch(nbytes, fmap.device)
     else:
-        fn, buf = "szn_fused_head_grouped_prepared", ws.prepared(nbytes, emb, K, E, st)
+        fn, buf = fn + "_prepared", ws.prepared(nbytes, emb, K, E, st)
     code = L.dtype_code(dmap.dtype) if dmap is not None else L.SZN_F32
     L.call(fn, stride, B, h, w, E, ld, 0, H, W, _CROP[stride], K, L.ptr(fmap), L.ptr(emb), L.ptr(target), classes, mode,
            L.ptr(gmap), L.ptr(loss), L.ptr(stats), L.ptr(pred), code, L.ptr(dmap), L.ptr(buf), st)
 
 
-def cosine_predict(stride, fmap, emb, H, W, target=None, mode=0, unseen=None, gmap=None):
-    """forward-only cosine head -> (loss 0-dim tensor or None, pred (B,H,W) int64)"""
+def embed_predict(kind, stride, fmap, emb, H, W, target=None, mode=0, unseen=None, gmap=None):
+    """forward-only embedding head -> (loss 0-dim tensor or None, pred (B,H,W) int64)"""
     B = fmap.shape[0]
     pred, tgt, loss = _outputs(B, H, W, fmap.device, target)
     stats = None if loss is None else torch.empty(B, 2, device=fmap.device)
-    cosine(stride, fmap, emb, H, W, pred, tgt, loss, stats, mode=mode, classes=L.class_set(unseen), gmap=gmap)
+    embed(kind, stride, fmap, emb, H, W, pred, tgt, loss, stats, mode=mode, classes=L.class_set(unseen), gmap=gmap)
     return (loss.reshape(()) if loss is not None else None), pred
+
+
+def cosine(*args, **kw):
+    """embed("cos", ...): the cosine loss (utils.cosine_loss)"""
+    embed("cos", *args, **kw)
+
+
+def cosine_predict(*args, **kw):
+    return embed_predict("cos", *args, **kw)
+
+
+def mse(*args, **kw):
+    """embed("mse", ...): the MSE loss (utils.mse_loss) -- same arguments, same pred"""
+    embed("mse", *args, **kw)
+
+
+def mse_predict(*args, **kw):
+    return embed_predict("mse", *args, **kw)
 
 
 # ---- softmax cross-entropy head -------------------------------------------------------------------------------------------

@@ -1388,17 +1388,19 @@ class FCN32s(nn.Module):
         ctx = self._engine.forward(x.detach() if isinstance(x, torch.Tensor) else x, train=False, keep=False)
         return ctx, 32, ctx.coarse
 
-    def embed_predict(self, x, embeddings, target=None):
+    def embed_predict(self, x, embeddings, target=None, loss="cos"):
         """forward pass + nearest-class-embedding prediction (+ cosine loss when `target` is given) WITHOUT materialising the
         (B,E,H,W) score: the fused-from-coarse head (szn_fused_head) evaluates upscore + crop (models.py:146-147), cosine_loss
         (utils.py:75-102) and infer_lbl (utils.py:159-185) per 32x32 cell of the 1/32 map (FCN8s: per 8x8 cell of the 1/8
         fused map).  -> (loss 0-dim tensor or None, pred (B,H,W) int64 device tensor), the prediction also in self._last_pred.
         Same numbers as `forward` + utils up to rounding order (class assignment differs only on pixels whose top-2 cosine margin
-        is < 1e-5).  Used by Trainer.validate."""
+        is < 1e-5).  loss="mse": the loss is utils.mse_loss's (utils.py:50-73, szn_fused_mse_head); the prediction is the same, bit
+        for bit.  Used by Trainer.validate."""
+        kind = heads.embed_kind(loss)
         with torch.no_grad():
             ctx, stride, fmap = self._head_map(x)
             emb = heads.embeddings(embeddings, self.n_class, fmap.device)
-            loss, self._last_pred = heads.cosine_predict(stride, fmap, emb, ctx.H, ctx.W, target)
+            loss, self._last_pred = heads.embed_predict(kind, stride, fmap, emb, ctx.H, ctx.W, target)
         return loss, self._last_pred
 
     def softmax_predict(self, x, target=None, weight=None):
@@ -1431,6 +1433,15 @@ class FCN32s(nn.Module):
         mode=1) up to rounding order (class assignment differs only on pixels whose top-2 cosine margin in the group is < 1e-5;
         the seen-mask decision is bit-identical).  FCN8s: the seen-mask head keeps its x32 geometry on the backbone's 1/32 map
         (as forward(mode='both')), the grouped head runs over the 8x8 cells of the 1/8 fused map.  Used by Trainer.validate."""
+        return self._szn_predict(x, embeddings, unseen, target, group, "cos")
+
+    def szn_predict_mse(self, x, embeddings, unseen, target=None, group='seenmask'):
+        """szn_predict for a network trained with the MSE loss (train.py -loss mse): the same class assignment bit for bit, the loss
+        is utils.mse_loss's (utils.py:50-73, szn_fused_mse_head).  A method of its own because szn_predict's parameter list is a
+        pinned part of the public interface."""
+        return self._szn_predict(x, embeddings, unseen, target, group, "mse")
+
+    def _szn_predict(self, x, embeddings, unseen, target, group, kind):
         mode = self._szn_group(group, target)
         with torch.no_grad():
             ctx, stride, fmap = self._head_map(x)
@@ -1438,7 +1449,7 @@ class FCN32s(nn.Module):
             self._last_group = None
             if mode == 1:
                 self._last_group = heads.seenmask_group(ctx.coarse, self.n_class, self._engine._images["up.w"], ctx.H, ctx.W)
-            return heads.cosine_predict(stride, fmap, emb, ctx.H, ctx.W, target, mode, unseen, self._last_group)
+            return heads.embed_predict(kind, stride, fmap, emb, ctx.H, ctx.W, target, mode, unseen, self._last_group)
 
     def seenmask_predict(self, x, target, n_class, unseen):
         """forward pass + seen-mask loss and prediction WITHOUT the (B,2,H,W) score: szn_seenmask_head evaluates the learned
@@ -1585,12 +1596,12 @@ class _Up8Crop(torch.autograd.Function):
 
 
 class _FusedHead8(torch.autograd.Function):
-    """upscore8 + crop + cosine loss + nearest-embedding prediction straight from the 1/8 fused map (heads.cosine at stride 8,
+    """upscore8 + crop + cosine loss + nearest-embedding prediction straight from the 1/8 fused map (heads.embed at stride 8,
     8x8 cells): the (B,E,H,W) score and its gradient never exist in HBM.  forward -> loss (0-dim); the prediction is left in
     model._last_pred; backward hands back d loss / d map, which the kernel produced in the same pass."""
 
     @staticmethod
-    def forward(ctx, model, x, emb, target, H, W, want_grad):
+    def forward(ctx, model, x, emb, target, H, W, want_grad, kind="cos"):
         x = x.contiguous()
         B, h, w, ld = x.shape
         dev = x.device
@@ -1598,14 +1609,14 @@ class _FusedHead8(torch.autograd.Function):
         loss = torch.empty(1, device=dev)
         stats = torch.empty(B, 2, device=dev)
         dx = torch.zeros(B, h, w, ld, device=dev, dtype=torch.float32) if want_grad else None
-        heads.cosine(8, x, emb, H, W, pred, target, loss, stats, dx)
+        heads.embed(kind, 8, x, emb, H, W, pred, target, loss, stats, dx)
         ctx.dx = dx
         model._last_pred = pred
         return loss.reshape(())
 
     @staticmethod
     def backward(ctx, g):
-        return None, ctx.dx * g, None, None, None, None, None
+        return None, ctx.dx * g, None, None, None, None, None, None
 
 
 class FCN8s(FCN32s):
@@ -1685,14 +1696,15 @@ class FCN8s(FCN32s):
         or None, pred (B,H,W) int64); see FCN32s.softmax_predict"""
         return super(FCN8s, self).softmax_predict(x, target, weight)
 
-    def embed_loss(self, x, embeddings, target, dropout_masks=None):
+    def embed_loss(self, x, embeddings, target, dropout_masks=None, loss="cos"):
         """training-time fused head: -> (cosine loss with autograd history, pred (B,H,W) int64).  Same numbers as
         utils.cosine_loss(self(x), target, embeddings) / utils.infer_lbl_device up to rounding order, without the
-        (B,E,H,W) score or its gradient in HBM."""
+        (B,E,H,W) score or its gradient in HBM.  loss="mse": utils.mse_loss instead (szn_fused_mse_head)."""
+        kind = heads.embed_kind(loss)
         emb = heads.embeddings(embeddings, self.n_class, x.device)
         _, fuse3 = self._fuse(x, self.training, dropout_masks)
         tgt = target.to(device=x.device, dtype=torch.int64).contiguous()
-        loss = _FusedHead8.apply(self, fuse3, emb, tgt, x.shape[2], x.shape[3], torch.is_grad_enabled())
+        loss = _FusedHead8.apply(self, fuse3, emb, tgt, x.shape[2], x.shape[3], torch.is_grad_enabled(), kind)
         return loss, self._last_pred
 
 

@@ -176,16 +176,21 @@ def freeze_for_seenmask(model):
         p.requires_grad = True
 
 
+def check_precision(precision, cfg):
+    """--precision fp16 trains only where loss scaling exists: the fused steps (engine.TrainStep / SeenmaskStep; see
+    trainer_fcn.Trainer.train_epoch) -- an embedding configuration with fcn_loss 'cos' or 'mse', or the softmax configuration"""
+    fused_cfg = (cfg['fcn_loss'] in ('cos', 'mse') and cfg['embed_dim']) or (cfg['fcn_loss'] == 'cross_entropy' and not cfg['embed_dim'])
+    if precision == 'fp16' and cfg['mode'] == 'train' and cfg['fcn_epochs'] > 0 and not fused_cfg:
+        raise Exception("--precision fp16 needs the fused training step: embedding configuration with fcn_loss 'cos' or 'mse', or "
+                        "the softmax configuration (fcn_loss 'cross_entropy', no embedding) (got loss %r, embed_dim %r); use bf16 "
+                        "or fp32" % (cfg['fcn_loss'], cfg['embed_dim']))
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     cfg = update_cfg_with_args(configurations[args.config], args)
     validate_cfg(cfg)
-    fused_cfg = (cfg['fcn_loss'] == 'cos' and cfg['embed_dim']) or (cfg['fcn_loss'] == 'cross_entropy' and not cfg['embed_dim'])
-    if args.precision == 'fp16' and cfg['mode'] == 'train' and cfg['fcn_epochs'] > 0 and not fused_cfg:
-        # loss scaling lives in the fused steps only (engine.TrainStep / SeenmaskStep); see trainer_fcn.Trainer.train_epoch
-        raise Exception("--precision fp16 needs the fused training step: embedding configuration with fcn_loss 'cos' or the "
-                        "softmax configuration (fcn_loss 'cross_entropy', no embedding) (got loss %r, embed_dim %r); use bf16 "
-                        "or fp32" % (cfg['fcn_loss'], cfg['embed_dim']))
+    check_precision(args.precision, cfg)
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", str(args.gpu)))

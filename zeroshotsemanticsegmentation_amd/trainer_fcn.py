@@ -159,8 +159,9 @@ class Trainer(object):
         return fcn_score, loss, lbl_pred, target.detach().cpu()
 
     # ---- training --------------------------------------------------------------------------------------------
-    def _cos_cfg(self):
-        return bool(self.pixel_embeddings) and self.loss_func == "cos"
+    def _embed_cfg(self):
+        """an embedding configuration whose loss has a fused head: cosine or mse (train.py -loss cos | mse)"""
+        return bool(self.pixel_embeddings) and self.loss_func in ("cos", "mse")
 
     def _ce_cfg(self):
         """the softmax configuration (train.py -c 1): cross entropy over the model's own n_class channels, at most 256 classes"""
@@ -168,10 +169,10 @@ class Trainer(object):
                 and self.model.n_class == self.n_class)
 
     def _fast_step(self):
-        """engine.TrainStep when the configuration allows it: embedding cosine loss (forced_unseen: the step's prediction is the
+        """engine.TrainStep when the configuration allows it: embedding cosine or mse loss (forced_unseen: the step's prediction is the
         forced-unseen one, trainer_fcn.py:110-112) or the softmax cross entropy (_ce_cfg), and an optimizer with exactly the reference's two parameter groups
         (train.py:126-133: all Conv2d weights | all Conv2d biases).  Hyper-parameters are read per group from the optimizer object; any other wiring keeps the autograd path."""
-        if self._step is not None or not (self._fused_step and (self._cos_cfg() or self._ce_cfg())):
+        if self._step is not None or not (self._fused_step and (self._embed_cfg() or self._ce_cfg())):
             return self._step
         from .optim import FusedAdam, FusedSGD
         from .models import opt_layers
@@ -197,7 +198,7 @@ class Trainer(object):
             # the softmax FCN (train.py -c 1): fused cross-entropy head, summed loss (self._loss), channel-argmax prediction
             kw.update(loss="cross_entropy", size_average=False)
         else:
-            kw.update(embeddings=self.embeddings, forced_unseen=self.unseen if self.forced_unseen else None)
+            kw.update(embeddings=self.embeddings, forced_unseen=self.unseen if self.forced_unseen else None, loss=self.loss_func)
         self._step = _engine.TrainStep(self.model, lr=gw['lr'], bias_lr=gb['lr'],
                                        bias_weight_decay=gb.get('weight_decay', 0.0), precision=self.precision,
                                        fused_head=True, keep_grads=os.environ.get("SZN_KEEP_GRADS", "0") == "1", **kw)
@@ -212,10 +213,10 @@ class Trainer(object):
         step = self._fast_step()
         if step is None and self.model._engine.dtype == torch.float16:
             # IEEE-half gradients need loss scaling, which only engine.TrainStep applies (d(coarse) is multiplied in fp32 before
-            # it enters the 16-bit backward pass); the autograd paths (mse / cross_entropy losses, non-reference optimizer
-            # wiring) would push ~1e-7-sized activation gradients through fp16 unscaled and lose them silently
-            raise RuntimeError("precision fp16 is only supported on the fused training step (embedding cosine loss, reference "
-                               "optimizer wiring); use bf16 or fp32 for this configuration")
+            # it enters the 16-bit backward pass); the autograd paths (non-reference optimizer wiring, more than 256 classes)
+            # would push ~1e-7-sized activation gradients through fp16 unscaled and lose them silently
+            raise RuntimeError("precision fp16 is only supported on the fused training step (embedding cosine / mse loss or "
+                               "softmax cross entropy, reference optimizer wiring); use bf16 or fp32 for this configuration")
         for batch_idx, (data, target) in enumerate(self.train_loader):
             if step is not None:
                 data, target, _ = self._unpack(data, target)
@@ -230,11 +231,11 @@ class Trainer(object):
                 metrics = utils._hist_to_metrics(packed[1:].reshape(self.n_class, self.n_class))
                 gsum = float('nan')                  # not read back on this path (a host sync per iteration for a debug print)
                 ssum = float('nan')                  # the (B,E,H,W) score is never materialised on this path
-            elif (hasattr(self.model, 'embed_loss') and self._fused_step and self.pixel_embeddings and self.loss_func == "cos"
+            elif (hasattr(self.model, 'embed_loss') and self._fused_step and self._embed_cfg()
                   and not self.forced_unseen and self.embeddings.shape[0] <= 256):
                 # FCN8s: autograd chain with the fused-from-1/8-map head (no (n,E,h,w) score), per-tensor fused optimizer
                 data, target, _ = self._unpack(data, target)
-                loss, pred = self.model.embed_loss(data, self.embeddings, target)
+                loss, pred = self.model.embed_loss(data, self.embeddings, target, loss=self.loss_func)
                 self.optim.zero_grad()
                 loss.backward()
                 _engine.allreduce_param_grads([p for g in self.optim.param_groups for p in g['params']])
@@ -271,17 +272,17 @@ class Trainer(object):
     def _predict_device(self, data, target, szn):
         """forward + loss + class assignment with everything left on the GPU -> (score, loss 0-dim, pred (n,h,w), target)"""
         data, target, target_embed = self._unpack(data, target)
-        if (self.pixel_embeddings and self.loss_func == "cos" and not szn and not self.forced_unseen and target_embed is None
+        if (self._embed_cfg() and not szn and not self.forced_unseen and target_embed is None
                 and not self.verbose_val and self.embeddings.shape[0] <= 256):
             # plain embedding inference: loss + class assignment straight from the 1/32 map (no (n,E,h,w) score in HBM)
-            loss, pred = self.model.embed_predict(data, self.embeddings, target)
+            loss, pred = self.model.embed_predict(data, self.embeddings, target, loss=self.loss_func)
             return None, loss, pred, target
-        if (self.pixel_embeddings and self.loss_func == "cos" and (szn or self.forced_unseen) and target_embed is None
+        if (self._embed_cfg() and (szn or self.forced_unseen) and target_embed is None
                 and not self.verbose_val and self.embeddings.shape[0] <= 256):
             # full SZN network (seen-mask-stitched) or forced-unseen inference, same route: the seen-mask group (or the target's)
             # picks the class subset per pixel inside the fused head -- neither (n,E,h,w) nor (n,2,h,w) score in HBM
-            loss, pred = self.model.szn_predict(data, self.embeddings, self.unseen, target,
-                                                group='seenmask' if szn else 'target')
+            predict = self.model.szn_predict if self.loss_func == "cos" else self.model.szn_predict_mse
+            loss, pred = predict(data, self.embeddings, self.unseen, target, group='seenmask' if szn else 'target')
             return None, loss, pred, target
         if self._ce_cfg() and self._fused_step and not szn and not self.verbose_val:
             # softmax inference: summed cross entropy + channel argmax straight from the coarse map (no (n,C,h,w) score in HBM)
