@@ -15,15 +15,11 @@
 // the prediction and the loss terms are bit-identical to the materialised chain.  d(coarse) is accumulated as the per-cell table
 // A[t][c] = sum_px w_t(px) * d_c(px): a lane sums over its own pixels, a reduce-scatter butterfly sums the wave (7 shuffles per
 // class for the 4 taps), the waves of a cell are combined through LDS in a fixed order.  A gather kernel sums the <= 4 cells that
-// use each coarse position.  Loss partials are doubles per cell, combined in a fixed order by a one-block finalize kernel, which
+// use each coarse position.  Bilinear weights and tap <-> position mappings: szn_upcell.h.  Loss partials are doubles per cell, combined in a fixed order by a one-block finalize kernel, which
 // also forms the 1/N of size_average (the gradient is linear in it: the cell pass runs with N = 1).  No atomics anywhere.
-#include "szn_common.h"
+#include "szn_upcell.h"
 
 namespace {
-
-// 1-D bilinear tap of get_upsampling_weight(k = 2 S), in double -- the formula of szn_head.hip's bil1d (models.py:13-20)
-template <int S>
-__device__ __forceinline__ double ce_bil1d(int t) { return 1.0 - fabs((double)t - ((double)S - 0.5)) / (double)S; }
 
 struct CeGeom {
     int B, h, w, C, ldc, c0, H, W, crop;
@@ -82,7 +78,7 @@ __global__ __launch_bounds__(256) void ce_cell_kernel(const float* __restrict__ 
     float* taps = lds + (long)lc * 4 * C;
     for (int k = ct; k < 4 * C; k += TPC) {
         const int c = k >> 2, tap = k & 3;
-        const int i = I - 1 + (tap >> 1), j = J - 1 + (tap & 1);
+        const int i = tap_i(I, tap), j = tap_j(J, tap);
         taps[k] = (active && i >= 0 && i < g.h && j >= 0 && j < g.w) ? coarse[(((long)b * g.h + i) * g.w + j) * g.ldc + g.c0 + c] : 0.f;
     }
     __syncthreads();
@@ -97,9 +93,7 @@ __global__ __launch_bounds__(256) void ce_cell_kernel(const float* __restrict__ 
         const int p = ct + TPC * r, ty = p / S, tx = p % S;
         const int y = S * I + ty - g.crop, x = S * J + tx - g.crop;
         inb[r] = active && y >= 0 && y < g.H && x >= 0 && x < g.W;
-        const double fx1 = ce_bil1d<S>(tx), fx0 = ce_bil1d<S>(tx + S);
-        const double fy1 = ce_bil1d<S>(ty), fy0 = ce_bil1d<S>(ty + S);
-        wt[r][0] = (float)(fy0 * fx0); wt[r][1] = (float)(fy0 * fx1); wt[r][2] = (float)(fy1 * fx0); wt[r][3] = (float)(fy1 * fx1);
+        cell_weights<S>(ty, tx, wt[r]);
         pix[r] = inb[r] ? ((long)b * g.H + y) * g.W + x : 0;
         lbl[r] = -1;
         if (target && inb[r]) {
@@ -184,7 +178,7 @@ __global__ __launch_bounds__(256) void ce_cell_kernel(const float* __restrict__ 
     const long cid = ce_cell_id(g, b, I, J);
     if (ct == 0) {
         double s = dred[wave][0], n = dred[wave][1];
-        if (TPC == 256) { s = (dred[0][0] + dred[1][0]) + (dred[2][0] + dred[3][0]); n = (dred[0][1] + dred[1][1]) + (dred[2][1] + dred[3][1]); }
+        if (TPC == 256) { s = combine4(dred[0][0], dred[1][0], dred[2][0], dred[3][0]); n = combine4(dred[0][1], dred[1][1], dred[2][1], dred[3][1]); }
         cellL[cid * 2] = s;
         cellL[cid * 2 + 1] = n;
     }
@@ -193,7 +187,7 @@ __global__ __launch_bounds__(256) void ce_cell_kernel(const float* __restrict__ 
         float* out = cellA + cid * 4 * C;
         for (int k = ct; k < 4 * C; k += TPC) {
             float v;
-            if (TPC == 256) v = (red[k] + red[4 * C + k]) + (red[8 * C + k] + red[12 * C + k]);
+            if (TPC == 256) v = combine4(red[k], red[4 * C + k], red[8 * C + k], red[12 * C + k]);
             else v = red[(long)wave * 4 * C + k];
             out[k] = v;
         }
@@ -220,8 +214,8 @@ __global__ __launch_bounds__(256) void ce_finalize_kernel(const double* __restri
         __syncthreads();                     // the previous image's readers are done with sh
         if ((t & 63) == 0) { sh[t >> 6][0] = s; sh[t >> 6][1] = n; }
         __syncthreads();
-        s = (sh[0][0] + sh[1][0]) + (sh[2][0] + sh[3][0]);
-        n = (sh[0][1] + sh[1][1]) + (sh[2][1] + sh[3][1]);
+        s = combine4(sh[0][0], sh[1][0], sh[2][0], sh[3][0]);
+        n = combine4(sh[0][1], sh[1][1], sh[2][1], sh[3][1]);
         if (t == 0 && stats) { stats[2 * b] = (float)s; stats[2 * b + 1] = (float)n; }
         tot += s;
         totn += n;
@@ -247,14 +241,12 @@ __global__ __launch_bounds__(256) void ce_gather_kernel(const float* __restrict_
     float acc = 0.f;
 #pragma unroll
     for (int tap = 0; tap < 4; ++tap) {
-        const int I = i + 1 - (tap >> 1), J = j + 1 - (tap & 1);         // (i, j) is tap (di, dj) of cell (i + 1 - di, j + 1 - dj)
+        const int I = tap_cell_I(i, tap), J = tap_cell_J(j, tap);
         if (I < g.I0 || I >= g.I0 + g.nI || J < g.J0 || J >= g.J0 + g.nJ) continue;
         acc += cellA[(ce_cell_id(g, b, I, J) * 4 + tap) * g.C + c];
     }
     elem<T>::st(dcoarse + pos * g.ldc + g.c0 + c, acc * gscale[0]);
 }
-
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 size_t ce_cells(int B, int h, int w) { return (size_t)B * (h + 1) * (w + 1); }
 

@@ -2,7 +2,7 @@
 // materialising the (B,E,H,W) score: bilinear x32 upsample + crop (models.py:146-147), cosine loss
 // (utils.py:75-102), nearest-class-embedding argmax (utils.py:159-185) and the gradient back to the
 // coarse map, per 32x32 output cell.  The same kernels are instantiated for stride 8 (8x8 cells of the 1/8 map: the last
-// stage of the FCN8s skip head, upscore8 + crop 31).
+// stage of the FCN8s skip head, upscore8 + crop 31).  The cell geometry (bilinear weights, tap <-> position) is szn_upcell.h's.
 //
 // Inside one cell (Y / S, X / S fixed) every pixel's score vector is a blend of the SAME four coarse
 // vectors C_t with per-pixel bilinear weights w_t, so
@@ -13,10 +13,15 @@
 //                                                         Bm[t][t'] = sum_px w_t w_t' cos / |s|^2
 // (all scaled by 1/(B N_b)).  HBM traffic: labels in, prediction out (16 B/px) + the coarse map.
 //
-// Kernel 1 (cell kernel): one block per (image, cell): builds G, Q, walks its <= 1024 pixels, writes pred,
-//   the cell's loss partial, A and Bm.  All reductions are fixed-order (bit-reproducible).
-// Kernel 2: loss_finalize (per-image sums, fixed order).  Kernel 3 (gather): one block per coarse
-//   position sums the contributions of the <= 4 cells that use it as a tap and writes dcoarse.
+// Kernels, in launch order (all reductions are fixed-order: bit-reproducible):
+//   fh_prep_kernel       the class matrix transposed + its norms, to the head of the workspace (szn_fused_head_prepare, or every call)
+//   fh_cell_kernel       stride 32: one block per (image, cell) builds G, Q from the four tap vectors, walks its 1024 pixels
+//   fh_tables_kernel     stride 8: per-POSITION tables D, N, from which ...
+//   fh_cell_tab_kernel   ... one wave per 8x8 cell looks its G, Q up, then walks its 64 pixels
+//   fh_image_sums_kernel per-image sums of the cells' loss partials -> stats;  fh_finalize_kernel: the images -> loss
+//   fh_gather_kernel     one block per coarse position sums the <= 4 cells that use it as a tap and writes dcoarse
+// Both cell kernels run the same per-pixel body (fh_pixel) and the same label loop (fh_scatter_A), and write per cell: pred, the
+// loss partial, A and Bm.
 //
 // MSE variant (template flag MSE; szn_fused_mse_head, utils.py:50-73): L_b = sum_px |s - e_lbl|^2 / N_b.  Prediction, G, Q and the
 // grouped modes are the cosine head's, bit for bit.  The gradient has the same shape with per-pixel coefficients 1,
@@ -25,12 +30,12 @@
 // |s|^2 - 2 s.e + |e|^2: that cancels once the net has learnt something (2e-2 of a cell's loss at C = e + 1e-3 |e| noise in fp32).
 // Layout chosen instead: the bilinear weights of a pixel sum to exactly 1 (multiples of 1/(2S)^2), so s - e_k = sum_t w_t (C_t - e_k) and
 //     |s - e_k|^2 = sum_{t,u} w_t w_u P_k[t][u],   P_k[t][u] = (C_t - e_k) . (C_u - e_k)      (10 distinct dot products of length E)
-// built from the vectors (differences first, then products: nothing large is subtracted) only for the classes that occur in the
-// cell; missing border taps are C_t = 0.  Stride 32: a first pass over the block's labels marks the classes present in
+// built from the vectors (fh_pk: differences first, then products: nothing large is subtracted) only for the classes that occur in
+// the cell; missing border taps are C_t = 0.  Stride 32: a first pass over the block's labels marks the classes present in
 // LDS, the four waves share the present classes round-robin and store P_k in LDS [KP][10] (each class built once per cell).
 // Stride 8: one wave owns the cell and already visits its labels class by class for A, so P_k lives in registers for the duration
 // of that class's turn, read from the coarse vectors themselves (the per-position tables D, N would only give the cancelling form).
-#include "szn_common.h"
+#include "szn_upcell.h"
 
 namespace {
 
@@ -49,33 +54,52 @@ __device__ __forceinline__ float mse_px(const float (&wt)[4], const float* P) {
     return l;
 }
 
-template <int S>
-__device__ __forceinline__ double bil1d(int t) { return 1.0 - fabs((double)t - ((double)S - 0.5)) / (double)S; }
+// P_k of one class (row ek of the class matrix) by one wave: 64 strided partial chains + xor butterfly; tap(t, c) is C_t[c]
+template <typename Tap>
+__device__ __forceinline__ void fh_pk(const float* __restrict__ ek, int E, int lane, Tap tap, float (&p)[10]) {
+#pragma unroll
+    for (int v = 0; v < 10; ++v) p[v] = 0.f;
+    for (int c = lane; c < E; c += 64) {
+        const float e = ek[c];
+        float d[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) d[t] = tap(t, c) - e;
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int u = t; u < 4; ++u) p[sym10(t, u)] = fmaf(d[t], d[u], p[sym10(t, u)]);
+    }
+#pragma unroll
+    for (int v = 0; v < 10; ++v) p[v] = wave_sum(p[v]);
+}
 
 struct FhArgs {
     const float* coarse; const float* embed; const int64_t* target;
     int64_t* pred; float* ws_f; double* part;
     int B, h, w, E, ldc, c0, H, W, crop, K, KP;
-    const int64_t* gmap; int gmode; ClassBits unseen;      // grouped class assignment (gmode 1 | 2), see fh_grouped_argmax
+    const int64_t* gmap; int gmode; ClassBits unseen;      // grouped class assignment (gmode 1 | 2), see fh_argmax
 };
 
-// Grouped class assignment (szn_fused_head_grouped; trainer_fcn.py:123-147, utils.py:188-204): the pixel competes among the classes
+// Nearest class embedding of one pixel: ascending classes, strictly larger replaces: the first index wins.
+// GROUPED (szn_fused_head_grouped; trainer_fcn.py:123-147, utils.py:188-204): the pixel competes among the classes
 // of ITS group only -- the unseen classes when it takes the unseen group, the others otherwise -- and every class outside that group
 // scores 0 / (sn * 1), exactly what a zeroed row of the seen-only / unseen-only matrix scores (trainer_fcn.py:56-64): it still
-// competes, and a zero-norm pixel gives NaN for every class like szn_embed_argmax_k mode 1.  Ascending classes, strictly larger
-// replaces: the first index wins.  The group bits stay in the kernel arguments: k is wave-uniform, so the word select and the bit
-// test are scalar instructions next to the per-class loop, no LDS read.
-template <int KP>
-__device__ __forceinline__ int fh_grouped_argmax(const FhArgs& a, const float (&wt)[4], const float* G, float sn,
-                                                 const float* __restrict__ en, size_t pix, long lbl) {
-    const bool take_unseen = (a.gmode == 1) ? (a.gmap[pix] == 0) : in_set(a.unseen, lbl);
+// competes, and a zero-norm pixel gives NaN for every class like szn_embed_argmax_k mode 1.  The group bits stay in the kernel
+// arguments: k is wave-uniform, so the word select and the bit test are scalar instructions next to the per-class loop, no LDS
+// read.  The plain instantiation does not touch them.
+template <int KP, bool GROUPED>
+__device__ __forceinline__ int fh_argmax(const FhArgs& a, const float (&wt)[4], const float* G, float sn,
+                                         const float* __restrict__ en, size_t pix, long lbl) {
+    bool take_unseen = false;
+    if constexpr (GROUPED) take_unseen = (a.gmode == 1) ? (a.gmap[pix] == 0) : in_set(a.unseen, lbl);
     const float zero_sim = 0.f / (sn * 1.f);
     int best = 0;
     float bv = 0.f;
     for (int k = 0; k < a.K; ++k) {
-        const bool un = (class_word(a.unseen, k >> 6) >> (k & 63)) & 1ull;
+        bool in_group = true;
+        if constexpr (GROUPED) in_group = (bool)((class_word(a.unseen, k >> 6) >> (k & 63)) & 1ull) == take_unseen;
         float sim = zero_sim;
-        if (un == take_unseen) {
+        if (in_group) {
             float d = 0.f;
 #pragma unroll
             for (int t = 0; t < 4; ++t) d = fmaf(wt[t], G[t * KP + k], d);
@@ -86,10 +110,124 @@ __device__ __forceinline__ int fh_grouped_argmax(const FhArgs& a, const float (&
     return best;
 }
 
-// workspace (floats): embT [E][KP] | en [KP] (0 -> 1, for the argmax) | ent [KP] (raw norms, for the loss)
-//                     | per cell: A [4][KP] , Bm [16]
+// what one pixel hands to the label loop (lbl < 0: nothing)
+struct FhPx { float wt[4]; long lbl; float aco; };
+
+// Pixel (ty, tx) of cell (I, J) of image b (live == false: the lane has none): its weights, |s|, the prediction, the loss term
+// and the Bm update; bm, cos_sum, cnt are what a lane sums over its pixels.  Pk: the cell's P_k rows (MSE, block kernel); null
+// where the caller adds the MSE loss term itself, in the class's turn of fh_scatter_A (wave kernel).
+template <int KP, int S, bool GROUPED, bool MSE>
+__device__ __forceinline__ FhPx fh_pixel(const FhArgs& a, int b, int I, int J, int ty, int tx, bool live, const float* G,
+                                         const float* Q, const float* __restrict__ en, const float* __restrict__ ent,
+                                         const float* Pk, float (&bm)[16], double& cos_sum, double& cnt) {
+    FhPx px = {{0.f, 0.f, 0.f, 0.f}, -1, 0.f};
+    const int y = S * I + ty - a.crop, x = S * J + tx - a.crop;        // image coords y = Y - crop
+    if (live && y >= 0 && y < a.H && x >= 0 && x < a.W) {
+        cell_weights<S>(ty, tx, px.wt);
+        const float (&wt)[4] = px.wt;
+        float ss = 0.f;
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) ss = fmaf(wt[t] * wt[u], Q[t * 4 + u], ss);
+        const float sn = sqrtf(ss);
+        const size_t pix = ((size_t)b * a.H + y) * a.W + x;
+        px.lbl = a.target ? a.target[pix] : -1;
+        if (GROUPED || a.pred) a.pred[pix] = fh_argmax<KP, GROUPED>(a, wt, G, sn, en, pix, px.lbl);
+        if (MSE && px.lbl >= 0) {
+            const int kl = px.lbl < a.K ? (int)px.lbl : 0;
+            if (Pk) cos_sum += (double)mse_px(wt, Pk + kl * 10);
+            cnt += 1.0;
+            px.aco = 1.f;
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int u = 0; u < 4; ++u) bm[t * 4 + u] += wt[t] * wt[u];
+        } else if (px.lbl >= 0) {
+            const int kl = px.lbl < a.K ? (int)px.lbl : 0;
+            float d = 0.f;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) d = fmaf(wt[t], G[t * KP + kl], d);
+            const float nt = ent[kl];
+            const float cosv = d / (sn * nt);
+            cos_sum += (double)cosv;
+            cnt += 1.0;
+            px.aco = 1.f / (sn * nt);
+            const float bco = cosv / ss;
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int u = 0; u < 4; ++u) bm[t * 4 + u] = fmaf(wt[t] * wt[u], bco, bm[t * 4 + u]);
+        }
+    }
+    return px;
+}
+
+// A[t][label] += w_t * aco over the pixels of a wave, label by label in a fixed order (wave-uniform loop).  class_turn(kl, mine)
+// runs first in the turn of every label kl; `mine`: this lane's pixel carries it.
+template <int KP, typename F>
+__device__ __forceinline__ void fh_scatter_A(const FhPx& px, int K, int lane, float* myA, F class_turn) {
+    unsigned long long todo = __ballot(px.lbl >= 0);
+    while (todo) {
+        const int src = __ffsll((long long)todo) - 1;
+        const int kl = (int)__shfl((int)(px.lbl < K ? px.lbl : 0), src, 64);
+        const bool mine = (px.lbl >= 0) && ((int)(px.lbl < K ? px.lbl : 0) == kl);
+        class_turn(kl, mine);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const float s = wave_sum(mine ? px.wt[t] * px.aco : 0.f);
+            if (lane == 0) myA[t * KP + kl] += s;
+        }
+        todo &= ~__ballot(mine);
+    }
+}
+
+// workspace: floats embT [E][KP] | en [KP] (0 -> 1, for the argmax) | ent [KP] (raw norms, for the loss)
+//                   | per cell: A [4][KP] , Bm [16]
+//            doubles (8-B aligned) part [cells][2] | sums [B][2] (per-image {sum, count})
+//            floats the per-position tables of the small-cell path: D [pos][KP] | N [pos][8]
 __host__ __device__ inline size_t ws_cell_off(int E, int KP) { return (size_t)E * KP + 2 * KP; }
 __host__ __device__ inline size_t ws_cell_stride(int KP) { return (size_t)4 * KP + 16; }
+struct FhWorkspace { size_t part, sums, tabD, tabN, bytes; };       // byte offsets
+inline FhWorkspace fh_workspace(int B, int h, int w, int E, int KP) {
+    const size_t cells = (size_t)B * (h + 1) * (w + 1), npos = (size_t)B * h * w;
+    FhWorkspace L;
+    L.part = (ws_cell_off(E, KP) + cells * ws_cell_stride(KP)) * sizeof(float);
+    L.part = (L.part + alignof(double) - 1) / alignof(double) * alignof(double);
+    L.sums = L.part + cells * 2 * sizeof(double);
+    L.tabD = L.sums + (size_t)B * 2 * sizeof(double);
+    L.tabN = L.tabD + npos * KP * sizeof(float);
+    L.bytes = L.tabN + npos * 8 * sizeof(float);
+    return L;
+}
+
+// dynamic LDS of fh_cell_kernel, offsets in floats
+struct FhLds {
+    int Ct;         // [4][E]
+    int G;          // [4][KP]
+    int Q;          // [16]
+    int Aw;         // [4 waves][4][KP]
+    int red;        // [4 waves][16]
+    int dred;       // [4 waves][2] doubles
+    int Pk;         // MSE only: [KP][10], rows of the classes present in this cell
+    int present;    // MSE only: [KP] ints
+    int end;
+    __host__ __device__ size_t bytes() const { return (size_t)end * sizeof(float); }
+};
+__host__ __device__ inline FhLds fh_lds(int E, int KP, bool mse) {
+    constexpr int kPerDouble = sizeof(double) / sizeof(float);
+    FhLds L;
+    L.Ct = 0;
+    L.G = L.Ct + 4 * E;
+    L.Q = L.G + 4 * KP;
+    L.Aw = L.Q + 16;
+    L.red = L.Aw + 16 * KP;
+    L.dred = (L.red + 64 + kPerDouble - 1) / kPerDouble * kPerDouble;
+    L.Pk = L.dred + 8 * kPerDouble;
+    L.present = L.Pk + (mse ? 10 * KP : 0);
+    L.end = L.present + (mse ? KP : 0);
+    return L;
+}
 
 __global__ __launch_bounds__(256) void fh_prep_kernel(const float* __restrict__ embed, float* __restrict__ ws, int E,
                                                       int K, int KP) {
@@ -129,14 +267,15 @@ __global__ __launch_bounds__(256) void fh_prep_kernel(const float* __restrict__ 
 template <int KP, int S, bool GROUPED, bool MSE>
 __global__ __launch_bounds__(256) void fh_cell_kernel(FhArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    float* Ct = sm;                       // [4][E]
-    float* G = Ct + 4 * a.E;              // [4][KP]
-    float* Q = G + 4 * KP;                // [16]
-    float* Aw = Q + 16;                   // [4 waves][4][KP]
-    float* red = Aw + 16 * KP;            // [4 waves][16]
-    double* dred = (double*)(red + 64);   // [4 waves][2]   (offset is a multiple of 8 B: all terms are multiples of 4 floats... see host check)
-    float* Pk = (float*)(dred + 8);       // MSE only: [KP][10], rows of the classes present in this cell
-    int* present = (int*)(Pk + 10 * KP);  // MSE only: [KP]
+    const FhLds L = fh_lds(a.E, KP, MSE);
+    float* Ct = sm + L.Ct;
+    float* G = sm + L.G;
+    float* Q = sm + L.Q;
+    float* Aw = sm + L.Aw;
+    float* red = sm + L.red;
+    double* dred = (double*)(sm + L.dred);
+    float* Pk = sm + L.Pk;
+    int* present = (int*)(sm + L.present);
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -151,11 +290,8 @@ __global__ __launch_bounds__(256) void fh_cell_kernel(FhArgs a) {
     // ---- the four tap vectors (missing taps are zero) ----
     for (int i = tid; i < 4 * a.E; i += 256) {
         const int t = i / a.E, c = i - t * a.E;
-        const int ci = I - 1 + (t >> 1), cj = J - 1 + (t & 1);
-        float v = 0.f;
-        if (ci >= 0 && ci < a.h && cj >= 0 && cj < a.w)
-            v = a.coarse[(((size_t)b * a.h + ci) * a.w + cj) * a.ldc + a.c0 + c];
-        Ct[i] = v;
+        const long tp = tap_pos(b, a.h, a.w, I, J, t);
+        Ct[i] = (tp >= 0) ? a.coarse[(size_t)tp * a.ldc + a.c0 + c] : 0.f;
     }
     for (int i = tid; i < 16 * KP; i += 256) Aw[i] = 0.f;
     if (MSE)
@@ -204,127 +340,46 @@ __global__ __launch_bounds__(256) void fh_cell_kernel(FhArgs a) {
     }
     __syncthreads();
     if (MSE) {
-        // P_k of the present classes, ascending k, dealt to the waves in turn: 64 strided partial chains + xor butterfly each
+        // P_k of the present classes, ascending k, dealt to the waves in turn
         int n = 0;
         for (int k = 0; k < a.K; ++k) {
             if (!present[k]) continue;
             if ((n++ & 3) != wave) continue;
             float p[10];
+            fh_pk(a.embed + (size_t)k * a.E, a.E, lane, [&](int t, int c) { return Ct[t * a.E + c]; }, p);
+            if (lane == 0) {
 #pragma unroll
-            for (int v = 0; v < 10; ++v) p[v] = 0.f;
-            const float* ek = a.embed + (size_t)k * a.E;
-            for (int c = lane; c < a.E; c += 64) {
-                const float e = ek[c];
-                float d[4];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) d[t] = Ct[t * a.E + c] - e;
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int u = t; u < 4; ++u) p[sym10(t, u)] = fmaf(d[t], d[u], p[sym10(t, u)]);
-            }
-#pragma unroll
-            for (int v = 0; v < 10; ++v) {
-                const float s = wave_sum(p[v]);
-                if (lane == 0) Pk[k * 10 + v] = s;
+                for (int v = 0; v < 10; ++v) Pk[k * 10 + v] = p[v];
             }
         }
         __syncthreads();
     }
 
-    // ---- pixels of this cell: Y in [S I, S I + S) x X in [S J, S J + S), image coords y = Y - crop ----
+    // ---- pixels of this cell: Y in [S I, S I + S) x X in [S J, S J + S) ----
     float bm[16];
 #pragma unroll
     for (int u = 0; u < 16; ++u) bm[u] = 0.f;
     double cos_sum = 0.0, cnt = 0.0;
     float* myA = Aw + wave * 4 * KP;
     for (int q = tid; q < S * S; q += 256) {         // S = 32: a wave covers 2 rows of the cell; S = 8: wave 0 holds the whole cell
-        const int ty = q / S, tx = q % S;
-        const int y = S * I + ty - a.crop, x = S * J + tx - a.crop;
-        const bool inside = (y >= 0 && y < a.H && x >= 0 && x < a.W);
-        long lbl = -1;
-        float wt[4] = {0.f, 0.f, 0.f, 0.f};
-        float aco = 0.f;
-        if (inside) {
-            const double fy1 = bil1d<S>(ty), fy0 = bil1d<S>(ty + S), fx1 = bil1d<S>(tx), fx0 = bil1d<S>(tx + S);
-            wt[0] = (float)(fy0 * fx0); wt[1] = (float)(fy0 * fx1); wt[2] = (float)(fy1 * fx0); wt[3] = (float)(fy1 * fx1);
-            float ss = 0.f;
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int u = 0; u < 4; ++u) ss = fmaf(wt[t] * wt[u], Q[t * 4 + u], ss);
-            const float sn = sqrtf(ss);
-            const size_t pix = ((size_t)b * a.H + y) * a.W + x;
-            lbl = a.target ? a.target[pix] : -1;
-            if (GROUPED) {
-                a.pred[pix] = fh_grouped_argmax<KP>(a, wt, G, sn, en, pix, lbl);
-            } else if (a.pred) {
-                int best = 0;
-                float bv = 0.f;
-                for (int k = 0; k < a.K; ++k) {
-                    float d = 0.f;
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) d = fmaf(wt[t], G[t * KP + k], d);
-                    const float sim = d / (sn * en[k]);
-                    if (k == 0 || sim > bv) { bv = sim; best = k; }
-                }
-                a.pred[pix] = best;
-            }
-            if (MSE && lbl >= 0) {
-                const int kl = lbl < a.K ? (int)lbl : 0;
-                cos_sum += (double)mse_px(wt, Pk + kl * 10);
-                cnt += 1.0;
-                aco = 1.f;
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) bm[t * 4 + u] += wt[t] * wt[u];
-            } else if (lbl >= 0) {
-                const int kl = lbl < a.K ? (int)lbl : 0;
-                float d = 0.f;
-#pragma unroll
-                for (int t = 0; t < 4; ++t) d = fmaf(wt[t], G[t * KP + kl], d);
-                const float nt = ent[kl];
-                const float cosv = d / (sn * nt);
-                cos_sum += (double)cosv;
-                cnt += 1.0;
-                aco = 1.f / (sn * nt);
-                const float bco = cosv / ss;
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) bm[t * 4 + u] = fmaf(wt[t] * wt[u], bco, bm[t * 4 + u]);
-            }
-        }
-        // A[t][label] += w_t * aco, label by label in a fixed order (wave-uniform loop)
-        unsigned long long todo = __ballot(lbl >= 0);
-        while (todo) {
-            const int src = __ffsll((long long)todo) - 1;
-            const int kl = (int)__shfl((int)(lbl < a.K ? lbl : 0), src, 64);
-            const bool mine = (lbl >= 0) && ((int)(lbl < a.K ? lbl : 0) == kl);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const float s = wave_sum(mine ? wt[t] * aco : 0.f);
-                if (lane == 0) myA[t * KP + kl] += s;
-            }
-            todo &= ~__ballot(mine);
-        }
+        const FhPx px = fh_pixel<KP, S, GROUPED, MSE>(a, b, I, J, q / S, q % S, true, G, Q, en, ent, Pk, bm, cos_sum, cnt);
+        fh_scatter_A<KP>(px, a.K, lane, myA, [](int, bool) {});
     }
     // ---- block reductions (fixed order) ----
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
-        const float s = wave_sum(bm[u]);
-        if (lane == 0) red[wave * 16 + u] = s;
+        const float r = wave_sum(bm[u]);
+        if (lane == 0) red[wave * 16 + u] = r;
     }
     cos_sum = wave_sum_d(cos_sum); cnt = wave_sum_d(cnt);
     if (lane == 0) { dred[wave * 2] = cos_sum; dred[wave * 2 + 1] = cnt; }
     __syncthreads();
     float* wc = a.ws_f + ws_cell_off(a.E, KP) + (size_t)blockIdx.x * ws_cell_stride(KP);
-    for (int i = tid; i < 4 * KP; i += 256) wc[i] = (Aw[i] + Aw[4 * KP + i]) + (Aw[8 * KP + i] + Aw[12 * KP + i]);
-    if (tid < 16) wc[4 * KP + tid] = (red[tid] + red[16 + tid]) + (red[32 + tid] + red[48 + tid]);
+    for (int i = tid; i < 4 * KP; i += 256) wc[i] = combine4(Aw[i], Aw[4 * KP + i], Aw[8 * KP + i], Aw[12 * KP + i]);
+    if (tid < 16) wc[4 * KP + tid] = combine4(red[tid], red[16 + tid], red[32 + tid], red[48 + tid]);
     if (tid == 0) {
-        a.part[(size_t)blockIdx.x * 2] = (dred[0] + dred[2]) + (dred[4] + dred[6]);
-        a.part[(size_t)blockIdx.x * 2 + 1] = (dred[1] + dred[3]) + (dred[5] + dred[7]);
+        a.part[(size_t)blockIdx.x * 2] = combine4(dred[0], dred[2], dred[4], dred[6]);
+        a.part[(size_t)blockIdx.x * 2 + 1] = combine4(dred[1], dred[3], dred[5], dred[7]);
     }
 }
 
@@ -391,10 +446,7 @@ __global__ __launch_bounds__(256) void fh_cell_tab_kernel(FhArgs a, const float*
     float* myA = As[wave];
     long tp[4];
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int ci = I - 1 + (t >> 1), cj = J - 1 + (t & 1);
-        tp[t] = (ci >= 0 && ci < a.h && cj >= 0 && cj < a.w) ? ((long)b * a.h + ci) * a.w + cj : -1;
-    }
+    for (int t = 0; t < 4; ++t) tp[t] = tap_pos(b, a.h, a.w, I, J, t);
     for (int k = lane; k < KP; k += 64) {
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
@@ -416,96 +468,16 @@ __global__ __launch_bounds__(256) void fh_cell_tab_kernel(FhArgs a, const float*
 #pragma unroll
     for (int u = 0; u < 16; ++u) bm[u] = 0.f;
     double cos_sum = 0.0, cnt = 0.0;
-    {
-        const int q = lane;
-        const int ty = q / S, tx = q % S;
-        const int y = S * I + ty - a.crop, x = S * J + tx - a.crop;
-        const bool inside = ok && q < S * S && (y >= 0 && y < a.H && x >= 0 && x < a.W);
-        long lbl = -1;
-        float wt[4] = {0.f, 0.f, 0.f, 0.f};
-        float aco = 0.f;
-        if (inside) {
-            const double fy1 = bil1d<S>(ty), fy0 = bil1d<S>(ty + S), fx1 = bil1d<S>(tx), fx0 = bil1d<S>(tx + S);
-            wt[0] = (float)(fy0 * fx0); wt[1] = (float)(fy0 * fx1); wt[2] = (float)(fy1 * fx0); wt[3] = (float)(fy1 * fx1);
-            float ss = 0.f;
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int u = 0; u < 4; ++u) ss = fmaf(wt[t] * wt[u], Q[t * 4 + u], ss);
-            const float sn = sqrtf(ss);
-            const size_t pix = ((size_t)b * a.H + y) * a.W + x;
-            lbl = a.target ? a.target[pix] : -1;
-            if (GROUPED) {
-                a.pred[pix] = fh_grouped_argmax<KP>(a, wt, G, sn, en, pix, lbl);
-            } else if (a.pred) {
-                int best = 0;
-                float bv = 0.f;
-                for (int k = 0; k < a.K; ++k) {
-                    float d = 0.f;
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) d = fmaf(wt[t], G[t * KP + k], d);
-                    const float sim = d / (sn * en[k]);
-                    if (k == 0 || sim > bv) { bv = sim; best = k; }
-                }
-                a.pred[pix] = best;
-            }
-            if (MSE && lbl >= 0) {
-                cnt += 1.0;                 // the loss term follows in the class loop below, where P_k is at hand
-                aco = 1.f;
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) bm[t * 4 + u] += wt[t] * wt[u];
-            } else if (lbl >= 0) {
-                const int kl = lbl < a.K ? (int)lbl : 0;
-                float d = 0.f;
-#pragma unroll
-                for (int t = 0; t < 4; ++t) d = fmaf(wt[t], G[t * KP + kl], d);
-                const float nt = ent[kl];
-                const float cosv = d / (sn * nt);
-                cos_sum += (double)cosv;
-                cnt += 1.0;
-                aco = 1.f / (sn * nt);
-                const float bco = cosv / ss;
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) bm[t * 4 + u] = fmaf(wt[t] * wt[u], bco, bm[t * 4 + u]);
-            }
+    const FhPx px = fh_pixel<KP, S, GROUPED, MSE>(a, b, I, J, lane / S, lane % S, ok && lane < S * S, G, Q, en, ent, nullptr, bm, cos_sum, cnt);
+    fh_scatter_A<KP>(px, a.K, lane, myA, [&](int kl, bool mine) {
+        if (MSE) {
+            // P_kl from the vectors (same chains as fh_cell_kernel), kept in registers; the loss term of the pixels that carry kl
+            float p[10];
+            fh_pk(a.embed + (size_t)kl * a.E, a.E, lane,
+                  [&](int t, int c) { return (tp[t] >= 0) ? a.coarse[(size_t)tp[t] * a.ldc + a.c0 + c] : 0.f; }, p);
+            if (mine) cos_sum += (double)mse_px(px.wt, p);
         }
-        unsigned long long todo = __ballot(lbl >= 0);
-        while (todo) {
-            const int src = __ffsll((long long)todo) - 1;
-            const int kl = (int)__shfl((int)(lbl < a.K ? lbl : 0), src, 64);
-            const bool mine = (lbl >= 0) && ((int)(lbl < a.K ? lbl : 0) == kl);
-            if (MSE) {
-                // P_kl from the vectors (same chains as fh_cell_kernel: 64 strided partials + xor butterfly), kept in registers
-                float p[10];
-#pragma unroll
-                for (int v = 0; v < 10; ++v) p[v] = 0.f;
-                const float* ek = a.embed + (size_t)kl * a.E;
-                for (int c = lane; c < a.E; c += 64) {
-                    const float e = ek[c];
-                    float d[4];
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) d[t] = ((tp[t] >= 0) ? a.coarse[(size_t)tp[t] * a.ldc + a.c0 + c] : 0.f) - e;
-#pragma unroll
-                    for (int t = 0; t < 4; ++t)
-#pragma unroll
-                        for (int u = t; u < 4; ++u) p[sym10(t, u)] = fmaf(d[t], d[u], p[sym10(t, u)]);
-                }
-#pragma unroll
-                for (int v = 0; v < 10; ++v) p[v] = wave_sum(p[v]);
-                if (mine) cos_sum += (double)mse_px(wt, p);
-            }
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const float s = wave_sum(mine ? wt[t] * aco : 0.f);
-                if (lane == 0) myA[t * KP + kl] += s;
-            }
-            todo &= ~__ballot(mine);
-        }
-    }
+    });
     float bs[16];
 #pragma unroll
     for (int u = 0; u < 16; ++u) bs[u] = wave_sum(bm[u]);
@@ -534,7 +506,7 @@ __global__ __launch_bounds__(256) void fh_image_sums_kernel(const double* __rest
     if (lane == 0) { red[wave][0] = s; red[wave][1] = n; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const double st = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]), nt = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+        const double st = combine4(red[0][0], red[1][0], red[2][0], red[3][0]), nt = combine4(red[0][1], red[1][1], red[2][1], red[3][1]);
         sums[2 * b] = st; sums[2 * b + 1] = nt;
         stats[2 * b] = (float)st; stats[2 * b + 1] = (float)nt;
     }
@@ -560,23 +532,23 @@ __global__ __launch_bounds__(256) void fh_gather_kernel(const float* __restrict_
     const int i = r / w, j = r % w;
     const int cells_w = w + 1, cells = (h + 1) * cells_w;
     const float* cellbase = ws + ws_cell_off(E, KP);
-    // cell u = (a, bb): this position is tap t = (a, bb) of cell (i + 1 - a, j + 1 - bb)
+    // this position is tap u of cell (tap_cell_I(i, u), tap_cell_J(j, u)), u = 0..3
     for (int idx = threadIdx.x; idx < 4 * KP + 16; idx += 256) {
         if (idx < 4 * KP) {
             const int u = idx / KP, k = idx % KP;
-            const int I = i + 1 - (u >> 1), J = j + 1 - (u & 1);
+            const int I = tap_cell_I(i, u), J = tap_cell_J(j, u);
             const float* wc = cellbase + ((size_t)b * cells + I * cells_w + J) * ws_cell_stride(KP);
             Al[u][k] = wc[u * KP + k];
         } else {
             const int q = idx - 4 * KP, u = q >> 2, t2 = q & 3;
-            const int I = i + 1 - (u >> 1), J = j + 1 - (u & 1);
+            const int I = tap_cell_I(i, u), J = tap_cell_J(j, u);
             const float* wc = cellbase + ((size_t)b * cells + I * cells_w + J) * ws_cell_stride(KP);
             Bl[u][t2] = wc[4 * KP + u * 4 + t2];
         }
     }
     __syncthreads();
     // the class term is linear in A: sum the four cells' rows first, one pass over the K embeddings instead of four
-    Al[0][threadIdx.x] = (threadIdx.x < KP) ? (Al[0][threadIdx.x] + Al[1][threadIdx.x]) + (Al[2][threadIdx.x] + Al[3][threadIdx.x]) : 0.f;
+    Al[0][threadIdx.x] = (threadIdx.x < KP) ? combine4(Al[0][threadIdx.x], Al[1][threadIdx.x], Al[2][threadIdx.x], Al[3][threadIdx.x]) : 0.f;
     __syncthreads();
     const float scale = (MSE ? 2.f : 1.f) / ((float)B * stats[2 * b + 1]);
     for (int c = threadIdx.x; c < E; c += 256) {
@@ -585,10 +557,10 @@ __global__ __launch_bounds__(256) void fh_gather_kernel(const float* __restrict_
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             float bu = 0.f;
-            const int I = i + 1 - (u >> 1), J = j + 1 - (u & 1);
+            const int I = tap_cell_I(i, u), J = tap_cell_J(j, u);
 #pragma unroll
             for (int t2 = 0; t2 < 4; ++t2) {
-                const int ci = I - 1 + (t2 >> 1), cj = J - 1 + (t2 & 1);
+                const int ci = tap_i(I, t2), cj = tap_j(J, t2);
                 if (ci >= 0 && ci < h && cj >= 0 && cj < w)
                     bu = fmaf(Bl[u][t2], coarse[(((size_t)b * h + ci) * w + cj) * ldc + c0 + c], bu);
             }
@@ -605,59 +577,45 @@ __global__ __launch_bounds__(256) void fh_gather_kernel(const float* __restrict_
 
 inline int kp_of(int K) { return K <= 24 ? 24 : (K <= 40 ? 40 : (K <= 64 ? 64 : (K + 63) / 64 * 64)); }      // K <= 256
 
-}  // namespace
-
-extern "C" size_t szn_fused_head_workspace_bytes(int B, int h, int w, int E, int K) {
-    if (B <= 0 || h <= 0 || w <= 0 || E <= 0 || K <= 0 || K > 256) return 0;
-    const int KP = kp_of(K);
-    const size_t cells = (size_t)B * (h + 1) * (w + 1);
-    size_t fl = ws_cell_off(E, KP) + cells * ws_cell_stride(KP);
-    fl = (fl + 1) / 2 * 2;                                   // keep the double region 8-B aligned
-    // + the per-position tables of the small-cell path (D [pos][KP], N [pos][8])
-    return fl * sizeof(float) + (cells + B) * 2 * sizeof(double) + (size_t)B * h * w * (KP + 8) * sizeof(float);
+// the cell pass: stride 32 a block per cell; stride 8 the position tables, then a wave per cell
+template <int KP, bool GROUPED, bool MSE>
+void fh_launch(int stride, const FhArgs& a, float* tabD, float* tabN, hipStream_t st) {
+    const int cells = (a.h + 1) * (a.w + 1);
+    if (stride == 8) {
+        hipLaunchKernelGGL(fh_tables_kernel<KP>, dim3((unsigned)(((long)a.B * a.h * a.w + 3) / 4)), dim3(256),
+                           (size_t)4 * a.E * sizeof(float), st, a, tabD, tabN);
+        hipLaunchKernelGGL((fh_cell_tab_kernel<KP, 8, GROUPED, MSE>), dim3((unsigned)(((long)a.B * cells + 3) / 4)), dim3(256), 0, st, a,
+                           (const float*)tabD, (const float*)tabN);
+    } else {
+        const size_t lds = fh_lds(a.E, KP, MSE).bytes();
+        auto kern = fh_cell_kernel<KP, 32, GROUPED, MSE>;
+        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(kern, dim3(a.B * cells), dim3(256), lds, st, a);
+    }
+}
+template <int KP>
+void fh_launch_kp(bool grouped, bool mse, int stride, const FhArgs& a, float* tabD, float* tabN, hipStream_t st) {
+    if (grouped) mse ? fh_launch<KP, true, true>(stride, a, tabD, tabN, st) : fh_launch<KP, true, false>(stride, a, tabD, tabN, st);
+    else mse ? fh_launch<KP, false, true>(stride, a, tabD, tabN, st) : fh_launch<KP, false, false>(stride, a, tabD, tabN, st);
 }
 
-static int fused_head_impl(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
-                           const float* coarse, const float* embed, const int64_t* target, float* loss,
-                           float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
-                           szn_stream_t stream, bool prep, const szn_class_set* unseen = nullptr, int group_mode = 0,
-                           const int64_t* group_map = nullptr, bool mse = false);
-
-extern "C" int szn_fused_head_strided(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
-                                      const float* coarse, const float* embed, const int64_t* target, float* loss,
-                                      float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
-                                      szn_stream_t stream) {
-    return fused_head_impl(stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype, dcoarse, workspace,
-                           stream, true);
+template <typename T, bool MSE>
+void fh_launch_gather(const FhArgs& a, const float* stats, void* dcoarse, hipStream_t st) {
+    hipLaunchKernelGGL((fh_gather_kernel<T, MSE>), dim3(a.B * a.h * a.w), dim3(256), 0, st, a.coarse, a.embed, (const float*)a.ws_f,
+                       stats, (T*)dcoarse, a.B, a.h, a.w, a.E, a.ldc, a.c0, a.K, a.KP);
+}
+template <typename T>
+void fh_launch_gather_t(bool mse, const FhArgs& a, const float* stats, void* dcoarse, hipStream_t st) {
+    mse ? fh_launch_gather<T, true>(a, stats, dcoarse, st) : fh_launch_gather<T, false>(a, stats, dcoarse, st);
 }
 
-// The class embeddings are constants of a training run (trainer_fcn.py:49-62 loads them once): their transpose and norms -- fh_prep_kernel, 23 us of
-// a 2.5-8 ms step, a chain of dependent loads -- need not be rebuilt every step.  szn_fused_head_prepare writes them to the head of `workspace`
-// once; szn_fused_head_prepared is szn_fused_head_strided without that launch, for a caller that keeps the workspace and re-prepares when the
-// embeddings (or the workspace) change.  Same tables, same bits.
-extern "C" int szn_fused_head_prepare(int E, int K, const float* embed, void* workspace, szn_stream_t stream) {
-    if (!embed || !workspace || E <= 0 || K <= 0) SZN_FAIL(SZN_ERR_ARG, "fused_head_prepare: bad argument");
-    if (K > 256) SZN_FAIL(SZN_ERR_UNSUPPORTED, "fused_head_prepare: K=%d > 256", K);
-    if (((uintptr_t)workspace) & 15) SZN_FAIL(SZN_ERR_ARG, "fused_head_prepare: workspace must be 16-B aligned");
-    const int KP = kp_of(K);
-    hipLaunchKernelGGL(fh_prep_kernel, dim3(szn_div_up((long)E * KP, 256)), dim3(256), 0, (hipStream_t)stream, embed, (float*)workspace, E, K, KP);
-    SZN_CHECK_LAUNCH("fh_prep_kernel");
-    return SZN_OK;
-}
-
-extern "C" int szn_fused_head_prepared(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
-                                       const float* coarse, const float* embed, const int64_t* target, float* loss,
-                                       float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
-                                       szn_stream_t stream) {
-    return fused_head_impl(stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype, dcoarse, workspace,
-                           stream, false);
-}
-
-static int fused_head_impl(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
-                           const float* coarse, const float* embed, const int64_t* target, float* loss,
-                           float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
-                           szn_stream_t stream, bool prep, const szn_class_set* unseen, int group_mode,
-                           const int64_t* group_map, bool mse) {
+// every szn_fused_*head* entry point: prep = build the embedding tables first; unseen / group_mode / group_map as in
+// szn_fused_head_grouped (NULL, 0, NULL: ungrouped); mse = the MSE loss instead of the cosine loss
+int fused_head_impl(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                    const float* coarse, const float* embed, const int64_t* target, float* loss,
+                    float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
+                    szn_stream_t stream, bool prep, const szn_class_set* unseen, int group_mode,
+                    const int64_t* group_map, bool mse) {
     if (stride != 32 && stride != 8) SZN_FAIL(SZN_ERR_UNSUPPORTED, "fused_head: stride %d (32 and 8 are built)", stride);
     if (!coarse || !embed || !workspace || B <= 0 || h <= 0 || w <= 0 || E <= 0 || c0 < 0 || ldc < c0 + E || H <= 0 ||
         W <= 0 || crop < 0 || K <= 0)
@@ -678,13 +636,13 @@ static int fused_head_impl(int stride, int B, int h, int w, int E, int ldc, int 
     hipStream_t st = (hipStream_t)stream;
     const int KP = kp_of(K);
     const int cells = (h + 1) * (w + 1);
-    float* ws_f = (float*)workspace;
-    size_t fl = ws_cell_off(E, KP) + (size_t)B * cells * ws_cell_stride(KP);
-    fl = (fl + 1) / 2 * 2;
-    double* part = (double*)(ws_f + fl);
-    double* sums = part + (size_t)B * cells * 2;             // per-image {sum cos, count}
-    float* tabD = (float*)(sums + 2 * (size_t)B);
-    float* tabN = tabD + (size_t)B * h * w * KP;
+    const FhWorkspace wl = fh_workspace(B, h, w, E, KP);
+    char* ws = (char*)workspace;
+    float* ws_f = (float*)ws;
+    double* part = (double*)(ws + wl.part);
+    double* sums = (double*)(ws + wl.sums);
+    float* tabD = (float*)(ws + wl.tabD);
+    float* tabN = (float*)(ws + wl.tabN);
     if (prep) {
         hipLaunchKernelGGL(fh_prep_kernel, dim3(szn_div_up((long)E * KP, 256)), dim3(256), 0, st, embed, ws_f, E, K, KP);
         SZN_CHECK_LAUNCH("fh_prep_kernel");
@@ -693,44 +651,15 @@ static int fused_head_impl(int stride, int B, int h, int w, int E, int ldc, int 
     a.coarse = coarse; a.embed = embed; a.target = target; a.pred = pred; a.ws_f = ws_f; a.part = part;
     a.B = B; a.h = h; a.w = w; a.E = E; a.ldc = ldc; a.c0 = c0; a.H = H; a.W = W; a.crop = crop; a.K = K; a.KP = KP;
     a.gmap = group_map; a.gmode = group_mode; a.unseen = ubits;
-    // LDS floats: Ct 4E | G 4KP | Q 16 | Aw 16KP | red 64 | dred 8 doubles; 4E + 20KP + 80 must be even for the doubles
-    // (+ the MSE variant's P [KP][10] and class marks [KP] behind the doubles)
-    size_t lfl = (size_t)4 * E + 20 * KP + 16 + 64;
-    const size_t lds = lfl * sizeof(float) + 8 * sizeof(double) + (mse ? (size_t)11 * KP * sizeof(float) : 0);
-    if (lds > 150 * 1024) SZN_FAIL(SZN_ERR_UNSUPPORTED, "fused_head: E=%d too large for LDS", E);
-#define SZN_FH_LAUNCH_GM(KPV, GR, MS)                                                                                \
-    do {                                                                                                             \
-        if (stride == 8) {                                                                                           \
-            hipLaunchKernelGGL(fh_tables_kernel<KPV>, dim3((unsigned)(((long)B * h * w + 3) / 4)), dim3(256),        \
-                               (size_t)4 * E * sizeof(float), st, a, tabD, tabN);                                    \
-            hipLaunchKernelGGL((fh_cell_tab_kernel<KPV, 8, GR, MS>), dim3((unsigned)(((long)B * cells + 3) / 4)), dim3(256), 0, st, a, \
-                               (const float*)tabD, (const float*)tabN);                                              \
-        } else {                                                                                                     \
-            auto kern = fh_cell_kernel<KPV, 32, GR, MS>;                                                             \
-            if (lds > 48 * 1024)                                                                                     \
-                (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);  \
-            hipLaunchKernelGGL(kern, dim3(B * cells), dim3(256), lds, st, a);                                        \
-        }                                                                                                            \
-    } while (0)
-#define SZN_FH_LAUNCH_G(KPV, GR)                                                                                     \
-    do {                                                                                                             \
-        if (mse) SZN_FH_LAUNCH_GM(KPV, GR, true);                                                                    \
-        else SZN_FH_LAUNCH_GM(KPV, GR, false);                                                                       \
-    } while (0)
-#define SZN_FH_LAUNCH(KPV)                                                                                           \
-    do {                                                                                                             \
-        if (grouped) SZN_FH_LAUNCH_G(KPV, true);                                                                     \
-        else SZN_FH_LAUNCH_G(KPV, false);                                                                            \
-    } while (0)
-    if (KP == 24) SZN_FH_LAUNCH(24);
-    else if (KP == 40) SZN_FH_LAUNCH(40);
-    else if (KP == 64) SZN_FH_LAUNCH(64);
-    else if (KP == 128) SZN_FH_LAUNCH(128);
-    else if (KP == 192) SZN_FH_LAUNCH(192);
-    else SZN_FH_LAUNCH(256);
-#undef SZN_FH_LAUNCH
-#undef SZN_FH_LAUNCH_G
-#undef SZN_FH_LAUNCH_GM
+    if (fh_lds(E, KP, mse).bytes() > 150 * 1024) SZN_FAIL(SZN_ERR_UNSUPPORTED, "fused_head: E=%d too large for LDS", E);
+    switch (KP) {
+        case 24: fh_launch_kp<24>(grouped, mse, stride, a, tabD, tabN, st); break;
+        case 40: fh_launch_kp<40>(grouped, mse, stride, a, tabD, tabN, st); break;
+        case 64: fh_launch_kp<64>(grouped, mse, stride, a, tabD, tabN, st); break;
+        case 128: fh_launch_kp<128>(grouped, mse, stride, a, tabD, tabN, st); break;
+        case 192: fh_launch_kp<192>(grouped, mse, stride, a, tabD, tabN, st); break;
+        default: fh_launch_kp<256>(grouped, mse, stride, a, tabD, tabN, st); break;
+    }
     SZN_CHECK_LAUNCH("fh_cell_kernel");
     if (loss) {
         hipLaunchKernelGGL(fh_image_sums_kernel, dim3(B), dim3(256), 0, st, (const double*)part, cells, stats, sums);
@@ -738,31 +667,58 @@ static int fused_head_impl(int stride, int B, int h, int w, int E, int ldc, int 
         SZN_CHECK_LAUNCH("fh_finalize_kernel");
     }
     if (dcoarse) {
-#define SZN_FH_GATHER(T, MS)                                                                                         \
-    hipLaunchKernelGGL((fh_gather_kernel<T, MS>), dim3(B * h * w), dim3(256), 0, st, coarse, embed, (const float*)ws_f, \
-                       (const float*)stats, (T*)dcoarse, B, h, w, E, ldc, c0, K, KP)
-#define SZN_FH_GATHER_T(T)                                                                                           \
-    do {                                                                                                             \
-        if (mse) SZN_FH_GATHER(T, true);                                                                             \
-        else SZN_FH_GATHER(T, false);                                                                                \
-    } while (0)
-        if (dcoarse_dtype == SZN_F32) SZN_FH_GATHER_T(float);
-        else if (dcoarse_dtype == SZN_BF16) SZN_FH_GATHER_T(bf16_raw);
-        else if (dcoarse_dtype == SZN_F16) SZN_FH_GATHER_T(f16_raw);
+        if (dcoarse_dtype == SZN_F32) fh_launch_gather_t<float>(mse, a, stats, dcoarse, st);
+        else if (dcoarse_dtype == SZN_BF16) fh_launch_gather_t<bf16_raw>(mse, a, stats, dcoarse, st);
+        else if (dcoarse_dtype == SZN_F16) fh_launch_gather_t<f16_raw>(mse, a, stats, dcoarse, st);
         else
             SZN_FAIL(SZN_ERR_ARG, "fused_head: bad dcoarse_dtype %d", dcoarse_dtype);
-#undef SZN_FH_GATHER_T
-#undef SZN_FH_GATHER
         SZN_CHECK_LAUNCH("fh_gather_kernel");
     }
+    return SZN_OK;
+}
+
+}  // namespace
+
+extern "C" size_t szn_fused_head_workspace_bytes(int B, int h, int w, int E, int K) {
+    if (B <= 0 || h <= 0 || w <= 0 || E <= 0 || K <= 0 || K > 256) return 0;
+    return fh_workspace(B, h, w, E, kp_of(K)).bytes;
+}
+
+// The class embeddings are constants of a training run (trainer_fcn.py:49-62 loads them once): their transpose and norms -- fh_prep_kernel, 23 us of
+// a 2.5-8 ms step, a chain of dependent loads -- need not be rebuilt every step.  szn_fused_head_prepare writes them to the head of `workspace`
+// once; the *_prepared entry points are their namesakes without that launch, for a caller that keeps the workspace and re-prepares when the
+// embeddings (or the workspace) change.  Same tables, same bits.
+extern "C" int szn_fused_head_prepare(int E, int K, const float* embed, void* workspace, szn_stream_t stream) {
+    if (!embed || !workspace || E <= 0 || K <= 0) SZN_FAIL(SZN_ERR_ARG, "fused_head_prepare: bad argument");
+    if (K > 256) SZN_FAIL(SZN_ERR_UNSUPPORTED, "fused_head_prepare: K=%d > 256", K);
+    if (((uintptr_t)workspace) & 15) SZN_FAIL(SZN_ERR_ARG, "fused_head_prepare: workspace must be 16-B aligned");
+    const int KP = kp_of(K);
+    hipLaunchKernelGGL(fh_prep_kernel, dim3(szn_div_up((long)E * KP, 256)), dim3(256), 0, (hipStream_t)stream, embed, (float*)workspace, E, K, KP);
+    SZN_CHECK_LAUNCH("fh_prep_kernel");
     return SZN_OK;
 }
 
 extern "C" int szn_fused_head(int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
                               const float* coarse, const float* embed, const int64_t* target, float* loss, float* stats,
                               int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace, szn_stream_t stream) {
-    return szn_fused_head_strided(32, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype,
-                                  dcoarse, workspace, stream);
+    return fused_head_impl(32, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype, dcoarse,
+                           workspace, stream, true, nullptr, 0, nullptr, false);
+}
+
+extern "C" int szn_fused_head_strided(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                                      const float* coarse, const float* embed, const int64_t* target, float* loss,
+                                      float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
+                                      szn_stream_t stream) {
+    return fused_head_impl(stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype, dcoarse,
+                           workspace, stream, true, nullptr, 0, nullptr, false);
+}
+
+extern "C" int szn_fused_head_prepared(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                                       const float* coarse, const float* embed, const int64_t* target, float* loss,
+                                       float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
+                                       szn_stream_t stream) {
+    return fused_head_impl(stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype, dcoarse,
+                           workspace, stream, false, nullptr, 0, nullptr, false);
 }
 
 // group mode 0: szn_fused_head_strided / _prepared bit for bit.  1: a pixel takes the unseen group where group_map == 0 (the seen-mask
@@ -772,7 +728,7 @@ extern "C" int szn_fused_head_grouped(int stride, int B, int h, int w, int E, in
                                       int group_mode, const int64_t* group_map, float* loss, float* stats, int64_t* pred,
                                       int dcoarse_dtype, void* dcoarse, void* workspace, szn_stream_t stream) {
     return fused_head_impl(stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype, dcoarse,
-                           workspace, stream, true, unseen, group_mode, group_map);
+                           workspace, stream, true, unseen, group_mode, group_map, false);
 }
 
 extern "C" int szn_fused_head_grouped_prepared(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
@@ -781,7 +737,7 @@ extern "C" int szn_fused_head_grouped_prepared(int stride, int B, int h, int w, 
                                                float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
                                                szn_stream_t stream) {
     return fused_head_impl(stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype, dcoarse,
-                           workspace, stream, false, unseen, group_mode, group_map);
+                           workspace, stream, false, unseen, group_mode, group_map, false);
 }
 
 // The MSE embedding loss (train.py -loss mse; trainer_fcn.py forward / forward_szn -> utils.py:50-73 mse_loss) through the same head:

@@ -9,13 +9,9 @@
 // Arithmetic contract shared with oracle/szn_oracle.c (bit-exact argmax): every per-pixel dot product
 // and squared norm is an fmaf chain over the channel index in ascending order, norms use correctly
 // rounded sqrtf, similarities use IEEE division; this file is compiled with -ffp-contract=off.
-#include "szn_common.h"
+#include "szn_upcell.h"
 
 namespace {
-
-// 1-D bilinear tap of get_upsampling_weight(k = 2 S): factor S, center S - 0.5 (models.py:13-20), in double
-template <int S>
-__device__ __forceinline__ double bil1d(int t) { return 1.0 - fabs((double)t - ((double)S - 0.5)) / (double)S; }
 
 // ---- upscore forward ---------------------------------------------------------------------------------------------------
 // Fixed bilinear ConvTranspose2d(E, E, 2 S, stride S) + crop; S = 32 is FCN32s' upscore (models.py:94,146-147), S = 8 the last
@@ -41,7 +37,6 @@ __global__ __launch_bounds__(256) void up_fwd_kernel(const float* __restrict__ c
     const int X = 256 * seg + threadIdx.x, x = X - crop;
     if (x < 0 || x >= W) return;
     const int jl = threadIdx.x / S, tx = threadIdx.x % S;            // cell inside the segment (J = NC seg + jl), column inside it
-    const double fx1 = bil1d<S>(tx), fx0 = bil1d<S>(tx + S);
     const float* t00 = taps + (0 * NJ + jl) * E;                      // (I-1, J-1)
     const float* t01 = t00 + E;                                       // (I-1, J)
     const float* t10 = taps + (1 * NJ + jl) * E;                      // (I,   J-1)
@@ -49,14 +44,14 @@ __global__ __launch_bounds__(256) void up_fwd_kernel(const float* __restrict__ c
     for (int ty = 0; ty < S; ++ty) {
         const int y = S * I + ty - crop;
         if (y < 0 || y >= H) continue;
-        const double fy1 = bil1d<S>(ty), fy0 = bil1d<S>(ty + S);
-        const float w00 = (float)(fy0 * fx0), w01 = (float)(fy0 * fx1), w10 = (float)(fy1 * fx0), w11 = (float)(fy1 * fx1);
+        float wt[4];
+        cell_weights<S>(ty, tx, wt);
         float* op = out + ((long)b * E * H + y) * W + x;
         for (int c = 0; c < E; ++c) {
-            float acc = fmaf(t00[c], w00, 0.f);
-            acc = fmaf(t01[c], w01, acc);
-            acc = fmaf(t10[c], w10, acc);
-            acc = fmaf(t11[c], w11, acc);
+            float acc = fmaf(t00[c], wt[0], 0.f);
+            acc = fmaf(t01[c], wt[1], acc);
+            acc = fmaf(t10[c], wt[2], acc);
+            acc = fmaf(t11[c], wt[3], acc);
             op[(long)c * H * W] = acc;
         }
     }
@@ -268,7 +263,7 @@ __global__ __launch_bounds__(256) void deconv_wgrad_kernel(const float* __restri
     part[q][kx] = acc;
     __syncthreads();
     if (q == 0) {
-        const float v = (part[0][kx] + part[1][kx]) + (part[2][kx] + part[3][kx]);
+        const float v = combine4(part[0][kx], part[1][kx], part[2][kx], part[3][kx]);
         const int gid = ((ci * C + co) * 64 + ky) * 64 + kx;
         dwt[gid] = accumulate ? dwt[gid] + v : v;
     }

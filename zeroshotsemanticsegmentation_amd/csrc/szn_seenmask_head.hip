@@ -19,7 +19,7 @@
 //
 // Arithmetic order per pixel is that of deconv_fwd_kernel / ce_fwd_kernel / ce_bwd_kernel (szn_head.hip): the fused score,
 // loss terms and class decisions are bit-identical to the materialised path.
-#include "szn_common.h"
+#include "szn_upcell.h"
 
 namespace {
 
@@ -40,7 +40,7 @@ __device__ __forceinline__ void block_sum8(float (&v)[8], float (*red)[8], float
         for (int q = 0; q < 8; ++q) red[wave][q] = v[q];
     }
     __syncthreads();
-    if (threadIdx.x < 8) out[threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+    if (threadIdx.x < 8) out[threadIdx.x] = combine4(red[0][threadIdx.x], red[1][threadIdx.x], red[2][threadIdx.x], red[3][threadIdx.x]);
 }
 
 // part[blk] = {sum of loss terms, valid pixels, conf[0..3]} (doubles); cellpart[cell][di][dj][ci]; slab[blk][kTaps]
@@ -162,7 +162,7 @@ __global__ __launch_bounds__(256) void smh_cell_kernel(const float* __restrict__
         for (int q = 0; q < 6; ++q) dred[t >> 6][q] = v[q];
     }
     __syncthreads();
-    if (t < 6) part[(long)blockIdx.x * 6 + t] = (dred[0][t] + dred[1][t]) + (dred[2][t] + dred[3][t]);
+    if (t < 6) part[(long)blockIdx.x * 6 + t] = combine4(dred[0][t], dred[1][t], dred[2][t], dred[3][t]);
 }
 
 // every block re-derives S = sum of loss terms and N = valid pixels in the same fixed order, then takes its share of the
@@ -185,14 +185,14 @@ __global__ __launch_bounds__(256) void smh_finalize_kernel(const double* __restr
         for (int q = 0; q < 6; ++q) sh[t >> 6][q] = v[q];
     }
     __syncthreads();
-    const double S = (sh[0][0] + sh[1][0]) + (sh[2][0] + sh[3][0]);
-    const double N = (sh[0][1] + sh[1][1]) + (sh[2][1] + sh[3][1]);
+    const double S = combine4(sh[0][0], sh[1][0], sh[2][0], sh[3][0]);
+    const double N = combine4(sh[0][1], sh[1][1], sh[2][1], sh[3][1]);
     if (blockIdx.x == 0) {
         if (t == 0) {
             loss[0] = (float)(S / N);
             if (stats) { stats[0] = (float)S; stats[1] = (float)N; }
         }
-        if (conf && t < 4) conf[t] += (int64_t)((sh[0][2 + t] + sh[1][2 + t]) + (sh[2][2 + t] + sh[3][2 + t]));
+        if (conf && t < 4) conf[t] += (int64_t)combine4(sh[0][2 + t], sh[1][2 + t], sh[2][2 + t], sh[3][2 + t]);
     }
     const float gs = (float)(1.0 / N);
     // weight gradient: 64 elements per block, the G slabs split over four thread groups (four independent chains of loads per
@@ -207,7 +207,7 @@ __global__ __launch_bounds__(256) void smh_finalize_kernel(const double* __restr
             for (int k = k0; k < k1; ++k) a += slab[(long)k * kTaps + e];
             wsum[q][t & 63] = a;
             __syncthreads();
-            if (t < 64) dweight[blockIdx.x * 64 + t] = ((wsum[0][t] + wsum[1][t]) + (wsum[2][t] + wsum[3][t])) * gs;
+            if (t < 64) dweight[blockIdx.x * 64 + t] = combine4(wsum[0][t], wsum[1][t], wsum[2][t], wsum[3][t]) * gs;
         }
         return;
     }
@@ -283,7 +283,7 @@ __global__ __launch_bounds__(256) void smh_score_reduce_kernel(const float* __re
         for (int s = s0; s < s1; ++s) a += slab[(long)s * 2 * F + e];
     part[q][t & 63] = a;
     __syncthreads();
-    if (t < 64 && e < 2L * F) dw[e] = (part[0][t] + part[1][t]) + (part[2][t] + part[3][t]);
+    if (t < 64 && e < 2L * F) dw[e] = combine4(part[0][t], part[1][t], part[2][t], part[3][t]);
     if (blockIdx.x == gridDim.x - 1 && t < 128 && db) {     // bias: one wave per channel, fixed order
         const int c = t >> 6, lane = t & 63;
         float b = 0.f;
@@ -306,8 +306,6 @@ int smh_grid(const SmhGeom& g) {
     const long ncell = (long)g.B * g.nci * g.ncj;
     return (int)(ncell < 256 ? ncell : 256);
 }
-
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 }  // namespace
 
