@@ -19,7 +19,9 @@ def test_header_declares_expected_surface():
     for must in ("szn_conv2d_fwd", "szn_conv2d_dgrad", "szn_conv2d_wgrad", "szn_gemm_proj_fwd", "szn_maxpool2x2_ceil_fwd",
                  "szn_bilinear_up32_crop_fwd", "szn_deconv64s32_wgrad", "szn_cosine_loss_fwd", "szn_cosine_loss_bwd",
                  "szn_mse_loss_fwd", "szn_ce2d_fwd", "szn_embed_argmax", "szn_confusion_hist", "szn_fused_head",
-                 "szn_adam_step", "szn_sgd_momentum_step", "szn_version", "szn_device_info", "szn_last_error"):
+                 "szn_adam_step", "szn_sgd_momentum_step", "szn_version", "szn_device_info", "szn_last_error",
+                 "szn_adam_step_g16", "szn_sgd_momentum_step_g16", "szn_adam_step_scaled", "szn_sgd_momentum_step_scaled",
+                 "szn_grad_check_finite", "szn_loss_scale_update", "szn_cast", "szn_dropout2d_mask"):
         assert must in syms
 
 
