@@ -624,6 +624,39 @@ int szn_proj_fp8_fwd(int x_dtype, int w_dtype, long M, int K, int N, int ldo, co
 int szn_image_u8_to_bgr_f32(int B, int H, int W, const uint8_t* rgb_hwc, const double* mean_bgr, float* out_nchw,
                             szn_stream_t stream);
 
+/* ---- validation visualisations (vis_utils.py:4-109; trainer_fcn.py:198-219, trainer_seenmask.py:117-133) -------------------
+ * The uint8 RGB panels the reference draws on the host per validation image, written by one kernel from the device tensors the
+ * validation pass already holds.  img: img_kind 0 = uint8 RGB [B][H][W][3]; 1 = the network input, f32 [B][3][H][W], BGR minus
+ * mean_bgr (host, three doubles, BGR order; required for kind 1).  lbl_true / lbl_pred: int64 [B][H][W] on the device.  out: image b
+ * starts at out + b * out_image_bytes, its rows are out_row_bytes apart (so a caller can render into a larger canvas); bytes outside
+ * the panels are never written.  Integer-exact contract, per source pixel (b, y, x):
+ *   pixel    kind 0: the bytes.  kind 1: v = (double)x_c + mean_bgr[c], u_c = clamp((int)floor(v + 0.5), 0, 255), BGR -> RGB.  (Rounded
+ *            where dataset.untransform truncates: u - mean -> f32 -> + mean comes back exactly u only with rounding, so both kinds
+ *            give the same bytes for an image that went through szn_image_u8_to_bgr_f32.)
+ *   grey     g = (19595 R + 38470 G + 7471 B + 32768) >> 16                                   (PIL's convert('L'))
+ *   colour   of class k in [0, K): for j = 0..7: r |= bit0(c) << (7-j), g |= bit1(c) << (7-j), b |= bit2(c) << (7-j), c >>= 3, from
+ *            c = k (the PASCAL map: 1 -> (128,0,0), 15 -> (192,128,128), 255 -> (224,224,192)); a label outside [0, K) is black
+ *   overlay  (colour + g) >> 1 per channel
+ *   mask     255 on all channels iff the label is in [0, K) and not in `unseen`, else 0
+ *   noise    byte_c = ((h >> 40) * 255) >> 24, h = splitmix64(seed * 0xD1342543DE82EF95 + 3 * ((b*H + y)*W + x) + c): 0..254, the
+ *            generator of szn_dropout2d_mask.  (The reference's noise is unseeded.)
+ * szn_viz_segmentation: panels H x W; columns image | colour | overlay | mask (the mask column only with unseen != NULL: n_col = 4,
+ * else 3); row 0 from lbl_true, row 1 from lbl_pred: the rendered image is 2H x n_col*W.  A pixel is unlabelled iff lbl_true is
+ * < 0 or >= K there (-1, the batch padding -2); an unlabelled pixel is noise in every panel but the image panels, in BOTH rows, the
+ * same three bytes everywhere.  lbl_true == NULL: only the prediction row (H x n_col*W), no noise.
+ * szn_viz_seenmask: one row of three panels, image | 255 * (lbl_true == 1) | 255 * (lbl_pred == 1); pixels with lbl_true < 0 are
+ * noise in panels 1 and 2.
+ * SZN_ERR_ARG: NULL img / lbl_pred / out (seen-mask: lbl_true too), an empty shape, an unknown img_kind, K outside
+ * [1, SZN_MAX_CLASSES], a set naming a class >= K, out_row_bytes below a panel row (3 * n_col * W), out_image_bytes below a rendered
+ * image ((rows*H - 1) * out_row_bytes + 3 * n_col * W).  szn_last_kernel(): viz_panels_kernel, or viz_panels_kernel_v4 when W % 4 == 0,
+ * out, out_row_bytes and out_image_bytes are multiples of 4 (every 4-pixel panel segment is then three aligned dword stores).   */
+int szn_viz_segmentation(int B, int H, int W, const void* img, int img_kind, const double* mean_bgr, const int64_t* lbl_true,
+                         const int64_t* lbl_pred, int K, const szn_class_set* unseen, uint64_t seed, uint8_t* out,
+                         long out_row_bytes, long out_image_bytes, szn_stream_t stream);
+int szn_viz_seenmask(int B, int H, int W, const void* img, int img_kind, const double* mean_bgr, const int64_t* lbl_true,
+                     const int64_t* lbl_pred, uint64_t seed, uint8_t* out, long out_row_bytes, long out_image_bytes,
+                     szn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

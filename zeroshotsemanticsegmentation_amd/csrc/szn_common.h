@@ -53,6 +53,15 @@ inline void szn_adam_scalars(float lr, float beta1, float beta2, int step, float
     *inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
 }
 
+// ---- counter-based random bits: splitmix64 of (seed * 0xD1342543DE82EF95 + counter).  Shared by dropout_mask_kernel (szn_elementwise.hip)
+//      and the noise of the visualisation panels (szn_viz.hip). ----
+__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
 // ---- class sets ---------------------------------------------------------------------------
 // class sets travel as kernel arguments (4 words = SZN_MAX_CLASSES bits).  Words are picked by selects, not by a dynamic index
 // into the by-value struct (which would put it in scratch).

@@ -796,12 +796,7 @@ __global__ void cast_kernel(const S* __restrict__ s, D* __restrict__ d, long n) 
         elem<D>::st(d + i, elem<S>::ld(s + i));
 }
 
-__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+// (splitmix64: szn_common.h -- shared with the visualisation kernel's noise)
 __global__ void dropout_mask_kernel(float* __restrict__ scale, long n, float p, uint64_t seed, uint64_t offset) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;

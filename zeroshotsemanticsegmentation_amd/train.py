@@ -10,6 +10,8 @@ Added for this implementation (none change the reference flags):
                        PASCAL-Context readers of datasets.py load <data_dir> in the reference's layout
   --batch-size B       images per GPU per step (reference: 1)
   --precision fp32|bf16|fp16|bf16x3 (bf16x3: fp32 tensors, conv GEMMs on split-bf16 matrix cores, fp32-accurate)
+  --viz N              render the first N validation images per epoch on the GPU into <log_dir>/{fcn,szn,seenmask}_viz/epoch<E>.jpg
+                       (vis_utils; 25 = the reference's behaviour, 0 = off)
   --init synthetic|vgg path handling: without the caffe VGG16 file the backbone starts from synth weights
   torchrun: RANK / LOCAL_RANK / WORLD_SIZE are honoured (one process per GPU, RCCL gradient all-reduce).
 """
@@ -61,6 +63,10 @@ def build_parser():
                    help="fcn32s = the reference's only backbone (train.py:103,105); fcn8s = the public FCN8s skip head "
                         "(not in the reference: BASELINE north_star wording, parity unpinned)")
     p.add_argument('--workers', type=int, default=2, help='DataLoader worker processes per loader (0 = load in the main process)')
+    p.add_argument('--viz', type=int, default=0, metavar='N',
+                   help="render the first N validation images of every epoch on the GPU and write the mosaic to "
+                        "<log_dir>/{fcn_viz,szn_viz,seenmask_viz}/epoch<E>.jpg (and to tensorboard); 25 is the reference's behaviour, "
+                        "0 (default) writes nothing")
     return p
 
 
@@ -298,7 +304,7 @@ def main(argv=None):
         cuda=True, model=model, optimizer=optim, train_loader=train_seen_loader, val_loader=val_loader, log_dir=log_dir,
         dataset=cfg['dataset'], max_epoch=cfg['fcn_epochs'], pixel_embeddings=cfg['embed_dim'], loss_func=cfg['fcn_loss'],
         tb_writer=tb_writer, unseen=all_unseen, val_unseen=cfg['val_unseen'], label_names=label_names,
-        forced_unseen=cfg['forced_unseen'], precision=precision, rank=rank)
+        forced_unseen=cfg['forced_unseen'], precision=precision, rank=rank, visualize=args.viz)
     fcn_trainer.epoch, fcn_trainer.iteration = start_epoch, start_iteration
 
     if cfg['mode'] == 'train':
@@ -322,7 +328,7 @@ def main(argv=None):
             seenmask_trainer = trainer_seenmask.Trainer(
                 cuda=True, model=model, optimizer=sm_optim, train_loader=train_loader, val_loader=val_loader,
                 log_dir=log_dir, dataset=cfg['dataset'], max_epoch=cfg['seenmask_epochs'], tb_writer=tb_writer,
-                checkpoint=checkpoint, unseen=cfg['train_unseen'], rank=rank)
+                checkpoint=checkpoint, unseen=cfg['train_unseen'], rank=rank, visualize=args.viz)
             seenmask_trainer.train()
     elif cfg['mode'] == 'test_fcn':
         fcn_trainer.validate(both_fcn_and_seenmask=False)

@@ -4,8 +4,9 @@ Same constructor / method surface and return contracts as /root/reference/traine
 forward :83-120, forward_szn :123-147, train_epoch :149-180, validate :182-292, train :294-306), on top of the
 HIP path: with an embedding loss 'cos' or the softmax cross entropy (train.py -c 1) the hot loop runs engine.TrainStep
 (fused head, flat-buffer optimizer, RCCL gradient all-reduce); other losses compose the same kernels through autograd.  Logging (CSV, optional
-tensorboard writer, checkpoints with the reference's dict keys) is host-side and kept format-compatible;
-JPEG tile visualisations (third-party `fcn` package in the reference) are out of scope and skipped.
+tensorboard writer, checkpoints with the reference's dict keys) is host-side and kept format-compatible.
+The JPEG tile visualisations of validation (reference :198-219,267; drawn there on the host through the third-party `fcn` package) are
+rendered on the GPU by vis_utils from the tensors validate() already holds: Trainer(visualize=N) / train.py --viz N, off by default.
 """
 import datetime
 import os
@@ -17,6 +18,7 @@ import torch
 
 from . import engine as _engine
 from . import utils
+from . import vis_utils
 
 _DATA = osp.join(osp.dirname(osp.abspath(__file__)), "data")      # package data: .npy re-saves of the reference's pickles
 
@@ -47,7 +49,7 @@ class Trainer(object):
 
     def __init__(self, cuda, model, optimizer, train_loader, val_loader, log_dir, dataset, max_epoch, tb_writer,
                  pixel_embeddings=None, loss_func=None, unseen=None, val_unseen=None, label_names=None,
-                 forced_unseen=False, embed_arr=None, precision=torch.float32, fused_step=True, rank=0):
+                 forced_unseen=False, embed_arr=None, precision=torch.float32, fused_step=True, rank=0, visualize=0):
         if not cuda:
             raise RuntimeError("this implementation runs on the GPU only (cuda=False has no CPU fallback)")
         self.cuda = cuda
@@ -66,6 +68,8 @@ class Trainer(object):
         self.label_names = label_names
         self.forced_unseen = forced_unseen
         self.rank = rank
+        self.visualize = int(visualize)             # validation images rendered per epoch (the reference: 25); 0 = none
+        self.last_viz = None                        # the last epoch's mosaic, (h, w, 3) uint8 numpy
 
         self.epoch = 0
         self.iteration = 0
@@ -269,9 +273,14 @@ class Trainer(object):
                     self.tb_writer.add_scalar('fcn/train/' + name, v, self.iteration)
             self.iteration += 1
 
-    def _predict_device(self, data, target, szn):
-        """forward + loss + class assignment with everything left on the GPU -> (score, loss 0-dim, pred (n,h,w), target)"""
+    def _predict_device(self, data, target, szn, with_image=False):
+        """forward + loss + class assignment with everything left on the GPU -> (score, loss 0-dim, pred (n,h,w), target), and with
+        `with_image` the device image the network read (n,3,h,w) as a fifth element (what validate() renders)"""
         data, target, target_embed = self._unpack(data, target)
+        out = self._predict_unpacked(data, target, target_embed, szn)
+        return out + (data,) if with_image else out
+
+    def _predict_unpacked(self, data, target, target_embed, szn):
         if (self._embed_cfg() and not szn and not self.forced_unseen and target_embed is None
                 and not self.verbose_val and self.embeddings.shape[0] <= 256):
             # plain embedding inference: loss + class assignment straight from the 1/32 map (no (n,E,h,w) score in HBM)
@@ -314,12 +323,19 @@ class Trainer(object):
         world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
         hist = torch.zeros(3, self.n_class, self.n_class, dtype=torch.int64, device=self.device)
         acc = torch.zeros(2, dtype=torch.float64, device=self.device)          # loss sum, image-batch count
+        n_viz = self.visualize if self.rank == 0 else 0                        # rank 0 renders the first images of its own shard
+        tiles = []                                                             # device pictures, kept there until the epoch ends
+        mean_bgr = vis_utils.dataset_mean_bgr(getattr(self.val_loader, 'dataset', None)) if n_viz else None
         with torch.no_grad():
             for batch_idx, (data, target) in enumerate(self.val_loader):
                 # a loader that is not already sharded per rank (train.py shards it: each rank decodes only its own images)
                 if world > 1 and not getattr(self.val_loader, 'szn_sharded', False) and batch_idx % world != self.rank:
                     continue
-                score, loss, pred, tgt = self._predict_device(data, target, both_fcn_and_seenmask)
+                score, loss, pred, tgt, img = self._predict_device(data, target, both_fcn_and_seenmask, with_image=True)
+                if len(tiles) < n_viz:
+                    # reference :198-206, for every image of the batch; no read-back, no host synchronisation
+                    viz = vis_utils.visualize_segmentation_device(img, tgt, pred, self.n_class, unseen=self.val_unseen, mean_bgr=mean_bgr)
+                    tiles.extend(viz[:n_viz - len(tiles)])
                 acc[0] += loss.double()
                 acc[1] += 1
                 utils.confusion_hist_device(tgt, pred, self.n_class, self.val_unseen if self.unseen else None, hist)
@@ -355,6 +371,11 @@ class Trainer(object):
                 for n, v in zip(names, ms):
                     self.tb_writer.add_scalar('fcn/val/%s%s' % (grp, n), v, self.epoch)
                     print('%s%s: %.3f' % ((grp.replace('/', ' ') or 'overall '), n, v))
+            if tiles:
+                out = osp.join(self.log_dir, 'szn_viz' if both_fcn_and_seenmask else 'fcn_viz')     # reference :209-219
+                os.makedirs(out, exist_ok=True)
+                self.last_viz = vis_utils.save_mosaic(tiles, osp.join(out, 'epoch%d.jpg' % self.epoch))
+                self.tb_writer.add_image('fcn/segmentations', self.last_viz, self.epoch, dataformats='HWC')
         mean_iu = metrics[2]
         is_best = mean_iu > self.best_mean_iu
         if is_best:

@@ -3,6 +3,7 @@
 Same surface as /root/reference/trainer_seenmask.py (Trainer.__init__ :21-48, forward :50-70, train_epoch :72-102,
 validate :104-166, train :168-172).  Target construction keeps the reference's rule: a pixel is "seen" (1) iff its
 label is a seen class, so unlabelled pixels (-1) become 0 = "unseen" and are NOT ignored (:55-56).
+Trainer(visualize=N) renders the reference's per-epoch seenmask_viz picture (:117-133,152) on the GPU through vis_utils.
 """
 import datetime
 import os
@@ -12,6 +13,7 @@ import numpy as np
 import torch
 
 from . import utils
+from . import vis_utils
 
 
 def _now():
@@ -26,7 +28,7 @@ class _NullWriter(object):
 class Trainer(object):
 
     def __init__(self, cuda, model, optimizer, train_loader, val_loader, log_dir, dataset, max_epoch, tb_writer,
-                 checkpoint, unseen, rank=0, fused_step=True):
+                 checkpoint, unseen, rank=0, fused_step=True, visualize=0):
         if not cuda:
             raise RuntimeError("this implementation runs on the GPU only (cuda=False has no CPU fallback)")
         self.cuda = cuda
@@ -43,6 +45,8 @@ class Trainer(object):
         self.rank = rank
         self._step = None
         self._fused_step = fused_step
+        self.visualize = int(visualize)             # validation images rendered per epoch (the reference: 25); 0 = none
+        self.last_viz = None                        # the last epoch's mosaic, (h, w, 3) uint8 numpy
 
         self.epoch = 0
         self.iteration = 0
@@ -74,8 +78,9 @@ class Trainer(object):
         b = self._seen_lut[idx]
         return torch.where(t < -1, torch.full_like(b, -1), b)
 
-    def _forward_device(self, data, target):
-        """-> (score, loss, pred (n,h,w) int64 device tensor, binary target device tensor)"""
+    def _forward_device(self, data, target, with_image=False):
+        """-> (score, loss, pred (n,h,w) int64 device tensor, binary target device tensor), and with `with_image` the device image the
+        network read as a fifth element"""
         if isinstance(target, (tuple, list)):
             target = target[0]
         target = self.binary_target(target)
@@ -85,7 +90,8 @@ class Trainer(object):
             data = data.to(self.device, non_blocking=True)
         score = self.model(data, mode='seenmask')
         loss = utils.cross_entropy2d(score, target, size_average=True)
-        return score, loss, utils.channel_argmax(score), target
+        out = (score, loss, utils.channel_argmax(score), target)
+        return out + (data,) if with_image else out
 
     def forward(self, data, target):
         """-> (score, loss, lbl_pred numpy int64 (n,h,w), lbl_true cpu tensor)   [reference :50-70]"""
@@ -176,6 +182,9 @@ class Trainer(object):
         world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
         hist = torch.zeros(3, self.n_class, self.n_class, dtype=torch.int64, device=self.device)
         acc = torch.zeros(2, dtype=torch.float64, device=self.device)
+        n_viz = self.visualize if self.rank == 0 else 0                        # rank 0 renders the first images of its own shard
+        tiles = []                                                             # device pictures, kept there until the epoch ends
+        mean_bgr = vis_utils.dataset_mean_bgr(getattr(self.val_loader, 'dataset', None)) if n_viz else None
         with torch.no_grad():
             for batch_idx, (data, target) in enumerate(self.val_loader):
                 # a loader that is not already sharded per rank (train.py shards it: each rank decodes only its own images)
@@ -189,7 +198,10 @@ class Trainer(object):
                     loss, pred = self.model.seenmask_predict(data, target.to(self.device), self.n_class, self.unseen)
                     tgt = self.binary_target(target)
                 else:
-                    score, loss, pred, tgt = self._forward_device(data, target)
+                    score, loss, pred, tgt, data = self._forward_device(data, target, with_image=True)
+                if len(tiles) < n_viz:
+                    viz = vis_utils.visualize_seenmask_device(data, tgt, pred, mean_bgr=mean_bgr)       # reference :117-125
+                    tiles.extend(viz[:n_viz - len(tiles)])
                 acc[0] += loss.double()
                 acc[1] += 1
                 utils.confusion_hist_device(tgt, pred, self.n_class, None, hist)
@@ -207,6 +219,11 @@ class Trainer(object):
             for n, v in zip(['pxl_acc', 'class_acc', 'mean_iu', 'fwavacc'], metrics):
                 self.tb_writer.add_scalar('seenmask/val/' + n, v, self.epoch)
                 print('%s: %.3f' % (n, v))
+            if tiles:
+                out = osp.join(self.log_dir, 'seenmask_viz')                                           # reference :127-133
+                os.makedirs(out, exist_ok=True)
+                self.last_viz = vis_utils.save_mosaic(tiles, osp.join(out, 'epoch%d.jpg' % self.epoch))
+                self.tb_writer.add_image('fcn/segmentations', self.last_viz, self.epoch, dataformats='HWC')
         if metrics[2] > self.best_mean_iu:
             self.best_mean_iu = metrics[2]
         if self.rank == 0:
