@@ -657,6 +657,36 @@ int szn_viz_seenmask(int B, int H, int W, const void* img, int img_kind, const d
                      const int64_t* lbl_pred, uint64_t seed, uint8_t* out, long out_row_bytes, long out_image_bytes,
                      szn_stream_t stream);
 
+/* ---- training augmentation (no reference counterpart: the reference shows every image as stored) ------------------------------
+ * Random scale, crop to a fixed size and horizontal flip of a raw batch, in one kernel: uint8 RGB canvases [B][Hm][Wm][3] and their
+ * int64 labels [B][Hm][Wm] (image b occupies the top-left h x w of its canvas) -> the (B,3,Ho,Wo) f32 BGR-minus-mean network input and
+ * the (B,Ho,Wo) int64 target.  params: DEVICE memory, SZN_AUG_NPARAM int32 per image, built on the host:
+ *   [0] h  [1] w           the image's own size inside the canvas
+ *   [2] Hs [3] Ws          its size after scaling
+ *   [4] step_y [5] step_x  source step per output pixel, 16.16 fixed point:  step_y = ((h << 16) + Hs/2) / Hs
+ *   [6] oy [7] ox          origin of the crop window in the scaled image; may be negative and may run past Hs / Ws
+ *   [8] flip               non-zero: mirror the crop horizontally
+ * mean_bgr: host, three doubles, BGR order.  Integer-exact contract, per output pixel (b, yo, xo):
+ *   position  xo' = flip ? Wo-1-xo : xo;  gy = yo + oy, gx = xo' + ox.  gy outside [0, Hs) or gx outside [0, Ws): the pixel is padding,
+ *             all three planes exactly 0.0f (the mean colour) and the label SZN_PAD_LABEL.  Otherwise
+ *             sy = (((2*gy + 1) * (int64)step_y) >> 1) - 32768 (the pixel-centre map of align_corners=False), sx likewise.
+ *   image     sy clamped to [0, (h-1) << 16]; y0 = sy >> 16, y1 = min(y0 + 1, h - 1), wy = (sy & 0xffff) >> 5 (11 bits); x0, x1, wx the
+ *             same from sx and w.  v = (2048-wy) * ((2048-wx)*p00 + wx*p01) + wy * ((2048-wx)*p10 + wx*p11) in int32 (<= 255 * 2^22:
+ *             no overflow, no rounding); out_c = (float)((double)v / 4194304.0 - mean_bgr[c]), plane c from source byte 2 - c.  With
+ *             step 65536, zero origin and no flip, v = p << 22: bit-identical to szn_image_u8_to_bgr_f32.  (Bilinear without
+ *             antialiasing when shrinking.)
+ *   label     nearest neighbour from the UNCLAMPED position: ly = clamp((sy + 32768) >> 16, 0, h-1), lx likewise; the value is copied
+ *             as is (-1 stays -1).
+ * Record fields that cannot be right are made harmless on the device, where alone they can be seen: h, w are clamped to [1, Hm] /
+ * [1, Wm] and every source index to the image, so no read leaves the canvas; Hs or Ws < 1 makes the whole image padding.
+ * SZN_ERR_ARG: a NULL pointer, a size that is not positive, B > 65535.  szn_last_kernel(): augment_u8_kernel_v4 when Wo % 4 == 0 and
+ * out_nchw, out_label are 16-byte aligned (a thread's 4 adjacent output pixels leave as 16-byte stores), else augment_u8_kernel
+ * (scalar stores; the last run of a row is partial).                                                                          */
+#define SZN_AUG_NPARAM 9
+#define SZN_PAD_LABEL (-2)          /* datasets.PAD_LABEL: ignored by every loss, class-assignment and histogram kernel */
+int szn_augment_u8(int B, int Hm, int Wm, const uint8_t* rgb_hwc, const int64_t* label, const int32_t* params,
+                   const double* mean_bgr, int Ho, int Wo, float* out_nchw, int64_t* out_label, szn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,7 @@ class AdamArgs(C.Structure):
 
 
 MAX_CLASSES = 256           # SZN_MAX_CLASSES
+AUG_NPARAM = 9              # SZN_AUG_NPARAM: int32 words of one image's augmentation record (szn_augment_u8)
 
 
 class ClassSet(C.Structure):
@@ -177,6 +178,7 @@ SIGNATURES = {
     "szn_proj_fp8_dgrad": (_I, [_I, _I, _L, _I, _I, _I, _P, _P, _P, _I, _I, _P, _I, _I, _P, _I, _P, _P]),
     "szn_proj_fp8_wgrad": (_I, [_I, _I, _L, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "szn_image_u8_to_bgr_f32": (_I, [_I, _I, _I, _P, C.POINTER(C.c_double), _P, _P]),
+    "szn_augment_u8": (_I, [_I, _I, _I, _P, _P, _P, C.POINTER(C.c_double), _I, _I, _P, _P, _P]),
     "szn_viz_segmentation": (_I, [_I, _I, _I, _P, _I, C.POINTER(C.c_double), _P, _P, _I, _CS, _U64, _P, _L, _L, _P]),
     "szn_viz_seenmask": (_I, [_I, _I, _I, _P, _I, C.POINTER(C.c_double), _P, _P, _U64, _P, _L, _L, _P]),
 }

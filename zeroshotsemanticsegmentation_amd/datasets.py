@@ -267,6 +267,66 @@ def pad_collate(batch):
     return out_i, out_l
 
 
+def augment_collate(batch):
+    """pad_collate for the augmented training route (train.py --crop-size): the same padded (B,Hm,Wm,3) uint8 canvases and (B,Hm,Wm)
+    int64 labels, plus the images' own sizes as a THIRD element, int32 (B,2) = (h, w) -- what Augment.params scales and the kernel needs to
+    keep the canvas padding out of its bilinear taps.  A trainer built with augment= unpacks three elements; the padded pair is never
+    shown to the network as it is."""
+    sizes = torch.tensor([tuple(torch.as_tensor(img).shape[:2]) for img, _ in batch], dtype=torch.int32).reshape(len(batch), 2)
+    out_i, out_l = pad_collate(batch)
+    return out_i, out_l, sizes
+
+
+class Augment(object):
+    """Random scale, crop to a fixed size and horizontal flip per training image (utils.augment_to_device / szn_augment_u8 do the
+    pixels; this class only draws the numbers).  crop = (H, W) of the network input; scale = (lo, hi): one isotropic s ~ U[lo, hi] per
+    image; flip: mirror with probability 1/2.  Where the scaled image is larger than the crop the window origin is uniform over
+    [0, Hs - H] x [0, Ws - W]; where it is smaller the origin is 0: the image sits top-left and PAD_LABEL padding fills the bottom and
+    right, as pad_collate pads.  Every draw is a pure function of (seed, rank, epoch, iteration, index in the batch) -- a Philox
+    counter-based generator keyed by (seed, rank) at counter (epoch, iteration, index) -- so a resumed run and every rank of a
+    data-parallel job reproduce their own stream, and ranks differ."""
+
+    def __init__(self, crop, scale=(0.5, 2.0), flip=True, seed=1337):
+        self.crop = (int(crop[0]), int(crop[1]))
+        self.scale = (float(scale[0]), float(scale[1]))
+        self.flip = bool(flip)
+        self.seed = int(seed)
+        if self.crop[0] < 1 or self.crop[1] < 1:
+            raise ValueError("Augment: crop %s must be positive" % (self.crop,))
+        if not 0.0 < self.scale[0] <= self.scale[1]:
+            raise ValueError("Augment: scale range %s must satisfy 0 < lo <= hi" % (self.scale,))
+
+    @staticmethod
+    def record(h, w, s, oy_u=0.0, ox_u=0.0, flip=False, crop=None):
+        """the int32 record of one image (include/szn.h): scaled size Hs = max(1, floor(h*s + 0.5)), 16.16 step ((h << 16) + Hs/2) / Hs,
+        window origin floor(u * (Hs - H + 1)) for u in [0, 1) where the scaled image exceeds the crop (H, W), else 0"""
+        h, w = int(h), int(w)
+        Hs, Ws = max(1, int(np.floor(h * s + 0.5))), max(1, int(np.floor(w * s + 0.5)))
+        if max(h, w, Hs, Ws) >= 1 << 15:
+            raise ValueError("Augment: image %d x %d scaled to %d x %d exceeds the 16.16 fixed-point range" % (h, w, Hs, Ws))
+        oy = min(int(oy_u * (Hs - crop[0] + 1)), Hs - crop[0]) if crop is not None and Hs > crop[0] else 0
+        ox = min(int(ox_u * (Ws - crop[1] + 1)), Ws - crop[1]) if crop is not None and Ws > crop[1] else 0
+        return [h, w, Hs, Ws, ((h << 16) + Hs // 2) // Hs, ((w << 16) + Ws // 2) // Ws, oy, ox, int(bool(flip))]
+
+    def params(self, sizes, epoch, iteration, rank=0):
+        """sizes (B,2) = (h, w) per image -> int32 numpy (B, AUG_NPARAM)"""
+        sizes = np.asarray(sizes).reshape(-1, 2)
+        out = np.empty((len(sizes), utils.L.AUG_NPARAM), dtype=np.int32)
+        lo, hi = self.scale
+        for i, (h, w) in enumerate(sizes):
+            bits = np.random.Philox(key=[self.seed, int(rank)], counter=[int(epoch), int(iteration), i, 0])
+            u = np.random.Generator(bits).random(4)
+            out[i] = self.record(h, w, lo + (hi - lo) * u[0], u[1], u[2], self.flip and u[3] < 0.5, self.crop)
+        return out
+
+    def apply(self, batch, epoch, iteration, rank=0, device=None, mean_bgr=utils.MEAN_BGR):
+        """one augment_collate batch (images, labels, sizes) -> (data (B,3,H,W) f32, target (B,H,W) int64) on the device"""
+        if not isinstance(batch, (tuple, list)) or len(batch) != 3:
+            raise ValueError("Augment needs (images, labels, sizes) batches: build the training loaders with collate_fn=datasets.augment_collate")
+        img, lbl, sizes = batch
+        return utils.augment_to_device(img, lbl, self.params(sizes, epoch, iteration, rank), self.crop, device, mean_bgr)
+
+
 def download(data_dir):
     """the reference fetches SBD / VOC2012 / the 33-class context labels over HTTP (pascal_dataset.py:148-172,
     context_dataset.py:162-183); this environment has no network, so the data must already be under data_dir"""

@@ -90,9 +90,14 @@ def bilinear_weight(cin, cout, k=64):
     return w
 
 
+def make_image_bytes(B, H, W, seed=1337):
+    """(B,H,W,3) float64 with integer values 0..255: the RGB bytes make_images starts from."""
+    return np.floor(uniform01(seed * 1000 + 900, B * H * W * 3) * 256.0).reshape(B, H, W, 3)
+
+
 def make_images(B, H, W, seed=1337):
     """(B,3,H,W) float32: uint8 RGB noise -> BGR -> minus mean_bgr (context_dataset.py:143-148)."""
-    u = np.floor(uniform01(seed * 1000 + 900, B * H * W * 3) * 256.0).reshape(B, H, W, 3)
+    u = make_image_bytes(B, H, W, seed)
     bgr = u[..., ::-1] - MEAN_BGR
     return np.ascontiguousarray(bgr.transpose(0, 3, 1, 2)).astype(np.float32)
 

@@ -5,6 +5,8 @@ There are no PASCAL images in this environment (no network); real-data loading i
 (next).  __getitem__ -> (img (3,H,W) f32 BGR minus mean, lbl (H,W) int64 with -1 = ignore) or, with embeddings,
 (img, (lbl, lbl)) -- the dense per-pixel embedding volume of the reference (315 MB per 512x512 image at E = 300) is
 replaced by the label itself: the target embedding is gathered on the GPU from the K x E matrix.
+`native=True` mirrors datasets.py's native samples instead: (uint8 (H,W,3) RGB -- the bytes the float image is made from --, lbl), for
+the routes that transform on the GPU (utils.image_to_device, utils.augment_to_device).
 """
 import numpy as np
 import torch
@@ -20,7 +22,8 @@ class SyntheticSegmentation(torch.utils.data.Dataset):
     mean_bgr = synth.MEAN_BGR
 
     def __init__(self, split='train', n_images=8, size=(512, 512), n_class=21, embed_dim=0, unseen=(), seed=1337,
-                 class_names=None):
+                 class_names=None, native=False):
+        self.native = native
         self.split, self.n_images, self.size, self.embed_dim, self.seed = split, n_images, size, embed_dim, seed
         self.class_names = class_names if class_names is not None else (
             PASCAL_CLASSES if n_class == 21 else np.array(['class%d' % i for i in range(n_class)]))
@@ -35,6 +38,9 @@ class SyntheticSegmentation(torch.utils.data.Dataset):
     def __getitem__(self, index):
         H, W = self.size
         s = self.seed + self.offset + index
+        if self.native:
+            img = torch.from_numpy(synth.make_image_bytes(1, H, W, seed=s)[0].astype(np.uint8))
+            return img, torch.from_numpy(synth.make_labels(1, H, W, self.n_class, seed=s, classes=self.classes)[0])
         img = torch.from_numpy(synth.make_images(1, H, W, seed=s)[0])
         lbl = torch.from_numpy(synth.make_labels(1, H, W, self.n_class, seed=s, classes=self.classes)[0])
         if self.embed_dim:

@@ -12,6 +12,8 @@ Added for this implementation (none change the reference flags):
   --precision fp32|bf16|fp16|bf16x3 (bf16x3: fp32 tensors, conv GEMMs on split-bf16 matrix cores, fp32-accurate)
   --viz N              render the first N validation images per epoch on the GPU into <log_dir>/{fcn,szn,seenmask}_viz/epoch<E>.jpg
                        (vis_utils; 25 = the reference's behaviour, 0 = off)
+  --crop-size H W      train on randomly scaled, cropped and mirrored images at a fixed H x W network input (datasets.Augment; one
+                       kernel on the GPU, szn_augment_u8); --scale-range LO HI (default 0.5 2.0), --no-flip.  Validation is untouched
   --init synthetic|vgg path handling: without the caffe VGG16 file the backbone starts from synth weights
   torchrun: RANK / LOCAL_RANK / WORLD_SIZE are honoured (one process per GPU, RCCL gradient all-reduce).
 """
@@ -67,6 +69,12 @@ def build_parser():
                    help="render the first N validation images of every epoch on the GPU and write the mosaic to "
                         "<log_dir>/{fcn_viz,szn_viz,seenmask_viz}/epoch<E>.jpg (and to tensorboard); 25 is the reference's behaviour, "
                         "0 (default) writes nothing")
+    p.add_argument('--crop-size', type=int, nargs=2, metavar=('H', 'W'), default=None,
+                   help="training augmentation on the GPU: every training image is randomly scaled, cropped to H x W and mirrored, so "
+                        "every step runs at one shape (padding carries the ignored label -2); validation is unchanged.  Off by default")
+    p.add_argument('--scale-range', type=float, nargs=2, metavar=('LO', 'HI'), default=[0.5, 2.0],
+                   help="with --crop-size: the isotropic scale of each image is drawn uniformly from [LO, HI]")
+    p.add_argument('--no-flip', action='store_true', help="with --crop-size: never mirror")
     return p
 
 
@@ -236,11 +244,19 @@ def main(argv=None):
     # 1. dataset
     all_unseen = cfg['train_unseen'] + cfg['val_unseen']
     collate = None
+    augment, train_collate = None, None
+    if args.crop_size:
+        # the training loaders hand out raw padded batches with their sizes (at every batch size, 1 included); the trainers scale,
+        # crop and mirror them on the GPU
+        from .datasets import Augment, augment_collate
+        augment = Augment(crop=args.crop_size, scale=args.scale_range, flip=not args.no_flip, seed=1337)
+        train_collate = augment_collate
     if args.synthetic:
         n_img, H, W = args.synthetic
         n_class = 21 if cfg['dataset'] == 'pascal' else 33
         mk = lambda split, unseen, n: SyntheticSegmentation(split=split, n_images=n, size=(H, W), n_class=n_class,
-                                                             embed_dim=cfg['embed_dim'], unseen=unseen, seed=1337)
+                                                             embed_dim=cfg['embed_dim'], unseen=unseen, seed=1337,
+                                                             native=augment is not None and split != 'val')
         # splits as in the reference (pascal_dataset.py:62-74, context_dataset.py:75-94): 'train' drops every image that
         # contains a val_unseen class, 'train_seen' additionally drops the train_unseen classes, 'val' keeps everything
         train_dataset = mk('train', cfg['val_unseen'], n_img)
@@ -262,6 +278,8 @@ def main(argv=None):
 
     def loader(ds, bs, shuffle):
         kw = dict(kwargs, collate_fn=collate) if (collate is not None and bs > 1) else kwargs
+        if train_collate is not None and shuffle:          # the two training loaders
+            kw = dict(kwargs, collate_fn=train_collate)
         if world > 1 and shuffle:       # every rank holds the same dataset; the sampler deals disjoint shards per epoch
             sampler = torch.utils.data.distributed.DistributedSampler(ds, num_replicas=world, rank=rank, shuffle=True, seed=1337)
             return torch.utils.data.DataLoader(ds, batch_size=bs, sampler=sampler, **kw)
@@ -304,7 +322,7 @@ def main(argv=None):
         cuda=True, model=model, optimizer=optim, train_loader=train_seen_loader, val_loader=val_loader, log_dir=log_dir,
         dataset=cfg['dataset'], max_epoch=cfg['fcn_epochs'], pixel_embeddings=cfg['embed_dim'], loss_func=cfg['fcn_loss'],
         tb_writer=tb_writer, unseen=all_unseen, val_unseen=cfg['val_unseen'], label_names=label_names,
-        forced_unseen=cfg['forced_unseen'], precision=precision, rank=rank, visualize=args.viz)
+        forced_unseen=cfg['forced_unseen'], precision=precision, rank=rank, visualize=args.viz, augment=augment)
     fcn_trainer.epoch, fcn_trainer.iteration = start_epoch, start_iteration
 
     if cfg['mode'] == 'train':
@@ -328,7 +346,8 @@ def main(argv=None):
             seenmask_trainer = trainer_seenmask.Trainer(
                 cuda=True, model=model, optimizer=sm_optim, train_loader=train_loader, val_loader=val_loader,
                 log_dir=log_dir, dataset=cfg['dataset'], max_epoch=cfg['seenmask_epochs'], tb_writer=tb_writer,
-                checkpoint=checkpoint, unseen=cfg['train_unseen'], rank=rank, visualize=args.viz)
+                checkpoint=checkpoint, unseen=cfg['train_unseen'], rank=rank, visualize=args.viz,
+                augment=augment)
             seenmask_trainer.train()
     elif cfg['mode'] == 'test_fcn':
         fcn_trainer.validate(both_fcn_and_seenmask=False)

@@ -49,7 +49,7 @@ class Trainer(object):
 
     def __init__(self, cuda, model, optimizer, train_loader, val_loader, log_dir, dataset, max_epoch, tb_writer,
                  pixel_embeddings=None, loss_func=None, unseen=None, val_unseen=None, label_names=None,
-                 forced_unseen=False, embed_arr=None, precision=torch.float32, fused_step=True, rank=0, visualize=0):
+                 forced_unseen=False, embed_arr=None, precision=torch.float32, fused_step=True, rank=0, visualize=0, augment=None):
         if not cuda:
             raise RuntimeError("this implementation runs on the GPU only (cuda=False has no CPU fallback)")
         self.cuda = cuda
@@ -70,6 +70,9 @@ class Trainer(object):
         self.rank = rank
         self.visualize = int(visualize)             # validation images rendered per epoch (the reference: 25); 0 = none
         self.last_viz = None                        # the last epoch's mosaic, (h, w, 3) uint8 numpy
+        # datasets.Augment or None: train_epoch sends every (images, labels, sizes) batch of the training loader (datasets.augment_collate)
+        # through it -- random scale / crop / flip on the GPU, a fixed network input size; validate() never augments
+        self.augment = augment
 
         self.epoch = 0
         self.iteration = 0
@@ -221,7 +224,11 @@ class Trainer(object):
             # would push ~1e-7-sized activation gradients through fp16 unscaled and lose them silently
             raise RuntimeError("precision fp16 is only supported on the fused training step (embedding cosine / mse loss or "
                                "softmax cross entropy, reference optimizer wiring); use bf16 or fp32 for this configuration")
-        for batch_idx, (data, target) in enumerate(self.train_loader):
+        for batch_idx, batch in enumerate(self.train_loader):
+            if self.augment is not None:
+                data, target = self.augment.apply(batch, self.epoch, self.iteration, self.rank, self.device)
+            else:
+                data, target = batch[:2]             # (an augment_collate loader without augment= is the padded route: sizes unused)
             if step is not None:
                 data, target, _ = self._unpack(data, target)
                 step.hist.zero_()

@@ -28,7 +28,7 @@ class _NullWriter(object):
 class Trainer(object):
 
     def __init__(self, cuda, model, optimizer, train_loader, val_loader, log_dir, dataset, max_epoch, tb_writer,
-                 checkpoint, unseen, rank=0, fused_step=True, visualize=0):
+                 checkpoint, unseen, rank=0, fused_step=True, visualize=0, augment=None):
         if not cuda:
             raise RuntimeError("this implementation runs on the GPU only (cuda=False has no CPU fallback)")
         self.cuda = cuda
@@ -47,6 +47,7 @@ class Trainer(object):
         self._fused_step = fused_step
         self.visualize = int(visualize)             # validation images rendered per epoch (the reference: 25); 0 = none
         self.last_viz = None                        # the last epoch's mosaic, (h, w, 3) uint8 numpy
+        self.augment = augment                      # datasets.Augment or None, as in trainer_fcn.Trainer: training batches only
 
         self.epoch = 0
         self.iteration = 0
@@ -132,7 +133,11 @@ class Trainer(object):
             # engine.SeenmaskStep keeps it in fp32
             raise RuntimeError("precision fp16 in phase 2 needs the fused seen-mask step (the reference's single Adam group over "
                                "seenmask_score / seenmask_upscore); use bf16 or fp32 with this optimizer")
-        for batch_idx, (data, target) in enumerate(self.train_loader):
+        for batch_idx, batch in enumerate(self.train_loader):
+            if self.augment is not None:
+                data, target = self.augment.apply(batch, self.epoch, self.iteration, self.rank, self.device)
+            else:
+                data, target = batch[:2]             # (an augment_collate loader without augment= is the padded route: sizes unused)
             if step is not None:
                 if isinstance(target, (tuple, list)):
                     target = target[0]
