@@ -687,6 +687,46 @@ int szn_viz_seenmask(int B, int H, int W, const void* img, int img_kind, const d
 int szn_augment_u8(int B, int Hm, int Wm, const uint8_t* rgb_hwc, const int64_t* label, const int32_t* params,
                    const double* mean_bgr, int Ho, int Wo, float* out_nchw, int64_t* out_label, szn_stream_t stream);
 
+/* ---- multi-scale / mirrored inference (no reference counterpart: the reference evaluates every image once, as stored) -----------
+ * szn_resize_flip_f32 makes one view of the network input: in (B,3,H,W) f32 NCHW -> out (B,3,Hs,Ws), bilinear without antialiasing,
+ * with the position map and the 11-bit weights of szn_augment_u8.  Per output pixel (b, yo, xo), xo' = flip ? Ws-1-xo : xo:
+ *   step_y = ((H << 16) + Hs/2) / Hs;  sy = (((2*yo + 1) * (int64)step_y) >> 1) - 32768 clamped to [0, (H-1) << 16];
+ *   y0 = sy >> 16, y1 = min(y0 + 1, H - 1), wy = (sy & 0xffff) >> 5;  x0, x1, wx the same from xo', W and Ws;
+ *   out = (float)(((2048-wy) * ((2048-wx)*(double)p00 + wx*(double)p01) + wy * ((2048-wx)*(double)p10 + wx*(double)p11)) / 4194304.0)
+ * in that operation order, no contraction.  Hs == H, Ws == W, flip == 0 reproduces the input bit for bit.
+ * SZN_ERR_ARG: a NULL pointer, a size that is not positive, B > 65535.                                                            */
+int szn_resize_flip_f32(int B, int H, int W, const float* in_nchw, int Hs, int Ws, int flip, float* out_nchw, szn_stream_t stream);
+
+/* szn_ms_head: the view-ensemble embedding head.  It reads the coarse maps the network produced for n_views views of one batch
+ * (szn_resize_flip_f32 of the (B,3,H,W) input) and writes the class prediction at the original size, without a per-pixel score in
+ * memory.  One view: its NHWC f32 coarse map (DEVICE pointer) [B][h][w] with pixel stride ldc, the E embedding channels at
+ * [c0, c0+E); Hs x Ws = the view's image size; flip = the view was mirrored.  The array of views is HOST memory, read during the call.
+ * Per original pixel (b, y, x) and view v, in array order:
+ *   xm = flip_v ? W-1-x : x; (y, xm) is mapped into the view's Hs x Ws grid by the map above (source size Hs, Ws; destination H, W):
+ *   four view pixels with 11-bit weights.  A view pixel's score vector is the stride-S bilinear upsample + crop of coarse_v
+ *   (szn_bilinear_up_crop_fwd's definition); s_v = the weighted sum of the four;
+ *   sim_v[k] = s_v . e_k / (||s_v|| * (||e_k|| == 0 ? 1 : ||e_k||))   (szn_embed_argmax's formula);   A[k] = sum_v sim_v[k], added in
+ *   fp32 in view order.
+ * pred = the first k whose value exceeds the running best, starting from k = 0 (a NaN gives class 0).  Group modes 0 / 1 / 2 are
+ * szn_fused_head_grouped's: a class outside the pixel's group competes with the value 0 instead of A[k]; negative labels take the
+ * seen group.  acc (optional, [B][H][W][K] f32) receives the ungrouped A; pred does not depend on it.  The E-long products are taken
+ * once per coarse position (C_pos . e_k and the Gram entries C_pos . C_q of the 13 neighbour offsets a pixel's 3 x 3 composite taps
+ * can pair), the pixel pass combines them.  Fixed order, no atomics: two calls are bit-equal.  szn_last_kernel(): ms_pixel_kernel.
+ * workspace: szn_ms_head_workspace_bytes (0 for arguments szn_ms_head refuses), 16-byte aligned; its head is a szn_fused_head_prepare
+ * image, written by the call.
+ * SZN_ERR_ARG, before any launch: n_views outside [1, SZN_MS_MAX_VIEWS]; stride not 8 or 32; a NULL views[i].coarse, embed, pred or
+ * workspace; a size that is not positive; a map with h or w > 32767 or B h w >= 2^33; Hs or Ws < 1; ldc < c0 + E; a view with Hs + crop > stride * (h + 1) or Ws + crop >
+ * stride * (w + 1); K > SZN_MAX_CLASSES; group mode 1 without group_map, 2 without target; a class in `unseen` >= K.             */
+typedef struct szn_ms_view {
+    const float* coarse;
+    int h, w, ldc, c0, Hs, Ws, flip;
+} szn_ms_view_t;
+#define SZN_MS_MAX_VIEWS 16
+size_t szn_ms_head_workspace_bytes(int stride, int B, int E, int K, int n_views, const szn_ms_view_t* views);
+int szn_ms_head(int stride, int B, int E, int K, int H, int W, int crop, int n_views, const szn_ms_view_t* views,
+                const float* embed, const szn_class_set* unseen, int group_mode, const int64_t* group_map,
+                const int64_t* target, int64_t* pred, float* acc, void* workspace, szn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

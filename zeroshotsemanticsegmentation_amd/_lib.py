@@ -75,10 +75,20 @@ def class_set(classes):
     return C.byref(cs) if any_ else None
 
 
+MS_MAX_VIEWS = 16           # SZN_MS_MAX_VIEWS
+
+
+class MsView(C.Structure):
+    """szn_ms_view_t (include/szn.h): one view of szn_ms_head -- its coarse map (device pointer), the map's geometry, the view's image
+    size and whether it was mirrored"""
+    _fields_ = [("coarse", C.c_void_p)] + [(n, C.c_int) for n in ("h", "w", "ldc", "c0", "Hs", "Ws", "flip")]
+
+
 _P, _I, _L, _F, _U64, _SZ = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_uint64, C.c_size_t
 _D = C.POINTER(ConvDesc)
 _IP = C.POINTER(C.c_int)
 _CS = C.POINTER(ClassSet)
+_MV = C.POINTER(MsView)
 
 # name -> (restype, argtypes); must list every symbol of include/szn.h (tests/test_abi.py checks that)
 SIGNATURES = {
@@ -179,6 +189,9 @@ SIGNATURES = {
     "szn_proj_fp8_wgrad": (_I, [_I, _I, _L, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "szn_image_u8_to_bgr_f32": (_I, [_I, _I, _I, _P, C.POINTER(C.c_double), _P, _P]),
     "szn_augment_u8": (_I, [_I, _I, _I, _P, _P, _P, C.POINTER(C.c_double), _I, _I, _P, _P, _P]),
+    "szn_resize_flip_f32": (_I, [_I, _I, _I, _P, _I, _I, _I, _P, _P]),
+    "szn_ms_head_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I, _MV]),
+    "szn_ms_head": (_I, [_I] * 8 + [_MV, _P, _CS, _I, _P, _P, _P, _P, _P, _P]),
     "szn_viz_segmentation": (_I, [_I, _I, _I, _P, _I, C.POINTER(C.c_double), _P, _P, _I, _CS, _U64, _P, _L, _L, _P]),
     "szn_viz_seenmask": (_I, [_I, _I, _I, _P, _I, C.POINTER(C.c_double), _P, _P, _U64, _P, _L, _L, _P]),
 }

@@ -186,7 +186,7 @@ __device__ __forceinline__ void fh_scatter_A(const FhPx& px, int K, int lane, fl
 //                   | per cell: A [4][KP] , Bm [16]
 //            doubles (8-B aligned) part [cells][2] | sums [B][2] (per-image {sum, count})
 //            floats the per-position tables of the small-cell path: D [pos][KP] | N [pos][8]
-__host__ __device__ inline size_t ws_cell_off(int E, int KP) { return (size_t)E * KP + 2 * KP; }
+__host__ __device__ inline size_t ws_cell_off(int E, int KP) { return prep_floats(E, KP); }
 __host__ __device__ inline size_t ws_cell_stride(int KP) { return (size_t)4 * KP + 16; }
 struct FhWorkspace { size_t part, sums, tabD, tabN, bytes; };       // byte offsets
 inline FhWorkspace fh_workspace(int B, int h, int w, int E, int KP) {
@@ -574,8 +574,6 @@ __global__ __launch_bounds__(256) void fh_gather_kernel(const float* __restrict_
         elem<T>::st(dcoarse + ((size_t)pos) * ldc + c0 + c, v);
     }
 }
-
-inline int kp_of(int K) { return K <= 24 ? 24 : (K <= 40 ? 40 : (K <= 64 ? 64 : (K + 63) / 64 * 64)); }      // K <= 256
 
 // the cell pass: stride 32 a block per cell; stride 8 the position tables, then a wave per cell
 template <int KP, bool GROUPED, bool MSE>

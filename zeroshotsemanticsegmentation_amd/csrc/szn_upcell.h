@@ -34,4 +34,9 @@ __device__ __forceinline__ long tap_pos(int b, int h, int w, int I, int J, int t
 template <typename T>
 __host__ __device__ __forceinline__ T combine4(T a0, T a1, T a2, T a3) { return (a0 + a1) + (a2 + a3); }
 
+// the embedding tables szn_fused_head_prepare writes to the head of a workspace: embT [E][KP] | en [KP] (0 -> 1) | ent [KP] floats,
+// KP = the class count padded (K <= 256).  szn_fused_head.hip writes and reads them, szn_msinfer.hip reads them.
+inline int kp_of(int K) { return K <= 24 ? 24 : (K <= 40 ? 40 : (K <= 64 ? 64 : (K + 63) / 64 * 64)); }
+__host__ __device__ inline size_t prep_floats(int E, int KP) { return (size_t)E * KP + 2 * KP; }
+
 inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }

@@ -9,6 +9,8 @@ szn_fused_ce_head and szn_seenmask_head_k goes through here (models.FCN32s / FCN
             Workspace tables; loss, stats and d(map) are those of sum |s - e_label|^2 / N_b.
   ce        the softmax cross-entropy head, stride 32 or 8.
   seenmask  the x32 seen-mask head on the 1/32 map: training, predict and pred-only (group map) calls.
+  ms        multi-scale / mirrored inference: the views of an input (szn_resize_flip_f32) and the view-ensemble head (szn_ms_head),
+            which reads the maps of all views and writes one prediction.
 
 The crop belongs to the stride (32: CROP, reference models.py:147; 8: CROP_UP8, FCN8s' upscore8).  A call without a `Workspace`
 allocates its scratch and builds the embedding tables itself (the predict methods); TrainStep keeps one `Workspace` across steps.
@@ -134,6 +136,61 @@ def mse(*args, **kw):
 
 def mse_predict(*args, **kw):
     return embed_predict("mse", *args, **kw)
+
+
+# ---- view-ensemble embedding head (multi-scale / mirrored inference) ---------------------------------------------------------
+def ms_views(H, W, scales, flip=False):
+    """the views of an H x W input: [(Hs, Ws, flipped)] by ascending scale, the plain view before the mirrored one;
+    Hs = max(1, floor(H * s + 0.5)).  `scales` must contain 1.0: the identity view's pass also gives the loss."""
+    scales = sorted(float(s) for s in scales)
+    if 1.0 not in scales:
+        raise L.SznError("multi-scale inference: scales must contain 1.0 (got %r)" % (scales,))
+    if any(not s > 0 for s in scales):
+        raise L.SznError("multi-scale inference: scales must be positive (got %r)" % (scales,))
+    views = []
+    for s in scales:
+        size = (max(1, int(H * s + 0.5)), max(1, int(W * s + 0.5)))
+        views += [size + (False,)] + ([size + (True,)] if flip else [])
+    if len(views) > L.MS_MAX_VIEWS:
+        raise L.SznError("multi-scale inference: %d views, at most %d" % (len(views), L.MS_MAX_VIEWS))
+    return views
+
+
+def resize_flip(x, Hs, Ws, flip=False):
+    """szn_resize_flip_f32: the (B,3,Hs,Ws) view of the (B,3,H,W) fp32 network input `x`, mirrored when `flip`"""
+    x = x.to(torch.float32).contiguous()
+    B, C, H, W = x.shape
+    if C != 3:
+        raise L.SznError("resize_flip: a (B,3,H,W) input is expected, got %r" % (tuple(x.shape),))
+    out = torch.empty(B, 3, Hs, Ws, dtype=torch.float32, device=x.device)
+    L.call("szn_resize_flip_f32", B, H, W, L.ptr(x), Hs, Ws, int(bool(flip)), L.ptr(out), L.stream_ptr())
+    return out
+
+
+def ms_predict(stride, views, emb, H, W, target=None, mode=0, unseen=None, gmap=None, want_acc=False):
+    """szn_ms_head: views = [(fmap, Hs, Ws, flipped)], each fmap the contiguous fp32 NHWC map (the E embedding channels first) of the
+    Hs x Ws view of one (B,3,H,W) batch, in ensemble order.  mode / unseen / gmap / target: the group rule of embed().
+    -> pred (B,H,W) int64, or (pred, acc (B,H,W,K) fp32: the summed similarities before the group rule) with want_acc."""
+    K, E = emb.shape
+    if not views or len(views) > L.MS_MAX_VIEWS:
+        raise L.SznError("ms_predict: %d views, between 1 and %d are taken" % (len(views), L.MS_MAX_VIEWS))
+    B, dev = views[0][0].shape[0], views[0][0].device
+    arr = (L.MsView * len(views))()
+    for rec, (fmap, Hs, Ws, flipped) in zip(arr, views):
+        if fmap.dtype != torch.float32 or not fmap.is_contiguous() or fmap.dim() != 4 or fmap.shape[0] != B:
+            raise L.SznError("ms_predict: every view's map must be a contiguous fp32 (B,h,w,C) tensor")
+        rec.coarse, rec.h, rec.w, rec.ldc, rec.c0 = fmap.data_ptr(), fmap.shape[1], fmap.shape[2], fmap.shape[3], 0
+        rec.Hs, rec.Ws, rec.flip = int(Hs), int(Ws), int(bool(flipped))
+    nbytes = L.load().szn_ms_head_workspace_bytes(stride, B, E, K, len(views), arr)
+    if nbytes == 0:
+        raise L.SznError("ms_predict: bad geometry (stride %d, B %d, E %d, K %d, %d views)" % (stride, B, E, K, len(views)))
+    buf = _scratch(nbytes, dev)
+    pred = torch.empty(B, H, W, dtype=torch.int64, device=dev)
+    acc = torch.empty(B, H, W, K, dtype=torch.float32, device=dev) if want_acc else None
+    tgt = None if target is None else target.to(device=dev, dtype=torch.int64).contiguous()
+    L.call("szn_ms_head", stride, B, E, K, H, W, _CROP[stride], len(views), arr, L.ptr(emb), L.class_set(unseen), mode, L.ptr(gmap),
+           L.ptr(tgt), L.ptr(pred), L.ptr(acc), L.ptr(buf), L.stream_ptr())
+    return (pred, acc) if want_acc else pred
 
 
 # ---- softmax cross-entropy head -------------------------------------------------------------------------------------------

@@ -1451,6 +1451,38 @@ class FCN32s(nn.Module):
                 self._last_group = heads.seenmask_group(ctx.coarse, self.n_class, self._engine._images["up.w"], ctx.H, ctx.W)
             return heads.embed_predict(kind, stride, fmap, emb, ctx.H, ctx.W, target, mode, unseen, self._last_group)
 
+    def ms_predict(self, x, embeddings, scales, flip=False, target=None, unseen=None, group=None, loss="cos"):
+        """multi-scale (and mirrored) inference: the network runs once per view of `x` -- every scale of `scales`, which must contain
+        1.0, by ascending scale, each followed by its mirror image when `flip` (heads.ms_views; the views are szn_resize_flip_f32 of
+        x) -- and the view-ensemble head (szn_ms_head) sums every class's cosine similarity over the views per original pixel and
+        takes the nearest class, without a per-pixel score of any view in HBM.  group=None: all classes compete (embed_predict's
+        rule); 'seenmask' | 'target' with `unseen`: szn_predict's groups -- the seen-mask group map is the identity view's.
+        -> (loss 0-dim tensor or None, pred (B,H,W) int64).  The loss is the identity view's: exactly what embed_predict /
+        szn_predict[_mse] return for x, bit for bit (that view's pass is shared with them); only the prediction comes from the
+        ensemble.  The class assignment is the cosine argmax whatever the loss.  Softmax models have no such head: SznError."""
+        if embeddings is None or loss == "cross_entropy":
+            raise L.SznError("ms_predict: multi-scale inference is built for the embedding heads (loss 'cos' | 'mse'); averaging "
+                             "softmax probabilities over views is not")
+        kind = heads.embed_kind(loss)
+        mode = 0 if group is None else self._szn_group(group, target)
+        H, W = int(x.shape[2]), int(x.shape[3])
+        plan = heads.ms_views(H, W, scales, flip)
+        with torch.no_grad():
+            ctx, stride, fmap = self._head_map(x)
+            emb = heads.embeddings(embeddings, self.n_class, fmap.device)
+            self._last_group = None
+            if mode == 1:
+                self._last_group = heads.seenmask_group(ctx.coarse, self.n_class, self._engine._images["up.w"], H, W)
+            loss_t, _ = heads.embed_predict(kind, stride, fmap, emb, H, W, target, mode, unseen if mode else None, self._last_group)
+            # every view's map is copied out before the next forward pass reuses the engine's buffers
+            maps = {(H, W, False): fmap.to(torch.float32, copy=True)}
+            for key in plan:
+                if key not in maps:
+                    maps[key] = self._head_map(heads.resize_flip(x, *key))[2].to(torch.float32, copy=True)
+            self._last_pred = heads.ms_predict(stride, [(maps[key],) + key for key in plan], emb, H, W, target, mode,
+                                               unseen if mode else None, self._last_group)
+        return loss_t, self._last_pred
+
     def seenmask_predict(self, x, target, n_class, unseen):
         """forward pass + seen-mask loss and prediction WITHOUT the (B,2,H,W) score: szn_seenmask_head evaluates the learned
         stride-32 deconv + crop (models.py:150-151), the binary target `label is a seen class` (trainer_seenmask.py:53-56), the

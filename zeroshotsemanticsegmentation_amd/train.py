@@ -75,6 +75,12 @@ def build_parser():
     p.add_argument('--scale-range', type=float, nargs=2, metavar=('LO', 'HI'), default=[0.5, 2.0],
                    help="with --crop-size: the isotropic scale of each image is drawn uniformly from [LO, HI]")
     p.add_argument('--no-flip', action='store_true', help="with --crop-size: never mirror")
+    p.add_argument('--eval-scales', type=float, nargs='+', metavar='S', default=None,
+                   help="multi-scale validation (per-epoch validation, -m test_fcn, -m test_all): every image is evaluated at each of "
+                        "these scales (1.0 must be among them) and the classes' cosine similarities are summed over the views; "
+                        "embedding configurations only.  Default: once, as stored")
+    p.add_argument('--eval-flip', action='store_true', help="validation also evaluates the mirror image of every view (alone: of the "
+                                                            "stored image)")
     return p
 
 
@@ -200,11 +206,23 @@ def check_precision(precision, cfg):
                         "or fp32" % (cfg['fcn_loss'], cfg['embed_dim']))
 
 
+def check_eval_views(scales, flip, cfg):
+    """--eval-scales / --eval-flip: an embedding configuration (the view-ensemble head sums cosine similarities) and 1.0 among the scales"""
+    if not scales and not flip:
+        return
+    if not (cfg['embed_dim'] and cfg['fcn_loss'] in ('cos', 'mse')):
+        raise Exception("--eval-scales / --eval-flip need an embedding configuration with fcn_loss 'cos' or 'mse' (got loss %r, "
+                        "embed_dim %r)" % (cfg['fcn_loss'], cfg['embed_dim']))
+    if scales and 1.0 not in [float(s) for s in scales]:
+        raise Exception("--eval-scales must contain 1 (got %r)" % (scales,))
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     cfg = update_cfg_with_args(configurations[args.config], args)
     validate_cfg(cfg)
     check_precision(args.precision, cfg)
+    check_eval_views(args.eval_scales, args.eval_flip, cfg)
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", str(args.gpu)))
@@ -322,7 +340,8 @@ def main(argv=None):
         cuda=True, model=model, optimizer=optim, train_loader=train_seen_loader, val_loader=val_loader, log_dir=log_dir,
         dataset=cfg['dataset'], max_epoch=cfg['fcn_epochs'], pixel_embeddings=cfg['embed_dim'], loss_func=cfg['fcn_loss'],
         tb_writer=tb_writer, unseen=all_unseen, val_unseen=cfg['val_unseen'], label_names=label_names,
-        forced_unseen=cfg['forced_unseen'], precision=precision, rank=rank, visualize=args.viz, augment=augment)
+        forced_unseen=cfg['forced_unseen'], precision=precision, rank=rank, visualize=args.viz, augment=augment,
+        eval_scales=args.eval_scales, eval_flip=args.eval_flip)
     fcn_trainer.epoch, fcn_trainer.iteration = start_epoch, start_iteration
 
     if cfg['mode'] == 'train':

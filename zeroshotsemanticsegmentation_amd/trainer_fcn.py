@@ -49,7 +49,8 @@ class Trainer(object):
 
     def __init__(self, cuda, model, optimizer, train_loader, val_loader, log_dir, dataset, max_epoch, tb_writer,
                  pixel_embeddings=None, loss_func=None, unseen=None, val_unseen=None, label_names=None,
-                 forced_unseen=False, embed_arr=None, precision=torch.float32, fused_step=True, rank=0, visualize=0, augment=None):
+                 forced_unseen=False, embed_arr=None, precision=torch.float32, fused_step=True, rank=0, visualize=0, augment=None,
+                 eval_scales=None, eval_flip=False):
         if not cuda:
             raise RuntimeError("this implementation runs on the GPU only (cuda=False has no CPU fallback)")
         self.cuda = cuda
@@ -73,6 +74,17 @@ class Trainer(object):
         # datasets.Augment or None: train_epoch sends every (images, labels, sizes) batch of the training loader (datasets.augment_collate)
         # through it -- random scale / crop / flip on the GPU, a fixed network input size; validate() never augments
         self.augment = augment
+        # multi-scale / mirrored validation (models.ms_predict): the scales every validation image is evaluated at (None: once, as
+        # stored) and whether each is also evaluated mirrored.  Training steps never see them.
+        self.eval_scales = tuple(float(s) for s in eval_scales) if eval_scales else None
+        self.eval_flip = bool(eval_flip)
+        self._ms_warned = False
+        if (self.eval_scales or self.eval_flip) and not (pixel_embeddings and loss_func in ("cos", "mse")):
+            from ._lib import SznError
+            raise SznError("eval_scales / eval_flip need an embedding configuration (loss 'cos' | 'mse'): averaging softmax "
+                           "probabilities over views is not built")
+        if self.eval_flip and not self.eval_scales:
+            self.eval_scales = (1.0,)
 
         self.epoch = 0
         self.iteration = 0
@@ -291,15 +303,26 @@ class Trainer(object):
         if (self._embed_cfg() and not szn and not self.forced_unseen and target_embed is None
                 and not self.verbose_val and self.embeddings.shape[0] <= 256):
             # plain embedding inference: loss + class assignment straight from the 1/32 map (no (n,E,h,w) score in HBM)
+            if self.eval_scales:
+                loss, pred = self.model.ms_predict(data, self.embeddings, self.eval_scales, self.eval_flip, target, loss=self.loss_func)
+                return None, loss, pred, target
             loss, pred = self.model.embed_predict(data, self.embeddings, target, loss=self.loss_func)
             return None, loss, pred, target
         if (self._embed_cfg() and (szn or self.forced_unseen) and target_embed is None
                 and not self.verbose_val and self.embeddings.shape[0] <= 256):
             # full SZN network (seen-mask-stitched) or forced-unseen inference, same route: the seen-mask group (or the target's)
             # picks the class subset per pixel inside the fused head -- neither (n,E,h,w) nor (n,2,h,w) score in HBM
+            if self.eval_scales:
+                loss, pred = self.model.ms_predict(data, self.embeddings, self.eval_scales, self.eval_flip, target, unseen=self.unseen,
+                                                   group='seenmask' if szn else 'target', loss=self.loss_func)
+                return None, loss, pred, target
             predict = self.model.szn_predict if self.loss_func == "cos" else self.model.szn_predict_mse
             loss, pred = predict(data, self.embeddings, self.unseen, target, group='seenmask' if szn else 'target')
             return None, loss, pred, target
+        if self.eval_scales and not self._ms_warned:
+            # dense target embeddings, SZN_VERBOSE_VAL and more than 256 classes keep the materialised-score route: one view
+            self._ms_warned = True
+            print("warning: eval_scales / eval_flip ignored: this validation route materialises the score and evaluates one view")
         if self._ce_cfg() and self._fused_step and not szn and not self.verbose_val:
             # softmax inference: summed cross entropy + channel argmax straight from the coarse map (no (n,C,h,w) score in HBM)
             loss, pred = self.model.softmax_predict(data, target)
