@@ -727,6 +727,44 @@ int szn_ms_head(int stride, int B, int E, int K, int H, int W, int crop, int n_v
                 const float* embed, const szn_class_set* unseen, int group_mode, const int64_t* group_map,
                 const int64_t* target, int64_t* pred, float* acc, void* workspace, szn_stream_t stream);
 
+/* ---- calibrated generalized zero-shot inference (calibrated stacking) ---------------------------------------------------------
+ * szn_calib_head: one scalar gamma is subtracted from the similarity of every SEEN class (a class not in `unseen`) before the argmax,
+ * for n_gammas candidate values in one pass over the pixels: per gamma a confusion histogram, and for one of them the prediction.
+ * coarse, embed, stride (32 | 8), crop, ldc and c0 are szn_fused_head_strided's.  gammas: HOST memory, read during the call, finite and
+ * strictly ascending.  Per pixel:
+ *   sim[k] = the ungrouped similarity of szn_fused_head_strided, the same operations in the same order (the G / Q tables, the fmaf chain
+ *            over the four taps, d / (sn * en[k]) with a zero norm replaced by 1);
+ *   a, va  = the first seen class holding the seen maximum (the running best starts at the first seen class, only a strictly larger
+ *            value replaces it);  b, vb = the same over the unseen classes;  m = va - vb, one fp32 subtraction;
+ *   pred_g = 0 if m is NaN; else a if m > gammas[g], or if m == gammas[g] and a < b; else b.
+ * The rule is written on the margin, not as an argmax over sim[k] - gamma: rounding the penalised values could create ties and reorder
+ * the classes inside the seen group.  Consequences: at gamma = 0 pred equals szn_fused_head_strided's pred bit for bit wherever the
+ * similarities are finite (m > 0 exactly when va > vb, an exact tie goes to the smaller index); a zero-norm pixel gives class 0 in both.
+ *   hist [n_gammas][K][K] int64 (device, or NULL):  hist[g][t][pred_g] += 1 for every pixel whose target t has 0 <= t < K
+ *            (szn_confusion_hist_k's rule: -1, the padding label and labels >= K are skipped).  The seen / unseen histograms of a
+ *            validation pass are row subsets of hist[g]; the caller takes them.
+ *   pred (B,H,W) int64 (device, or NULL): pred_g for g = pred_index.
+ * With ascending gammas the g at which a pixel takes b are upward closed, so a pixel is described by (t, a, b, bin), bin = the first g
+ * at which it takes b (n_gammas: never).  The pixel pass adds the pixel to two crossing tables XA[t][a][bin], XB[t][b][bin] in the
+ * workspace (zeroed by the call; equal keys of a wave are combined first, one 64-bit integer atomic add per distinct key and table), a
+ * second small kernel adds sum_{bin > g} XA[t][k][bin] + sum_{bin <= g} XB[t][k][bin] to hist[g][t][k]: the cost does not grow with
+ * n_gammas.  The counts are integers: any accumulation order gives the same result, two calls are bit-equal.
+ * szn_last_kernel(): calib_hist_kernel when hist is given (szn_prev_kernel(): the pixel kernel), else the pixel kernel --
+ * calib_cell_kernel (stride 32) or calib_cell_tab_kernel (stride 8).
+ * workspace: szn_calib_head_workspace_bytes (0 for arguments szn_calib_head refuses), 16-byte aligned: a szn_fused_head_prepare image
+ * written by the call, the stride-8 position tables, and the crossing tables, 2 * K^2 * (n_gammas + 1) int64 (1.9 MB at K = 59, 33 gammas).
+ * SZN_ERR_ARG, before any launch: stride not 8 or 32; n_gammas outside [1, SZN_CALIB_MAX_GAMMAS]; a gamma that is not finite, or gammas
+ * not strictly ascending; hist and pred both NULL; hist without target; pred with pred_index outside [0, n_gammas); NULL coarse, embed,
+ * workspace or gammas; `unseen` NULL or empty, or containing every class below K (both groups must be non-empty); a class in `unseen`
+ * >= K; K > SZN_MAX_CLASSES; a size that is not positive, ldc < c0 + E, a crop window larger than the deconv output, a workspace that is
+ * not 16-byte aligned (szn_fused_head_strided's checks).                                                                            */
+#define SZN_CALIB_MAX_GAMMAS 64
+size_t szn_calib_head_workspace_bytes(int stride, int B, int h, int w, int E, int K, int n_gammas);
+int szn_calib_head(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                   const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
+                   int n_gammas, const float* gammas, int64_t* hist, int pred_index, int64_t* pred,
+                   void* workspace, szn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,6 +76,7 @@ def class_set(classes):
 
 
 MS_MAX_VIEWS = 16           # SZN_MS_MAX_VIEWS
+CALIB_MAX_GAMMAS = 64       # SZN_CALIB_MAX_GAMMAS
 
 
 class MsView(C.Structure):
@@ -89,6 +90,7 @@ _D = C.POINTER(ConvDesc)
 _IP = C.POINTER(C.c_int)
 _CS = C.POINTER(ClassSet)
 _MV = C.POINTER(MsView)
+_FP = C.POINTER(C.c_float)      # a HOST float array
 
 # name -> (restype, argtypes); must list every symbol of include/szn.h (tests/test_abi.py checks that)
 SIGNATURES = {
@@ -192,6 +194,8 @@ SIGNATURES = {
     "szn_resize_flip_f32": (_I, [_I, _I, _I, _P, _I, _I, _I, _P, _P]),
     "szn_ms_head_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I, _MV]),
     "szn_ms_head": (_I, [_I] * 8 + [_MV, _P, _CS, _I, _P, _P, _P, _P, _P, _P]),
+    "szn_calib_head_workspace_bytes": (_SZ, [_I] * 7),
+    "szn_calib_head": (_I, [_I] * 11 + [_P, _P, _P, _CS, _I, _FP, _P, _I, _P, _P, _P]),
     "szn_viz_segmentation": (_I, [_I, _I, _I, _P, _I, C.POINTER(C.c_double), _P, _P, _I, _CS, _U64, _P, _L, _L, _P]),
     "szn_viz_seenmask": (_I, [_I, _I, _I, _P, _I, C.POINTER(C.c_double), _P, _P, _U64, _P, _L, _L, _P]),
 }

@@ -20,6 +20,8 @@
 //   fh_cell_tab_kernel   ... one wave per 8x8 cell looks its G, Q up, then walks its 64 pixels
 //   fh_image_sums_kernel per-image sums of the cells' loss partials -> stats;  fh_finalize_kernel: the images -> loss
 //   fh_gather_kernel     one block per coarse position sums the <= 4 cells that use it as a tap and writes dcoarse
+//   calib_cell_kernel / calib_cell_tab_kernel / calib_hist_kernel   szn_calib_head (calibrated stacking): the cell kernels' G and Q (fh_load_taps,
+//                        fh_build_GQ, fh_lookup_GQ), two running bests per pixel (fh_two_best), crossing tables, prefix sums -> hist
 // Both cell kernels run the same per-pixel body (fh_pixel) and the same label loop (fh_scatter_A), and write per cell: pred, the
 // loss partial, A and Bm.
 //
@@ -80,6 +82,23 @@ struct FhArgs {
     const int64_t* gmap; int gmode; ClassBits unseen;      // grouped class assignment (gmode 1 | 2), see fh_argmax
 };
 
+// |s|^2 of one pixel from the cell's Gram matrix, and its similarity to class k from the cell's G: the arithmetic every head shares
+__device__ __forceinline__ float fh_ss(const float (&wt)[4], const float* Q) {
+    float ss = 0.f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) ss = fmaf(wt[t] * wt[u], Q[t * 4 + u], ss);
+    return ss;
+}
+template <int KP>
+__device__ __forceinline__ float fh_sim(const float (&wt)[4], const float* G, float sn, const float* __restrict__ en, int k) {
+    float d = 0.f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) d = fmaf(wt[t], G[t * KP + k], d);
+    return d / (sn * en[k]);
+}
+
 // Nearest class embedding of one pixel: ascending classes, strictly larger replaces: the first index wins.
 // GROUPED (szn_fused_head_grouped; trainer_fcn.py:123-147, utils.py:188-204): the pixel competes among the classes
 // of ITS group only -- the unseen classes when it takes the unseen group, the others otherwise -- and every class outside that group
@@ -99,15 +118,29 @@ __device__ __forceinline__ int fh_argmax(const FhArgs& a, const float (&wt)[4], 
         bool in_group = true;
         if constexpr (GROUPED) in_group = (bool)((class_word(a.unseen, k >> 6) >> (k & 63)) & 1ull) == take_unseen;
         float sim = zero_sim;
-        if (in_group) {
-            float d = 0.f;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) d = fmaf(wt[t], G[t * KP + k], d);
-            sim = d / (sn * en[k]);
-        }
+        if (in_group) sim = fh_sim<KP>(wt, G, sn, en, k);
         if (k == 0 || sim > bv) { bv = sim; best = k; }
     }
     return best;
+}
+
+// The same trip through the classes with two running bests (szn_calib_head): ia / va over the classes outside `unseen`, ib / vb over
+// its members, each the first index holding its group's maximum.  The group bit is wave-uniform like in_group above: a scalar select,
+// no divergence, no second pass.  Both groups are non-empty (checked on the host).
+struct FhTwoBest { int ia, ib; float va, vb; };
+template <int KP>
+__device__ __forceinline__ FhTwoBest fh_two_best(const FhArgs& a, const float (&wt)[4], const float* G, float sn,
+                                                 const float* __restrict__ en) {
+    FhTwoBest r = {-1, -1, 0.f, 0.f};
+    for (int k = 0; k < a.K; ++k) {
+        const bool u = (bool)((class_word(a.unseen, k >> 6) >> (k & 63)) & 1ull);
+        const float sim = fh_sim<KP>(wt, G, sn, en, k);
+        const bool first = u ? r.ib < 0 : r.ia < 0;
+        const bool take = first || sim > (u ? r.vb : r.va);
+        if (take && u) { r.vb = sim; r.ib = k; }
+        if (take && !u) { r.va = sim; r.ia = k; }
+    }
+    return r;
 }
 
 // what one pixel hands to the label loop (lbl < 0: nothing)
@@ -125,11 +158,7 @@ __device__ __forceinline__ FhPx fh_pixel(const FhArgs& a, int b, int I, int J, i
     if (live && y >= 0 && y < a.H && x >= 0 && x < a.W) {
         cell_weights<S>(ty, tx, px.wt);
         const float (&wt)[4] = px.wt;
-        float ss = 0.f;
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) ss = fmaf(wt[t] * wt[u], Q[t * 4 + u], ss);
+        const float ss = fh_ss(wt, Q);
         const float sn = sqrtf(ss);
         const size_t pix = ((size_t)b * a.H + y) * a.W + x;
         px.lbl = a.target ? a.target[pix] : -1;
@@ -229,6 +258,52 @@ __host__ __device__ inline FhLds fh_lds(int E, int KP, bool mse) {
     return L;
 }
 
+// the four tap vectors of cell (I, J) of image b into LDS Ct [4][E] (missing taps are zero); the caller synchronises
+__device__ __forceinline__ void fh_load_taps(const FhArgs& a, int b, int I, int J, int tid, float* Ct) {
+    for (int i = tid; i < 4 * a.E; i += 256) {
+        const int t = i / a.E, c = i - t * a.E;
+        const long tp = tap_pos(b, a.h, a.w, I, J, t);
+        Ct[i] = (tp >= 0) ? a.coarse[(size_t)tp * a.ldc + a.c0 + c] : 0.f;
+    }
+}
+
+// G [4][KP] and Q [4][4] of a block's cell from its tap vectors in LDS: wave t builds row t of both; the caller synchronises
+template <int KP>
+__device__ __forceinline__ void fh_build_GQ(const FhArgs& a, const float* __restrict__ embT, const float* Ct, int lane, int wave,
+                                            float* G, float* Q) {
+    // G[t][k]: wave t, lane k (+ 64, + 128, + 192 when KP > 64)
+    for (int k = lane; k < KP; k += 64) {
+        float g = 0.f;
+        const float* ct = Ct + wave * a.E;
+        // (the chain is sequential by contract; 20 independent L2 loads per batch keep it fed)
+        int c = 0;
+        for (; c + 20 <= a.E; c += 20) {
+            float ev[20];
+#pragma unroll
+            for (int u = 0; u < 20; ++u) ev[u] = embT[(size_t)(c + u) * KP + k];
+#pragma unroll
+            for (int u = 0; u < 20; ++u) g = fmaf(ct[c + u], ev[u], g);
+        }
+        for (; c < a.E; ++c) g = fmaf(ct[c], embT[(size_t)c * KP + k], g);
+        G[wave * KP + k] = g;
+    }
+    // Q[t][t']: wave t computes its row; lanes stride over c, fixed-order wave reduction
+    {
+        float q[4] = {0.f, 0.f, 0.f, 0.f};
+        const float* ct = Ct + wave * a.E;
+        for (int c = lane; c < a.E; c += 64) {
+            const float v = ct[c];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) q[u] = fmaf(v, Ct[u * a.E + c], q[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const float s = wave_sum(q[u]);
+            if (lane == 0) Q[wave * 4 + u] = s;
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void fh_prep_kernel(const float* __restrict__ embed, float* __restrict__ ws, int E,
                                                       int K, int KP) {
     float* embT = ws;
@@ -288,11 +363,7 @@ __global__ __launch_bounds__(256) void fh_cell_kernel(FhArgs a) {
     const float* ent = en + KP;
 
     // ---- the four tap vectors (missing taps are zero) ----
-    for (int i = tid; i < 4 * a.E; i += 256) {
-        const int t = i / a.E, c = i - t * a.E;
-        const long tp = tap_pos(b, a.h, a.w, I, J, t);
-        Ct[i] = (tp >= 0) ? a.coarse[(size_t)tp * a.ldc + a.c0 + c] : 0.f;
-    }
+    fh_load_taps(a, b, I, J, tid, Ct);
     for (int i = tid; i < 16 * KP; i += 256) Aw[i] = 0.f;
     if (MSE)
         for (int i = tid; i < KP; i += 256) present[i] = 0;
@@ -307,37 +378,7 @@ __global__ __launch_bounds__(256) void fh_cell_kernel(FhArgs a) {
             }
         }
     }
-    // G[t][k]: wave t, lane k (+ 64, + 128, + 192 when KP > 64)
-    for (int k = lane; k < KP; k += 64) {
-        float g = 0.f;
-        const float* ct = Ct + wave * a.E;
-        // (the chain is sequential by contract; 20 independent L2 loads per batch keep it fed)
-        int c = 0;
-        for (; c + 20 <= a.E; c += 20) {
-            float ev[20];
-#pragma unroll
-            for (int u = 0; u < 20; ++u) ev[u] = embT[(size_t)(c + u) * KP + k];
-#pragma unroll
-            for (int u = 0; u < 20; ++u) g = fmaf(ct[c + u], ev[u], g);
-        }
-        for (; c < a.E; ++c) g = fmaf(ct[c], embT[(size_t)c * KP + k], g);
-        G[wave * KP + k] = g;
-    }
-    // Q[t][t']: wave t computes its row; lanes stride over c, fixed-order wave reduction
-    {
-        float q[4] = {0.f, 0.f, 0.f, 0.f};
-        const float* ct = Ct + wave * a.E;
-        for (int c = lane; c < a.E; c += 64) {
-            const float v = ct[c];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) q[u] = fmaf(v, Ct[u * a.E + c], q[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const float s = wave_sum(q[u]);
-            if (lane == 0) Q[wave * 4 + u] = s;
-        }
-    }
+    fh_build_GQ<KP>(a, embT, Ct, lane, wave, G, Q);
     __syncthreads();
     if (MSE) {
         // P_k of the present classes, ascending k, dealt to the waves in turn
@@ -423,6 +464,24 @@ __global__ __launch_bounds__(256) void fh_tables_kernel(FhArgs a, float* __restr
     }
 }
 
+// G [4][KP] and Q [4][4] of a wave's cell looked up in the position tables (tp: the cell's four tap positions, -1 = outside the map)
+template <int KP>
+__device__ __forceinline__ void fh_lookup_GQ(const long (&tp)[4], const float* __restrict__ D, const float* __restrict__ N, int lane,
+                                             float* G, float* Q) {
+    for (int k = lane; k < KP; k += 64) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) G[t * KP + k] = (tp[t] >= 0) ? D[(size_t)tp[t] * KP + k] : 0.f;
+    }
+    if (lane < 16) {
+        const int t = min(lane >> 2, lane & 3), u = max(lane >> 2, lane & 3);
+        // (t, u) -> neighbour slot of the LOWER tap: self, E, S, SE | (1,2) SW, (1,3) S | (2,3) E
+        const int slot = (t == u) ? 0 : (t == 0 ? u : (t == 1 ? (u == 2 ? 4 : 2) : 1));
+        const long pt = (t == 0) ? tp[0] : (t == 1) ? tp[1] : (t == 2) ? tp[2] : tp[3];
+        const long pu = (u == 0) ? tp[0] : (u == 1) ? tp[1] : (u == 2) ? tp[2] : tp[3];
+        Q[lane] = (pt >= 0 && pu >= 0) ? N[(size_t)pt * 8 + slot] : 0.f;
+    }
+}
+
 // one wave per cell (S * S <= 64 pixels), four cells per block; same per-pixel arithmetic and the same outputs as fh_cell_kernel
 template <int KP, int S, bool GROUPED, bool MSE>
 __global__ __launch_bounds__(256) void fh_cell_tab_kernel(FhArgs a, const float* __restrict__ D, const float* __restrict__ N) {
@@ -447,21 +506,8 @@ __global__ __launch_bounds__(256) void fh_cell_tab_kernel(FhArgs a, const float*
     long tp[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) tp[t] = tap_pos(b, a.h, a.w, I, J, t);
-    for (int k = lane; k < KP; k += 64) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            G[t * KP + k] = (tp[t] >= 0) ? D[(size_t)tp[t] * KP + k] : 0.f;
-            myA[t * KP + k] = 0.f;
-        }
-    }
-    if (lane < 16) {
-        const int t = min(lane >> 2, lane & 3), u = max(lane >> 2, lane & 3);
-        // (t, u) -> neighbour slot of the LOWER tap: self, E, S, SE | (1,2) SW, (1,3) S | (2,3) E
-        const int slot = (t == u) ? 0 : (t == 0 ? u : (t == 1 ? (u == 2 ? 4 : 2) : 1));
-        const long pt = (t == 0) ? tp[0] : (t == 1) ? tp[1] : (t == 2) ? tp[2] : tp[3];
-        const long pu = (u == 0) ? tp[0] : (u == 1) ? tp[1] : (u == 2) ? tp[2] : tp[3];
-        Q[lane] = (pt >= 0 && pu >= 0) ? N[(size_t)pt * 8 + slot] : 0.f;
-    }
+    for (int i = lane; i < 4 * KP; i += 64) myA[i] = 0.f;
+    fh_lookup_GQ<KP>(tp, D, N, lane, G, Q);
     __syncthreads();
 
     float bm[16];
@@ -573,6 +619,157 @@ __global__ __launch_bounds__(256) void fh_gather_kernel(const float* __restrict_
         if (MSE) asm volatile("" : "+v"(v));
         elem<T>::st(dcoarse + ((size_t)pos) * ldc + c0 + c, v);
     }
+}
+
+// ---- calibrated stacking (szn_calib_head): the cells' G and Q as above, two running bests per pixel, crossing tables ------------
+// A pixel is (t, a, b, bin): target, best seen class, best unseen class, first gamma at which it takes b (n: never; include/szn.h).
+// XA [K][K][n + 1] counts (t, a, bin), XB (t, b, bin), both int64, zeroed by the call.  Integer atomics: the result does not depend on
+// their order.  The gammas travel as kernel arguments; the per-pixel search is a wave-uniform loop over them (scalar loads).
+struct CalArgs {
+    float gamma[SZN_CALIB_MAX_GAMMAS];
+    unsigned long long* XA; unsigned long long* XB;
+    int64_t* pred; int n, pred_index;
+};
+
+// Pixel (ty, tx) of cell (I, J) of image b: the prediction at gammas[pred_index] (where wanted) and the pixel's key
+// t | a << 8 | b << 16 | bin << 24, or -1 where it is not counted (no histogram, outside the image, label outside [0, K))
+template <int KP, int S>
+__device__ __forceinline__ int calib_pixel(const FhArgs& a, const CalArgs& c, int b, int I, int J, int ty, int tx, bool live,
+                                           const float* G, const float* Q, const float* __restrict__ en) {
+    const int y = S * I + ty - a.crop, x = S * J + tx - a.crop;
+    if (!(live && y >= 0 && y < a.H && x >= 0 && x < a.W)) return -1;
+    float wt[4];
+    cell_weights<S>(ty, tx, wt);
+    const float sn = sqrtf(fh_ss(wt, Q));
+    FhTwoBest r = fh_two_best<KP>(a, wt, G, sn, en);
+    const float m = r.va - r.vb;
+    int bin = 0;
+    if (m != m) { r.ia = 0; r.ib = 0; bin = c.n; }        // NaN: class 0 at every gamma
+    else
+        for (int g = 0; g < c.n; ++g) bin += (m > c.gamma[g] || (m == c.gamma[g] && r.ia < r.ib)) ? 1 : 0;   // ascending: a prefix
+    const size_t pix = ((size_t)b * a.H + y) * a.W + x;
+    if (c.pred) c.pred[pix] = bin > c.pred_index ? r.ia : r.ib;
+    if (!c.XA) return -1;
+    const long t = a.target[pix];
+    if (t < 0 || t >= a.K) return -1;
+    return (int)t | r.ia << 8 | r.ib << 16 | bin << 24;
+}
+
+// the keys of a wave, equal ones combined: one atomic add of the popcount per distinct key and table
+__device__ __forceinline__ void calib_count(const FhArgs& a, const CalArgs& c, int key, int lane) {
+    unsigned long long todo = __ballot(key >= 0);
+    while (todo) {
+        const int src = __ffsll((long long)todo) - 1;
+        const int k0 = __shfl(key, src, 64);
+        const unsigned long long same = __ballot(key == k0);
+        if (lane == src) {
+            const unsigned long long cnt = (unsigned long long)__popcll(same);
+            const int t = k0 & 255, ia = (k0 >> 8) & 255, ib = (k0 >> 16) & 255, bin = (k0 >> 24) & 127;
+            atomicAdd(c.XA + ((size_t)t * a.K + ia) * (c.n + 1) + bin, cnt);
+            atomicAdd(c.XB + ((size_t)t * a.K + ib) * (c.n + 1) + bin, cnt);
+        }
+        todo &= ~same;
+    }
+}
+
+template <int KP>
+__global__ __launch_bounds__(256) void calib_cell_kernel(FhArgs a, CalArgs c) {      // stride 32: one block per (image, cell)
+    constexpr int S = 32;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const FhLds L = fh_lds(a.E, KP, false);
+    float* Ct = sm + L.Ct;
+    float* G = sm + L.G;
+    float* Q = sm + L.Q;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int cells_w = a.w + 1, cells = (a.h + 1) * cells_w;
+    const int b = blockIdx.x / cells, cell = blockIdx.x % cells;
+    const int I = cell / cells_w, J = cell % cells_w;
+    const float* embT = a.ws_f;
+    const float* en = a.ws_f + (size_t)a.E * KP;
+    fh_load_taps(a, b, I, J, tid, Ct);
+    __syncthreads();
+    fh_build_GQ<KP>(a, embT, Ct, lane, wave, G, Q);
+    __syncthreads();
+    for (int q = tid; q < S * S; q += 256)
+        calib_count(a, c, calib_pixel<KP, S>(a, c, b, I, J, q / S, q % S, true, G, Q, en), lane);
+}
+
+template <int KP>
+__global__ __launch_bounds__(256) void calib_cell_tab_kernel(FhArgs a, CalArgs c, const float* __restrict__ D,
+                                                             const float* __restrict__ N) {      // stride 8: one wave per cell
+    constexpr int S = 8;
+    __shared__ float Gs[4][4 * KP];
+    __shared__ float Qs[4][16];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int cells_w = a.w + 1, cells = (a.h + 1) * cells_w;
+    const long ncell = (long)a.B * cells;
+    const long cid = (long)blockIdx.x * 4 + wave;
+    const bool ok = cid < ncell;
+    const long cc = ok ? cid : 0;
+    const int b = (int)(cc / cells), cell = (int)(cc % cells);
+    const int I = cell / cells_w, J = cell % cells_w;
+    const float* en = a.ws_f + (size_t)a.E * KP;
+    long tp[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) tp[t] = tap_pos(b, a.h, a.w, I, J, t);
+    fh_lookup_GQ<KP>(tp, D, N, lane, Gs[wave], Qs[wave]);
+    __syncthreads();
+    calib_count(a, c, calib_pixel<KP, S>(a, c, b, I, J, lane / S, lane % S, ok && lane < S * S, Gs[wave], Qs[wave], en), lane);
+}
+
+// hist[g][t][k] += sum_{bin > g} XA[t][k][bin] + sum_{bin <= g} XB[t][k][bin]: one thread per (t, k), running prefixes over the bins
+__global__ __launch_bounds__(256) void calib_hist_kernel(const unsigned long long* __restrict__ XA,
+                                                         const unsigned long long* __restrict__ XB, int K, int n,
+                                                         int64_t* __restrict__ hist) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= K * K) return;
+    const unsigned long long* xa = XA + (size_t)i * (n + 1);
+    const unsigned long long* xb = XB + (size_t)i * (n + 1);
+    unsigned long long above = 0, below = 0;
+    for (int bin = 0; bin <= n; ++bin) above += xa[bin];
+    for (int g = 0; g < n; ++g) {
+        above -= xa[g];
+        below += xb[g];
+        hist[(size_t)g * K * K + i] += (int64_t)(above + below);
+    }
+}
+
+template <int KP>
+void calib_launch(int stride, const FhArgs& a, const CalArgs& c, float* tabD, float* tabN, hipStream_t st) {
+    const int cells = (a.h + 1) * (a.w + 1);
+    if (stride == 8) {
+        hipLaunchKernelGGL(fh_tables_kernel<KP>, dim3((unsigned)(((long)a.B * a.h * a.w + 3) / 4)), dim3(256),
+                           (size_t)4 * a.E * sizeof(float), st, a, tabD, tabN);
+        hipLaunchKernelGGL(calib_cell_tab_kernel<KP>, dim3((unsigned)(((long)a.B * cells + 3) / 4)), dim3(256), 0, st, a, c,
+                           (const float*)tabD, (const float*)tabN);
+    } else {
+        const size_t lds = (size_t)(fh_lds(a.E, KP, false).Q + 16) * sizeof(float);       // Ct | G | Q
+        auto kern = calib_cell_kernel<KP>;
+        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(kern, dim3(a.B * cells), dim3(256), lds, st, a, c);
+    }
+}
+
+// workspace of szn_calib_head: the fused head's (embedding tables at its head, the stride-8 position tables) | XA | XB
+struct CalWorkspace { size_t XA, XB, bytes; };       // byte offsets
+inline CalWorkspace calib_workspace(int B, int h, int w, int E, int K, int n) {
+    CalWorkspace L;
+    const size_t tab = (size_t)K * K * (n + 1) * sizeof(unsigned long long);
+    L.XA = align256(fh_workspace(B, h, w, E, kp_of(K)).bytes);
+    L.XB = L.XA + tab;
+    L.bytes = L.XB + tab;
+    return L;
+}
+
+// what szn_calib_head and its workspace query refuse about sizes; 0 = fine
+const char* calib_bad_geometry(int stride, int B, int h, int w, int E, int K, int n_gammas) {
+    if (stride != 32 && stride != 8) return "stride must be 8 or 32";
+    if (n_gammas < 1 || n_gammas > SZN_CALIB_MAX_GAMMAS) return "n_gammas outside [1, SZN_CALIB_MAX_GAMMAS]";
+    if (B <= 0 || h <= 0 || w <= 0 || E <= 0 || K <= 0) return "a size that is not positive";
+    if (K > SZN_MAX_CLASSES) return "K above SZN_MAX_CLASSES";
+    return nullptr;
 }
 
 // the cell pass: stride 32 a block per cell; stride 8 the position tables, then a wave per cell
@@ -757,4 +954,72 @@ extern "C" int szn_fused_mse_head_prepared(int stride, int B, int h, int w, int 
                                            szn_stream_t stream) {
     return fused_head_impl(stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype, dcoarse,
                            workspace, stream, false, unseen, group_mode, group_map, true);
+}
+
+// Calibrated stacking (include/szn.h): the seen-class penalty gamma swept over n_gammas values in one pass over the pixels.
+extern "C" size_t szn_calib_head_workspace_bytes(int stride, int B, int h, int w, int E, int K, int n_gammas) {
+    if (calib_bad_geometry(stride, B, h, w, E, K, n_gammas)) return 0;
+    return calib_workspace(B, h, w, E, K, n_gammas).bytes;
+}
+
+extern "C" int szn_calib_head(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                              const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
+                              int n_gammas, const float* gammas, int64_t* hist, int pred_index, int64_t* pred, void* workspace,
+                              szn_stream_t stream) {
+    if (const char* why = calib_bad_geometry(stride, B, h, w, E, K, n_gammas)) SZN_FAIL(SZN_ERR_ARG, "calib_head: %s", why);
+    if (!coarse || !embed || !workspace || !gammas) SZN_FAIL(SZN_ERR_ARG, "calib_head: coarse, embed, workspace and gammas are required");
+    if (c0 < 0 || ldc < c0 + E || H <= 0 || W <= 0 || crop < 0) SZN_FAIL(SZN_ERR_ARG, "calib_head: bad argument");
+    if (H + crop > stride * h + stride || W + crop > stride * w + stride)
+        SZN_FAIL(SZN_ERR_ARG, "calib_head: crop window exceeds the deconv output");
+    if (((uintptr_t)workspace) & 15) SZN_FAIL(SZN_ERR_ARG, "calib_head: workspace must be 16-B aligned");
+    for (int g = 0; g < n_gammas; ++g) {
+        if (!isfinite(gammas[g])) SZN_FAIL(SZN_ERR_ARG, "calib_head: gammas[%d] is not finite", g);
+        if (g && !(gammas[g] > gammas[g - 1])) SZN_FAIL(SZN_ERR_ARG, "calib_head: gammas must be strictly ascending (at %d)", g);
+    }
+    if (!hist && !pred) SZN_FAIL(SZN_ERR_ARG, "calib_head: hist and pred are both NULL");
+    if (hist && !target) SZN_FAIL(SZN_ERR_ARG, "calib_head: hist needs target");
+    if (pred && (pred_index < 0 || pred_index >= n_gammas)) SZN_FAIL(SZN_ERR_ARG, "calib_head: pred_index %d outside [0, %d)", pred_index, n_gammas);
+    const ClassBits ubits = class_bits(unseen);
+    if (!class_bits_any(ubits)) SZN_FAIL(SZN_ERR_ARG, "calib_head: the unseen set is empty");
+    if (!class_bits_fit(ubits, K)) SZN_FAIL(SZN_ERR_ARG, "calib_head: the unseen set names a class >= K = %d", K);
+    int n_unseen = 0;
+    for (int i = 0; i < 4; ++i) n_unseen += __builtin_popcountll(ubits.w[i]);
+    if (n_unseen >= K) SZN_FAIL(SZN_ERR_ARG, "calib_head: every class below K = %d is unseen (both groups must be non-empty)", K);
+    const int KP = kp_of(K);
+    if (fh_lds(E, KP, false).bytes() > 150 * 1024) SZN_FAIL(SZN_ERR_UNSUPPORTED, "calib_head: E=%d too large for LDS", E);
+
+    hipStream_t st = (hipStream_t)stream;
+    const FhWorkspace wl = fh_workspace(B, h, w, E, KP);
+    const CalWorkspace cl = calib_workspace(B, h, w, E, K, n_gammas);
+    char* ws = (char*)workspace;
+    hipLaunchKernelGGL(fh_prep_kernel, dim3(szn_div_up((long)E * KP, 256)), dim3(256), 0, st, embed, (float*)ws, E, K, KP);
+    SZN_CHECK_LAUNCH("fh_prep_kernel");
+    FhArgs a{};
+    a.coarse = coarse; a.embed = embed; a.target = target; a.ws_f = (float*)ws;
+    a.B = B; a.h = h; a.w = w; a.E = E; a.ldc = ldc; a.c0 = c0; a.H = H; a.W = W; a.crop = crop; a.K = K; a.KP = KP;
+    a.unseen = ubits;
+    CalArgs c{};
+    for (int g = 0; g < n_gammas; ++g) c.gamma[g] = gammas[g];
+    c.n = n_gammas; c.pred = pred; c.pred_index = pred ? pred_index : 0;
+    if (hist) {
+        c.XA = (unsigned long long*)(ws + cl.XA); c.XB = (unsigned long long*)(ws + cl.XB);
+        if (hipMemsetAsync(ws + cl.XA, 0, cl.bytes - cl.XA, st) != hipSuccess) SZN_FAIL(SZN_ERR_LAUNCH, "calib_head: clearing the crossing tables failed");
+    }
+    float* tabD = (float*)(ws + wl.tabD);
+    float* tabN = (float*)(ws + wl.tabN);
+    switch (KP) {
+        case 24: calib_launch<24>(stride, a, c, tabD, tabN, st); break;
+        case 40: calib_launch<40>(stride, a, c, tabD, tabN, st); break;
+        case 64: calib_launch<64>(stride, a, c, tabD, tabN, st); break;
+        case 128: calib_launch<128>(stride, a, c, tabD, tabN, st); break;
+        case 192: calib_launch<192>(stride, a, c, tabD, tabN, st); break;
+        default: calib_launch<256>(stride, a, c, tabD, tabN, st); break;
+    }
+    SZN_CHECK_LAUNCH(stride == 8 ? "calib_cell_tab_kernel" : "calib_cell_kernel");
+    if (hist) {
+        hipLaunchKernelGGL(calib_hist_kernel, dim3(szn_div_up((long)K * K, 256)), dim3(256), 0, st, (const unsigned long long*)c.XA,
+                           (const unsigned long long*)c.XB, K, n_gammas, hist);
+        SZN_CHECK_LAUNCH("calib_hist_kernel");
+    }
+    return SZN_OK;
 }

@@ -11,6 +11,8 @@ szn_fused_ce_head and szn_seenmask_head_k goes through here (models.FCN32s / FCN
   seenmask  the x32 seen-mask head on the 1/32 map: training, predict and pred-only (group map) calls.
   ms        multi-scale / mirrored inference: the views of an input (szn_resize_flip_f32) and the view-ensemble head (szn_ms_head),
             which reads the maps of all views and writes one prediction.
+  calib     calibrated stacking (szn_calib_head): a penalty gamma on every seen class, swept over up to 64 values in one pass --
+            per gamma a confusion histogram, for one of them the prediction.
 
 The crop belongs to the stride (32: CROP, reference models.py:147; 8: CROP_UP8, FCN8s' upscore8).  A call without a `Workspace`
 allocates its scratch and builds the embedding tables itself (the predict methods); TrainStep keeps one `Workspace` across steps.
@@ -191,6 +193,55 @@ def ms_predict(stride, views, emb, H, W, target=None, mode=0, unseen=None, gmap=
     L.call("szn_ms_head", stride, B, E, K, H, W, _CROP[stride], len(views), arr, L.ptr(emb), L.class_set(unseen), mode, L.ptr(gmap),
            L.ptr(tgt), L.ptr(pred), L.ptr(acc), L.ptr(buf), L.stream_ptr())
     return (pred, acc) if want_acc else pred
+
+
+# ---- calibrated stacking: seen-class penalty, one-pass sweep -----------------------------------------------------------------
+def calib_gammas(gammas):
+    """the candidate penalties as the float32 HOST array szn_calib_head reads: 1 to CALIB_MAX_GAMMAS finite, strictly ascending values"""
+    import numpy as np
+    g = np.ascontiguousarray(np.asarray(gammas, dtype=np.float32).reshape(-1))
+    if not 1 <= g.size <= L.CALIB_MAX_GAMMAS:
+        raise L.SznError("calibration: %d gammas, between 1 and %d are taken" % (g.size, L.CALIB_MAX_GAMMAS))
+    if not np.isfinite(g).all() or not (np.diff(g) > 0).all():
+        raise L.SznError("calibration: the gammas must be finite and strictly ascending as float32 (got %r)" % (g.tolist(),))
+    return g
+
+
+def calib(stride, fmap, emb, H, W, unseen, gammas, target=None, hist=None, pred_index=None):
+    """szn_calib_head on the contiguous fp32 NHWC map `fmap` (the E embedding channels first): gamma is subtracted from the
+    similarity of every class NOT in `unseen` before the argmax, for every gamma of `gammas` (ascending) in one pass.
+    target given: hist (G,K,K) int64 += the confusion counts of every gamma (allocated as zeros when None).  pred_index given: pred
+    (B,H,W) int64 at gammas[pred_index].  -> (hist or None, pred or None)"""
+    import ctypes as C
+    B, h, w, ld = fmap.shape
+    K, E = emb.shape
+    if fmap.dtype != torch.float32 or not fmap.is_contiguous():
+        raise L.SznError("calib: the map must be a contiguous fp32 (B,h,w,C) tensor")
+    g = calib_gammas(gammas)
+    G = int(g.size)
+    if target is None and hist is not None:
+        raise L.SznError("calib: a histogram needs the target")
+    if target is None and pred_index is None:
+        raise L.SznError("calib: nothing to compute (no target for a histogram, no pred_index for a prediction)")
+    if pred_index is not None and not 0 <= int(pred_index) < G:
+        raise L.SznError("calib: pred_index %r outside [0, %d)" % (pred_index, G))
+    dev = fmap.device
+    tgt = None
+    if target is not None:
+        tgt = target.to(device=dev, dtype=torch.int64).contiguous()
+        if hist is None:
+            hist = torch.zeros(G, K, K, dtype=torch.int64, device=dev)
+        elif hist.dtype != torch.int64 or tuple(hist.shape) != (G, K, K) or not hist.is_contiguous() or hist.device != dev:
+            raise L.SznError("calib: hist must be a contiguous int64 (%d,%d,%d) tensor on %s" % (G, K, K, dev))
+    pred = torch.empty(B, H, W, dtype=torch.int64, device=dev) if pred_index is not None else None
+    nbytes = L.load().szn_calib_head_workspace_bytes(stride, B, h, w, E, K, G)
+    if nbytes == 0:
+        raise L.SznError("calib: bad geometry (stride %d, B %d, map %d x %d, E %d, K %d, %d gammas)" % (stride, B, h, w, E, K, G))
+    buf = _scratch(nbytes, dev)
+    L.call("szn_calib_head", stride, B, h, w, E, ld, 0, H, W, _CROP[stride], K, L.ptr(fmap), L.ptr(emb), L.ptr(tgt),
+           L.class_set(unseen), G, g.ctypes.data_as(C.POINTER(C.c_float)), L.ptr(hist), -1 if pred_index is None else int(pred_index),
+           L.ptr(pred), L.ptr(buf), L.stream_ptr())
+    return hist, pred
 
 
 # ---- softmax cross-entropy head -------------------------------------------------------------------------------------------

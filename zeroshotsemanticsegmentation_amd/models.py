@@ -1483,6 +1483,26 @@ class FCN32s(nn.Module):
                                                unseen if mode else None, self._last_group)
         return loss_t, self._last_pred
 
+    def calib_predict(self, x, embeddings, unseen, gammas, target=None, hist=None, pred_index=None, loss="cos"):
+        """calibrated generalized zero-shot inference (calibrated stacking): one forward pass, then on the same map the plain head
+        for the loss and szn_calib_head, which subtracts a penalty gamma from the similarity of every class NOT in `unseen` before
+        the argmax -- for every value of `gammas` (ascending, at most 64) in one pass over the pixels.
+        -> (loss, pred, hist): the loss is embed_predict's on that map, bit for bit (None without a target); pred (B,H,W) int64 is
+        the calibrated prediction at gammas[pred_index], or embed_predict's own when pred_index is None; hist (G,K,K) int64 holds
+        the confusion counts of every gamma: `hist` accumulated in place when given, a fresh one with a target, else None."""
+        kind = heads.embed_kind(loss)
+        with torch.no_grad():
+            ctx, stride, fmap = self._head_map(x)
+            emb = heads.embeddings(embeddings, self.n_class, fmap.device)
+            loss_t, pred = heads.embed_predict(kind, stride, fmap, emb, ctx.H, ctx.W, target)
+            if target is not None or pred_index is not None:
+                fmap32 = fmap if fmap.dtype == torch.float32 else fmap.to(torch.float32)
+                hist, cpred = heads.calib(stride, fmap32, emb, ctx.H, ctx.W, unseen, gammas, target, hist, pred_index)
+                if pred_index is not None:
+                    pred = cpred
+            self._last_pred = pred
+        return loss_t, pred, hist
+
     def seenmask_predict(self, x, target, n_class, unseen):
         """forward pass + seen-mask loss and prediction WITHOUT the (B,2,H,W) score: szn_seenmask_head evaluates the learned
         stride-32 deconv + crop (models.py:150-151), the binary target `label is a seen class` (trainer_seenmask.py:53-56), the

@@ -14,6 +14,10 @@ Added for this implementation (none change the reference flags):
                        (vis_utils; 25 = the reference's behaviour, 0 = off)
   --crop-size H W      train on randomly scaled, cropped and mirrored images at a fixed H x W network input (datasets.Augment; one
                        kernel on the GPU, szn_augment_u8); --scale-range LO HI (default 0.5 2.0), --no-flip.  Validation is untouched
+  --calibration GAMMA  calibrated stacking in validation and -m test_fcn: GAMMA is subtracted from the cosine similarity of every seen
+                       class before the argmax (szn_calib_head); --calib-sweep LO HI N also writes the metrics of N penalties between
+                       LO and HI, and their harmonic mean of seen and unseen mIoU, to <log_dir>/calib_log.csv at one extra head launch
+                       per validation batch
   --init synthetic|vgg path handling: without the caffe VGG16 file the backbone starts from synth weights
   torchrun: RANK / LOCAL_RANK / WORLD_SIZE are honoured (one process per GPU, RCCL gradient all-reduce).
 """
@@ -81,6 +85,12 @@ def build_parser():
                         "embedding configurations only.  Default: once, as stored")
     p.add_argument('--eval-flip', action='store_true', help="validation also evaluates the mirror image of every view (alone: of the "
                                                             "stored image)")
+    p.add_argument('--calibration', type=float, default=None, metavar='GAMMA',
+                   help="calibrated stacking: validation (and -m test_fcn) subtracts GAMMA from the cosine similarity of every seen "
+                        "class before the argmax; needs unseen classes and an embedding configuration.  Default: no penalty")
+    p.add_argument('--calib-sweep', type=float, nargs=3, metavar=('LO', 'HI', 'N'), default=None,
+                   help="every validation also evaluates N penalties (2 to 64) evenly spaced from LO to HI in one extra pass of the "
+                        "head and appends their metrics and the harmonic mean of seen and unseen mIoU to <log_dir>/calib_log.csv")
     return p
 
 
@@ -217,12 +227,46 @@ def check_eval_views(scales, flip, cfg):
         raise Exception("--eval-scales must contain 1 (got %r)" % (scales,))
 
 
+def calib_sweep_values(sweep):
+    """--calib-sweep LO HI N -> the N float32 penalties numpy.linspace(LO, HI, N), or None without the flag"""
+    if sweep is None:
+        return None
+    import numpy as np
+    lo, hi, n = sweep
+    if n != int(n) or not 2 <= int(n) <= 64:
+        raise Exception("--calib-sweep: N must be an integer from 2 to 64 (got %r)" % (n,))
+    if not (np.isfinite([lo, hi]).all() and lo < hi):
+        raise Exception("--calib-sweep: LO < HI, both finite (got %r, %r)" % (lo, hi))
+    vals = np.linspace(lo, hi, int(n)).astype(np.float32)
+    if not (np.diff(vals) > 0).all():
+        raise Exception("--calib-sweep: %d values between %r and %r are not distinct in float32" % (int(n), lo, hi))
+    return vals
+
+
+def check_calibration(calibration, sweep, cfg, eval_scales=None, eval_flip=False):
+    """--calibration / --calib-sweep: unseen classes, an embedding configuration, and none of the other class-assignment rules
+    (forced unseen, -m test_all, multi-scale views); more than 256 classes and SZN_VERBOSE_VAL keep the materialised score"""
+    if calibration is None and sweep is None:
+        return
+    calib_sweep_values(sweep)
+    if calibration is not None and calibration != calibration or calibration in (float('inf'), float('-inf')):
+        raise Exception("--calibration: GAMMA must be finite (got %r)" % (calibration,))
+    n_class = 21 if cfg['dataset'] == 'pascal' else 33
+    why = trainer_fcn.calibration_refused(bool(cfg['train_unseen'] or cfg['val_unseen']),
+                                          bool(cfg['embed_dim']) and cfg['fcn_loss'] in ('cos', 'mse'), bool(cfg['forced_unseen']),
+                                          cfg['mode'] == 'test_all', bool(eval_scales or eval_flip), n_class,
+                                          os.environ.get("SZN_VERBOSE_VAL", "0") == "1")
+    if why:
+        raise Exception("--calibration / --calib-sweep: " + why)
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     cfg = update_cfg_with_args(configurations[args.config], args)
     validate_cfg(cfg)
     check_precision(args.precision, cfg)
     check_eval_views(args.eval_scales, args.eval_flip, cfg)
+    check_calibration(args.calibration, args.calib_sweep, cfg, args.eval_scales, args.eval_flip)
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", str(args.gpu)))
@@ -341,7 +385,8 @@ def main(argv=None):
         dataset=cfg['dataset'], max_epoch=cfg['fcn_epochs'], pixel_embeddings=cfg['embed_dim'], loss_func=cfg['fcn_loss'],
         tb_writer=tb_writer, unseen=all_unseen, val_unseen=cfg['val_unseen'], label_names=label_names,
         forced_unseen=cfg['forced_unseen'], precision=precision, rank=rank, visualize=args.viz, augment=augment,
-        eval_scales=args.eval_scales, eval_flip=args.eval_flip)
+        calibration=args.calibration, calib_sweep=calib_sweep_values(args.calib_sweep), eval_scales=args.eval_scales,
+        eval_flip=args.eval_flip)
     fcn_trainer.epoch, fcn_trainer.iteration = start_epoch, start_iteration
 
     if cfg['mode'] == 'train':

@@ -39,6 +39,27 @@ def _now():
     return datetime.datetime.now(datetime.timezone(datetime.timedelta(hours=-5)))      # 'US/Eastern' (no DST handling)
 
 
+def calibration_refused(has_unseen, embed_cfg, forced_unseen, test_all, eval_views, n_class, verbose_val=False):
+    """why a configuration cannot run calibrated stacking (calibration= / calib_sweep=, train.py --calibration / --calib-sweep), or
+    None: it penalises the seen classes of the plain embedding head, so it needs unseen classes and an embedding configuration, and it
+    replaces the other class-assignment rules rather than combining with them"""
+    if not has_unseen:
+        return "calibration needs unseen classes (train_unseen / val_unseen): without them there is no seen group to penalise"
+    if not embed_cfg:
+        return "calibration needs an embedding configuration (loss 'cos' | 'mse'): a softmax network has no unseen-class scores"
+    if forced_unseen:
+        return "calibration and forced_unseen are two different class-assignment rules: pick one"
+    if test_all:
+        return "calibration replaces the seen-mask classifier of -m test_all: use -m test_fcn"
+    if eval_views:
+        return "calibration with eval_scales / eval_flip is not built (the view-ensemble head has no penalty)"
+    if n_class > 256:
+        return "calibration: the fused head holds at most 256 classes, got %d" % n_class
+    if verbose_val:
+        return "calibration: SZN_VERBOSE_VAL needs the materialised score, which the calibrated head never forms"
+    return None
+
+
 class _NullWriter(object):
     def add_scalar(self, *a, **k): pass
     def add_text(self, *a, **k): pass
@@ -50,7 +71,7 @@ class Trainer(object):
     def __init__(self, cuda, model, optimizer, train_loader, val_loader, log_dir, dataset, max_epoch, tb_writer,
                  pixel_embeddings=None, loss_func=None, unseen=None, val_unseen=None, label_names=None,
                  forced_unseen=False, embed_arr=None, precision=torch.float32, fused_step=True, rank=0, visualize=0, augment=None,
-                 eval_scales=None, eval_flip=False):
+                 calibration=None, calib_sweep=None, eval_scales=None, eval_flip=False):
         if not cuda:
             raise RuntimeError("this implementation runs on the GPU only (cuda=False has no CPU fallback)")
         self.cuda = cuda
@@ -85,6 +106,16 @@ class Trainer(object):
                            "probabilities over views is not built")
         if self.eval_flip and not self.eval_scales:
             self.eval_scales = (1.0,)
+        # calibrated stacking (models.calib_predict): `calibration` = the penalty gamma subtracted from every seen class's similarity
+        # in validation; `calib_sweep` = ascending candidate gammas whose metrics validate() writes to calib_log.csv, one extra head
+        # launch per batch.  Training steps never see them.
+        self.calibration = None if calibration is None else float(np.float32(calibration))
+        self.calib_sweep = None
+        if calib_sweep is not None:
+            from .heads import calib_gammas
+            self.calib_sweep = calib_gammas(calib_sweep)
+        self.best_gamma = None
+        self.best_harmonic_mean_iu = None
 
         self.epoch = 0
         self.iteration = 0
@@ -97,6 +128,15 @@ class Trainer(object):
         self._step = None
         self._fused_step = fused_step
         self.verbose_val = os.environ.get("SZN_VERBOSE_VAL", "0") == "1"   # per-image prints cost a host sync each
+        if self.calibration is not None or self.calib_sweep is not None:
+            why = calibration_refused(bool(self.unseen), bool(pixel_embeddings) and loss_func in ("cos", "mse"), forced_unseen,
+                                      False, bool(self.eval_scales), self.n_class, self.verbose_val)
+            if why:
+                from ._lib import SznError
+                raise SznError(why)
+            if self.calibration is not None and not np.isfinite(self.calibration):
+                from ._lib import SznError
+                raise SznError("calibration: gamma must be finite (got %r)" % (calibration,))
 
         if self.pixel_embeddings:
             arr = np.asarray(embed_arr, dtype=np.float32) if embed_arr is not None else \
@@ -306,6 +346,12 @@ class Trainer(object):
             if self.eval_scales:
                 loss, pred = self.model.ms_predict(data, self.embeddings, self.eval_scales, self.eval_flip, target, loss=self.loss_func)
                 return None, loss, pred, target
+            if self.calibration is not None or self._calib_hist is not None:
+                # calibrated stacking: the penalised classes are those not in self.unseen.  One forward pass; the sweep's histogram
+                # and the calibrated prediction come from szn_calib_head launches on the map the loss used
+                loss, pred, _ = self.model.calib_predict(data, self.embeddings, self.unseen, self._calib_gammas(), target,
+                                                         hist=self._calib_hist, pred_index=self._calib_index(), loss=self.loss_func)
+                return None, loss, pred, target
             loss, pred = self.model.embed_predict(data, self.embeddings, target, loss=self.loss_func)
             return None, loss, pred, target
         if (self._embed_cfg() and (szn or self.forced_unseen) and target_embed is None
@@ -344,6 +390,44 @@ class Trainer(object):
             pred = utils.infer_lbl_device(score, self.embeddings)
         return score, loss, pred, target
 
+    # calibrated stacking: with a sweep and a calibration the penalty in use joins the sweep's gammas for the call (one launch gives
+    # both); the histogram rows of the sweep's own gammas are picked out afterwards
+    _calib_hist = None                          # the (G,K,K) device histogram of the running validate(), None outside a sweep
+
+    def _calib_gammas(self):
+        if self._calib_hist is None:
+            return [self.calibration]
+        return self._calib_all
+
+    def _calib_index(self):
+        if self.calibration is None:
+            return None
+        return 0 if self._calib_hist is None else int(np.searchsorted(self._calib_all, np.float32(self.calibration)))
+
+    def _calib_report(self, hist_all):
+        """rank 0, once per epoch: one calib_log.csv row per gamma of the sweep, and the gamma with the largest harmonic mean"""
+        keep = np.searchsorted(self._calib_all, self.calib_sweep)
+        path = osp.join(self.log_dir, 'calib_log.csv')
+        if not osp.exists(path):
+            with open(path, 'w') as f:
+                f.write('epoch,iteration,gamma,val/pxl_acc,val/mean_iu,val/seen/mean_iu,val/unseen/mean_iu,val/harmonic_mean_iu\n')
+        best = None
+        with open(path, 'a') as f:
+            for gamma, g in zip(self.calib_sweep, keep):
+                m, ms, mu = utils.calib_rows(hist_all[g], self.n_class, self.val_unseen)
+                hm = utils.harmonic_mean_iu(ms, mu)
+                f.write(','.join(map(str, [self.epoch, self.iteration, float(gamma), m[0], m[2], ms[2], mu[2], hm])) + '\n')
+                # the largest harmonic mean; ties go to the gamma nearest 0 (a NaN never wins)
+                if not np.isnan(hm) and (best is None or hm > best[1] or (hm == best[1] and abs(float(gamma)) < abs(best[0]))):
+                    best = (float(gamma), hm)
+        if best is not None:
+            self.best_gamma, self.best_harmonic_mean_iu = best
+            print('calibration: best gamma %g, harmonic mean IU %.3f' % best)
+            self.tb_writer.add_scalar('fcn/val/calib/best_gamma', best[0], self.epoch)
+            self.tb_writer.add_scalar('fcn/val/calib/best_harmonic_mean_iu', best[1], self.epoch)
+        else:
+            print('calibration: no gamma has a harmonic mean IU (the validation set holds no seen or no unseen pixels)')
+
     def validate(self, both_fcn_and_seenmask=False):
         """reference :182-292.  The {all, seen, unseen} K x K histograms and the loss sum are accumulated on the GPU
         (szn_confusion_hist on the device prediction) and read back ONCE per epoch; under data parallelism the validation
@@ -353,6 +437,16 @@ class Trainer(object):
         world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
         hist = torch.zeros(3, self.n_class, self.n_class, dtype=torch.int64, device=self.device)
         acc = torch.zeros(2, dtype=torch.float64, device=self.device)          # loss sum, image-batch count
+        if both_fcn_and_seenmask and (self.calibration is not None or self.calib_sweep is not None):
+            from ._lib import SznError
+            raise SznError(calibration_refused(True, True, False, True, False, self.n_class))
+        if self.calib_sweep is not None:
+            extra = [] if self.calibration is None else [np.float32(self.calibration)]
+            self._calib_all = np.unique(np.concatenate([self.calib_sweep, np.asarray(extra, dtype=np.float32)]))
+            if self._calib_all.size > 64:
+                from ._lib import SznError
+                raise SznError("calibration: a 64-gamma sweep has no room for a calibration value that is not one of its gammas")
+            self._calib_hist = torch.zeros(self._calib_all.size, self.n_class, self.n_class, dtype=torch.int64, device=self.device)
         n_viz = self.visualize if self.rank == 0 else 0                        # rank 0 renders the first images of its own shard
         tiles = []                                                             # device pictures, kept there until the epoch ends
         mean_bgr = vis_utils.dataset_mean_bgr(getattr(self.val_loader, 'dataset', None)) if n_viz else None
@@ -372,10 +466,17 @@ class Trainer(object):
                 if self.verbose_val and self.rank == 0:
                     print("Test Epoch {:<5} | Iteration {:<5} | Loss {:5.5f} | Score Sum {:10.5f}".format(
                         int(self.epoch), int(batch_idx), float(loss.item()), float(score.sum().item())))
+        calib_hist, self._calib_hist = self._calib_hist, None
         if world > 1:
             dist.all_reduce(hist)
             dist.all_reduce(acc)
+            if calib_hist is not None:
+                dist.all_reduce(calib_hist)
         h = hist.cpu().numpy()
+        if calib_hist is not None:
+            calib_hist = calib_hist.cpu().numpy()
+            if self.rank == 0:
+                self._calib_report(calib_hist)
         accn = acc.cpu().numpy()
         if np.isnan(accn[0]):
             raise ValueError('loss is nan while validating')

@@ -287,6 +287,28 @@ def _hist_to_metrics(hist):
     return acc, acc_cls, mean_iu, fwavacc
 
 
+def harmonic_mean_iu(seen_metrics, unseen_metrics):
+    """the generalized zero-shot score: the harmonic mean 2 s u / (s + u) of the seen and the unseen mean IU (the mean_iu entries of
+    two _hist_to_metrics tuples).  0.0 when s + u == 0, NaN when either is NaN."""
+    s, u = float(seen_metrics[2]), float(unseen_metrics[2])
+    if np.isnan(s) or np.isnan(u):
+        return float('nan')
+    if s + u == 0:
+        return 0.0
+    return 2.0 * s * u / (s + u)
+
+
+def calib_rows(hist, n_class, unseen):
+    """one gamma's (K,K) confusion histogram -> (metrics, seen metrics, unseen metrics): the seen / unseen histograms are its rows
+    with the target outside / inside `unseen`, the others zero (what szn_confusion_hist_k fills)"""
+    hist = np.asarray(hist)
+    is_unseen = np.zeros(n_class, dtype=bool)
+    is_unseen[list(unseen)] = True
+    seen_h = np.where(is_unseen[:, None], 0, hist)
+    unseen_h = np.where(is_unseen[:, None], hist, 0)
+    return _hist_to_metrics(hist), _hist_to_metrics(seen_h), _hist_to_metrics(unseen_h)
+
+
 def _fast_hist(label_true, label_pred, n_class, target='all', unseen=None):
     """host restatement of utils.py:104-119 for numpy label maps (validation logs on the host)"""
     label_true = np.asarray(label_true)
