@@ -101,6 +101,6 @@ def test_every_knob_has_a_case():
         if fn.endswith((".hip", ".h")):
             for ln in open(os.path.join(src, fn)).read().splitlines():
                 if "getenv(" in ln:
-                    assert fn == "szn_elementwise.hip" and "getenv(name)" in ln, (fn, ln.strip())
+                    assert fn == "szn_runtime.hip" and "getenv(name)" in ln, (fn, ln.strip())
 
 

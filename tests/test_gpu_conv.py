@@ -277,9 +277,10 @@ def test_conv_epilogue_scale_and_padded_strides():
 
 
 @pytest.mark.parametrize("geom", [(2, 13, 9, 100), (1, 20, 37, 1), (1, 5, 70, 0)])
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
 def test_conv1_1(dtype, geom):
     B, H, W, pad = geom
+    is16 = dtype != torch.float32
     g = torch.Generator().manual_seed(3)
     x = torch.randn(B, 3, H, W, generator=g) * 50
     w = torch.randn(64, 3, 3, 3, generator=g) / 5
@@ -293,22 +294,48 @@ def test_conv1_1(dtype, geom):
     wd, xd, bd = nhwc(w.detach()).cuda(), x.cuda(), bias.cuda()   # keep the device tensors alive across the calls
     L.call("szn_conv1_1_fwd", dt, B, H, W, pad, L.ptr(xd), L.ptr(wd), L.ptr(bd), L.ptr(out), L.stream_ptr())
     torch.cuda.synchronize()
-    tol = 1e-5 if dtype == torch.float32 else 1e-2
+    tol = 1e-2 if is16 else 1e-5
     assert relerr(out.float().cpu().permute(0, 3, 1, 2), ref) < tol
     dout = torch.randn(B, 64, Ho, Wo, generator=g)
-    if dtype == torch.bfloat16:
-        dout = dout.bfloat16().float()
+    if is16:
+        dout = dout.to(dtype).float()
     pre.backward(dout)
     dw = torch.empty(64, 3, 3, 3, device="cuda"); db = torch.empty(64, device="cuda")
     doutd = nhwc(dout).cuda().to(dtype)
     ws = torch.empty(L.load().szn_conv1_1_wgrad_workspace_bytes(dt, B, H, W, pad), dtype=torch.uint8, device="cuda")
     L.call("szn_conv1_1_wgrad", dt, B, H, W, pad, L.ptr(xd), L.ptr(doutd), L.ptr(dw), L.ptr(db), 0, L.ptr(ws), L.stream_ptr())
-    if dtype == torch.bfloat16:     # fused kernel (no im2col image), then the bias-gradient kernel
+    if is16:     # fused kernel (no im2col image), then the bias-gradient kernel
         assert L.prev_kernel() == "conv1_1_wgrad_reduce", L.prev_kernel()
     torch.cuda.synchronize()
-    # bf16 path: the im2col image is bf16 (pixel values up to ~150 keep 8 mantissa bits)
-    assert relerr(dw.cpu().permute(0, 3, 1, 2), w.grad) < (1e-4 if dtype == torch.float32 else 1e-2)
+    # 16-bit path: the im2col image is 16-bit (pixel values up to ~150 keep 8 mantissa bits in bf16)
+    assert relerr(dw.cpu().permute(0, 3, 1, 2), w.grad) < (1e-2 if is16 else 1e-4)
     assert relerr(db.cpu(), dout.sum((0, 2, 3))) < 1e-4
+
+
+# Forward only, bit for bit.  Image values are integers in [-4, 4], weights k/4 (|k| <= 8), bias k/8 (|k| <= 16): all exact in bf16 and fp16,
+# every product is a multiple of 1/4 and every partial sum of the 27 products plus the bias is a multiple of 1/8 with magnitude
+# <= 27 * 4 * 2 + 2 = 218 -- exact in fp32 whatever order the MFMA adds in.  So the kernel must give relu(conv2d), computed in fp32 and
+# rounded to the storage type (RNE on both sides), exactly: any slip in the tap decode, the swap pairing or the 8-pixel exchange shows.
+#   (17, 130, 130, 1): 17 * 130 * 2 = 4,420 runs for the 4,096 waves of the capped grid -- 324 waves take a second run, all of them touching
+#                      the image (the prefetch-then-store hand-over); 9 segments per row = a ragged last run and a ragged last segment
+#   (8, 102, 40, 100): 300 x 238 outputs, 4,800 runs, mostly padding: constant-piece stores, runs whose successor does / does not touch the image
+#   (1, 5, 70, 0):     small ragged geometry
+@pytest.mark.parametrize("geom", [(17, 130, 130, 1), (8, 102, 40, 100), (1, 5, 70, 0)])
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+def test_conv1_1_fwd_exact(dtype, geom):
+    B, H, W, pad = geom
+    g = torch.Generator().manual_seed(5)
+    x = torch.randint(-4, 5, (B, 3, H, W), generator=g).float()
+    w = torch.randint(-8, 9, (64, 3, 3, 3), generator=g).float() / 4
+    bias = torch.randint(-16, 17, (64,), generator=g).float() / 8
+    ref = nhwc(F.relu(F.conv2d(x, w, bias, padding=pad))).to(dtype)
+    Ho, Wo = H + 2 * pad - 2, W + 2 * pad - 2
+    out = torch.empty(B, Ho, Wo, 64, device="cuda", dtype=dtype)
+    wd, xd, bd = nhwc(w).cuda(), x.cuda(), bias.cuda()   # keep the device tensors alive across the call
+    L.call("szn_conv1_1_fwd", L.dtype_code(dtype), B, H, W, pad, L.ptr(xd), L.ptr(wd), L.ptr(bd), L.ptr(out), L.stream_ptr())
+    torch.cuda.synchronize()
+    assert L.last_kernel() == "conv1_1_fwd_kernel", L.last_kernel()
+    assert torch.equal(out.cpu(), ref)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])

@@ -28,13 +28,13 @@ static inline void szn_publish_result(const szn_conv_desc_t* d) {
     if (d && d->result) { d->result->colsum_rows = szn_noted_colsum_rows(); d->result->work_fraction = szn_noted_work_fraction(); }
 }
 void szn_note_work_fraction(float f);
-int szn_knob(const char* name, int dflt);        /* environment knob, registered in szn_elementwise.hip's table (aborts on an unlisted name) */
+int szn_knob(const char* name, int dflt);        /* environment knob, registered in szn_runtime.hip's table (aborts on an unlisted name) */
 int szn_knob_live(const char* name, int dflt);   /* the same, re-read on every call (the tests flip it inside one process) */            /* thread-local: fraction of the dense tiles the last conv call executed (constant-border hint) */
 #define SZN_CHECK_LAUNCH(name) do { hipError_t e__ = hipGetLastError(); szn_note_kernel(name); \
     if (e__ != hipSuccess) SZN_FAIL(SZN_ERR_LAUNCH, "%s: %s", name, hipGetErrorString(e__)); } while (0)
 
 // ---- Adam, one element (torch.optim.Adam's scalar chain; no contraction: -ffp-contract=off).  Shared by adam_kernel
-//      (szn_elementwise.hip) and the epilogue of conv_wgrad_wide<T, true> (szn_conv2d_wgrad_adam): the same instructions on the same
+//      (szn_optim.hip) and the epilogue of conv_wgrad_wide<T, true> (szn_conv2d_wgrad_adam): the same instructions on the same
 //      values, so the fused and the separate update agree bit for bit. ----
 __device__ __forceinline__ float adam_elem(float& pi, float gi, float& mi, float& vi, float b1, float b2, float eps, float wd,
                                            float step_size, float inv_bc2_sqrt, float gscale) {
@@ -198,3 +198,21 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 }
 
 static inline int szn_div_up(long a, long b) { return (int)((a + b - 1) / b); }
+// blocks of a grid-stride launch over n items: at least 1, at most cap
+static inline int szn_grid_for(long n, int per_block = 256, int cap = 8192) {
+    long b = (n + per_block - 1) / per_block;
+    if (b > cap) b = cap;
+    if (b < 1) b = 1;
+    return (int)b;
+}
+
+// ---- dtype code -> storage tag ----------------------------------------------------------------
+// Calls f with bf16_raw{} / f16_raw{} / float{} for SZN_BF16 / SZN_F16 / SZN_F32 (f: a generic lambda that launches the kernel instantiated
+// on decltype of its argument).  Any other code: f is not called and the result is false -- the caller keeps its own error text.
+template <typename F> static inline bool szn_by_dtype(int dtype, F&& f) {
+    if (dtype == SZN_BF16) f(bf16_raw{});
+    else if (dtype == SZN_F16) f(f16_raw{});
+    else if (dtype == SZN_F32) f(float{});
+    else return false;
+    return true;
+}

@@ -313,7 +313,7 @@ extern "C" int szn_conv1_1_wgrad_reads(int dtype, int B, int H, int W, int pad, 
     return (rect[0] > 0 || rect[1] < Ho || rect[2] > 0 || rect[3] < Wo) ? 1 : 0;
 }
 
-// bf16 path of szn_conv1_1_wgrad (szn_elementwise.hip).  workspace: >= nblocks * 8 KiB.  Returns 1 if not applicable.
+// bf16 path of szn_conv1_1_wgrad (szn_conv1_1.hip).  workspace: >= nblocks * 8 KiB.  Returns 1 if not applicable.
 int szn_conv1_1_wgrad_fused_try(int dtype, int B, int H, int W, int pad, const float* x, const void* dout, float* dw, int accumulate,
                                 void* workspace, size_t workspace_bytes, szn_stream_t stream, const int* cutv) {
     const int Ho = H + 2 * pad - 2, Wo = W + 2 * pad - 2;
