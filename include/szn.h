@@ -514,6 +514,32 @@ int szn_fused_mse_head_prepared(int stride, int B, int h, int w, int E, int ldc,
                                 float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
                                 szn_stream_t stream);
 
+/* ---- fused similarity cross-entropy head (train.py -loss sim_ce): a softmax over the seen classes' cosines, without the score --------
+ * Equivalent to szn_bilinear_up_crop_fwd(stride) -> utils.sim_ce_loss (forward and autograd backward) -> szn_embed_argmax_k ->
+ * szn_bilinear_up_crop_bwd(stride).  Arguments, strides (32 | 8), group modes, NULL rules (pred-only, loss-only, no dcoarse), error
+ * codes, workspace (szn_fused_head_workspace_bytes) and prepare step (szn_fused_head_prepare for _prepared) are those of
+ * szn_fused_mse_head[_prepared]; pred is szn_fused_head_grouped's pred bit for bit (the class assignment is the cosine argmax whatever
+ * the loss).  For a pixel with upsampled score s (fp32 arithmetic):
+ *   cos_k = s.e_k / (|s| n_k), n_k = |e_k| (1 where |e_k| = 0);  S = the classes of [0, K) not in `exclude` (NULL: all K compete);
+ *   z_k = cos_k / temperature for k in S;  term = logsumexp_{k in S} z_k - z_label (the maximum subtracted first).
+ * A pixel counts when 0 <= label < K and label is in S: -1, -2 (padding), labels >= K and labels in `exclude` are ignored (the CE head's
+ * rule for labels >= K, not the cosine head's row 0).  stats f32 [B][2] = {sum of terms, number of counted px}; loss = mean_b S_b / N_b.
+ * dcoarse = d loss / d coarse with, p = softmax_S(z) (0 outside S) and y = onehot(label),
+ *   d term / d s = (1 / temperature) sum_k (p_k - y_k) (e_k / (|s| n_k) - cos_k s / |s|^2),
+ * scaled by 1 / (B N_b) and carried back through the upsample, channels [c0, c0+E) only, in dcoarse_dtype.  A pred-only call
+ * (target NULL) evaluates no softmax.  Errors, all before any launch: temperature <= 0 or not finite, a class in `exclude` >= K, and an
+ * `exclude` that leaves no class competing are SZN_ERR_ARG.  Fixed-order reductions, no atomics: two calls give bitwise-equal outputs. */
+int szn_fused_simce_head(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                         const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
+                         int group_mode, const int64_t* group_map, const szn_class_set* exclude, float temperature,
+                         float* loss, float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
+                         szn_stream_t stream);
+int szn_fused_simce_head_prepared(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                                  const float* coarse, const float* embed, const int64_t* target,
+                                  const szn_class_set* unseen, int group_mode, const int64_t* group_map,
+                                  const szn_class_set* exclude, float temperature, float* loss, float* stats, int64_t* pred,
+                                  int dcoarse_dtype, void* dcoarse, void* workspace, szn_stream_t stream);
+
 /* ---- fused softmax cross-entropy head: coarse -> (loss, stats, prediction, dcoarse) without the (B,C,H,W) score ---------
  * Equivalent to szn_bilinear_up_crop_fwd(stride) -> szn_ce2d_fwd (pred = channel argmax) -> szn_ce2d_bwd (gout NULL) ->
  * szn_bilinear_up_crop_bwd(stride) (models.py:94,146-147 upscore + crop, utils.py:19-48 cross_entropy2d, trainer_fcn.py:117

@@ -22,6 +22,8 @@
 //   fh_gather_kernel     one block per coarse position sums the <= 4 cells that use it as a tap and writes dcoarse
 //   calib_cell_kernel / calib_cell_tab_kernel / calib_hist_kernel   szn_calib_head (calibrated stacking): the cell kernels' G and Q (fh_load_taps,
 //                        fh_build_GQ, fh_lookup_GQ), two running bests per pixel (fh_two_best), crossing tables, prefix sums -> hist
+//   sce_cell_kernel / sce_cell_tab_kernel   szn_fused_simce_head (similarity cross-entropy): the same G and Q, a softmax over the classes per
+//                        pixel (sce_pixel) and a dense A through a per-wave LDS tile (sce_dense_A); sums, finalize and gather as above
 // Both cell kernels run the same per-pixel body (fh_pixel) and the same label loop (fh_scatter_A), and write per cell: pred, the
 // loss partial, A and Bm.
 //
@@ -540,6 +542,219 @@ __global__ __launch_bounds__(256) void fh_cell_tab_kernel(FhArgs a, const float*
     }
 }
 
+// ---- similarity cross-entropy (szn_fused_simce_head): softmax over the competing classes' cosines ------------------------------------
+// term = logsumexp_{k in S} cos_k / T - cos_label / T over the classes S outside `excl`.  The cell algebra is the cosine head's (G, Q,
+// fh_sim, fh_argmax: pred is that head's bit for bit); the per-pixel coefficients are dense in k:
+//     A[t][k] = sum_px w_t (y_k - p_k) / (T |s| n_k),      Bm[t][u] = sum_px w_t w_u (cos_label - sum_k p_k cos_k) / (T |s|^2)
+// so fh_gather_kernel<T, false> and the `mse` form of fh_finalize_kernel serve it unchanged.  A pixel walks the classes three times
+// (max, sum of exps, coefficients) re-deriving cos_k from G each time (sce_cos: 4 broadcast LDS reads, 4 fmaf, 2 products), cheaper than
+// holding K values per lane.  Dense A: 64 classes at a time, every lane writes its pixel's coefficients to row `lane` of a per-wave LDS tile
+// [64][65] (the odd row stride keeps both the row-wise writes and the column-wise reads free of bank conflicts), then lane k walks
+// the 64 pixels of column k in ascending order, one fmaf chain per tap: fixed order, no cross-lane traffic, no atomics.
+struct SceArgs { ClassBits excl; float inv_t; };
+constexpr int kSceRow = 65;                         // tile row stride in floats
+constexpr int kSceWave = 64 * kSceRow + 64 * 4;     // per wave: tile [64][65] | the pixels' tap weights [64][4]
+
+__device__ __forceinline__ bool sce_competes(const SceArgs& s, int k) { return !((class_word(s.excl, k >> 6) >> (k & 63)) & 1ull); }
+
+// what one pixel hands to the dense-A pass (counted == false: all its coefficients are zero)
+struct ScePx { float wt[4]; long lbl; bool counted; float rsn, m, rsum; };
+
+// cos_k of the softmax passes: fh_sim's dot product times 1 / |s| (one division per pixel) and the hardware reciprocal of n_k (1 ulp),
+// instead of a division per class and pass.  All three passes call this one function, so max_k z_k is the maximum of the very
+// values the exponentials see.  (The prediction keeps fh_sim's division: its bits are the cosine head's.)
+template <int KP>
+__device__ __forceinline__ float sce_cos(const float (&wt)[4], const float* G, float rsn, const float* __restrict__ en, int k) {
+    float d = 0.f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) d = fmaf(wt[t], G[t * KP + k], d);
+    return d * (rsn * __builtin_amdgcn_rcpf(en[k]));
+}
+
+// Pixel (ty, tx) of cell (I, J) of image b: prediction (fh_pixel's), and for a counted pixel the softmax statistics, the loss term and
+// the Bm update.  No target: nothing but the prediction.
+template <int KP, int S, bool GROUPED>
+__device__ __forceinline__ ScePx sce_pixel(const FhArgs& a, const SceArgs& s, int b, int I, int J, int ty, int tx, bool live,
+                                           const float* G, const float* Q, const float* __restrict__ en, float (&bm)[16],
+                                           double& term_sum, double& cnt) {
+    ScePx px = {{0.f, 0.f, 0.f, 0.f}, -1, false, 0.f, 0.f, 0.f};
+    const int y = S * I + ty - a.crop, x = S * J + tx - a.crop;
+    if (live && y >= 0 && y < a.H && x >= 0 && x < a.W) {
+        cell_weights<S>(ty, tx, px.wt);
+        const float (&wt)[4] = px.wt;
+        const float ss = fh_ss(wt, Q);
+        const float sn = sqrtf(ss);
+        const size_t pix = ((size_t)b * a.H + y) * a.W + x;
+        px.lbl = a.target ? a.target[pix] : -1;
+        if (GROUPED || a.pred) a.pred[pix] = fh_argmax<KP, GROUPED>(a, wt, G, sn, en, pix, px.lbl);
+        if (px.lbl >= 0 && px.lbl < a.K && !in_set(s.excl, px.lbl)) {
+            const float rsn = 1.f / sn;
+            float m = -INFINITY;
+            for (int k = 0; k < a.K; ++k)
+                if (sce_competes(s, k)) m = fmaxf(m, sce_cos<KP>(wt, G, rsn, en, k) * s.inv_t);
+            float sum = 0.f, sc = 0.f;
+            for (int k = 0; k < a.K; ++k)
+                if (sce_competes(s, k)) {
+                    const float c = sce_cos<KP>(wt, G, rsn, en, k);
+                    const float e = expf(c * s.inv_t - m);
+                    sum += e;
+                    sc = fmaf(e, c, sc);
+                }
+            const float cl = sce_cos<KP>(wt, G, rsn, en, (int)px.lbl);
+            term_sum += (double)((m - cl * s.inv_t) + logf(sum));
+            cnt += 1.0;
+            px.counted = true; px.rsn = rsn; px.m = m; px.rsum = 1.f / sum;
+            const float bco = (cl - sc * px.rsum) * s.inv_t / ss;
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int u = 0; u < 4; ++u) bm[t * 4 + u] = fmaf(wt[t] * wt[u], bco, bm[t * 4 + u]);
+        }
+    }
+    return px;
+}
+
+// A[t][k] += sum over the wave's 64 pixels of w_t (y_k - p_k) / (T |s| n_k), every k < K.  wl: this wave's kSceWave floats of LDS.
+// Block-uniform control flow (the barriers order the tile writes before the column reads, and the reads before the next writes).
+template <int KP>
+__device__ __forceinline__ void sce_dense_A(const FhArgs& a, const SceArgs& s, const ScePx& px, const float* G,
+                                            const float* __restrict__ en, int lane, float* wl, float* myA) {
+    float* tile = wl;
+    float* wpx = wl + 64 * kSceRow;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) wpx[lane * 4 + t] = px.wt[t];
+    const float aco = s.inv_t * px.rsn;
+    for (int k0 = 0; k0 < a.K; k0 += 64) {
+        const int nk = min(64, a.K - k0);
+        for (int kk = 0; kk < nk; ++kk) {
+            const int k = k0 + kk;
+            float c = 0.f;
+            if (px.counted && sce_competes(s, k)) {
+                const float p = expf(sce_cos<KP>(px.wt, G, px.rsn, en, k) * s.inv_t - px.m) * px.rsum;
+                c = (((long)k == px.lbl ? 1.f : 0.f) - p) * (aco * __builtin_amdgcn_rcpf(en[k]));
+            }
+            tile[lane * kSceRow + kk] = c;
+        }
+        __syncthreads();
+        if (lane < nk) {
+            float acc[4] = {0.f, 0.f, 0.f, 0.f};
+            for (int p = 0; p < 64; ++p) {
+                const float c = tile[p * kSceRow + lane];
+#pragma unroll
+                for (int t = 0; t < 4; ++t) acc[t] = fmaf(wpx[p * 4 + t], c, acc[t]);
+            }
+#pragma unroll
+            for (int t = 0; t < 4; ++t) myA[t * KP + k0 + lane] += acc[t];
+        }
+        __syncthreads();
+    }
+}
+
+// dynamic LDS in floats: stride 32 fh_lds(E, KP, false) | 4 waves' tiles; stride 8 G [4][4 KP] | A [4][4 KP] | Q [4][16] | the tiles
+__host__ __device__ inline size_t sce_lds_floats(int stride, int E, int KP) {
+    return (stride == 8 ? (size_t)32 * KP + 64 : (size_t)fh_lds(E, KP, false).end) + 4 * kSceWave;
+}
+
+template <int KP, bool GROUPED>
+__global__ __launch_bounds__(256) void sce_cell_kernel(FhArgs a, SceArgs s) {        // stride 32: one block per (image, cell)
+    constexpr int S = 32;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const FhLds L = fh_lds(a.E, KP, false);
+    float* Ct = sm + L.Ct;
+    float* G = sm + L.G;
+    float* Q = sm + L.Q;
+    float* Aw = sm + L.Aw;
+    float* red = sm + L.red;
+    double* dred = (double*)(sm + L.dred);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    float* wl = sm + L.end + wave * kSceWave;
+    const int cells_w = a.w + 1, cells = (a.h + 1) * cells_w;
+    const int b = blockIdx.x / cells, cell = blockIdx.x % cells;
+    const int I = cell / cells_w, J = cell % cells_w;
+    const float* embT = a.ws_f;
+    const float* en = a.ws_f + (size_t)a.E * KP;
+
+    fh_load_taps(a, b, I, J, tid, Ct);
+    for (int i = tid; i < 16 * KP; i += 256) Aw[i] = 0.f;
+    __syncthreads();
+    fh_build_GQ<KP>(a, embT, Ct, lane, wave, G, Q);
+    __syncthreads();
+
+    float bm[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) bm[u] = 0.f;
+    double term_sum = 0.0, cnt = 0.0;
+    float* myA = Aw + wave * 4 * KP;
+    for (int q = tid; q < S * S; q += 256) {         // four rounds for every thread: the barriers of sce_dense_A are block-uniform
+        const ScePx px = sce_pixel<KP, S, GROUPED>(a, s, b, I, J, q / S, q % S, true, G, Q, en, bm, term_sum, cnt);
+        if (a.target) sce_dense_A<KP>(a, s, px, G, en, lane, wl, myA);
+    }
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+        const float r = wave_sum(bm[u]);
+        if (lane == 0) red[wave * 16 + u] = r;
+    }
+    term_sum = wave_sum_d(term_sum); cnt = wave_sum_d(cnt);
+    if (lane == 0) { dred[wave * 2] = term_sum; dred[wave * 2 + 1] = cnt; }
+    __syncthreads();
+    float* wc = a.ws_f + ws_cell_off(a.E, KP) + (size_t)blockIdx.x * ws_cell_stride(KP);
+    for (int i = tid; i < 4 * KP; i += 256) wc[i] = combine4(Aw[i], Aw[4 * KP + i], Aw[8 * KP + i], Aw[12 * KP + i]);
+    if (tid < 16) wc[4 * KP + tid] = combine4(red[tid], red[16 + tid], red[32 + tid], red[48 + tid]);
+    if (tid == 0) {
+        a.part[(size_t)blockIdx.x * 2] = combine4(dred[0], dred[2], dred[4], dred[6]);
+        a.part[(size_t)blockIdx.x * 2 + 1] = combine4(dred[1], dred[3], dred[5], dred[7]);
+    }
+}
+
+template <int KP, bool GROUPED>
+__global__ __launch_bounds__(256) void sce_cell_tab_kernel(FhArgs a, SceArgs s, const float* __restrict__ D,
+                                                           const float* __restrict__ N) {      // stride 8: one wave per cell
+    constexpr int S = 8;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    float* G = sm + wave * 4 * KP;
+    float* myA = sm + 16 * KP + wave * 4 * KP;
+    float* Q = sm + 32 * KP + wave * 16;
+    float* wl = sm + 32 * KP + 64 + wave * kSceWave;
+    const int cells_w = a.w + 1, cells = (a.h + 1) * cells_w;
+    const long ncell = (long)a.B * cells;
+    const long cid = (long)blockIdx.x * 4 + wave;
+    const bool ok = cid < ncell;
+    const long cc = ok ? cid : 0;
+    const int b = (int)(cc / cells), cell = (int)(cc % cells);
+    const int I = cell / cells_w, J = cell % cells_w;
+    const float* en = a.ws_f + (size_t)a.E * KP;
+    long tp[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) tp[t] = tap_pos(b, a.h, a.w, I, J, t);
+    for (int i = lane; i < 4 * KP; i += 64) myA[i] = 0.f;
+    fh_lookup_GQ<KP>(tp, D, N, lane, G, Q);
+    __syncthreads();
+
+    float bm[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) bm[u] = 0.f;
+    double term_sum = 0.0, cnt = 0.0;
+    const ScePx px = sce_pixel<KP, S, GROUPED>(a, s, b, I, J, lane / S, lane % S, ok && lane < S * S, G, Q, en, bm, term_sum, cnt);
+    if (a.target) sce_dense_A<KP>(a, s, px, G, en, lane, wl, myA);
+    float bs[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) bs[u] = wave_sum(bm[u]);
+    term_sum = wave_sum_d(term_sum); cnt = wave_sum_d(cnt);
+    __syncthreads();
+    if (!ok) return;
+    float* wc = a.ws_f + ws_cell_off(a.E, KP) + (size_t)cid * ws_cell_stride(KP);
+    for (int i = lane; i < 4 * KP; i += 64) wc[i] = myA[i];
+    if (lane == 0) {
+#pragma unroll
+        for (int u = 0; u < 16; ++u) wc[4 * KP + u] = bs[u];
+        a.part[(size_t)cid * 2] = term_sum;
+        a.part[(size_t)cid * 2 + 1] = cnt;
+    }
+}
+
 // loss = mean_b (N_b - S_b)/N_b (cosine) | mean_b S_b / N_b (mse); stats[b] = {S_b, N_b}.  One block per image sums its cells (fixed order: 256 strided double
 // chains, wave butterflies, then the four wave totals), a single wave combines the images.
 __global__ __launch_bounds__(256) void fh_image_sums_kernel(const double* __restrict__ part, int cells, float* __restrict__ stats,
@@ -794,6 +1009,29 @@ void fh_launch_kp(bool grouped, bool mse, int stride, const FhArgs& a, float* ta
     else mse ? fh_launch<KP, false, true>(stride, a, tabD, tabN, st) : fh_launch<KP, false, false>(stride, a, tabD, tabN, st);
 }
 
+// the similarity cross-entropy cell pass: the same two shapes; the LDS is dynamic at both strides (the tiles take it past 48 KB)
+template <int KP, bool GROUPED>
+void sce_launch(int stride, const FhArgs& a, const SceArgs& s, float* tabD, float* tabN, hipStream_t st) {
+    const int cells = (a.h + 1) * (a.w + 1);
+    const size_t lds = sce_lds_floats(stride, a.E, KP) * sizeof(float);
+    if (stride == 8) {
+        hipLaunchKernelGGL(fh_tables_kernel<KP>, dim3((unsigned)(((long)a.B * a.h * a.w + 3) / 4)), dim3(256),
+                           (size_t)4 * a.E * sizeof(float), st, a, tabD, tabN);
+        auto kern = sce_cell_tab_kernel<KP, GROUPED>;
+        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(kern, dim3((unsigned)(((long)a.B * cells + 3) / 4)), dim3(256), lds, st, a, s, (const float*)tabD,
+                           (const float*)tabN);
+    } else {
+        auto kern = sce_cell_kernel<KP, GROUPED>;
+        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(kern, dim3(a.B * cells), dim3(256), lds, st, a, s);
+    }
+}
+template <int KP>
+void sce_launch_kp(bool grouped, int stride, const FhArgs& a, const SceArgs& s, float* tabD, float* tabN, hipStream_t st) {
+    grouped ? sce_launch<KP, true>(stride, a, s, tabD, tabN, st) : sce_launch<KP, false>(stride, a, s, tabD, tabN, st);
+}
+
 template <typename T, bool MSE>
 void fh_launch_gather(const FhArgs& a, const float* stats, void* dcoarse, hipStream_t st) {
     hipLaunchKernelGGL((fh_gather_kernel<T, MSE>), dim3(a.B * a.h * a.w), dim3(256), 0, st, a.coarse, a.embed, (const float*)a.ws_f,
@@ -805,12 +1043,14 @@ void fh_launch_gather_t(bool mse, const FhArgs& a, const float* stats, void* dco
 }
 
 // every szn_fused_*head* entry point: prep = build the embedding tables first; unseen / group_mode / group_map as in
-// szn_fused_head_grouped (NULL, 0, NULL: ungrouped); mse = the MSE loss instead of the cosine loss
+// szn_fused_head_grouped (NULL, 0, NULL: ungrouped); kind = the loss; exclude / temperature: FH_SIMCE only
+enum FhKind { FH_COS, FH_MSE, FH_SIMCE };
 int fused_head_impl(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
                     const float* coarse, const float* embed, const int64_t* target, float* loss,
                     float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
                     szn_stream_t stream, bool prep, const szn_class_set* unseen, int group_mode,
-                    const int64_t* group_map, bool mse) {
+                    const int64_t* group_map, FhKind kind, const szn_class_set* exclude = nullptr, float temperature = 1.f) {
+    const bool mse = kind == FH_MSE;
     if (stride != 32 && stride != 8) SZN_FAIL(SZN_ERR_UNSUPPORTED, "fused_head: stride %d (32 and 8 are built)", stride);
     if (!coarse || !embed || !workspace || B <= 0 || h <= 0 || w <= 0 || E <= 0 || c0 < 0 || ldc < c0 + E || H <= 0 ||
         W <= 0 || crop < 0 || K <= 0)
@@ -827,10 +1067,22 @@ int fused_head_impl(int stride, int B, int h, int w, int E, int ldc, int c0, int
     if (group_mode == 1 && !group_map) SZN_FAIL(SZN_ERR_ARG, "fused_head_grouped: group mode 1 needs group_map");
     if (group_mode == 2 && !target) SZN_FAIL(SZN_ERR_ARG, "fused_head_grouped: group mode 2 needs target");
     if (!class_bits_fit(ubits, K)) SZN_FAIL(SZN_ERR_ARG, "fused_head_grouped: the unseen set names a class >= K = %d", K);
+    SceArgs sce{};
+    if (kind == FH_SIMCE) {
+        if (!(temperature > 0.f) || !isfinite(temperature)) SZN_FAIL(SZN_ERR_ARG, "fused_simce_head: temperature %g is not a positive finite number", (double)temperature);
+        sce.excl = class_bits(exclude);
+        if (!class_bits_fit(sce.excl, K)) SZN_FAIL(SZN_ERR_ARG, "fused_simce_head: the exclude set names a class >= K = %d", K);
+        int n_excl = 0;
+        for (int i = 0; i < 4; ++i) n_excl += __builtin_popcountll(sce.excl.w[i]);
+        if (n_excl >= K) SZN_FAIL(SZN_ERR_ARG, "fused_simce_head: the exclude set leaves none of the %d classes competing", K);
+        sce.inv_t = 1.f / temperature;
+    }
     const bool grouped = group_mode != 0;
     hipStream_t st = (hipStream_t)stream;
     const int KP = kp_of(K);
     const int cells = (h + 1) * (w + 1);
+    if (fh_lds(E, KP, mse).bytes() > 150 * 1024 || (kind == FH_SIMCE && sce_lds_floats(stride, E, KP) * sizeof(float) > 150 * 1024))
+        SZN_FAIL(SZN_ERR_UNSUPPORTED, "fused_head: E=%d too large for LDS", E);
     const FhWorkspace wl = fh_workspace(B, h, w, E, KP);
     char* ws = (char*)workspace;
     float* ws_f = (float*)ws;
@@ -846,8 +1098,15 @@ int fused_head_impl(int stride, int B, int h, int w, int E, int ldc, int c0, int
     a.coarse = coarse; a.embed = embed; a.target = target; a.pred = pred; a.ws_f = ws_f; a.part = part;
     a.B = B; a.h = h; a.w = w; a.E = E; a.ldc = ldc; a.c0 = c0; a.H = H; a.W = W; a.crop = crop; a.K = K; a.KP = KP;
     a.gmap = group_map; a.gmode = group_mode; a.unseen = ubits;
-    if (fh_lds(E, KP, mse).bytes() > 150 * 1024) SZN_FAIL(SZN_ERR_UNSUPPORTED, "fused_head: E=%d too large for LDS", E);
-    switch (KP) {
+    if (kind == FH_SIMCE) switch (KP) {
+        case 24: sce_launch_kp<24>(grouped, stride, a, sce, tabD, tabN, st); break;
+        case 40: sce_launch_kp<40>(grouped, stride, a, sce, tabD, tabN, st); break;
+        case 64: sce_launch_kp<64>(grouped, stride, a, sce, tabD, tabN, st); break;
+        case 128: sce_launch_kp<128>(grouped, stride, a, sce, tabD, tabN, st); break;
+        case 192: sce_launch_kp<192>(grouped, stride, a, sce, tabD, tabN, st); break;
+        default: sce_launch_kp<256>(grouped, stride, a, sce, tabD, tabN, st); break;
+    }
+    else switch (KP) {
         case 24: fh_launch_kp<24>(grouped, mse, stride, a, tabD, tabN, st); break;
         case 40: fh_launch_kp<40>(grouped, mse, stride, a, tabD, tabN, st); break;
         case 64: fh_launch_kp<64>(grouped, mse, stride, a, tabD, tabN, st); break;
@@ -858,7 +1117,7 @@ int fused_head_impl(int stride, int B, int h, int w, int E, int ldc, int c0, int
     SZN_CHECK_LAUNCH("fh_cell_kernel");
     if (loss) {
         hipLaunchKernelGGL(fh_image_sums_kernel, dim3(B), dim3(256), 0, st, (const double*)part, cells, stats, sums);
-        hipLaunchKernelGGL(fh_finalize_kernel, dim3(1), dim3(64), 0, st, (const double*)sums, B, mse ? 1 : 0, loss);
+        hipLaunchKernelGGL(fh_finalize_kernel, dim3(1), dim3(64), 0, st, (const double*)sums, B, kind != FH_COS ? 1 : 0, loss);
         SZN_CHECK_LAUNCH("fh_finalize_kernel");
     }
     if (dcoarse) {
@@ -897,7 +1156,7 @@ extern "C" int szn_fused_head(int B, int h, int w, int E, int ldc, int c0, int H
                               const float* coarse, const float* embed, const int64_t* target, float* loss, float* stats,
                               int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace, szn_stream_t stream) {
     return fused_head_impl(32, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype, dcoarse,
-                           workspace, stream, true, nullptr, 0, nullptr, false);
+                           workspace, stream, true, nullptr, 0, nullptr, FH_COS);
 }
 
 extern "C" int szn_fused_head_strided(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
@@ -905,7 +1164,7 @@ extern "C" int szn_fused_head_strided(int stride, int B, int h, int w, int E, in
                                       float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
                                       szn_stream_t stream) {
     return fused_head_impl(stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype, dcoarse,
-                           workspace, stream, true, nullptr, 0, nullptr, false);
+                           workspace, stream, true, nullptr, 0, nullptr, FH_COS);
 }
 
 extern "C" int szn_fused_head_prepared(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
@@ -913,7 +1172,7 @@ extern "C" int szn_fused_head_prepared(int stride, int B, int h, int w, int E, i
                                        float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
                                        szn_stream_t stream) {
     return fused_head_impl(stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype, dcoarse,
-                           workspace, stream, false, nullptr, 0, nullptr, false);
+                           workspace, stream, false, nullptr, 0, nullptr, FH_COS);
 }
 
 // group mode 0: szn_fused_head_strided / _prepared bit for bit.  1: a pixel takes the unseen group where group_map == 0 (the seen-mask
@@ -923,7 +1182,7 @@ extern "C" int szn_fused_head_grouped(int stride, int B, int h, int w, int E, in
                                       int group_mode, const int64_t* group_map, float* loss, float* stats, int64_t* pred,
                                       int dcoarse_dtype, void* dcoarse, void* workspace, szn_stream_t stream) {
     return fused_head_impl(stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype, dcoarse,
-                           workspace, stream, true, unseen, group_mode, group_map, false);
+                           workspace, stream, true, unseen, group_mode, group_map, FH_COS);
 }
 
 extern "C" int szn_fused_head_grouped_prepared(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
@@ -932,7 +1191,7 @@ extern "C" int szn_fused_head_grouped_prepared(int stride, int B, int h, int w, 
                                                float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
                                                szn_stream_t stream) {
     return fused_head_impl(stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype, dcoarse,
-                           workspace, stream, false, unseen, group_mode, group_map, false);
+                           workspace, stream, false, unseen, group_mode, group_map, FH_COS);
 }
 
 // The MSE embedding loss (train.py -loss mse; trainer_fcn.py forward / forward_szn -> utils.py:50-73 mse_loss) through the same head:
@@ -944,7 +1203,7 @@ extern "C" int szn_fused_mse_head(int stride, int B, int h, int w, int E, int ld
                                   int group_mode, const int64_t* group_map, float* loss, float* stats, int64_t* pred,
                                   int dcoarse_dtype, void* dcoarse, void* workspace, szn_stream_t stream) {
     return fused_head_impl(stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype, dcoarse,
-                           workspace, stream, true, unseen, group_mode, group_map, true);
+                           workspace, stream, true, unseen, group_mode, group_map, FH_MSE);
 }
 
 extern "C" int szn_fused_mse_head_prepared(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
@@ -953,7 +1212,27 @@ extern "C" int szn_fused_mse_head_prepared(int stride, int B, int h, int w, int 
                                            float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
                                            szn_stream_t stream) {
     return fused_head_impl(stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype, dcoarse,
-                           workspace, stream, false, unseen, group_mode, group_map, true);
+                           workspace, stream, false, unseen, group_mode, group_map, FH_MSE);
+}
+
+// The similarity cross-entropy loss (train.py -loss sim_ce; utils.sim_ce_loss) through the same head: softmax over the cosines of the
+// classes outside `exclude`, divided by `temperature`, cross-entropy against the label (include/szn.h).
+extern "C" int szn_fused_simce_head(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                                    const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
+                                    int group_mode, const int64_t* group_map, const szn_class_set* exclude, float temperature,
+                                    float* loss, float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
+                                    szn_stream_t stream) {
+    return fused_head_impl(stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype, dcoarse,
+                           workspace, stream, true, unseen, group_mode, group_map, FH_SIMCE, exclude, temperature);
+}
+
+extern "C" int szn_fused_simce_head_prepared(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                                             const float* coarse, const float* embed, const int64_t* target,
+                                             const szn_class_set* unseen, int group_mode, const int64_t* group_map,
+                                             const szn_class_set* exclude, float temperature, float* loss, float* stats,
+                                             int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace, szn_stream_t stream) {
+    return fused_head_impl(stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype, dcoarse,
+                           workspace, stream, false, unseen, group_mode, group_map, FH_SIMCE, exclude, temperature);
 }
 
 // Calibrated stacking (include/szn.h): the seen-class penalty gamma swept over n_gammas values in one pass over the pixels.

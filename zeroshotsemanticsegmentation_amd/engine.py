@@ -375,7 +375,7 @@ class TrainStep(object):
                  adam_weight_decay=0.0, grad_comm_dtype=None, loss_scale=None, dynamic_loss_scale=None,
                  scale_growth=2.0, scale_backoff=0.5, scale_growth_interval=2000, force_comm=None, reserved_cus=None,
                  fused_adam=None, keep_grads=True, exchange=None, direct_wire=None, sharded=None, forced_unseen=None,
-                 class_weight=None, size_average=False):
+                 class_weight=None, size_average=False, sim_exclude=None, sim_temperature=None):
         """Data-parallel knobs (the reference is single-GPU): grad_comm_dtype (SZN_GRAD_COMM = fp32 | bf16) = the
         wire format of the gradient buckets; exchange=False (SZN_GRAD_COMM=off) = no exchange at all (bench.py's comm-off timing);
         direct_wire (default: on for a 16-bit wire with keep_grads=False; SZN_WIRE_DIRECT=0 turns it off) = the weight-gradient
@@ -388,9 +388,17 @@ class TrainStep(object):
         loss="cross_entropy" (embeddings=None; the softmax FCN of train.py -c 1, utils.py:19-48 with trainer_fcn.py:133's
         size_average=False): K = C = model.n_class classes, the head is szn_fused_ce_head (fused_head=False: upscore -> szn_ce2d_fwd
         -> szn_ce2d_bwd -> head_backward), the prediction is the channel argmax; class_weight = optional [C] class weights.  Under
-        data parallelism the update uses the mean of the rank gradients, as allreduce_param_grads gives the autograd route."""
-        if loss not in ("cos", "mse", "cross_entropy"):
-            raise L.SznError("TrainStep: loss must be 'cos', 'mse' or 'cross_entropy', got %r" % (loss,))
+        data parallelism the update uses the mean of the rank gradients, as allreduce_param_grads gives the autograd route.
+        loss="sim_ce" (utils.sim_ce_loss; szn_fused_simce_head): a softmax over the cosines of the classes outside sim_exclude (a list
+        of class indices, the trainer's unseen classes; None: all compete) divided by sim_temperature (None: heads.SIM_TEMPERATURE),
+        cross entropy against the label.  Fused head only: fused_head=False raises (no materialised kernels were built for it)."""
+        if loss not in ("cos", "mse", "sim_ce", "cross_entropy"):
+            raise L.SznError("TrainStep: loss must be 'cos', 'mse', 'sim_ce' or 'cross_entropy', got %r" % (loss,))
+        if loss != "sim_ce" and (sim_exclude is not None or sim_temperature is not None):
+            raise L.SznError("TrainStep: sim_exclude / sim_temperature belong to loss 'sim_ce', not %r" % (loss,))
+        if loss == "sim_ce" and not fused_head:
+            raise L.SznError("TrainStep: the sim_ce loss runs on the fused head only; the materialised score goes through autograd "
+                             "(utils.sim_ce_loss)")
         self.ce = loss == "cross_entropy"
         if self.ce and (embeddings is not None or forced_unseen is not None):
             raise L.SznError("TrainStep: the cross-entropy head takes no embeddings and no forced_unseen classes")
@@ -445,6 +453,15 @@ class TrainStep(object):
             raise L.SznError("TrainStep: forced_unseen names a class outside [0, %d)" % self.K)
         self._unseen_cs = L.class_set(self.forced_unseen) if self.forced_unseen is not None else None
         self._group = 0 if self.forced_unseen is None else 2          # heads.embed group mode: plain / forced unseen
+        self._sim_kw = {}                                             # heads.embed's extra keywords of loss "sim_ce"
+        if loss == "sim_ce":
+            excl = sorted(set(int(k) for k in (sim_exclude or [])))
+            if any(not 0 <= k < self.K for k in excl) or len(excl) >= self.K:
+                raise L.SznError("TrainStep: sim_exclude must name classes of [0, %d) and leave one competing" % self.K)
+            temp = float(heads.SIM_TEMPERATURE if sim_temperature is None else sim_temperature)
+            if not 0 < temp < float("inf"):
+                raise L.SznError("TrainStep: sim_temperature must be positive and finite, got %r" % (sim_temperature,))
+            self._sim_kw = dict(exclude=excl, temperature=temp)
         # static loss scaling for the fp16 path: gradients below 6e-8 vanish in IEEE half, so d(loss)/d(coarse) is multiplied
         # by loss_scale in fp32 before it enters the 16-bit backward pass and the optimizer kernel divides it out again
         # (grad_scale).  The .grad views then hold loss_scale x gradient.  bf16 / fp32 need none.
@@ -459,6 +476,13 @@ class TrainStep(object):
         # for per-channel residuals up to 2^10.  At the product shape (eight 512 x 512 images) the factor is ~450 x smaller, 512 is
         # merely conservative there and the dynamic scale grows (x2 per 2000 clean steps); too high a start costs skipped steps
         # at once, too low a start only resolution that growth wins back.
+        # The sim_ce head starts at the cosine head's 4096.  Its per-pixel gradient is (1/T) sum_k (p_k - y_k) d cos_k / d s with
+        # |d cos_k / d s| <= 1 / |s| (the cosine head's own bound) and sum_k |p_k - y_k| <= 2, so |dL/ds| <= 2 / (T |s|): the cosine
+        # bound times 2 / T, 20 x at the default T = 0.1, with the same 1 / (B N_b) and the same geometry.  The bound is reached only
+        # by a pixel whose whole probability sits on wrong classes that all pull one way; a position's S^2 weights / (B N_b) times
+        # 4096 x 2 / (T |s|) stays under 65504 once |s| > 0.07 at the worst shape above (B N_b / S^2 = 18), and the scores of a fresh
+        # or trained head are orders above that.  Should a batch overflow all the same, the dynamic scale pays log2(2 / T) ~ 5
+        # skipped steps at the very start (x 1/2 per overflowing step) and nothing afterwards.
         fp16_scale0 = 1.0 if self.ce else (512.0 if loss == "mse" else 4096.0)
         self._loss_scale0 = float(loss_scale) if loss_scale is not None else (fp16_scale0 if precision == torch.float16 else 1.0)
         # dynamic loss scaling (default for fp16): the scale, the overflow flag and the count of APPLIED optimizer steps live
@@ -746,7 +770,7 @@ class TrainStep(object):
                      ws=self.head_ws, stream=st)
         else:
             heads.embed(self.loss_kind, stride, fmap, self.emb, H, W, pred, target, self.loss, stats, dmap, self._group,
-                        self._unseen_cs, ws=self.head_ws, stream=st)
+                        self._unseen_cs, ws=self.head_ws, stream=st, **self._sim_kw)
 
     def _dcoarse_buffer(self, ctx):
         """d(loss)/d(coarse) of the fused head: it writes channels [0, E) and the padding channels stay zero, so the buffer of the

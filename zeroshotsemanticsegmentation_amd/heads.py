@@ -1,12 +1,14 @@
 """heads.py -- the host side of the fused heads: every call into szn_fused_head_grouped[_prepared], szn_fused_mse_head[_prepared],
 szn_fused_ce_head and szn_seenmask_head_k goes through here (models.FCN32s / FCN8s predict methods, engine.TrainStep, engine.SeenmaskStep).
 
-  embed     the embedding head, kind "cos" | "mse" (wrappers cosine / cosine_predict, mse / mse_predict):
+  embed     the embedding head, kind "cos" | "mse" | "sim_ce" (wrappers cosine / cosine_predict, mse / mse_predict, sim_ce / sim_ce_predict):
   cosine    loss, stats, nearest-embedding prediction and d(map) from an NHWC map: stride 32 on the 1/32 map, stride 8 on FCN8s'
             1/8 fused map (fp32).  Group mode 0 = plain (szn_fused_head_grouped launches exactly what szn_fused_head_strided
             launches, bit for bit), 1 = seen / unseen group from the seen-mask prediction, 2 = forced unseen (group from the target).
   mse       the same head with the MSE embedding loss (szn_fused_mse_head): same arguments, same prediction bit for bit, same
             Workspace tables; loss, stats and d(map) are those of sum |s - e_label|^2 / N_b.
+  sim_ce    the same head with the similarity cross-entropy loss (szn_fused_simce_head): a softmax over the cosines of the classes
+            outside `exclude`, divided by `temperature`; same prediction bit for bit, same Workspace tables.
   ce        the softmax cross-entropy head, stride 32 or 8.
   seenmask  the x32 seen-mask head on the 1/32 map: training, predict and pred-only (group map) calls.
   ms        multi-scale / mirrored inference: the views of an input (szn_resize_flip_f32) and the view-ensemble head (szn_ms_head),
@@ -82,21 +84,33 @@ def _outputs(B, H, W, device, target):
     return pred, target.to(device=device, dtype=torch.int64).contiguous(), torch.empty(1, device=device)
 
 
-# ---- embedding heads (cosine | mse) -----------------------------------------------------------------------------------------
-_EMBED_ENTRY = {"cos": "szn_fused_head_grouped", "mse": "szn_fused_mse_head"}      # both share workspace and prepare step
+# ---- embedding heads (cosine | mse | sim_ce) --------------------------------------------------------------------------------
+_EMBED_ENTRY = {"cos": "szn_fused_head_grouped", "mse": "szn_fused_mse_head",      # all share workspace and prepare step
+                "sim_ce": "szn_fused_simce_head"}
+SIM_TEMPERATURE = 0.1        # the default of train.py --sim-temperature: a hyper-parameter default, not a tuned value
 
 
 def embed_kind(loss):
-    """the embedding heads' loss argument checked: "cos" | "mse" """
+    """the embedding heads' loss argument checked: "cos" | "mse" | "sim_ce" """
     if loss not in _EMBED_ENTRY:
-        raise L.SznError("embedding head: loss must be 'cos' or 'mse', got %r" % (loss,))
+        raise L.SznError("embedding head: loss must be 'cos', 'mse' or 'sim_ce', got %r" % (loss,))
     return loss
 
 
+def _sim_args(kind, exclude, temperature):
+    """the two extra C arguments of kind "sim_ce" (exclude: None or an iterable of classes; temperature: None = SIM_TEMPERATURE);
+    an error for the other kinds"""
+    if kind != "sim_ce":
+        if exclude is not None or temperature is not None:
+            raise L.SznError("embedding head: exclude / temperature belong to loss 'sim_ce', not %r" % (kind,))
+        return ()
+    return (L.class_set(exclude), float(SIM_TEMPERATURE if temperature is None else temperature))
+
+
 def embed(kind, stride, fmap, emb, H, W, pred, target=None, loss=None, stats=None, dmap=None, mode=0, classes=None, gmap=None,
-          ws=None, stream=None):
-    """szn_fused_head_grouped (kind "cos") / szn_fused_mse_head (kind "mse") on the contiguous NHWC map `fmap` (the E embedding
-    channels first).  target / loss / stats go together; dmap (zero-padded, [E, ld) stays untouched) receives d loss / d fmap in its
+          ws=None, stream=None, exclude=None, temperature=None):
+    """szn_fused_head_grouped (kind "cos") / szn_fused_mse_head (kind "mse") / szn_fused_simce_head (kind "sim_ce", with exclude = the
+    classes that do not compete and temperature) on the contiguous NHWC map `fmap` (the E embedding channels first).  target / loss / stats go together; dmap (zero-padded, [E, ld) stays untouched) receives d loss / d fmap in its
     dtype.  classes = the unseen class set (L.class_set) of modes 1 / 2, gmap the group map of mode 1.  ws: a Workspace (its
     embedding tables are reused, whichever kind wrote them) or None."""
     B, h, w, ld = fmap.shape
@@ -104,21 +118,23 @@ def embed(kind, stride, fmap, emb, H, W, pred, target=None, loss=None, stats=Non
     st = L.stream_ptr() if stream is None else stream
     nbytes = L.load().szn_fused_head_workspace_bytes(B, h, w, E, K)
     fn = _EMBED_ENTRY[kind]
+    sim = _sim_args(kind, exclude, temperature)
     if ws is None:
         buf = _scratch(nbytes, fmap.device)
     else:
         fn, buf = fn + "_prepared", ws.prepared(nbytes, emb, K, E, st)
     code = L.dtype_code(dmap.dtype) if dmap is not None else L.SZN_F32
     L.call(fn, stride, B, h, w, E, ld, 0, H, W, _CROP[stride], K, L.ptr(fmap), L.ptr(emb), L.ptr(target), classes, mode,
-           L.ptr(gmap), L.ptr(loss), L.ptr(stats), L.ptr(pred), code, L.ptr(dmap), L.ptr(buf), st)
+           L.ptr(gmap), *(sim + (L.ptr(loss), L.ptr(stats), L.ptr(pred), code, L.ptr(dmap), L.ptr(buf), st)))
 
 
-def embed_predict(kind, stride, fmap, emb, H, W, target=None, mode=0, unseen=None, gmap=None):
+def embed_predict(kind, stride, fmap, emb, H, W, target=None, mode=0, unseen=None, gmap=None, exclude=None, temperature=None):
     """forward-only embedding head -> (loss 0-dim tensor or None, pred (B,H,W) int64)"""
     B = fmap.shape[0]
     pred, tgt, loss = _outputs(B, H, W, fmap.device, target)
     stats = None if loss is None else torch.empty(B, 2, device=fmap.device)
-    embed(kind, stride, fmap, emb, H, W, pred, tgt, loss, stats, mode=mode, classes=L.class_set(unseen), gmap=gmap)
+    embed(kind, stride, fmap, emb, H, W, pred, tgt, loss, stats, mode=mode, classes=L.class_set(unseen), gmap=gmap, exclude=exclude,
+          temperature=temperature)
     return (loss.reshape(()) if loss is not None else None), pred
 
 
@@ -138,6 +154,15 @@ def mse(*args, **kw):
 
 def mse_predict(*args, **kw):
     return embed_predict("mse", *args, **kw)
+
+
+def sim_ce(*args, **kw):
+    """embed("sim_ce", ...): the similarity cross-entropy loss (utils.sim_ce_loss) -- same arguments plus exclude / temperature, same pred"""
+    embed("sim_ce", *args, **kw)
+
+
+def sim_ce_predict(*args, **kw):
+    return embed_predict("sim_ce", *args, **kw)
 
 
 # ---- view-ensemble embedding head (multi-scale / mirrored inference) ---------------------------------------------------------

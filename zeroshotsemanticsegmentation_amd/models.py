@@ -1388,6 +1388,20 @@ class FCN32s(nn.Module):
         ctx = self._engine.forward(x.detach() if isinstance(x, torch.Tensor) else x, train=False, keep=False)
         return ctx, 32, ctx.coarse
 
+    # loss="sim_ce" (similarity cross-entropy, szn_fused_simce_head) has two settings of its own.  They live on the model
+    # (set_sim_ce) rather than in the predict methods' parameter lists, which are a pinned part of the public interface.
+    _sim_ce = (None, None)
+
+    def set_sim_ce(self, exclude=None, temperature=None):
+        """the settings every loss="sim_ce" call of this model uses: `exclude` = the classes that do not compete in the softmax
+        (the trainer passes its unseen classes; None: all compete), `temperature` (None: heads.SIM_TEMPERATURE).  -> self"""
+        self._sim_ce = (None if exclude is None else [int(k) for k in exclude], None if temperature is None else float(temperature))
+        return self
+
+    def _sim_kw(self, kind):
+        """the extra keywords of heads.embed / embed_predict for `kind`"""
+        return dict(exclude=self._sim_ce[0], temperature=self._sim_ce[1]) if kind == "sim_ce" else {}
+
     def embed_predict(self, x, embeddings, target=None, loss="cos"):
         """forward pass + nearest-class-embedding prediction (+ cosine loss when `target` is given) WITHOUT materialising the
         (B,E,H,W) score: the fused-from-coarse head (szn_fused_head) evaluates upscore + crop (models.py:146-147), cosine_loss
@@ -1395,12 +1409,13 @@ class FCN32s(nn.Module):
         fused map).  -> (loss 0-dim tensor or None, pred (B,H,W) int64 device tensor), the prediction also in self._last_pred.
         Same numbers as `forward` + utils up to rounding order (class assignment differs only on pixels whose top-2 cosine margin
         is < 1e-5).  loss="mse": the loss is utils.mse_loss's (utils.py:50-73, szn_fused_mse_head); the prediction is the same, bit
-        for bit.  Used by Trainer.validate."""
+        for bit.  loss="sim_ce": utils.sim_ce_loss's with the model's set_sim_ce settings (szn_fused_simce_head), same prediction.
+        Used by Trainer.validate."""
         kind = heads.embed_kind(loss)
         with torch.no_grad():
             ctx, stride, fmap = self._head_map(x)
             emb = heads.embeddings(embeddings, self.n_class, fmap.device)
-            loss, self._last_pred = heads.embed_predict(kind, stride, fmap, emb, ctx.H, ctx.W, target)
+            loss, self._last_pred = heads.embed_predict(kind, stride, fmap, emb, ctx.H, ctx.W, target, **self._sim_kw(kind))
         return loss, self._last_pred
 
     def softmax_predict(self, x, target=None, weight=None):
@@ -1441,6 +1456,11 @@ class FCN32s(nn.Module):
         pinned part of the public interface."""
         return self._szn_predict(x, embeddings, unseen, target, group, "mse")
 
+    def szn_predict_sim_ce(self, x, embeddings, unseen, target=None, group='seenmask'):
+        """szn_predict for a network trained with the similarity cross-entropy (train.py -loss sim_ce): the same class assignment bit
+        for bit, the loss is utils.sim_ce_loss's with the model's set_sim_ce settings (szn_fused_simce_head)."""
+        return self._szn_predict(x, embeddings, unseen, target, group, "sim_ce")
+
     def _szn_predict(self, x, embeddings, unseen, target, group, kind):
         mode = self._szn_group(group, target)
         with torch.no_grad():
@@ -1449,7 +1469,8 @@ class FCN32s(nn.Module):
             self._last_group = None
             if mode == 1:
                 self._last_group = heads.seenmask_group(ctx.coarse, self.n_class, self._engine._images["up.w"], ctx.H, ctx.W)
-            return heads.embed_predict(kind, stride, fmap, emb, ctx.H, ctx.W, target, mode, unseen, self._last_group)
+            return heads.embed_predict(kind, stride, fmap, emb, ctx.H, ctx.W, target, mode, unseen, self._last_group,
+                                       **self._sim_kw(kind))
 
     def ms_predict(self, x, embeddings, scales, flip=False, target=None, unseen=None, group=None, loss="cos"):
         """multi-scale (and mirrored) inference: the network runs once per view of `x` -- every scale of `scales`, which must contain
@@ -1461,7 +1482,7 @@ class FCN32s(nn.Module):
         szn_predict[_mse] return for x, bit for bit (that view's pass is shared with them); only the prediction comes from the
         ensemble.  The class assignment is the cosine argmax whatever the loss.  Softmax models have no such head: SznError."""
         if embeddings is None or loss == "cross_entropy":
-            raise L.SznError("ms_predict: multi-scale inference is built for the embedding heads (loss 'cos' | 'mse'); averaging "
+            raise L.SznError("ms_predict: multi-scale inference is built for the embedding heads (loss 'cos' | 'mse' | 'sim_ce'); averaging "
                              "softmax probabilities over views is not")
         kind = heads.embed_kind(loss)
         mode = 0 if group is None else self._szn_group(group, target)
@@ -1473,7 +1494,8 @@ class FCN32s(nn.Module):
             self._last_group = None
             if mode == 1:
                 self._last_group = heads.seenmask_group(ctx.coarse, self.n_class, self._engine._images["up.w"], H, W)
-            loss_t, _ = heads.embed_predict(kind, stride, fmap, emb, H, W, target, mode, unseen if mode else None, self._last_group)
+            loss_t, _ = heads.embed_predict(kind, stride, fmap, emb, H, W, target, mode, unseen if mode else None, self._last_group,
+                                            **self._sim_kw(kind))
             # every view's map is copied out before the next forward pass reuses the engine's buffers
             maps = {(H, W, False): fmap.to(torch.float32, copy=True)}
             for key in plan:
@@ -1494,7 +1516,7 @@ class FCN32s(nn.Module):
         with torch.no_grad():
             ctx, stride, fmap = self._head_map(x)
             emb = heads.embeddings(embeddings, self.n_class, fmap.device)
-            loss_t, pred = heads.embed_predict(kind, stride, fmap, emb, ctx.H, ctx.W, target)
+            loss_t, pred = heads.embed_predict(kind, stride, fmap, emb, ctx.H, ctx.W, target, **self._sim_kw(kind))
             if target is not None or pred_index is not None:
                 fmap32 = fmap if fmap.dtype == torch.float32 else fmap.to(torch.float32)
                 hist, cpred = heads.calib(stride, fmap32, emb, ctx.H, ctx.W, unseen, gammas, target, hist, pred_index)
@@ -1654,6 +1676,7 @@ class _FusedHead8(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, x, emb, target, H, W, want_grad, kind="cos"):
+        # (kind "sim_ce": exclude / temperature are the model's set_sim_ce settings)
         x = x.contiguous()
         B, h, w, ld = x.shape
         dev = x.device
@@ -1661,7 +1684,7 @@ class _FusedHead8(torch.autograd.Function):
         loss = torch.empty(1, device=dev)
         stats = torch.empty(B, 2, device=dev)
         dx = torch.zeros(B, h, w, ld, device=dev, dtype=torch.float32) if want_grad else None
-        heads.embed(kind, 8, x, emb, H, W, pred, target, loss, stats, dx)
+        heads.embed(kind, 8, x, emb, H, W, pred, target, loss, stats, dx, **model._sim_kw(kind))
         ctx.dx = dx
         model._last_pred = pred
         return loss.reshape(())
@@ -1751,7 +1774,8 @@ class FCN8s(FCN32s):
     def embed_loss(self, x, embeddings, target, dropout_masks=None, loss="cos"):
         """training-time fused head: -> (cosine loss with autograd history, pred (B,H,W) int64).  Same numbers as
         utils.cosine_loss(self(x), target, embeddings) / utils.infer_lbl_device up to rounding order, without the
-        (B,E,H,W) score or its gradient in HBM.  loss="mse": utils.mse_loss instead (szn_fused_mse_head)."""
+        (B,E,H,W) score or its gradient in HBM.  loss="mse": utils.mse_loss instead (szn_fused_mse_head); loss="sim_ce":
+        utils.sim_ce_loss with the model's set_sim_ce settings (szn_fused_simce_head)."""
         kind = heads.embed_kind(loss)
         emb = heads.embeddings(embeddings, self.n_class, x.device)
         _, fuse3 = self._fuse(x, self.training, dropout_masks)

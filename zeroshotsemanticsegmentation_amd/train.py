@@ -18,6 +18,9 @@ Added for this implementation (none change the reference flags):
                        class before the argmax (szn_calib_head); --calib-sweep LO HI N also writes the metrics of N penalties between
                        LO and HI, and their harmonic mean of seen and unseen mIoU, to <log_dir>/calib_log.csv at one extra head launch
                        per validation batch
+  -loss sim_ce         similarity cross-entropy: softmax over the seen classes' cosine similarities to the pixel embedding, cross
+                       entropy against the label (szn_fused_simce_head; the unseen classes do not compete); --sim-temperature T
+                       (default 0.1, a hyper-parameter default, not a tuned value) divides the similarities
   --init synthetic|vgg path handling: without the caffe VGG16 file the backbone starts from synth weights
   torchrun: RANK / LOCAL_RANK / WORLD_SIZE are honoured (one process per GPU, RCCL gradient all-reduce).
 """
@@ -33,6 +36,7 @@ import yaml
 from . import engine as _engine
 from . import models, trainer_fcn, trainer_seenmask
 from .configs import configurations
+from .heads import SIM_TEMPERATURE
 from .optim import FusedAdam, FusedSGD
 from .synthetic_dataset import SyntheticSegmentation
 
@@ -53,7 +57,7 @@ def build_parser():
     p.add_argument('-e', '--embed_dim', type=int, choices=[2, 5, 10, 20, 21, 50, 100, 200, 300])
     p.add_argument('-ve', '--fcn_epochs', type=int)
     p.add_argument('-lr', '--fcn_learning_rate', type=float)
-    p.add_argument('-loss', '--fcn_loss', type=str, choices=['cos', 'mse', 'cross_entropy'])
+    p.add_argument('-loss', '--fcn_loss', type=str, choices=['cos', 'mse', 'sim_ce', 'cross_entropy'])
     p.add_argument('-o', '--fcn_optim', type=str, choices=['sgd', 'adam'])
     p.add_argument('-se', '--seenmask_epochs', type=int)
     p.add_argument('-slr', '--seenmask_learning_rate', type=float)
@@ -91,6 +95,10 @@ def build_parser():
     p.add_argument('--calib-sweep', type=float, nargs=3, metavar=('LO', 'HI', 'N'), default=None,
                    help="every validation also evaluates N penalties (2 to 64) evenly spaced from LO to HI in one extra pass of the "
                         "head and appends their metrics and the harmonic mean of seen and unseen mIoU to <log_dir>/calib_log.csv")
+    p.add_argument('--sim-temperature', type=float, default=None, metavar='T',
+                   help="with -loss sim_ce (softmax over the seen classes' cosine similarities to the pixel embedding, cross entropy "
+                        "against the label): the temperature the similarities are divided by.  Default %g: a hyper-parameter default, "
+                        "not a tuned value.  An error without -loss sim_ce" % SIM_TEMPERATURE)
     return p
 
 
@@ -111,6 +119,9 @@ def update_cfg_with_args(cfg, args):
     return cfg
 
 
+_EMBED_LOSSES = trainer_fcn._EMBED_LOSSES          # 'cos' | 'mse' | 'sim_ce': the losses of an embedding configuration
+
+
 # configuration sanity rules (the reference's checks, train.py:232-251, with its messages: the CLI contract): (broken?, message)
 _ONE_HOT_WIDTH = {"pascal": 21, "context": 33}      # classes of the dataset = width of a one-hot class embedding
 _CFG_RULES = (
@@ -120,7 +131,7 @@ _CFG_RULES = (
      'must load model path via -r flag for test mode'),
     (lambda c: c['seenmask_epochs'] > 0 and not c['train_unseen'],
      "can't train the seenmask classifier without train_unseen specified"),
-    (lambda c: c['embed_dim'] == 0 and c['fcn_loss'] in ('cos', 'mse'),
+    (lambda c: c['embed_dim'] == 0 and c['fcn_loss'] in _EMBED_LOSSES,
      "invalid loss function because pixel embedding dimensionality not defined"),
 )
 
@@ -208,10 +219,10 @@ def freeze_for_seenmask(model):
 
 def check_precision(precision, cfg):
     """--precision fp16 trains only where loss scaling exists: the fused steps (engine.TrainStep / SeenmaskStep; see
-    trainer_fcn.Trainer.train_epoch) -- an embedding configuration with fcn_loss 'cos' or 'mse', or the softmax configuration"""
-    fused_cfg = (cfg['fcn_loss'] in ('cos', 'mse') and cfg['embed_dim']) or (cfg['fcn_loss'] == 'cross_entropy' and not cfg['embed_dim'])
+    trainer_fcn.Trainer.train_epoch) -- an embedding configuration with fcn_loss 'cos', 'mse' or 'sim_ce', or the softmax configuration"""
+    fused_cfg = (cfg['fcn_loss'] in _EMBED_LOSSES and cfg['embed_dim']) or (cfg['fcn_loss'] == 'cross_entropy' and not cfg['embed_dim'])
     if precision == 'fp16' and cfg['mode'] == 'train' and cfg['fcn_epochs'] > 0 and not fused_cfg:
-        raise Exception("--precision fp16 needs the fused training step: embedding configuration with fcn_loss 'cos' or 'mse', or "
+        raise Exception("--precision fp16 needs the fused training step: embedding configuration with fcn_loss 'cos', 'mse' or 'sim_ce', or "
                         "the softmax configuration (fcn_loss 'cross_entropy', no embedding) (got loss %r, embed_dim %r); use bf16 "
                         "or fp32" % (cfg['fcn_loss'], cfg['embed_dim']))
 
@@ -220,8 +231,8 @@ def check_eval_views(scales, flip, cfg):
     """--eval-scales / --eval-flip: an embedding configuration (the view-ensemble head sums cosine similarities) and 1.0 among the scales"""
     if not scales and not flip:
         return
-    if not (cfg['embed_dim'] and cfg['fcn_loss'] in ('cos', 'mse')):
-        raise Exception("--eval-scales / --eval-flip need an embedding configuration with fcn_loss 'cos' or 'mse' (got loss %r, "
+    if not (cfg['embed_dim'] and cfg['fcn_loss'] in _EMBED_LOSSES):
+        raise Exception("--eval-scales / --eval-flip need an embedding configuration with fcn_loss 'cos', 'mse' or 'sim_ce' (got loss %r, "
                         "embed_dim %r)" % (cfg['fcn_loss'], cfg['embed_dim']))
     if scales and 1.0 not in [float(s) for s in scales]:
         raise Exception("--eval-scales must contain 1 (got %r)" % (scales,))
@@ -253,17 +264,28 @@ def check_calibration(calibration, sweep, cfg, eval_scales=None, eval_flip=False
         raise Exception("--calibration: GAMMA must be finite (got %r)" % (calibration,))
     n_class = 21 if cfg['dataset'] == 'pascal' else 33
     why = trainer_fcn.calibration_refused(bool(cfg['train_unseen'] or cfg['val_unseen']),
-                                          bool(cfg['embed_dim']) and cfg['fcn_loss'] in ('cos', 'mse'), bool(cfg['forced_unseen']),
+                                          bool(cfg['embed_dim']) and cfg['fcn_loss'] in _EMBED_LOSSES, bool(cfg['forced_unseen']),
                                           cfg['mode'] == 'test_all', bool(eval_scales or eval_flip), n_class,
                                           os.environ.get("SZN_VERBOSE_VAL", "0") == "1")
     if why:
         raise Exception("--calibration / --calib-sweep: " + why)
 
 
+def check_sim_temperature(temperature, cfg):
+    """--sim-temperature: only with fcn_loss 'sim_ce', positive and finite"""
+    if temperature is None:
+        return
+    if cfg['fcn_loss'] != 'sim_ce':
+        raise Exception("--sim-temperature needs -loss sim_ce (got loss %r)" % (cfg['fcn_loss'],))
+    if not 0 < temperature < float('inf'):
+        raise Exception("--sim-temperature: T must be positive and finite (got %r)" % (temperature,))
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     cfg = update_cfg_with_args(configurations[args.config], args)
     validate_cfg(cfg)
+    check_sim_temperature(args.sim_temperature, cfg)
     check_precision(args.precision, cfg)
     check_eval_views(args.eval_scales, args.eval_flip, cfg)
     check_calibration(args.calibration, args.calib_sweep, cfg, args.eval_scales, args.eval_flip)
@@ -385,7 +407,7 @@ def main(argv=None):
         dataset=cfg['dataset'], max_epoch=cfg['fcn_epochs'], pixel_embeddings=cfg['embed_dim'], loss_func=cfg['fcn_loss'],
         tb_writer=tb_writer, unseen=all_unseen, val_unseen=cfg['val_unseen'], label_names=label_names,
         forced_unseen=cfg['forced_unseen'], precision=precision, rank=rank, visualize=args.viz, augment=augment,
-        calibration=args.calibration, calib_sweep=calib_sweep_values(args.calib_sweep), eval_scales=args.eval_scales,
+        sim_temperature=args.sim_temperature, calibration=args.calibration, calib_sweep=calib_sweep_values(args.calib_sweep), eval_scales=args.eval_scales,
         eval_flip=args.eval_flip)
     fcn_trainer.epoch, fcn_trainer.iteration = start_epoch, start_iteration
 

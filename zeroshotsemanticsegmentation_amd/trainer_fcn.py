@@ -35,6 +35,9 @@ def load_embeddings(dataset, dim):
     raise IOError("no embedding matrix for dataset=%s dim=%s (looked for %s.pkl and %s)" % (dataset, dim, pkl, npy))
 
 
+_EMBED_LOSSES = ("cos", "mse", "sim_ce")          # the embedding losses: each has a fused head (heads.embed)
+
+
 def _now():
     return datetime.datetime.now(datetime.timezone(datetime.timedelta(hours=-5)))      # 'US/Eastern' (no DST handling)
 
@@ -46,7 +49,7 @@ def calibration_refused(has_unseen, embed_cfg, forced_unseen, test_all, eval_vie
     if not has_unseen:
         return "calibration needs unseen classes (train_unseen / val_unseen): without them there is no seen group to penalise"
     if not embed_cfg:
-        return "calibration needs an embedding configuration (loss 'cos' | 'mse'): a softmax network has no unseen-class scores"
+        return "calibration needs an embedding configuration (loss 'cos' | 'mse' | 'sim_ce'): a softmax network has no unseen-class scores"
     if forced_unseen:
         return "calibration and forced_unseen are two different class-assignment rules: pick one"
     if test_all:
@@ -71,7 +74,7 @@ class Trainer(object):
     def __init__(self, cuda, model, optimizer, train_loader, val_loader, log_dir, dataset, max_epoch, tb_writer,
                  pixel_embeddings=None, loss_func=None, unseen=None, val_unseen=None, label_names=None,
                  forced_unseen=False, embed_arr=None, precision=torch.float32, fused_step=True, rank=0, visualize=0, augment=None,
-                 calibration=None, calib_sweep=None, eval_scales=None, eval_flip=False):
+                 sim_temperature=None, calibration=None, calib_sweep=None, eval_scales=None, eval_flip=False):
         if not cuda:
             raise RuntimeError("this implementation runs on the GPU only (cuda=False has no CPU fallback)")
         self.cuda = cuda
@@ -95,14 +98,23 @@ class Trainer(object):
         # datasets.Augment or None: train_epoch sends every (images, labels, sizes) batch of the training loader (datasets.augment_collate)
         # through it -- random scale / crop / flip on the GPU, a fixed network input size; validate() never augments
         self.augment = augment
+        # loss_func "sim_ce" (utils.sim_ce_loss, szn_fused_simce_head): the softmax runs over the seen classes -- its `exclude` is
+        # self.unseen -- at this temperature (None: heads.SIM_TEMPERATURE); every fused call reads both from the model
+        if sim_temperature is not None and loss_func != "sim_ce":
+            from ._lib import SznError
+            raise SznError("sim_temperature belongs to loss 'sim_ce' (got loss %r)" % (loss_func,))
+        from .heads import SIM_TEMPERATURE
+        self.sim_temperature = float(SIM_TEMPERATURE if sim_temperature is None else sim_temperature)
+        if loss_func == "sim_ce" and pixel_embeddings:
+            model.set_sim_ce(self.unseen, self.sim_temperature)
         # multi-scale / mirrored validation (models.ms_predict): the scales every validation image is evaluated at (None: once, as
         # stored) and whether each is also evaluated mirrored.  Training steps never see them.
         self.eval_scales = tuple(float(s) for s in eval_scales) if eval_scales else None
         self.eval_flip = bool(eval_flip)
         self._ms_warned = False
-        if (self.eval_scales or self.eval_flip) and not (pixel_embeddings and loss_func in ("cos", "mse")):
+        if (self.eval_scales or self.eval_flip) and not (pixel_embeddings and loss_func in _EMBED_LOSSES):
             from ._lib import SznError
-            raise SznError("eval_scales / eval_flip need an embedding configuration (loss 'cos' | 'mse'): averaging softmax "
+            raise SznError("eval_scales / eval_flip need an embedding configuration (loss 'cos' | 'mse' | 'sim_ce'): averaging softmax "
                            "probabilities over views is not built")
         if self.eval_flip and not self.eval_scales:
             self.eval_scales = (1.0,)
@@ -129,7 +141,7 @@ class Trainer(object):
         self._fused_step = fused_step
         self.verbose_val = os.environ.get("SZN_VERBOSE_VAL", "0") == "1"   # per-image prints cost a host sync each
         if self.calibration is not None or self.calib_sweep is not None:
-            why = calibration_refused(bool(self.unseen), bool(pixel_embeddings) and loss_func in ("cos", "mse"), forced_unseen,
+            why = calibration_refused(bool(self.unseen), bool(pixel_embeddings) and loss_func in _EMBED_LOSSES, forced_unseen,
                                       False, bool(self.eval_scales), self.n_class, self.verbose_val)
             if why:
                 from ._lib import SznError
@@ -188,6 +200,8 @@ class Trainer(object):
             return utils.cosine_loss(score, target, te)
         if self.loss_func == "mse":
             return utils.mse_loss(score, target, te)
+        if self.loss_func == "sim_ce":
+            return utils.sim_ce_loss(score, target, self.embeddings, self.unseen, self.sim_temperature)
         if self.loss_func == "cross_entropy":
             return utils.cross_entropy2d(score, target, size_average=False)
         raise ValueError("unknown loss_func %r" % (self.loss_func,))
@@ -219,8 +233,8 @@ class Trainer(object):
 
     # ---- training --------------------------------------------------------------------------------------------
     def _embed_cfg(self):
-        """an embedding configuration whose loss has a fused head: cosine or mse (train.py -loss cos | mse)"""
-        return bool(self.pixel_embeddings) and self.loss_func in ("cos", "mse")
+        """an embedding configuration whose loss has a fused head: cosine, mse or sim_ce (train.py -loss cos | mse | sim_ce)"""
+        return bool(self.pixel_embeddings) and self.loss_func in _EMBED_LOSSES
 
     def _ce_cfg(self):
         """the softmax configuration (train.py -c 1): cross entropy over the model's own n_class channels, at most 256 classes"""
@@ -258,6 +272,8 @@ class Trainer(object):
             kw.update(loss="cross_entropy", size_average=False)
         else:
             kw.update(embeddings=self.embeddings, forced_unseen=self.unseen if self.forced_unseen else None, loss=self.loss_func)
+            if self.loss_func == "sim_ce":
+                kw.update(sim_exclude=self.unseen, sim_temperature=self.sim_temperature)
         self._step = _engine.TrainStep(self.model, lr=gw['lr'], bias_lr=gb['lr'],
                                        bias_weight_decay=gb.get('weight_decay', 0.0), precision=self.precision,
                                        fused_head=True, keep_grads=os.environ.get("SZN_KEEP_GRADS", "0") == "1", **kw)
@@ -362,7 +378,8 @@ class Trainer(object):
                 loss, pred = self.model.ms_predict(data, self.embeddings, self.eval_scales, self.eval_flip, target, unseen=self.unseen,
                                                    group='seenmask' if szn else 'target', loss=self.loss_func)
                 return None, loss, pred, target
-            predict = self.model.szn_predict if self.loss_func == "cos" else self.model.szn_predict_mse
+            predict = {"cos": self.model.szn_predict, "mse": self.model.szn_predict_mse,
+                       "sim_ce": self.model.szn_predict_sim_ce}[self.loss_func]
             loss, pred = predict(data, self.embeddings, self.unseen, target, group='seenmask' if szn else 'target')
             return None, loss, pred, target
         if self.eval_scales and not self._ms_warned:
