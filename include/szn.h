@@ -791,6 +791,41 @@ int szn_calib_head(int stride, int B, int h, int w, int E, int ldc, int c0, int 
                    int n_gammas, const float* gammas, int64_t* hist, int pred_index, int64_t* pred,
                    void* workspace, szn_stream_t stream);
 
+/* ---- self-training on the hidden pixels: top-p% pseudo labels ------------------------------------------------------------------
+ * szn_pseudo_head: the network's own calibrated prediction labels the most confident keep_permille / 1000 of the pixels whose label is
+ * hidden (target == cand_label, a negative value: datasets.HIDDEN_LABEL), per unseen class, and writes the relabelled target.
+ * coarse, embed, stride (32 | 8), crop, ldc, c0 and unseen are szn_calib_head's.  sim[k], a, va, b, vb and m = va - vb per pixel are that
+ * head's, the same operations in the same order (the same device functions).  Three passes:
+ *   1. candidates.  A pixel is a candidate when target[pix] == cand_label, m is not NaN, the calibrated rule at `gamma` picks b -- NOT
+ *      (m > gamma or (m == gamma and a < b)) -- and vb >= conf_floor (a conf_floor <= -2 disables the floor).  Its class is b, its
+ *      confidence c = vb (fp32), its bin q = clamp((int)floorf(fmaf(c, 512.f, 512.f)), 0, 1023): c * 512 is exact in fp32, so the
+ *      float32 expression c * 512 + 512 gives the same q.  Every candidate adds 1 to Q[b][q], a [K][SZN_PSEUDO_BINS] integer table in the
+ *      workspace, zeroed on the stream by the call (equal keys of a wave are combined first, one 64-bit integer atomic add per distinct
+ *      key).  Pixels of other labels are not evaluated at all; pixels of a cell outside the image contribute nothing.
+ *   2. thresholds, per class k, integers only: n_k = sum_q Q[k][q]; keep_k = (n_k * keep_permille + 999) / 1000; thr[k] = the largest
+ *      bin t with sum_{q >= t} Q[k][q] >= keep_k, SZN_PSEUDO_BINS when n_k == 0; counts[k] = { n_k, sum_{q >= thr[k]} Q[k][q] }.  The
+ *      whole threshold bin is taken: the selection does not depend on any order inside it, and selected_k >= keep_k.
+ *   3. relabel, elementwise: target_out[pix] = b for a candidate with q >= thr[b]; target[pix] verbatim everywhere else (-1, the padding
+ *      label, labels >= K, candidates that were not selected).
+ * target_out (B,H,W) int64 is required and must not alias target.  Inspection copies, each NULL or device memory, all written (not
+ * accumulated): cand (B,H,W) int64 (-1: no candidate), conf (B,H,W) fp32 (NaN: no candidate), qhist [K][SZN_PSEUDO_BINS] int64,
+ * thr [K] int32, counts [K][2] int64.  gamma, conf_floor, keep_permille and cand_label are kernel arguments: no host synchronisation, no
+ * allocation, capturable in a hipGraph.  Integer atomics only: two calls give bit-equal outputs.
+ * szn_last_kernel(): pseudo_relabel_kernel; szn_prev_kernel(): pseudo_thr_kernel (before them pseudo_cell_kernel at stride 32,
+ * pseudo_cell_tab_kernel at stride 8).
+ * workspace: szn_pseudo_head_workspace_bytes (0 for shapes szn_pseudo_head refuses), 16-byte aligned: a szn_fused_head_prepare image written
+ * by the call, the stride-8 position tables, Q, thr and the per-pixel record of pass 1 (8 bytes per pixel).
+ * SZN_ERR_ARG, before any launch: everything szn_calib_head refuses about the arguments the two share (stride, sizes, K, ldc / c0, the crop
+ * window, the workspace alignment, NULL coarse / embed / workspace, an `unseen` set that is NULL, empty, names a class >= K or holds every
+ * class); gamma or conf_floor not finite; keep_permille outside [1, 1000]; cand_label >= 0; NULL target or target_out; target_out == target. */
+#define SZN_PSEUDO_BINS 1024
+size_t szn_pseudo_head_workspace_bytes(int stride, int B, int h, int w, int E, int K, int H, int W);
+int szn_pseudo_head(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                    const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
+                    float gamma, float conf_floor, int keep_permille, int64_t cand_label,
+                    int64_t* target_out, int64_t* cand, float* conf, int64_t* qhist, int32_t* thr, int64_t* counts,
+                    void* workspace, szn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -77,6 +77,7 @@ def class_set(classes):
 
 MS_MAX_VIEWS = 16           # SZN_MS_MAX_VIEWS
 CALIB_MAX_GAMMAS = 64       # SZN_CALIB_MAX_GAMMAS
+PSEUDO_BINS = 1024          # SZN_PSEUDO_BINS
 
 
 class MsView(C.Structure):
@@ -85,7 +86,7 @@ class MsView(C.Structure):
     _fields_ = [("coarse", C.c_void_p)] + [(n, C.c_int) for n in ("h", "w", "ldc", "c0", "Hs", "Ws", "flip")]
 
 
-_P, _I, _L, _F, _U64, _SZ = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_uint64, C.c_size_t
+_P, _I, _L, _F, _U64, _SZ, _I64 = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_uint64, C.c_size_t, C.c_int64
 _D = C.POINTER(ConvDesc)
 _IP = C.POINTER(C.c_int)
 _CS = C.POINTER(ClassSet)
@@ -198,6 +199,8 @@ SIGNATURES = {
     "szn_ms_head": (_I, [_I] * 8 + [_MV, _P, _CS, _I, _P, _P, _P, _P, _P, _P]),
     "szn_calib_head_workspace_bytes": (_SZ, [_I] * 7),
     "szn_calib_head": (_I, [_I] * 11 + [_P, _P, _P, _CS, _I, _FP, _P, _I, _P, _P, _P]),
+    "szn_pseudo_head_workspace_bytes": (_SZ, [_I] * 8),
+    "szn_pseudo_head": (_I, [_I] * 11 + [_P, _P, _P, _CS, _F, _F, _I, _I64] + [_P] * 8),
     "szn_viz_segmentation": (_I, [_I, _I, _I, _P, _I, C.POINTER(C.c_double), _P, _P, _I, _CS, _U64, _P, _L, _L, _P]),
     "szn_viz_seenmask": (_I, [_I, _I, _I, _P, _I, C.POINTER(C.c_double), _P, _P, _U64, _P, _L, _L, _P]),
 }

@@ -22,6 +22,8 @@
 //   fh_gather_kernel     one block per coarse position sums the <= 4 cells that use it as a tap and writes dcoarse
 //   calib_cell_kernel / calib_cell_tab_kernel / calib_hist_kernel   szn_calib_head (calibrated stacking): the cell kernels' G and Q (fh_load_taps,
 //                        fh_build_GQ, fh_lookup_GQ), two running bests per pixel (fh_two_best), crossing tables, prefix sums -> hist
+//   pseudo_cell_kernel / pseudo_cell_tab_kernel / pseudo_thr_kernel / pseudo_relabel_kernel   szn_pseudo_head (self-training): the same G, Q
+//                        and fh_two_best on the pixels labelled cand_label, a per-class confidence histogram, thresholds, the relabelled target
 //   sce_cell_kernel / sce_cell_tab_kernel   szn_fused_simce_head (similarity cross-entropy): the same G and Q, a softmax over the classes per
 //                        pixel (sce_pixel) and a dense A through a per-wave LDS tile (sce_dense_A); sums, finalize and gather as above
 // Both cell kernels run the same per-pixel body (fh_pixel) and the same label loop (fh_scatter_A), and write per cell: pred, the
@@ -987,6 +989,216 @@ const char* calib_bad_geometry(int stride, int B, int h, int w, int E, int K, in
     return nullptr;
 }
 
+// ---- self-training pseudo labels (szn_pseudo_head): the calibrated head's per-pixel quantities, a per-class confidence histogram,
+// an on-device threshold search, a relabel pass ------------------------------------------------------------------------------------------
+// Pass 1 (pseudo_cell_kernel / pseudo_cell_tab_kernel: calib_cell_kernel / calib_cell_tab_kernel with another per-pixel body) looks at
+// the pixels whose target is cand_label only -- every other pixel skips the trip through the classes -- and leaves per pixel a record
+// {class or -1, confidence bits} in the workspace (8 B); candidates add 1 to QH[class][bin], equal keys of a wave combined first
+// (calib_count's scheme, one 64-bit integer atomic add per distinct key).  Pass 2 (pseudo_thr_kernel): one block per class, a suffix
+// scan over the 1024 bins.  Pass 3 (pseudo_relabel_kernel): elementwise over the records.  Integers throughout: bit-reproducible.
+struct PseudoArgs {
+    float gamma, conf_floor;
+    long cand_label;
+    unsigned long long* QH;      // [K][SZN_PSEUDO_BINS], zeroed by the call
+    int2* rec;                   // [B][H][W]: x = the candidate's class or -1, y = the bits of its confidence (NaN: none)
+};
+
+// bin of a confidence: clamp(floor(c * 512 + 512), 0, 1023); c * 512 is exact, so the fma is the two-step form's bits
+__device__ __forceinline__ int pseudo_bin(float c) {
+    return (int)fminf(fmaxf(floorf(fmaf(c, 512.f, 512.f)), 0.f), (float)(SZN_PSEUDO_BINS - 1));
+}
+
+// Pixel (ty, tx) of cell (I, J) of image b: its record, and its key class << 10 | bin, or -1 where it is no candidate
+template <int KP, int S>
+__device__ __forceinline__ int pseudo_pixel(const FhArgs& a, const PseudoArgs& p, int b, int I, int J, int ty, int tx, bool live,
+                                            const float* G, const float* Q, const float* __restrict__ en) {
+    const int y = S * I + ty - a.crop, x = S * J + tx - a.crop;
+    if (!(live && y >= 0 && y < a.H && x >= 0 && x < a.W)) return -1;
+    const size_t pix = ((size_t)b * a.H + y) * a.W + x;
+    int cls = -1;
+    float conf = __int_as_float(0x7fc00000);
+    if (a.target[pix] == p.cand_label) {
+        float wt[4];
+        cell_weights<S>(ty, tx, wt);
+        const float sn = sqrtf(fh_ss(wt, Q));
+        const FhTwoBest r = fh_two_best<KP>(a, wt, G, sn, en);
+        const float m = r.va - r.vb;
+        const bool takes_a = m > p.gamma || (m == p.gamma && r.ia < r.ib);         // szn_calib_head's rule at this gamma
+        if (m == m && !takes_a && (p.conf_floor <= -2.f || r.vb >= p.conf_floor)) { cls = r.ib; conf = r.vb; }
+    }
+    p.rec[pix] = make_int2(cls, __float_as_int(conf));
+    return cls < 0 ? -1 : (cls << 10 | pseudo_bin(conf));
+}
+
+// the keys of a wave, equal ones combined: one atomic add of the popcount per distinct key (the key is the index into QH)
+__device__ __forceinline__ void pseudo_count(const PseudoArgs& p, int key, int lane) {
+    static_assert(SZN_PSEUDO_BINS == 1 << 10, "the key packs the bin into 10 bits");
+    unsigned long long todo = __ballot(key >= 0);
+    while (todo) {
+        const int src = __ffsll((long long)todo) - 1;
+        const int k0 = __shfl(key, src, 64);
+        const unsigned long long same = __ballot(key == k0);
+        if (lane == src) atomicAdd(p.QH + k0, (unsigned long long)__popcll(same));
+        todo &= ~same;
+    }
+}
+
+template <int KP>
+__global__ __launch_bounds__(256) void pseudo_cell_kernel(FhArgs a, PseudoArgs p) {      // stride 32: one block per (image, cell)
+    constexpr int S = 32;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const FhLds L = fh_lds(a.E, KP, false);
+    float* Ct = sm + L.Ct;
+    float* G = sm + L.G;
+    float* Q = sm + L.Q;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int cells_w = a.w + 1, cells = (a.h + 1) * cells_w;
+    const int b = blockIdx.x / cells, cell = blockIdx.x % cells;
+    const int I = cell / cells_w, J = cell % cells_w;
+    const float* embT = a.ws_f;
+    const float* en = a.ws_f + (size_t)a.E * KP;
+    fh_load_taps(a, b, I, J, tid, Ct);
+    __syncthreads();
+    fh_build_GQ<KP>(a, embT, Ct, lane, wave, G, Q);
+    __syncthreads();
+    for (int q = tid; q < S * S; q += 256)
+        pseudo_count(p, pseudo_pixel<KP, S>(a, p, b, I, J, q / S, q % S, true, G, Q, en), lane);
+}
+
+template <int KP>
+__global__ __launch_bounds__(256) void pseudo_cell_tab_kernel(FhArgs a, PseudoArgs p, const float* __restrict__ D,
+                                                              const float* __restrict__ N) {      // stride 8: one wave per cell
+    constexpr int S = 8;
+    __shared__ float Gs[4][4 * KP];
+    __shared__ float Qs[4][16];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int cells_w = a.w + 1, cells = (a.h + 1) * cells_w;
+    const long ncell = (long)a.B * cells;
+    const long cid = (long)blockIdx.x * 4 + wave;
+    const bool ok = cid < ncell;
+    const long cc = ok ? cid : 0;
+    const int b = (int)(cc / cells), cell = (int)(cc % cells);
+    const int I = cell / cells_w, J = cell % cells_w;
+    const float* en = a.ws_f + (size_t)a.E * KP;
+    long tp[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) tp[t] = tap_pos(b, a.h, a.w, I, J, t);
+    fh_lookup_GQ<KP>(tp, D, N, lane, Gs[wave], Qs[wave]);
+    __syncthreads();
+    pseudo_count(p, pseudo_pixel<KP, S>(a, p, b, I, J, lane / S, lane % S, ok && lane < S * S, Gs[wave], Qs[wave], en), lane);
+}
+
+// Class k = blockIdx.x: n = sum_q QH[k][q], keep = ceil(n * keep_permille / 1000), thr = the largest bin t whose suffix sum
+// sum_{q >= t} QH[k][q] reaches keep (SZN_PSEUDO_BINS when n == 0), counts = {n, that suffix sum}.  Thread t owns bins 4 t .. 4 t + 3;
+// an inclusive suffix scan of the 256 partial sums in LDS, then every thread tests its own four bins: the suffix sums fall with t
+// from n >= keep to 0 < keep, so exactly one bin has its own sum at or above keep and its successor's below.
+__global__ __launch_bounds__(256) void pseudo_thr_kernel(const unsigned long long* __restrict__ QH, int keep_permille,
+                                                         int32_t* __restrict__ thr_ws, int64_t* __restrict__ qhist,
+                                                         int32_t* __restrict__ thr, int64_t* __restrict__ counts) {
+    static_assert(SZN_PSEUDO_BINS == 4 * 256, "four bins per thread");
+    __shared__ unsigned long long suf[257];
+    const int k = blockIdx.x, t = threadIdx.x;
+    const unsigned long long* row = QH + (size_t)k * SZN_PSEUDO_BINS;
+    unsigned long long v[4], s = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        v[i] = row[4 * t + i];
+        s += v[i];
+        if (qhist) qhist[(size_t)k * SZN_PSEUDO_BINS + 4 * t + i] = (int64_t)v[i];
+    }
+    suf[t] = s;
+    if (t == 0) suf[256] = 0;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {
+        const unsigned long long add = (t + d < 256) ? suf[t + d] : 0;
+        __syncthreads();
+        suf[t] += add;
+        __syncthreads();
+    }
+    const unsigned long long n = suf[0];
+    const unsigned long long keep = (n * (unsigned long long)keep_permille + 999) / 1000;
+    if (n == 0) {
+        if (t == 0) {
+            thr_ws[k] = SZN_PSEUDO_BINS;
+            if (thr) thr[k] = SZN_PSEUDO_BINS;
+            if (counts) { counts[2 * k] = 0; counts[2 * k + 1] = 0; }
+        }
+        return;
+    }
+    unsigned long long above = suf[t + 1];              // the suffix sum from the first bin of the next thread on
+#pragma unroll
+    for (int i = 3; i >= 0; --i) {
+        const unsigned long long next = above;
+        above += v[i];                                   // the suffix sum from bin 4 t + i on
+        if (above >= keep && next < keep) {
+            thr_ws[k] = 4 * t + i;
+            if (thr) thr[k] = 4 * t + i;
+            if (counts) { counts[2 * k] = (int64_t)n; counts[2 * k + 1] = (int64_t)above; }
+        }
+    }
+}
+
+// target_out = the candidate's class where its bin reaches its class's threshold, else the target verbatim; the inspection copies
+__global__ __launch_bounds__(256) void pseudo_relabel_kernel(const int64_t* __restrict__ target, const int2* __restrict__ rec,
+                                                             const int32_t* __restrict__ thr_ws, long n,
+                                                             int64_t* __restrict__ target_out, int64_t* __restrict__ cand,
+                                                             float* __restrict__ conf) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int2 r = rec[i];
+    const float c = __int_as_float(r.y);
+    int64_t lbl = target[i];
+    if (r.x >= 0 && pseudo_bin(c) >= thr_ws[r.x]) lbl = r.x;
+    target_out[i] = lbl;
+    if (cand) cand[i] = r.x;
+    if (conf) conf[i] = c;
+}
+
+template <int KP>
+void pseudo_launch(int stride, const FhArgs& a, const PseudoArgs& p, float* tabD, float* tabN, hipStream_t st) {
+    const int cells = (a.h + 1) * (a.w + 1);
+    if (stride == 8) {
+        hipLaunchKernelGGL(fh_tables_kernel<KP>, dim3((unsigned)(((long)a.B * a.h * a.w + 3) / 4)), dim3(256),
+                           (size_t)4 * a.E * sizeof(float), st, a, tabD, tabN);
+        hipLaunchKernelGGL(pseudo_cell_tab_kernel<KP>, dim3((unsigned)(((long)a.B * cells + 3) / 4)), dim3(256), 0, st, a, p,
+                           (const float*)tabD, (const float*)tabN);
+    } else {
+        const size_t lds = (size_t)(fh_lds(a.E, KP, false).Q + 16) * sizeof(float);       // Ct | G | Q
+        auto kern = pseudo_cell_kernel<KP>;
+        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(kern, dim3(a.B * cells), dim3(256), lds, st, a, p);
+    }
+}
+
+// workspace of szn_pseudo_head: the fused head's (embedding tables at its head, the stride-8 position tables) | QH | thr | rec
+struct PseudoWorkspace { size_t QH, thr, rec, bytes; };       // byte offsets
+inline PseudoWorkspace pseudo_workspace(int B, int h, int w, int E, int K, int H, int W) {
+    PseudoWorkspace L;
+    L.QH = align256(fh_workspace(B, h, w, E, kp_of(K)).bytes);
+    L.thr = L.QH + (size_t)K * SZN_PSEUDO_BINS * sizeof(unsigned long long);
+    L.rec = align256(L.thr + (size_t)K * sizeof(int32_t));
+    L.bytes = L.rec + (size_t)B * H * W * sizeof(int2);
+    return L;
+}
+
+// what szn_calib_head and szn_pseudo_head refuse about the arguments they share (after calib_bad_geometry); SZN_OK = fine
+int calib_check_shared(const char* who, int stride, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                       const ClassBits& ubits, const void* workspace) {
+    if (c0 < 0 || ldc < c0 + E || H <= 0 || W <= 0 || crop < 0) SZN_FAIL(SZN_ERR_ARG, "%s: bad argument", who);
+    if (H + crop > stride * h + stride || W + crop > stride * w + stride)
+        SZN_FAIL(SZN_ERR_ARG, "%s: crop window exceeds the deconv output", who);
+    if (((uintptr_t)workspace) & 15) SZN_FAIL(SZN_ERR_ARG, "%s: workspace must be 16-B aligned", who);
+    if (!class_bits_any(ubits)) SZN_FAIL(SZN_ERR_ARG, "%s: the unseen set is empty", who);
+    if (!class_bits_fit(ubits, K)) SZN_FAIL(SZN_ERR_ARG, "%s: the unseen set names a class >= K = %d", who, K);
+    int n_unseen = 0;
+    for (int i = 0; i < 4; ++i) n_unseen += __builtin_popcountll(ubits.w[i]);
+    if (n_unseen >= K) SZN_FAIL(SZN_ERR_ARG, "%s: every class below K = %d is unseen (both groups must be non-empty)", who, K);
+    if (fh_lds(E, kp_of(K), false).bytes() > 150 * 1024) SZN_FAIL(SZN_ERR_UNSUPPORTED, "%s: E=%d too large for LDS", who, E);
+    return SZN_OK;
+}
+
 // the cell pass: stride 32 a block per cell; stride 8 the position tables, then a wave per cell
 template <int KP, bool GROUPED, bool MSE>
 void fh_launch(int stride, const FhArgs& a, float* tabD, float* tabN, hipStream_t st) {
@@ -1247,10 +1459,8 @@ extern "C" int szn_calib_head(int stride, int B, int h, int w, int E, int ldc, i
                               szn_stream_t stream) {
     if (const char* why = calib_bad_geometry(stride, B, h, w, E, K, n_gammas)) SZN_FAIL(SZN_ERR_ARG, "calib_head: %s", why);
     if (!coarse || !embed || !workspace || !gammas) SZN_FAIL(SZN_ERR_ARG, "calib_head: coarse, embed, workspace and gammas are required");
-    if (c0 < 0 || ldc < c0 + E || H <= 0 || W <= 0 || crop < 0) SZN_FAIL(SZN_ERR_ARG, "calib_head: bad argument");
-    if (H + crop > stride * h + stride || W + crop > stride * w + stride)
-        SZN_FAIL(SZN_ERR_ARG, "calib_head: crop window exceeds the deconv output");
-    if (((uintptr_t)workspace) & 15) SZN_FAIL(SZN_ERR_ARG, "calib_head: workspace must be 16-B aligned");
+    const ClassBits ubits = class_bits(unseen);
+    if (int rc = calib_check_shared("calib_head", stride, h, w, E, ldc, c0, H, W, crop, K, ubits, workspace)) return rc;
     for (int g = 0; g < n_gammas; ++g) {
         if (!isfinite(gammas[g])) SZN_FAIL(SZN_ERR_ARG, "calib_head: gammas[%d] is not finite", g);
         if (g && !(gammas[g] > gammas[g - 1])) SZN_FAIL(SZN_ERR_ARG, "calib_head: gammas must be strictly ascending (at %d)", g);
@@ -1258,14 +1468,7 @@ extern "C" int szn_calib_head(int stride, int B, int h, int w, int E, int ldc, i
     if (!hist && !pred) SZN_FAIL(SZN_ERR_ARG, "calib_head: hist and pred are both NULL");
     if (hist && !target) SZN_FAIL(SZN_ERR_ARG, "calib_head: hist needs target");
     if (pred && (pred_index < 0 || pred_index >= n_gammas)) SZN_FAIL(SZN_ERR_ARG, "calib_head: pred_index %d outside [0, %d)", pred_index, n_gammas);
-    const ClassBits ubits = class_bits(unseen);
-    if (!class_bits_any(ubits)) SZN_FAIL(SZN_ERR_ARG, "calib_head: the unseen set is empty");
-    if (!class_bits_fit(ubits, K)) SZN_FAIL(SZN_ERR_ARG, "calib_head: the unseen set names a class >= K = %d", K);
-    int n_unseen = 0;
-    for (int i = 0; i < 4; ++i) n_unseen += __builtin_popcountll(ubits.w[i]);
-    if (n_unseen >= K) SZN_FAIL(SZN_ERR_ARG, "calib_head: every class below K = %d is unseen (both groups must be non-empty)", K);
     const int KP = kp_of(K);
-    if (fh_lds(E, KP, false).bytes() > 150 * 1024) SZN_FAIL(SZN_ERR_UNSUPPORTED, "calib_head: E=%d too large for LDS", E);
 
     hipStream_t st = (hipStream_t)stream;
     const FhWorkspace wl = fh_workspace(B, h, w, E, KP);
@@ -1300,5 +1503,64 @@ extern "C" int szn_calib_head(int stride, int B, int h, int w, int E, int ldc, i
                            (const unsigned long long*)c.XB, K, n_gammas, hist);
         SZN_CHECK_LAUNCH("calib_hist_kernel");
     }
+    return SZN_OK;
+}
+
+// Self-training pseudo labels (include/szn.h): the calibrated rule at one gamma picks the candidates among the pixels labelled cand_label,
+// the most confident keep_permille of them per unseen class take their class as the label.
+extern "C" size_t szn_pseudo_head_workspace_bytes(int stride, int B, int h, int w, int E, int K, int H, int W) {
+    if (calib_bad_geometry(stride, B, h, w, E, K, 1) || H <= 0 || W <= 0) return 0;
+    return pseudo_workspace(B, h, w, E, K, H, W).bytes;
+}
+
+extern "C" int szn_pseudo_head(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                               const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
+                               float gamma, float conf_floor, int keep_permille, int64_t cand_label, int64_t* target_out,
+                               int64_t* cand, float* conf, int64_t* qhist, int32_t* thr, int64_t* counts, void* workspace,
+                               szn_stream_t stream) {
+    if (const char* why = calib_bad_geometry(stride, B, h, w, E, K, 1)) SZN_FAIL(SZN_ERR_ARG, "pseudo_head: %s", why);
+    if (!coarse || !embed || !workspace || !target || !target_out)
+        SZN_FAIL(SZN_ERR_ARG, "pseudo_head: coarse, embed, workspace, target and target_out are required");
+    const ClassBits ubits = class_bits(unseen);
+    if (int rc = calib_check_shared("pseudo_head", stride, h, w, E, ldc, c0, H, W, crop, K, ubits, workspace)) return rc;
+    if (!isfinite(gamma) || !isfinite(conf_floor)) SZN_FAIL(SZN_ERR_ARG, "pseudo_head: gamma and conf_floor must be finite");
+    if (keep_permille < 1 || keep_permille > 1000) SZN_FAIL(SZN_ERR_ARG, "pseudo_head: keep_permille %d outside [1, 1000]", keep_permille);
+    if (cand_label >= 0) SZN_FAIL(SZN_ERR_ARG, "pseudo_head: cand_label %lld must be negative (a class label cannot mark the hidden pixels)", (long long)cand_label);
+    if (target_out == target) SZN_FAIL(SZN_ERR_ARG, "pseudo_head: target_out must not alias target");
+    const int KP = kp_of(K);
+
+    hipStream_t st = (hipStream_t)stream;
+    const FhWorkspace wl = fh_workspace(B, h, w, E, KP);
+    const PseudoWorkspace pl = pseudo_workspace(B, h, w, E, K, H, W);
+    char* ws = (char*)workspace;
+    hipLaunchKernelGGL(fh_prep_kernel, dim3(szn_div_up((long)E * KP, 256)), dim3(256), 0, st, embed, (float*)ws, E, K, KP);
+    SZN_CHECK_LAUNCH("fh_prep_kernel");
+    FhArgs a{};
+    a.coarse = coarse; a.embed = embed; a.target = target; a.ws_f = (float*)ws;
+    a.B = B; a.h = h; a.w = w; a.E = E; a.ldc = ldc; a.c0 = c0; a.H = H; a.W = W; a.crop = crop; a.K = K; a.KP = KP;
+    a.unseen = ubits;
+    PseudoArgs p{};
+    p.gamma = gamma; p.conf_floor = conf_floor; p.cand_label = (long)cand_label;
+    p.QH = (unsigned long long*)(ws + pl.QH); p.rec = (int2*)(ws + pl.rec);
+    int32_t* thr_ws = (int32_t*)(ws + pl.thr);
+    if (hipMemsetAsync(ws + pl.QH, 0, pl.thr - pl.QH, st) != hipSuccess) SZN_FAIL(SZN_ERR_LAUNCH, "pseudo_head: clearing the confidence histogram failed");
+    float* tabD = (float*)(ws + wl.tabD);
+    float* tabN = (float*)(ws + wl.tabN);
+    switch (KP) {
+        case 24: pseudo_launch<24>(stride, a, p, tabD, tabN, st); break;
+        case 40: pseudo_launch<40>(stride, a, p, tabD, tabN, st); break;
+        case 64: pseudo_launch<64>(stride, a, p, tabD, tabN, st); break;
+        case 128: pseudo_launch<128>(stride, a, p, tabD, tabN, st); break;
+        case 192: pseudo_launch<192>(stride, a, p, tabD, tabN, st); break;
+        default: pseudo_launch<256>(stride, a, p, tabD, tabN, st); break;
+    }
+    SZN_CHECK_LAUNCH(stride == 8 ? "pseudo_cell_tab_kernel" : "pseudo_cell_kernel");
+    hipLaunchKernelGGL(pseudo_thr_kernel, dim3(K), dim3(256), 0, st, (const unsigned long long*)p.QH, keep_permille, thr_ws, qhist, thr,
+                       counts);
+    SZN_CHECK_LAUNCH("pseudo_thr_kernel");
+    const long n = (long)B * H * W;
+    hipLaunchKernelGGL(pseudo_relabel_kernel, dim3((unsigned)szn_div_up(n, 256)), dim3(256), 0, st, target, (const int2*)p.rec,
+                       (const int32_t*)thr_ws, n, target_out, cand, conf);
+    SZN_CHECK_LAUNCH("pseudo_relabel_kernel");
     return SZN_OK;
 }

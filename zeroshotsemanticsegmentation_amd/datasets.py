@@ -56,8 +56,13 @@ class _SegmentationDataset(torch.utils.data.Dataset):
     name = None
 
     def __init__(self, split='train', transform=False, embed_dim=None, one_hot_embed=False, data_dir='data', train_unseen=(),
-                 val_unseen=(), native=False, split_dir=None, embed_arr=None, cache=True):
+                 val_unseen=(), native=False, split_dir=None, embed_arr=None, cache=True, hide_unseen=False):
+        """hide_unseen (split 'train_seen' only): keep the images the split drops for their unseen classes and hand those classes' pixels
+        out as HIDDEN_LABEL instead -- the split then bans only what 'train_seen' bans apart from the unseen classes (_banned_mask)"""
         self.split = split
+        self.hide_unseen = bool(hide_unseen)
+        if self.hide_unseen and split != 'train_seen':
+            raise Exception("hide_unseen belongs to split 'train_seen' (got %r): the other splits show their unseen classes" % (split,))
         self._transform = transform
         self.embed_dim = embed_dim
         self.one_hot_embed = one_hot_embed
@@ -163,11 +168,13 @@ class _SegmentationDataset(torch.utils.data.Dataset):
         f = self.files[index]
         img = _open_image(f['img'])
         lbl = self._read_label(f['lbl'])
+        if self.hide_unseen:
+            lbl = np.where(np.isin(lbl, self.train_unseen + self.val_unseen), HIDDEN_LABEL, lbl).astype(lbl.dtype)
         if self.native:
             return torch.from_numpy(np.ascontiguousarray(img)), torch.from_numpy(lbl.astype(np.int64))
         lbl_vec = None
         if self.embed_dim:
-            idx = np.where(lbl == -1, 0, lbl)                          # row 0 stands in for ignore pixels
+            idx = np.where(lbl < 0, 0, lbl)                            # row 0 stands in for ignore (and hidden) pixels
             lbl_vec = torch.from_numpy(np.ascontiguousarray(self.embed_arr[idx].transpose(2, 0, 1)))
         if self._transform:
             img, lbl = self.transform(img, lbl)
@@ -185,7 +192,8 @@ class _SegmentationDataset(torch.utils.data.Dataset):
 
 class PascalContext(_SegmentationDataset):
     """33-class PASCAL-Context (context_dataset.py:14-160): label PNGs are 1-based, 0 = unlabelled -> -1 after `lbl - 1`.
-    EVERY split drops images that contain unlabelled pixels; 'train' also drops val_unseen classes, 'train_seen' all unseen."""
+    EVERY split drops images that contain unlabelled pixels; 'train' also drops val_unseen classes, 'train_seen' all unseen
+    (hide_unseen=True: 'train_seen' keeps them and hides those classes' pixels as HIDDEN_LABEL)."""
     class_names = CONTEXT33_CLASSES
     name = 'context'
 
@@ -198,7 +206,7 @@ class PascalContext(_SegmentationDataset):
 
     def _banned_mask(self):
         extra = {'train': self.val_unseen, 'train_seen': self.train_unseen + self.val_unseen, 'val': []}[self.split]
-        return self._bits([-1] + list(extra))
+        return self._bits([-1] + ([] if self.hide_unseen else list(extra)))
 
 
 class PascalVOC(_SegmentationDataset):
@@ -227,13 +235,17 @@ class PascalVOC(_SegmentationDataset):
 
     def _banned_mask(self):
         extra = {'train': self.val_unseen, 'train_seen': self.train_unseen + self.val_unseen, 'val': []}[self.split]
-        return self._bits(list(extra))
+        return self._bits([] if self.hide_unseen else list(extra))
 
 
 MEAN_RGB_U8 = tuple(int(round(v)) for v in utils.MEAN_BGR[::-1])       # the uint8 colour closest to the mean: ~0 after the transform
 
 
 PAD_LABEL = -2     # label of the pixels pad_collate adds: ignored by every loss / metric kernel, in BOTH phases (see pad_collate)
+# label of the pixels whose unseen class a hide_unseen dataset hides.  Like PAD_LABEL it is below -1, so every existing loss, metric and
+# seen-mask kernel ignores it (`target >= 0` in phase 1; szn_seenmask_head and Trainer.binary_target leave labels below -1 out); only
+# szn_pseudo_head looks for it (heads.pseudo: the self-training candidates)
+HIDDEN_LABEL = -3
 
 
 def pad_collate(batch):

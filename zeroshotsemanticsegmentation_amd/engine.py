@@ -375,7 +375,7 @@ class TrainStep(object):
                  adam_weight_decay=0.0, grad_comm_dtype=None, loss_scale=None, dynamic_loss_scale=None,
                  scale_growth=2.0, scale_backoff=0.5, scale_growth_interval=2000, force_comm=None, reserved_cus=None,
                  fused_adam=None, keep_grads=True, exchange=None, direct_wire=None, sharded=None, forced_unseen=None,
-                 class_weight=None, size_average=False, sim_exclude=None, sim_temperature=None):
+                 class_weight=None, size_average=False, sim_exclude=None, sim_temperature=None, pseudo=None):
         """Data-parallel knobs (the reference is single-GPU): grad_comm_dtype (SZN_GRAD_COMM = fp32 | bf16) = the
         wire format of the gradient buckets; exchange=False (SZN_GRAD_COMM=off) = no exchange at all (bench.py's comm-off timing);
         direct_wire (default: on for a 16-bit wire with keep_grads=False; SZN_WIRE_DIRECT=0 turns it off) = the weight-gradient
@@ -391,7 +391,17 @@ class TrainStep(object):
         data parallelism the update uses the mean of the rank gradients, as allreduce_param_grads gives the autograd route.
         loss="sim_ce" (utils.sim_ce_loss; szn_fused_simce_head): a softmax over the cosines of the classes outside sim_exclude (a list
         of class indices, the trainer's unseen classes; None: all compete) divided by sim_temperature (None: heads.SIM_TEMPERATURE),
-        cross entropy against the label.  Fused head only: fused_head=False raises (no materialised kernels were built for it)."""
+        cross entropy against the label.  Fused head only: fused_head=False raises (no materialised kernels were built for it).
+        pseudo=dict(unseen=[...], gamma=0.0, keep=0.3, conf_floor=-2.0) (embedding losses only): self-training on the pixels a
+        hide_unseen dataset hides (label datasets.HIDDEN_LABEL).  After the forward pass szn_pseudo_head runs on the step's own head map
+        (the 1/32 map, FCN8s: the 1/8 fused map) and stream: the calibrated rule at gamma picks the hidden pixels it gives to an unseen
+        class with a similarity of at least conf_floor, per class the most confident `keep` of them take that class as their label, and
+        the head -- fused or the fused_head=False referee -- trains on the relabelled target.  The train-metric histogram keeps the
+        caller's target.  set_pseudo_active(False) makes the step the plain step again, launch for launch; with loss "sim_ce" the active
+        step empties sim_exclude (the unseen classes now have positives), the inactive one restores it.  pseudo_counts, a device (K,2) int64
+        tensor, accumulates {candidates, selected} per class until the caller zeroes it; with keep_ctx the relabelled target of the last
+        step stays in last_pseudo_target.  Under data parallelism the thresholds are those of each rank's own batch: nothing is
+        exchanged, a rank's labels depend on its own pixels only."""
         if loss not in ("cos", "mse", "sim_ce", "cross_entropy"):
             raise L.SznError("TrainStep: loss must be 'cos', 'mse', 'sim_ce' or 'cross_entropy', got %r" % (loss,))
         if loss != "sim_ce" and (sim_exclude is not None or sim_temperature is not None):
@@ -399,6 +409,8 @@ class TrainStep(object):
         if loss == "sim_ce" and not fused_head:
             raise L.SznError("TrainStep: the sim_ce loss runs on the fused head only; the materialised score goes through autograd "
                              "(utils.sim_ce_loss)")
+        if pseudo is not None:
+            pseudo = self._check_pseudo(pseudo, loss)
         self.ce = loss == "cross_entropy"
         if self.ce and (embeddings is not None or forced_unseen is not None):
             raise L.SznError("TrainStep: the cross-entropy head takes no embeddings and no forced_unseen classes")
@@ -462,6 +474,11 @@ class TrainStep(object):
             if not 0 < temp < float("inf"):
                 raise L.SznError("TrainStep: sim_temperature must be positive and finite, got %r" % (sim_temperature,))
             self._sim_kw = dict(exclude=excl, temperature=temp)
+        self._pseudo = None                                           # szn_pseudo_head's arguments, see set_pseudo_active
+        self._pseudo_active = False
+        self.last_pseudo_target = None                                # (keep_ctx) the relabelled target the last step's head read
+        if pseudo is not None:
+            self._init_pseudo(pseudo)
         # static loss scaling for the fp16 path: gradients below 6e-8 vanish in IEEE half, so d(loss)/d(coarse) is multiplied
         # by loss_scale in fp32 before it enters the 16-bit backward pass and the optimizer kernel divides it out again
         # (grad_scale).  The .grad views then hold loss_scale x gradient.  bf16 / fp32 need none.
@@ -539,6 +556,64 @@ class TrainStep(object):
         self.keep_ctx = False        # tests: keep the forward state of the last step (activations stay alive one step longer)
         self.last_ctx = None
         self.last_fuse3 = None           # (FCN8s, keep_ctx) the 1/8 fused map of the last step
+
+    # ---- self-training pseudo labels ----------------------------------------------------------------------------------------
+    @staticmethod
+    def _check_pseudo(cfg, loss):
+        """pseudo= checked as far as the host alone can (before anything touches a device) -> (unseen, gamma, permille, conf_floor)"""
+        import math
+        if loss == "cross_entropy":
+            raise L.SznError("TrainStep: pseudo labels need an embedding loss ('cos' | 'mse' | 'sim_ce'): the cross-entropy head has "
+                             "no unseen-class scores")
+        if not isinstance(cfg, dict):
+            raise L.SznError("TrainStep: pseudo must be a dict(unseen=, gamma=, keep=, conf_floor=), got %r" % (cfg,))
+        cfg = dict(cfg)
+        unseen = sorted(set(int(k) for k in (cfg.pop("unseen", None) or [])))
+        gamma, keep, floor = cfg.pop("gamma", 0.0), cfg.pop("keep", 0.3), cfg.pop("conf_floor", -2.0)
+        if cfg:
+            raise L.SznError("TrainStep: pseudo takes unseen, gamma, keep and conf_floor, not %s" % sorted(cfg))
+        if not unseen or unseen[0] < 0:
+            raise L.SznError("TrainStep: pseudo['unseen'] must name the unseen classes (got %r)" % (unseen,))
+        gamma, floor = float(0.0 if gamma is None else gamma), float(floor)
+        if not (math.isfinite(gamma) and math.isfinite(floor)):
+            raise L.SznError("TrainStep: pseudo gamma and conf_floor must be finite (got %r, %r)" % (gamma, floor))
+        return unseen, gamma, heads.pseudo_permille(keep), floor
+
+    def _init_pseudo(self, checked):
+        unseen, gamma, permille, floor = checked
+        if unseen[-1] >= self.K or len(unseen) >= self.K:
+            raise L.SznError("TrainStep: pseudo['unseen'] must name some, not all, classes of [0, %d)" % self.K)
+        self._pseudo = dict(unseen=L.class_set(unseen), gamma=gamma, permille=permille, floor=floor)
+        self.pseudo_counts = torch.zeros(self.K, 2, dtype=torch.int64, device=self.dev)
+        self._pseudo_step_counts = torch.zeros(self.K, 2, dtype=torch.int64, device=self.dev)
+        self._pseudo_ws = None
+        self._sim_exclude = self._sim_kw.get("exclude")
+        self.set_pseudo_active(True)
+
+    def set_pseudo_active(self, active):
+        """turn the pseudo-label pass of a step built with pseudo= on or off; off, the step is the plain step launch for launch"""
+        if self._pseudo is None:
+            if active:
+                raise L.SznError("TrainStep: set_pseudo_active(True) on a step built without pseudo=")
+            return
+        self._pseudo_active = bool(active)
+        if self.loss_kind == "sim_ce":
+            self._sim_kw["exclude"] = [] if self._pseudo_active else self._sim_exclude
+
+    def _pseudo_target(self, stride, fmap, target, H, W, st):
+        """the target the head trains on: the caller's, or -- pseudo labels active -- szn_pseudo_head's relabelled copy of it"""
+        if not self._pseudo_active:
+            return target
+        p = self._pseudo
+        nbytes = heads.pseudo_workspace_bytes(stride, fmap, self.emb, H, W)
+        if self._pseudo_ws is None or self._pseudo_ws.numel() < nbytes:
+            self._pseudo_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+        out = torch.empty_like(target)
+        heads.pseudo_call(stride, fmap, self.emb, H, W, target, p["unseen"], p["gamma"], p["permille"], p["floor"], heads.HIDDEN_LABEL,
+                          out, self._pseudo_ws, st, counts=self._pseudo_step_counts)
+        self.pseudo_counts += self._pseudo_step_counts
+        self.last_pseudo_target = out if self.keep_ctx else None
+        return out
 
     # the class-embedding matrix: assigning a new tensor (or calling invalidate_head_prep() after writing into it behind torch's back --
     # a raw kernel does not bump _version, and a new tensor may reuse the address of the old one) makes the fused head rebuild its tables
@@ -729,16 +804,17 @@ class TrainStep(object):
         if self.is8:
             fuse4, fuse3 = self._chain8(ctx)
             dmap = torch.zeros(B, fuse3.shape[1], fuse3.shape[2], m.head_width, device=self.dev, dtype=torch.float32)
-            self._head(8, fuse3, target, H, W, stats, pred, dmap, st)
+            self._head(8, fuse3, self._pseudo_target(8, fuse3, target, H, W, st), H, W, stats, pred, dmap, st)
             if self._scaled:                            # d(fuse3) is scaled in fp32; the chain's backward converts
                 dmap = self._scale(dmap, torch.float32)
             dcoarse, skips = self._chain8_backward(ctx, fuse4, dmap)
         else:
+            head_target = self._pseudo_target(32, ctx.coarse, target, H, W, st)
             if self.fused_head:
                 dcoarse = self._dcoarse_buffer(ctx)
-                self._head(32, ctx.coarse, target, H, W, stats, pred, dcoarse, st)
+                self._head(32, ctx.coarse, head_target, H, W, stats, pred, dcoarse, st)
             else:
-                dcoarse = self._referee(ctx, target, stats, pred, st)
+                dcoarse = self._referee(ctx, head_target, stats, pred, st)
             if self._scaled:
                 dcoarse = self._scale(dcoarse, eng.dtype)
         self.stats = stats

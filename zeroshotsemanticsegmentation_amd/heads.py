@@ -15,6 +15,8 @@ szn_fused_ce_head and szn_seenmask_head_k goes through here (models.FCN32s / FCN
             which reads the maps of all views and writes one prediction.
   calib     calibrated stacking (szn_calib_head): a penalty gamma on every seen class, swept over up to 64 values in one pass --
             per gamma a confusion histogram, for one of them the prediction.
+  pseudo    self-training pseudo labels (szn_pseudo_head): the calibrated prediction labels the most confident share of the hidden
+            pixels per unseen class; the relabelled target is what a training head then reads.
 
 The crop belongs to the stride (32: CROP, reference models.py:147; 8: CROP_UP8, FCN8s' upscore8).  A call without a `Workspace`
 allocates its scratch and builds the embedding tables itself (the predict methods); TrainStep keeps one `Workspace` across steps.
@@ -22,6 +24,7 @@ allocates its scratch and builds the embedding tables itself (the predict method
 import torch
 
 from . import _lib as L
+from .datasets import HIDDEN_LABEL
 
 CROP = 19            # models.py:147
 CROP_UP8 = 31        # FCN8s upscore8 (public pytorch-fcn definition)
@@ -267,6 +270,75 @@ def calib(stride, fmap, emb, H, W, unseen, gammas, target=None, hist=None, pred_
            L.class_set(unseen), G, g.ctypes.data_as(C.POINTER(C.c_float)), L.ptr(hist), -1 if pred_index is None else int(pred_index),
            L.ptr(pred), L.ptr(buf), L.stream_ptr())
     return hist, pred
+
+
+# ---- self-training: top-p% pseudo labels on the hidden pixels ------------------------------------------------------------------
+_PSEUDO_EXTRAS = ("cand", "conf", "qhist", "thr", "counts")
+
+
+def pseudo_permille(keep):
+    """the share of the candidates to keep, a number in (0, 1], as the integer permille szn_pseudo_head takes (rounded; at least 1)"""
+    try:
+        k = float(keep)
+    except (TypeError, ValueError):
+        raise L.SznError("pseudo labels: keep must be a number in (0, 1], got %r" % (keep,))
+    if not 0.0 < k <= 1.0:
+        raise L.SznError("pseudo labels: keep must lie in (0, 1], got %r" % (keep,))
+    return max(1, int(round(k * 1000.0)))
+
+
+def pseudo_call(stride, fmap, emb, H, W, target, unseen_cs, gamma, permille, conf_floor, cand_label, target_out, ws_buf, stream,
+                cand=None, conf=None, qhist=None, thr=None, counts=None):
+    """szn_pseudo_head with every buffer supplied by the caller (engine.TrainStep: no allocation on the step path)"""
+    B, h, w, ld = fmap.shape
+    K, E = emb.shape
+    L.call("szn_pseudo_head", stride, B, h, w, E, ld, 0, H, W, _CROP[stride], K, L.ptr(fmap), L.ptr(emb), L.ptr(target), unseen_cs,
+           float(gamma), float(conf_floor), int(permille), int(cand_label), L.ptr(target_out), L.ptr(cand), L.ptr(conf), L.ptr(qhist),
+           L.ptr(thr), L.ptr(counts), L.ptr(ws_buf), stream)
+
+
+def pseudo_workspace_bytes(stride, fmap, emb, H, W):
+    B, h, w, _ = fmap.shape
+    K, E = emb.shape
+    nbytes = L.load().szn_pseudo_head_workspace_bytes(stride, B, h, w, E, K, H, W)
+    if nbytes == 0:
+        raise L.SznError("pseudo: bad geometry (stride %d, B %d, map %d x %d, E %d, K %d, image %d x %d)" % (stride, B, h, w, E, K, H, W))
+    return nbytes
+
+
+def pseudo(stride, fmap, emb, H, W, target, unseen, gamma=0.0, keep=0.3, conf_floor=-2.0, cand_label=HIDDEN_LABEL, want=()):
+    """szn_pseudo_head on the contiguous fp32 NHWC map `fmap` (the E embedding channels first): among the pixels whose target is
+    cand_label, those the calibrated rule at `gamma` gives to an unseen class with a similarity of at least conf_floor are candidates;
+    per unseen class the most confident `keep` of them (whole confidence bins of 1/512) take that class as their label.
+    -> target_out (B,H,W) int64, or (target_out, {name: tensor}) with want = names among cand, conf, qhist, thr, counts."""
+    import math
+    K, E = emb.shape
+    B = fmap.shape[0]
+    if fmap.dtype != torch.float32 or not fmap.is_contiguous() or fmap.dim() != 4:
+        raise L.SznError("pseudo: the map must be a contiguous fp32 (B,h,w,C) tensor")
+    permille = pseudo_permille(keep)
+    if not (math.isfinite(float(gamma)) and math.isfinite(float(conf_floor))):
+        raise L.SznError("pseudo: gamma and conf_floor must be finite (got %r, %r)" % (gamma, conf_floor))
+    if int(cand_label) >= 0:
+        raise L.SznError("pseudo: cand_label must be negative (got %r): a class label cannot mark the hidden pixels" % (cand_label,))
+    want = (want,) if isinstance(want, str) else tuple(want)
+    bad = [n for n in want if n not in _PSEUDO_EXTRAS]
+    if bad:
+        raise L.SznError("pseudo: want names %r; known: %s" % (bad, ", ".join(_PSEUDO_EXTRAS)))
+    if target is None:
+        raise L.SznError("pseudo: the target is required")
+    dev = fmap.device
+    tgt = target.to(device=dev, dtype=torch.int64).contiguous()
+    if tuple(tgt.shape) != (B, H, W):
+        raise L.SznError("pseudo: target shape %r, expected %r" % (tuple(tgt.shape), (B, H, W)))
+    out = torch.empty(B, H, W, dtype=torch.int64, device=dev)
+    shapes = dict(cand=((B, H, W), torch.int64), conf=((B, H, W), torch.float32), qhist=((K, L.PSEUDO_BINS), torch.int64),
+                  thr=((K,), torch.int32), counts=((K, 2), torch.int64))
+    extra = {n: torch.empty(shapes[n][0], dtype=shapes[n][1], device=dev) for n in want}
+    buf = _scratch(pseudo_workspace_bytes(stride, fmap, emb, H, W), dev)
+    pseudo_call(stride, fmap, emb, H, W, tgt, L.class_set(unseen), gamma, permille, conf_floor, cand_label, out, buf, L.stream_ptr(),
+                **extra)
+    return (out, extra) if want else out
 
 
 # ---- softmax cross-entropy head -------------------------------------------------------------------------------------------

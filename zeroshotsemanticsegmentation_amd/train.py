@@ -21,6 +21,11 @@ Added for this implementation (none change the reference flags):
   -loss sim_ce         similarity cross-entropy: softmax over the seen classes' cosine similarities to the pixel embedding, cross
                        entropy against the label (szn_fused_simce_head; the unseen classes do not compete); --sim-temperature T
                        (default 0.1, a hyper-parameter default, not a tuned value) divides the similarities
+  --pseudo-label KEEP  self-training on the unseen classes: the training set keeps the images 'train_seen' drops for their unseen classes,
+                       with those pixels hidden (--hide-unseen, implied), and every step labels the most confident KEEP (0 < KEEP <= 1) of
+                       the hidden pixels per unseen class with its own calibrated prediction (szn_pseudo_head) and trains on them;
+                       --pseudo-gamma G (default: --calibration, else 0), --pseudo-floor C (smallest similarity a label may have,
+                       default none), --pseudo-start-epoch N (default 0); counts per epoch and class in <log_dir>/pseudo_log.csv
   --init synthetic|vgg path handling: without the caffe VGG16 file the backbone starts from synth weights
   torchrun: RANK / LOCAL_RANK / WORLD_SIZE are honoured (one process per GPU, RCCL gradient all-reduce).
 """
@@ -99,6 +104,19 @@ def build_parser():
                    help="with -loss sim_ce (softmax over the seen classes' cosine similarities to the pixel embedding, cross entropy "
                         "against the label): the temperature the similarities are divided by.  Default %g: a hyper-parameter default, "
                         "not a tuned value.  An error without -loss sim_ce" % SIM_TEMPERATURE)
+    p.add_argument('--pseudo-label', type=float, default=None, metavar='KEEP',
+                   help="self-training: every training step labels the most confident KEEP (0 < KEEP <= 1) of the hidden pixels per "
+                        "unseen class with its own calibrated prediction and trains on them; implies --hide-unseen; needs unseen "
+                        "classes and an embedding configuration.  Default: off")
+    p.add_argument('--pseudo-gamma', type=float, default=None, metavar='G',
+                   help="with --pseudo-label: the seen-class penalty of the labelling rule (default: --calibration, else 0)")
+    p.add_argument('--pseudo-floor', type=float, default=None, metavar='C',
+                   help="with --pseudo-label: the smallest cosine similarity a pseudo label may have (default: none)")
+    p.add_argument('--pseudo-start-epoch', type=int, default=None, metavar='N',
+                   help="with --pseudo-label: the first epoch that self-trains (default 0)")
+    p.add_argument('--hide-unseen', action='store_true',
+                   help="the FCN phase trains on every image 'train_seen' would drop for an unseen class as well, with the pixels of "
+                        "the unseen classes hidden from every loss and metric (label -3)")
     return p
 
 
@@ -271,6 +289,30 @@ def check_calibration(calibration, sweep, cfg, eval_scales=None, eval_flip=False
         raise Exception("--calibration / --calib-sweep: " + why)
 
 
+def check_pseudo(keep, gamma, floor, start_epoch, hide_unseen, cfg):
+    """--pseudo-label / --pseudo-gamma / --pseudo-floor / --pseudo-start-epoch / --hide-unseen: KEEP in (0, 1], finite G and C, N >= 0;
+    the satellites only with --pseudo-label; unseen classes and an embedding configuration (trainer_fcn.pseudo_refused)"""
+    import math
+    has_unseen = bool(cfg['train_unseen'] or cfg['val_unseen'])
+    if keep is None:
+        if gamma is not None or floor is not None or start_epoch is not None:
+            raise Exception("--pseudo-gamma / --pseudo-floor / --pseudo-start-epoch need --pseudo-label")
+        if hide_unseen and not has_unseen:
+            raise Exception("--hide-unseen needs unseen classes (train_unseen / val_unseen)")
+        return
+    if not 0.0 < keep <= 1.0:
+        raise Exception("--pseudo-label: KEEP must lie in (0, 1] (got %r)" % (keep,))
+    for name, v in (("--pseudo-gamma", gamma), ("--pseudo-floor", floor)):
+        if v is not None and not math.isfinite(v):
+            raise Exception("%s must be finite (got %r)" % (name, v))
+    if start_epoch is not None and start_epoch < 0:
+        raise Exception("--pseudo-start-epoch: N must not be negative (got %r)" % (start_epoch,))
+    n_class = 21 if cfg['dataset'] == 'pascal' else 33
+    why = trainer_fcn.pseudo_refused(has_unseen, bool(cfg['embed_dim']) and cfg['fcn_loss'] in _EMBED_LOSSES, n_class)
+    if why:
+        raise Exception("--pseudo-label: " + why)
+
+
 def check_sim_temperature(temperature, cfg):
     """--sim-temperature: only with fcn_loss 'sim_ce', positive and finite"""
     if temperature is None:
@@ -289,6 +331,8 @@ def main(argv=None):
     check_precision(args.precision, cfg)
     check_eval_views(args.eval_scales, args.eval_flip, cfg)
     check_calibration(args.calibration, args.calib_sweep, cfg, args.eval_scales, args.eval_flip)
+    check_pseudo(args.pseudo_label, args.pseudo_gamma, args.pseudo_floor, args.pseudo_start_epoch, args.hide_unseen, cfg)
+    hide_unseen = args.hide_unseen or args.pseudo_label is not None
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", str(args.gpu)))
@@ -340,7 +384,8 @@ def main(argv=None):
         n_class = 21 if cfg['dataset'] == 'pascal' else 33
         mk = lambda split, unseen, n: SyntheticSegmentation(split=split, n_images=n, size=(H, W), n_class=n_class,
                                                              embed_dim=cfg['embed_dim'], unseen=unseen, seed=1337,
-                                                             native=augment is not None and split != 'val')
+                                                             native=augment is not None and split != 'val',
+                                                             hide_unseen=hide_unseen and split == 'train_seen')
         # splits as in the reference (pascal_dataset.py:62-74, context_dataset.py:75-94): 'train' drops every image that
         # contains a val_unseen class, 'train_seen' additionally drops the train_unseen classes, 'val' keeps everything
         train_dataset = mk('train', cfg['val_unseen'], n_img)
@@ -356,7 +401,7 @@ def main(argv=None):
         cls = PascalVOC if cfg['dataset'] == 'pascal' else PascalContext
         mkr = lambda split: cls(split=split, embed_dim=cfg['embed_dim'], one_hot_embed=cfg['one_hot_embed'],
                                 data_dir=args.data_dir, train_unseen=cfg['train_unseen'], val_unseen=cfg['val_unseen'],
-                                native=True)
+                                native=True, hide_unseen=hide_unseen and split == 'train_seen')
         train_dataset, train_seen_dataset, val_dataset = mkr('train'), mkr('train_seen'), mkr('val')
     kwargs = {'num_workers': args.workers, 'pin_memory': True}
 
@@ -407,7 +452,10 @@ def main(argv=None):
         dataset=cfg['dataset'], max_epoch=cfg['fcn_epochs'], pixel_embeddings=cfg['embed_dim'], loss_func=cfg['fcn_loss'],
         tb_writer=tb_writer, unseen=all_unseen, val_unseen=cfg['val_unseen'], label_names=label_names,
         forced_unseen=cfg['forced_unseen'], precision=precision, rank=rank, visualize=args.viz, augment=augment,
-        sim_temperature=args.sim_temperature, calibration=args.calibration, calib_sweep=calib_sweep_values(args.calib_sweep), eval_scales=args.eval_scales,
+        sim_temperature=args.sim_temperature,
+        pseudo=None if args.pseudo_label is None else dict(keep=args.pseudo_label, gamma=args.pseudo_gamma,
+                                                           conf_floor=-2.0 if args.pseudo_floor is None else args.pseudo_floor),
+        pseudo_start_epoch=args.pseudo_start_epoch or 0, calibration=args.calibration, calib_sweep=calib_sweep_values(args.calib_sweep), eval_scales=args.eval_scales,
         eval_flip=args.eval_flip)
     fcn_trainer.epoch, fcn_trainer.iteration = start_epoch, start_iteration
 

@@ -63,6 +63,18 @@ def calibration_refused(has_unseen, embed_cfg, forced_unseen, test_all, eval_vie
     return None
 
 
+def pseudo_refused(has_unseen, embed_cfg, n_class):
+    """why a configuration cannot self-train on pseudo labels (pseudo=, train.py --pseudo-label), or None: the labels are the unseen
+    classes' calibrated predictions of the fused embedding head"""
+    if not has_unseen:
+        return "pseudo labels need unseen classes (train_unseen / val_unseen): there is nothing hidden to label"
+    if not embed_cfg:
+        return "pseudo labels need an embedding configuration (loss 'cos' | 'mse' | 'sim_ce'): a softmax network has no unseen-class scores"
+    if n_class > 256:
+        return "pseudo labels: the fused head holds at most 256 classes, got %d" % n_class
+    return None
+
+
 class _NullWriter(object):
     def add_scalar(self, *a, **k): pass
     def add_text(self, *a, **k): pass
@@ -74,7 +86,8 @@ class Trainer(object):
     def __init__(self, cuda, model, optimizer, train_loader, val_loader, log_dir, dataset, max_epoch, tb_writer,
                  pixel_embeddings=None, loss_func=None, unseen=None, val_unseen=None, label_names=None,
                  forced_unseen=False, embed_arr=None, precision=torch.float32, fused_step=True, rank=0, visualize=0, augment=None,
-                 sim_temperature=None, calibration=None, calib_sweep=None, eval_scales=None, eval_flip=False):
+                 sim_temperature=None, pseudo=None, pseudo_start_epoch=0, calibration=None, calib_sweep=None, eval_scales=None,
+                 eval_flip=False):
         if not cuda:
             raise RuntimeError("this implementation runs on the GPU only (cuda=False has no CPU fallback)")
         self.cuda = cuda
@@ -149,6 +162,31 @@ class Trainer(object):
             if self.calibration is not None and not np.isfinite(self.calibration):
                 from ._lib import SznError
                 raise SznError("calibration: gamma must be finite (got %r)" % (calibration,))
+
+        # self-training (engine.TrainStep pseudo=): from epoch pseudo_start_epoch on every training step labels the most confident
+        # `keep` of the hidden pixels (datasets.HIDDEN_LABEL: a hide_unseen training set) per unseen class with the step's own
+        # calibrated prediction and trains on them.  pseudo = dict(keep=, gamma=, conf_floor=); the unseen classes are self.unseen,
+        # gamma defaults to `calibration`.  Per epoch one row per unseen class in pseudo_log.csv: candidates and selected pixels
+        self.pseudo = None
+        self.pseudo_start_epoch = int(pseudo_start_epoch)
+        if pseudo is not None:
+            from ._lib import SznError
+            why = pseudo_refused(bool(self.unseen), bool(pixel_embeddings) and loss_func in _EMBED_LOSSES, self.n_class)
+            if why:
+                raise SznError(why)
+            if not fused_step:
+                raise SznError("pseudo labels run inside the fused training step (fused_step=True)")
+            cfg = dict(pseudo)
+            if cfg.get("gamma") is None:
+                cfg["gamma"] = self.calibration if self.calibration is not None else 0.0
+            cfg["unseen"] = list(self.unseen)
+            _engine.TrainStep._check_pseudo(cfg, loss_func)
+            self.pseudo = cfg
+            if self.rank == 0:
+                os.makedirs(self.log_dir, exist_ok=True)
+                if not osp.exists(osp.join(self.log_dir, 'pseudo_log.csv')):
+                    with open(osp.join(self.log_dir, 'pseudo_log.csv'), 'w') as f:
+                        f.write('epoch,class,candidates,selected\n')
 
         if self.pixel_embeddings:
             arr = np.asarray(embed_arr, dtype=np.float32) if embed_arr is not None else \
@@ -274,6 +312,8 @@ class Trainer(object):
             kw.update(embeddings=self.embeddings, forced_unseen=self.unseen if self.forced_unseen else None, loss=self.loss_func)
             if self.loss_func == "sim_ce":
                 kw.update(sim_exclude=self.unseen, sim_temperature=self.sim_temperature)
+            if self.pseudo is not None:
+                kw.update(pseudo=self.pseudo)
         self._step = _engine.TrainStep(self.model, lr=gw['lr'], bias_lr=gb['lr'],
                                        bias_weight_decay=gb.get('weight_decay', 0.0), precision=self.precision,
                                        fused_head=True, keep_grads=os.environ.get("SZN_KEEP_GRADS", "0") == "1", **kw)
@@ -286,6 +326,12 @@ class Trainer(object):
     def train_epoch(self):
         self.model.train()
         step = self._fast_step()
+        if self.pseudo is not None:
+            if step is None:
+                from ._lib import SznError
+                raise SznError("pseudo labels run inside the fused training step, which this optimizer wiring does not allow")
+            step.set_pseudo_active(self.epoch >= self.pseudo_start_epoch)
+            step.pseudo_counts.zero_()
         if step is None and self.model._engine.dtype == torch.float16:
             # IEEE-half gradients need loss scaling, which only engine.TrainStep applies (d(coarse) is multiplied in fp32 before
             # it enters the 16-bit backward pass); the autograd paths (non-reference optimizer wiring, more than 256 classes)
@@ -347,6 +393,21 @@ class Trainer(object):
                 for name, v in zip(['loss', 'pxl_acc', 'class_acc', 'mean_iu', 'fwavacc'], [lossv] + list(metrics)):
                     self.tb_writer.add_scalar('fcn/train/' + name, v, self.iteration)
             self.iteration += 1
+        if self.pseudo is not None:
+            self._pseudo_report(step)
+
+    def _pseudo_report(self, step):
+        """once per epoch: the step's {candidates, selected} counts per class, summed over the ranks, as pseudo_log.csv rows (rank 0)"""
+        import torch.distributed as dist
+        counts = step.pseudo_counts.clone()
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            dist.all_reduce(counts)
+        counts = counts.cpu().numpy()
+        self.last_pseudo_counts = counts
+        if self.rank == 0:
+            with open(osp.join(self.log_dir, 'pseudo_log.csv'), 'a') as f:
+                for k in self.unseen:
+                    f.write('%d,%d,%d,%d\n' % (self.epoch, k, counts[k, 0], counts[k, 1]))
 
     def _predict_device(self, data, target, szn, with_image=False):
         """forward + loss + class assignment with everything left on the GPU -> (score, loss 0-dim, pred (n,h,w), target), and with
