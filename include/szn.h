@@ -826,6 +826,46 @@ int szn_pseudo_head(int stride, int B, int h, int w, int E, int ldc, int c0, int
                     int64_t* target_out, int64_t* cand, float* conf, int64_t* qhist, int32_t* thr, int64_t* counts,
                     void* workspace, szn_stream_t stream);
 
+/* ---- hard-pixel mining for the embedding losses: keep the hardest labelled pixels of every image ---------------------------------
+ * szn_ohem_head: per image, the keep_permille / 1000 of the labelled pixels whose own-class cosine is lowest -- and every pixel whose
+ * cosine lies below `thresh` -- keep their label; every other labelled pixel reads drop_label (a negative value the heads ignore) in
+ * target_out.  The head kernels are untouched: they train on target_out.  coarse, embed, stride (32 | 8), crop, ldc and c0 are
+ * szn_fused_head_strided's.  Three passes, everything per image (the heads normalise per image):
+ *   1. evaluate.  A pixel is evaluated when 0 <= target[pix] < K and its label is not in `skip` (NULL: the empty set; the exclude set of
+ *      szn_fused_simce_head, whose pixels that head ignores and which must not use up the budget).  Its value c is the cosine-loss term
+ *      of the fused head, the same operations in the same order: the fmaf chain over the four taps of G[t][label], divided by
+ *      (sn * ent[label]) with the raw norm; c is NaN for a zero-norm pixel or class row.  Its bin q = 0 when c is NaN, else
+ *      clamp((int)floorf(fmaf(c, 512.f, 512.f)), 0, 1023) (szn_pseudo_head's bin).  Every evaluated pixel adds 1 to Q[b][q], a
+ *      [B][SZN_OHEM_BINS] integer table in the workspace, zeroed on the stream by the call (the bins of a block are counted in LDS first,
+ *      one 64-bit integer atomic add per non-empty bin).  Pixels that are not evaluated skip the arithmetic.
+ *   2. cut, per image b, integers only: n_b = sum_q Q[b][q]; keep_b = (n_b * keep_permille + 999) / 1000; tmin_b = the smallest t in
+ *      [1, 1024] with sum_{q < t} Q[b][q] >= keep_b; tbin = clamp((int)floorf(thresh * 512 + 512), 0, 1024) (thresh rounded down to a bin
+ *      edge; multiples of 1/512 are exact; thresh <= -1 turns it off); cut_b = max(tmin_b, tbin), 0 when n_b == 0;
+ *      counts[b] = { n_b, sum_{q < cut_b} Q[b][q] }.  Whole bins are taken: the selection does not depend on any order inside a bin, at
+ *      least keep_b >= 1 pixels of every image that has any are kept (no image is left without a counted pixel), and bin 0 is always
+ *      kept (a NaN pixel reaches the head as it does without this call).
+ *   3. relabel, elementwise: target_out[pix] = drop_label for an evaluated pixel with q >= cut_b; target[pix] verbatim everywhere else
+ *      (kept pixels, negative labels, labels >= K, labels in `skip`).
+ * target_out (B,H,W) int64 is required and must not alias target.  Inspection copies, each NULL or device memory, all written (not
+ * accumulated): conf (B,H,W) fp32 (c where the pixel was evaluated, NaN elsewhere), qhist [B][SZN_OHEM_BINS] int64, cut [B] int32,
+ * counts [B][2] int64.  keep_permille, thresh and drop_label are kernel arguments: no host synchronisation, no allocation, capturable in
+ * a hipGraph.  Integer atomics only: two calls give bit-equal outputs.
+ * szn_last_kernel(): ohem_relabel_kernel; szn_prev_kernel(): ohem_cut_kernel (before them ohem_cell_kernel at stride 32,
+ * ohem_cell_tab_kernel at stride 8).
+ * workspace: szn_ohem_head_workspace_bytes (0 for shapes szn_ohem_head refuses), 16-byte aligned: a szn_fused_head_prepare image written
+ * by the call, the stride-8 position tables, Q, cut and the per-pixel record of pass 1 (4 bytes per pixel).
+ * SZN_ERR_ARG, before any launch: everything szn_pseudo_head refuses about the arguments the two share (stride, sizes, K, ldc / c0, the
+ * crop window, the workspace alignment, NULL coarse / embed / workspace; an E too large for LDS is SZN_ERR_UNSUPPORTED as there);
+ * keep_permille outside [1, 1000]; thresh not finite; drop_label >= 0; a class in `skip` >= K; a `skip` that holds every class; NULL
+ * target or target_out; target_out == target. */
+#define SZN_OHEM_BINS 1024
+size_t szn_ohem_head_workspace_bytes(int stride, int B, int h, int w, int E, int K, int H, int W);
+int szn_ohem_head(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                  const float* coarse, const float* embed, const int64_t* target, const szn_class_set* skip,
+                  int keep_permille, float thresh, int64_t drop_label,
+                  int64_t* target_out, float* conf, int64_t* qhist, int32_t* cut, int64_t* counts,
+                  void* workspace, szn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

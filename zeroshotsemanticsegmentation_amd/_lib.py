@@ -78,6 +78,7 @@ def class_set(classes):
 MS_MAX_VIEWS = 16           # SZN_MS_MAX_VIEWS
 CALIB_MAX_GAMMAS = 64       # SZN_CALIB_MAX_GAMMAS
 PSEUDO_BINS = 1024          # SZN_PSEUDO_BINS
+OHEM_BINS = 1024            # SZN_OHEM_BINS
 
 
 class MsView(C.Structure):
@@ -201,6 +202,8 @@ SIGNATURES = {
     "szn_calib_head": (_I, [_I] * 11 + [_P, _P, _P, _CS, _I, _FP, _P, _I, _P, _P, _P]),
     "szn_pseudo_head_workspace_bytes": (_SZ, [_I] * 8),
     "szn_pseudo_head": (_I, [_I] * 11 + [_P, _P, _P, _CS, _F, _F, _I, _I64] + [_P] * 8),
+    "szn_ohem_head_workspace_bytes": (_SZ, [_I] * 8),
+    "szn_ohem_head": (_I, [_I] * 11 + [_P, _P, _P, _CS, _I, _F, _I64] + [_P] * 7),
     "szn_viz_segmentation": (_I, [_I, _I, _I, _P, _I, C.POINTER(C.c_double), _P, _P, _I, _CS, _U64, _P, _L, _L, _P]),
     "szn_viz_seenmask": (_I, [_I, _I, _I, _P, _I, C.POINTER(C.c_double), _P, _P, _U64, _P, _L, _L, _P]),
 }

@@ -24,6 +24,9 @@
 //                        fh_build_GQ, fh_lookup_GQ), two running bests per pixel (fh_two_best), crossing tables, prefix sums -> hist
 //   pseudo_cell_kernel / pseudo_cell_tab_kernel / pseudo_thr_kernel / pseudo_relabel_kernel   szn_pseudo_head (self-training): the same G, Q
 //                        and fh_two_best on the pixels labelled cand_label, a per-class confidence histogram, thresholds, the relabelled target
+//   ohem_cell_kernel / ohem_cell_tab_kernel / ohem_cut_kernel / ohem_relabel_kernel   szn_ohem_head (hard-pixel mining), in launch order: the
+//                        same G and Q, fh_pixel's own-class cosine of every labelled pixel, a per-image histogram counted in LDS, the cut
+//                        (a prefix scan), the target with the easy pixels dropped
 //   sce_cell_kernel / sce_cell_tab_kernel   szn_fused_simce_head (similarity cross-entropy): the same G and Q, a softmax over the classes per
 //                        pixel (sce_pixel) and a dense A through a per-wave LDS tile (sce_dense_A); sums, finalize and gather as above
 // Both cell kernels run the same per-pixel body (fh_pixel) and the same label loop (fh_scatter_A), and write per cell: pred, the
@@ -1183,13 +1186,18 @@ inline PseudoWorkspace pseudo_workspace(int B, int h, int w, int E, int K, int H
     return L;
 }
 
-// what szn_calib_head and szn_pseudo_head refuse about the arguments they share (after calib_bad_geometry); SZN_OK = fine
-int calib_check_shared(const char* who, int stride, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
-                       const ClassBits& ubits, const void* workspace) {
+// what every head of this family refuses about channels, the crop window and the workspace alignment (szn_ohem_head shares this much)
+int calib_check_window(const char* who, int stride, int h, int w, int E, int ldc, int c0, int H, int W, int crop, const void* workspace) {
     if (c0 < 0 || ldc < c0 + E || H <= 0 || W <= 0 || crop < 0) SZN_FAIL(SZN_ERR_ARG, "%s: bad argument", who);
     if (H + crop > stride * h + stride || W + crop > stride * w + stride)
         SZN_FAIL(SZN_ERR_ARG, "%s: crop window exceeds the deconv output", who);
     if (((uintptr_t)workspace) & 15) SZN_FAIL(SZN_ERR_ARG, "%s: workspace must be 16-B aligned", who);
+    return SZN_OK;
+}
+// what szn_calib_head and szn_pseudo_head refuse about the arguments they share (after calib_bad_geometry); SZN_OK = fine
+int calib_check_shared(const char* who, int stride, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                       const ClassBits& ubits, const void* workspace) {
+    if (int rc = calib_check_window(who, stride, h, w, E, ldc, c0, H, W, crop, workspace)) return rc;
     if (!class_bits_any(ubits)) SZN_FAIL(SZN_ERR_ARG, "%s: the unseen set is empty", who);
     if (!class_bits_fit(ubits, K)) SZN_FAIL(SZN_ERR_ARG, "%s: the unseen set names a class >= K = %d", who, K);
     int n_unseen = 0;
@@ -1197,6 +1205,230 @@ int calib_check_shared(const char* who, int stride, int h, int w, int E, int ldc
     if (n_unseen >= K) SZN_FAIL(SZN_ERR_ARG, "%s: every class below K = %d is unseen (both groups must be non-empty)", who, K);
     if (fh_lds(E, kp_of(K), false).bytes() > 150 * 1024) SZN_FAIL(SZN_ERR_UNSUPPORTED, "%s: E=%d too large for LDS", who, E);
     return SZN_OK;
+}
+
+// ---- hard-pixel mining (szn_ohem_head): the own-class cosine of every labelled pixel, a per-image histogram, an on-device cut, a
+// relabel pass ----------------------------------------------------------------------------------------------------------------------
+// Pass 1 (ohem_cell_kernel / ohem_cell_tab_kernel: the pseudo cell kernels with another per-pixel body) evaluates the pixels whose label
+// is a class outside `skip` -- one class per pixel, fh_pixel's cosine term -- and leaves the cosine's bits per pixel in the workspace
+// (4 B; NaN: not evaluated, or a zero norm: both keep their label).  This pass sees every labelled pixel and a wave's cosines fall into
+// dozens of bins, so combining equal keys per wave would still issue about one global atomic per pixel: the bins are counted in LDS first
+// (stride 32: the block is one cell of one image, one table; stride 8: the block's four cells touch at most two images, one table each)
+// and every non-empty LDS bin becomes one 64-bit integer atomic add on QH[image][bin].  Pass 2 (ohem_cut_kernel): one block per image, a
+// prefix scan over the 1024 bins.  Pass 3 (ohem_relabel_kernel): elementwise over the records.  Integers throughout: bit-reproducible.
+static_assert(SZN_OHEM_BINS == SZN_PSEUDO_BINS, "pseudo_bin is the bin of both heads");
+struct OhemArgs {
+    ClassBits skip;              // labels the head ignores (sim_ce's exclude set): not evaluated, passed through
+    unsigned long long* QH;      // [B][SZN_OHEM_BINS], zeroed by the call
+    float* rec;                  // [B][H][W]: the pixel's own-class cosine, NaN where it was not evaluated
+};
+
+// Pixel (ty, tx) of cell (I, J) of image b: its record, and its bin, or -1 where it is not evaluated
+template <int KP, int S>
+__device__ __forceinline__ int ohem_pixel(const FhArgs& a, const OhemArgs& p, int b, int I, int J, int ty, int tx, bool live,
+                                          const float* G, const float* Q, const float* __restrict__ ent) {
+    const int y = S * I + ty - a.crop, x = S * J + tx - a.crop;
+    if (!(live && y >= 0 && y < a.H && x >= 0 && x < a.W)) return -1;
+    const size_t pix = ((size_t)b * a.H + y) * a.W + x;
+    const long lbl = a.target[pix];
+    int q = -1;
+    float c = __int_as_float(0x7fc00000);
+    if (lbl >= 0 && lbl < a.K && !in_set(p.skip, lbl)) {
+        float wt[4];
+        cell_weights<S>(ty, tx, wt);
+        const float sn = sqrtf(fh_ss(wt, Q));
+        const int kl = (int)lbl;
+        float d = 0.f;                                                     // fh_pixel's cosine term, operation for operation
+#pragma unroll
+        for (int t = 0; t < 4; ++t) d = fmaf(wt[t], G[t * KP + kl], d);
+        c = d / (sn * ent[kl]);
+        q = (c == c) ? pseudo_bin(c) : 0;
+    }
+    p.rec[pix] = c;
+    return q;
+}
+
+template <int KP>
+__global__ __launch_bounds__(256) void ohem_cell_kernel(FhArgs a, OhemArgs p) {      // stride 32: one block per (image, cell)
+    constexpr int S = 32;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const FhLds L = fh_lds(a.E, KP, false);
+    float* Ct = sm + L.Ct;
+    float* G = sm + L.G;
+    float* Q = sm + L.Q;
+    unsigned int* hist = (unsigned int*)(sm + L.Aw);                      // [SZN_OHEM_BINS], behind Ct | G | Q
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int cells_w = a.w + 1, cells = (a.h + 1) * cells_w;
+    const int b = blockIdx.x / cells, cell = blockIdx.x % cells;
+    const int I = cell / cells_w, J = cell % cells_w;
+    const float* embT = a.ws_f;
+    const float* ent = a.ws_f + (size_t)a.E * KP + KP;
+    for (int i = tid; i < SZN_OHEM_BINS; i += 256) hist[i] = 0u;
+    fh_load_taps(a, b, I, J, tid, Ct);
+    __syncthreads();
+    fh_build_GQ<KP>(a, embT, Ct, lane, wave, G, Q);
+    __syncthreads();
+    for (int q = tid; q < S * S; q += 256) {
+        const int bin = ohem_pixel<KP, S>(a, p, b, I, J, q / S, q % S, true, G, Q, ent);
+        if (bin >= 0) atomicAdd(hist + bin, 1u);
+    }
+    __syncthreads();
+    for (int i = tid; i < SZN_OHEM_BINS; i += 256) {
+        const unsigned int v = hist[i];
+        if (v) atomicAdd(p.QH + (size_t)b * SZN_OHEM_BINS + i, (unsigned long long)v);
+    }
+}
+
+template <int KP>
+__global__ __launch_bounds__(256) void ohem_cell_tab_kernel(FhArgs a, OhemArgs p, const float* __restrict__ D,
+                                                            const float* __restrict__ N) {      // stride 8: one wave per cell
+    constexpr int S = 8;
+    __shared__ float Gs[4][4 * KP];
+    __shared__ float Qs[4][16];
+    __shared__ unsigned int hist[2][SZN_OHEM_BINS];       // the image of the block's first cell, and the next one
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int cells_w = a.w + 1, cells = (a.h + 1) * cells_w;          // >= 4: four consecutive cells touch at most two images
+    const long ncell = (long)a.B * cells;
+    const long cid = (long)blockIdx.x * 4 + wave;
+    const bool ok = cid < ncell;
+    const long cc = ok ? cid : 0;
+    const int b = (int)(cc / cells), cell = (int)(cc % cells);
+    const int b0 = (int)(((long)blockIdx.x * 4) / cells);
+    const int I = cell / cells_w, J = cell % cells_w;
+    const float* ent = a.ws_f + (size_t)a.E * KP + KP;
+    long tp[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) tp[t] = tap_pos(b, a.h, a.w, I, J, t);
+    for (int i = threadIdx.x; i < 2 * SZN_OHEM_BINS; i += 256) (&hist[0][0])[i] = 0u;
+    fh_lookup_GQ<KP>(tp, D, N, lane, Gs[wave], Qs[wave]);
+    __syncthreads();
+    const int bin = ohem_pixel<KP, S>(a, p, b, I, J, lane / S, lane % S, ok && lane < S * S, Gs[wave], Qs[wave], ent);
+    if (bin >= 0) atomicAdd(&hist[b - b0][bin], 1u);                   // bin >= 0 only where ok: b is b0 or b0 + 1
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2 * SZN_OHEM_BINS; i += 256) {
+        const unsigned int v = (&hist[0][0])[i];
+        if (v) atomicAdd(p.QH + (size_t)b0 * SZN_OHEM_BINS + i, (unsigned long long)v);      // v > 0 in the second table: b0 + 1 < B
+    }
+}
+
+// Image b = blockIdx.x: n = sum_q QH[b][q], keep = ceil(n * keep_permille / 1000), tmin = the smallest t in [1, 1024] whose prefix sum
+// P(t) = sum_{q < t} QH[b][q] reaches keep, cut = max(tmin, tbin) (0 when n == 0), counts = {n, P(cut)}.  Thread t owns bins
+// 4 t .. 4 t + 3; an inclusive prefix scan of the 256 partial sums in LDS, then every thread tests its own four bins: P rises with t
+// from P(0) = 0 < keep to P(1024) = n >= keep, so exactly one t has P(t) >= keep and P(t - 1) < keep.
+__global__ __launch_bounds__(256) void ohem_cut_kernel(const unsigned long long* __restrict__ QH, int keep_permille, float thresh,
+                                                       int32_t* __restrict__ cut_ws, int64_t* __restrict__ qhist,
+                                                       int32_t* __restrict__ cut, int64_t* __restrict__ counts) {
+    static_assert(SZN_OHEM_BINS == 4 * 256, "four bins per thread");
+    __shared__ unsigned long long pre[257];
+    __shared__ int s_tmin;
+    const int b = blockIdx.x, t = threadIdx.x;
+    const unsigned long long* row = QH + (size_t)b * SZN_OHEM_BINS;
+    unsigned long long v[4], s = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        v[i] = row[4 * t + i];
+        s += v[i];
+        if (qhist) qhist[(size_t)b * SZN_OHEM_BINS + 4 * t + i] = (int64_t)v[i];
+    }
+    pre[t + 1] = s;
+    if (t == 0) pre[0] = 0;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {
+        const unsigned long long add = (t + 1 > d) ? pre[t + 1 - d] : 0;
+        __syncthreads();
+        pre[t + 1] += add;
+        __syncthreads();
+    }
+    const unsigned long long n = pre[256];
+    if (n == 0) {
+        if (t == 0) {
+            cut_ws[b] = 0;
+            if (cut) cut[b] = 0;
+            if (counts) { counts[2 * b] = 0; counts[2 * b + 1] = 0; }
+        }
+        return;
+    }
+    const unsigned long long keep = (n * (unsigned long long)keep_permille + 999) / 1000;
+    unsigned long long below = pre[t];                  // P(4 t)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const unsigned long long prev = below;
+        below += v[i];                                   // P(4 t + i + 1)
+        if (below >= keep && prev < keep) s_tmin = 4 * t + i + 1;
+    }
+    __syncthreads();
+    // thresh rounded down to a bin edge; thresh * 512 is exact, so the fma is the two-step form's bits
+    const int tbin = (int)fminf(fmaxf(floorf(fmaf(thresh, 512.f, 512.f)), 0.f), (float)SZN_OHEM_BINS);
+    const int c = max(s_tmin, tbin);                     // in [1, 1024]
+    if (t == (c - 1) >> 2) {
+        unsigned long long kept = pre[t];
+        for (int i = 0; i <= ((c - 1) & 3); ++i) kept += v[i];
+        cut_ws[b] = c;
+        if (cut) cut[b] = c;
+        if (counts) { counts[2 * b] = (int64_t)n; counts[2 * b + 1] = (int64_t)kept; }
+    }
+}
+
+// target_out = drop_label where the pixel was evaluated and its bin reaches its image's cut, else the target verbatim; conf = the record.
+// Four pixels per thread; VEC (every pointer 16-byte aligned, H * W >= 4): 16-byte accesses on all whole groups of four.
+__device__ __forceinline__ int64_t ohem_relabel_one(int64_t lbl, float c, int cut, int64_t drop_label) {
+    return (c == c && pseudo_bin(c) >= cut) ? drop_label : lbl;
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void ohem_relabel_kernel(const int64_t* __restrict__ target, const float* __restrict__ rec,
+                                                           const int32_t* __restrict__ cut_ws, long n, long hw, int64_t drop_label,
+                                                           int64_t* __restrict__ target_out, float* __restrict__ conf) {
+    const long i0 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i0 >= n) return;
+    if (VEC && i0 + 4 <= n) {
+        const float4 c = *(const float4*)(rec + i0);
+        const longlong2 l0 = *(const longlong2*)(target + i0), l1 = *(const longlong2*)(target + i0 + 2);
+        const long ba = i0 / hw, next = (ba + 1) * hw;       // hw >= 4 (host): the four pixels belong to image ba or ba + 1
+        const int ca = cut_ws[ba], cb = (i0 + 3 >= next) ? cut_ws[ba + 1] : ca;
+        longlong2 o0, o1;
+        o0.x = ohem_relabel_one(l0.x, c.x, ca, drop_label);
+        o0.y = ohem_relabel_one(l0.y, c.y, i0 + 1 >= next ? cb : ca, drop_label);
+        o1.x = ohem_relabel_one(l1.x, c.z, i0 + 2 >= next ? cb : ca, drop_label);
+        o1.y = ohem_relabel_one(l1.y, c.w, cb, drop_label);
+        *(longlong2*)(target_out + i0) = o0;
+        *(longlong2*)(target_out + i0 + 2) = o1;
+        if (conf) *(float4*)(conf + i0) = c;
+        return;
+    }
+    for (long i = i0; i < n && i < i0 + 4; ++i) {
+        const float c = rec[i];
+        target_out[i] = ohem_relabel_one(target[i], c, cut_ws[i / hw], drop_label);
+        if (conf) conf[i] = c;
+    }
+}
+
+template <int KP>
+void ohem_launch(int stride, const FhArgs& a, const OhemArgs& p, float* tabD, float* tabN, hipStream_t st) {
+    const int cells = (a.h + 1) * (a.w + 1);
+    if (stride == 8) {
+        hipLaunchKernelGGL(fh_tables_kernel<KP>, dim3((unsigned)(((long)a.B * a.h * a.w + 3) / 4)), dim3(256),
+                           (size_t)4 * a.E * sizeof(float), st, a, tabD, tabN);
+        hipLaunchKernelGGL(ohem_cell_tab_kernel<KP>, dim3((unsigned)(((long)a.B * cells + 3) / 4)), dim3(256), 0, st, a, p,
+                           (const float*)tabD, (const float*)tabN);
+    } else {
+        const size_t lds = (size_t)(fh_lds(a.E, KP, false).Aw + SZN_OHEM_BINS) * sizeof(float);       // Ct | G | Q | hist
+        auto kern = ohem_cell_kernel<KP>;
+        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(kern, dim3(a.B * cells), dim3(256), lds, st, a, p);
+    }
+}
+
+// workspace of szn_ohem_head: the fused head's (embedding tables at its head, the stride-8 position tables) | QH | cut | rec
+struct OhemWorkspace { size_t QH, cut, rec, bytes; };       // byte offsets
+inline OhemWorkspace ohem_workspace(int B, int h, int w, int E, int K, int H, int W) {
+    OhemWorkspace L;
+    L.QH = align256(fh_workspace(B, h, w, E, kp_of(K)).bytes);
+    L.cut = L.QH + (size_t)B * SZN_OHEM_BINS * sizeof(unsigned long long);
+    L.rec = align256(L.cut + (size_t)B * sizeof(int32_t));
+    L.bytes = L.rec + (size_t)B * H * W * sizeof(float);
+    return L;
 }
 
 // the cell pass: stride 32 a block per cell; stride 8 the position tables, then a wave per cell
@@ -1562,5 +1794,73 @@ extern "C" int szn_pseudo_head(int stride, int B, int h, int w, int E, int ldc, 
     hipLaunchKernelGGL(pseudo_relabel_kernel, dim3((unsigned)szn_div_up(n, 256)), dim3(256), 0, st, target, (const int2*)p.rec,
                        (const int32_t*)thr_ws, n, target_out, cand, conf);
     SZN_CHECK_LAUNCH("pseudo_relabel_kernel");
+    return SZN_OK;
+}
+
+// Hard-pixel mining (include/szn.h): per image the keep_permille labelled pixels with the lowest own-class cosine, and every one below
+// `thresh`, keep their label; the others read drop_label.
+extern "C" size_t szn_ohem_head_workspace_bytes(int stride, int B, int h, int w, int E, int K, int H, int W) {
+    if (calib_bad_geometry(stride, B, h, w, E, K, 1) || H <= 0 || W <= 0) return 0;
+    return ohem_workspace(B, h, w, E, K, H, W).bytes;
+}
+
+extern "C" int szn_ohem_head(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                             const float* coarse, const float* embed, const int64_t* target, const szn_class_set* skip,
+                             int keep_permille, float thresh, int64_t drop_label, int64_t* target_out, float* conf, int64_t* qhist,
+                             int32_t* cut, int64_t* counts, void* workspace, szn_stream_t stream) {
+    if (const char* why = calib_bad_geometry(stride, B, h, w, E, K, 1)) SZN_FAIL(SZN_ERR_ARG, "ohem_head: %s", why);
+    if (!coarse || !embed || !workspace || !target || !target_out)
+        SZN_FAIL(SZN_ERR_ARG, "ohem_head: coarse, embed, workspace, target and target_out are required");
+    if (int rc = calib_check_window("ohem_head", stride, h, w, E, ldc, c0, H, W, crop, workspace)) return rc;
+    if (keep_permille < 1 || keep_permille > 1000) SZN_FAIL(SZN_ERR_ARG, "ohem_head: keep_permille %d outside [1, 1000]", keep_permille);
+    if (!isfinite(thresh)) SZN_FAIL(SZN_ERR_ARG, "ohem_head: thresh must be finite (a value <= -1 turns it off)");
+    if (drop_label >= 0) SZN_FAIL(SZN_ERR_ARG, "ohem_head: drop_label %lld must be negative (a label every head ignores)", (long long)drop_label);
+    const ClassBits sbits = class_bits(skip);
+    if (!class_bits_fit(sbits, K)) SZN_FAIL(SZN_ERR_ARG, "ohem_head: the skip set names a class >= K = %d", K);
+    int n_skip = 0;
+    for (int i = 0; i < 4; ++i) n_skip += __builtin_popcountll(sbits.w[i]);
+    if (n_skip >= K) SZN_FAIL(SZN_ERR_ARG, "ohem_head: the skip set holds every class below K = %d", K);
+    if (target_out == target) SZN_FAIL(SZN_ERR_ARG, "ohem_head: target_out must not alias target");
+    const int KP = kp_of(K);
+    if (fh_lds(E, KP, false).bytes() > 150 * 1024) SZN_FAIL(SZN_ERR_UNSUPPORTED, "ohem_head: E=%d too large for LDS", E);
+
+    hipStream_t st = (hipStream_t)stream;
+    const FhWorkspace wl = fh_workspace(B, h, w, E, KP);
+    const OhemWorkspace ol = ohem_workspace(B, h, w, E, K, H, W);
+    char* ws = (char*)workspace;
+    hipLaunchKernelGGL(fh_prep_kernel, dim3(szn_div_up((long)E * KP, 256)), dim3(256), 0, st, embed, (float*)ws, E, K, KP);
+    SZN_CHECK_LAUNCH("fh_prep_kernel");
+    FhArgs a{};
+    a.coarse = coarse; a.embed = embed; a.target = target; a.ws_f = (float*)ws;
+    a.B = B; a.h = h; a.w = w; a.E = E; a.ldc = ldc; a.c0 = c0; a.H = H; a.W = W; a.crop = crop; a.K = K; a.KP = KP;
+    OhemArgs p{};
+    p.skip = sbits;
+    p.QH = (unsigned long long*)(ws + ol.QH); p.rec = (float*)(ws + ol.rec);
+    int32_t* cut_ws = (int32_t*)(ws + ol.cut);
+    if (hipMemsetAsync(ws + ol.QH, 0, ol.cut - ol.QH, st) != hipSuccess) SZN_FAIL(SZN_ERR_LAUNCH, "ohem_head: clearing the histogram failed");
+    float* tabD = (float*)(ws + wl.tabD);
+    float* tabN = (float*)(ws + wl.tabN);
+    switch (KP) {
+        case 24: ohem_launch<24>(stride, a, p, tabD, tabN, st); break;
+        case 40: ohem_launch<40>(stride, a, p, tabD, tabN, st); break;
+        case 64: ohem_launch<64>(stride, a, p, tabD, tabN, st); break;
+        case 128: ohem_launch<128>(stride, a, p, tabD, tabN, st); break;
+        case 192: ohem_launch<192>(stride, a, p, tabD, tabN, st); break;
+        default: ohem_launch<256>(stride, a, p, tabD, tabN, st); break;
+    }
+    SZN_CHECK_LAUNCH(stride == 8 ? "ohem_cell_tab_kernel" : "ohem_cell_kernel");
+    hipLaunchKernelGGL(ohem_cut_kernel, dim3(B), dim3(256), 0, st, (const unsigned long long*)p.QH, keep_permille, thresh, cut_ws, qhist,
+                       cut, counts);
+    SZN_CHECK_LAUNCH("ohem_cut_kernel");
+    const long n = (long)B * H * W, hw = (long)H * W;
+    const bool vec = hw >= 4 && !((((uintptr_t)target) | ((uintptr_t)target_out) | ((uintptr_t)conf)) & 15);     // rec is 256-B aligned
+    const dim3 grid((unsigned)szn_div_up(n, 1024));
+    if (vec)
+        hipLaunchKernelGGL(ohem_relabel_kernel<true>, grid, dim3(256), 0, st, target, (const float*)p.rec, (const int32_t*)cut_ws, n, hw,
+                           drop_label, target_out, conf);
+    else
+        hipLaunchKernelGGL(ohem_relabel_kernel<false>, grid, dim3(256), 0, st, target, (const float*)p.rec, (const int32_t*)cut_ws, n, hw,
+                           drop_label, target_out, conf);
+    SZN_CHECK_LAUNCH("ohem_relabel_kernel");
     return SZN_OK;
 }

@@ -375,7 +375,7 @@ class TrainStep(object):
                  adam_weight_decay=0.0, grad_comm_dtype=None, loss_scale=None, dynamic_loss_scale=None,
                  scale_growth=2.0, scale_backoff=0.5, scale_growth_interval=2000, force_comm=None, reserved_cus=None,
                  fused_adam=None, keep_grads=True, exchange=None, direct_wire=None, sharded=None, forced_unseen=None,
-                 class_weight=None, size_average=False, sim_exclude=None, sim_temperature=None, pseudo=None):
+                 class_weight=None, size_average=False, sim_exclude=None, sim_temperature=None, pseudo=None, ohem=None):
         """Data-parallel knobs (the reference is single-GPU): grad_comm_dtype (SZN_GRAD_COMM = fp32 | bf16) = the
         wire format of the gradient buckets; exchange=False (SZN_GRAD_COMM=off) = no exchange at all (bench.py's comm-off timing);
         direct_wire (default: on for a 16-bit wire with keep_grads=False; SZN_WIRE_DIRECT=0 turns it off) = the weight-gradient
@@ -401,7 +401,18 @@ class TrainStep(object):
         step empties sim_exclude (the unseen classes now have positives), the inactive one restores it.  pseudo_counts, a device (K,2) int64
         tensor, accumulates {candidates, selected} per class until the caller zeroes it; with keep_ctx the relabelled target of the last
         step stays in last_pseudo_target.  Under data parallelism the thresholds are those of each rank's own batch: nothing is
-        exchanged, a rank's labels depend on its own pixels only."""
+        exchanged, a rank's labels depend on its own pixels only.
+        ohem=dict(keep=, thresh=None) (embedding losses only): hard-pixel mining.  After the forward pass (and after the pseudo-label pass,
+        on its result: pseudo-labelled pixels are mined like real labels) szn_ohem_head runs on the step's own head map and stream: per
+        image the `keep` (a share in (0, 1]) of the labelled pixels whose cosine to their own class embedding is lowest, and every pixel
+        whose cosine lies below `thresh` (None: no threshold; bins of 1/512), keep their label, the others read heads.OHEM_DROP_LABEL,
+        and the head -- fused or the fused_head=False referee -- trains on that target.  Hardness is the own-class cosine for all three
+        losses; with loss "sim_ce" the labels in the exclude set the step is using at that moment are neither counted nor dropped.  The
+        caller's target tensor is never written and the train-metric histogram keeps it (with forced_unseen the dropped pixels of the
+        train prediction compete in the seen group, like every ignored pixel).  set_ohem_active(False) makes the step the plain step
+        again, launch for launch.  ohem_counts, a device (2,) int64 tensor, accumulates {evaluated, kept} over images and steps until the
+        caller zeroes it; with keep_ctx the mined target of the last step stays in last_ohem_target.  Under data parallelism the cuts
+        belong to each rank's own images: nothing is exchanged."""
         if loss not in ("cos", "mse", "sim_ce", "cross_entropy"):
             raise L.SznError("TrainStep: loss must be 'cos', 'mse', 'sim_ce' or 'cross_entropy', got %r" % (loss,))
         if loss != "sim_ce" and (sim_exclude is not None or sim_temperature is not None):
@@ -411,6 +422,8 @@ class TrainStep(object):
                              "(utils.sim_ce_loss)")
         if pseudo is not None:
             pseudo = self._check_pseudo(pseudo, loss)
+        if ohem is not None:
+            ohem = self._check_ohem(ohem, loss)
         self.ce = loss == "cross_entropy"
         if self.ce and (embeddings is not None or forced_unseen is not None):
             raise L.SznError("TrainStep: the cross-entropy head takes no embeddings and no forced_unseen classes")
@@ -479,6 +492,11 @@ class TrainStep(object):
         self.last_pseudo_target = None                                # (keep_ctx) the relabelled target the last step's head read
         if pseudo is not None:
             self._init_pseudo(pseudo)
+        self._ohem = None                                             # szn_ohem_head's arguments, see set_ohem_active
+        self._ohem_active = False
+        self.last_ohem_target = None                                  # (keep_ctx) the mined target the last step's head read
+        if ohem is not None:
+            self._init_ohem(ohem)
         # static loss scaling for the fp16 path: gradients below 6e-8 vanish in IEEE half, so d(loss)/d(coarse) is multiplied
         # by loss_scale in fp32 before it enters the 16-bit backward pass and the optimizer kernel divides it out again
         # (grad_scale).  The .grad views then hold loss_scale x gradient.  bf16 / fp32 need none.
@@ -600,6 +618,10 @@ class TrainStep(object):
         if self.loss_kind == "sim_ce":
             self._sim_kw["exclude"] = [] if self._pseudo_active else self._sim_exclude
 
+    def _head_target(self, stride, fmap, target, H, W, st):
+        """the caller's target through the pseudo-label pass, then the mining pass (each the identity while it is inactive)"""
+        return self._ohem_target(stride, fmap, self._pseudo_target(stride, fmap, target, H, W, st), H, W, st)
+
     def _pseudo_target(self, stride, fmap, target, H, W, st):
         """the target the head trains on: the caller's, or -- pseudo labels active -- szn_pseudo_head's relabelled copy of it"""
         if not self._pseudo_active:
@@ -613,6 +635,68 @@ class TrainStep(object):
                           out, self._pseudo_ws, st, counts=self._pseudo_step_counts)
         self.pseudo_counts += self._pseudo_step_counts
         self.last_pseudo_target = out if self.keep_ctx else None
+        return out
+
+    # ---- hard-pixel mining --------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _check_ohem(cfg, loss):
+        """ohem= checked as far as the host alone can (before anything touches a device) -> (permille, thresh; -2.0: no threshold)"""
+        import math
+        if loss == "cross_entropy":
+            raise L.SznError("TrainStep: ohem needs an embedding loss ('cos' | 'mse' | 'sim_ce'): hardness is the cosine to the "
+                             "pixel's own class embedding, which the cross-entropy head does not have")
+        if not isinstance(cfg, dict):
+            raise L.SznError("TrainStep: ohem must be a dict(keep=, thresh=None), got %r" % (cfg,))
+        cfg = dict(cfg)
+        if "keep" not in cfg:
+            raise L.SznError("TrainStep: ohem needs keep, the share of every image's labelled pixels to train on, in (0, 1]")
+        keep, thresh = cfg.pop("keep"), cfg.pop("thresh", None)
+        if cfg:
+            raise L.SznError("TrainStep: ohem takes keep and thresh, not %s" % sorted(cfg))
+        try:
+            thresh = -2.0 if thresh is None else float(thresh)
+        except (TypeError, ValueError):
+            raise L.SznError("TrainStep: ohem thresh must be a finite number or None (got %r)" % (thresh,))
+        if not math.isfinite(thresh):
+            raise L.SznError("TrainStep: ohem thresh must be finite or None (got %r)" % (thresh,))
+        return heads.ohem_permille(keep), thresh
+
+    def _init_ohem(self, checked):
+        permille, thresh = checked
+        self._ohem = dict(permille=permille, thresh=thresh)
+        self.ohem_counts = torch.zeros(2, dtype=torch.int64, device=self.dev)
+        self._ohem_step_counts = None                                 # (B,2), sized by the first batch
+        self._ohem_ws = None
+        self._ohem_skip = (None, None)                                # (the exclude list, its class set)
+        self.set_ohem_active(True)
+
+    def set_ohem_active(self, active):
+        """turn the mining pass of a step built with ohem= on or off; off, the step is the plain step launch for launch"""
+        if self._ohem is None:
+            if active:
+                raise L.SznError("TrainStep: set_ohem_active(True) on a step built without ohem=")
+            return
+        self._ohem_active = bool(active)
+
+    def _ohem_target(self, stride, fmap, target, H, W, st):
+        """the target the head trains on: the one handed in, or -- mining active -- szn_ohem_head's copy of it with the easy pixels dropped"""
+        if not self._ohem_active:
+            return target
+        o = self._ohem
+        B = target.shape[0]
+        nbytes = heads.ohem_workspace_bytes(stride, fmap, self.emb, H, W)
+        if self._ohem_ws is None or self._ohem_ws.numel() < nbytes:
+            self._ohem_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+        if self._ohem_step_counts is None or self._ohem_step_counts.shape[0] != B:
+            self._ohem_step_counts = torch.zeros(B, 2, dtype=torch.int64, device=self.dev)
+        excl = self._sim_kw.get("exclude") if self.loss_kind == "sim_ce" else None      # the set the head uses in this very step
+        if excl is not self._ohem_skip[0]:
+            self._ohem_skip = (excl, L.class_set(excl))
+        out = torch.empty_like(target)
+        heads.ohem_call(stride, fmap, self.emb, H, W, target, self._ohem_skip[1], o["permille"], o["thresh"], heads.OHEM_DROP_LABEL, out,
+                        self._ohem_ws, st, counts=self._ohem_step_counts)
+        self.ohem_counts += self._ohem_step_counts.sum(0)
+        self.last_ohem_target = out if self.keep_ctx else None
         return out
 
     # the class-embedding matrix: assigning a new tensor (or calling invalidate_head_prep() after writing into it behind torch's back --
@@ -804,12 +888,12 @@ class TrainStep(object):
         if self.is8:
             fuse4, fuse3 = self._chain8(ctx)
             dmap = torch.zeros(B, fuse3.shape[1], fuse3.shape[2], m.head_width, device=self.dev, dtype=torch.float32)
-            self._head(8, fuse3, self._pseudo_target(8, fuse3, target, H, W, st), H, W, stats, pred, dmap, st)
+            self._head(8, fuse3, self._head_target(8, fuse3, target, H, W, st), H, W, stats, pred, dmap, st)
             if self._scaled:                            # d(fuse3) is scaled in fp32; the chain's backward converts
                 dmap = self._scale(dmap, torch.float32)
             dcoarse, skips = self._chain8_backward(ctx, fuse4, dmap)
         else:
-            head_target = self._pseudo_target(32, ctx.coarse, target, H, W, st)
+            head_target = self._head_target(32, ctx.coarse, target, H, W, st)
             if self.fused_head:
                 dcoarse = self._dcoarse_buffer(ctx)
                 self._head(32, ctx.coarse, head_target, H, W, stats, pred, dcoarse, st)

@@ -17,6 +17,8 @@ szn_fused_ce_head and szn_seenmask_head_k goes through here (models.FCN32s / FCN
             per gamma a confusion histogram, for one of them the prediction.
   pseudo    self-training pseudo labels (szn_pseudo_head): the calibrated prediction labels the most confident share of the hidden
             pixels per unseen class; the relabelled target is what a training head then reads.
+  ohem      hard-pixel mining (szn_ohem_head): per image the labelled pixels with the lowest own-class cosine keep their label, the
+            others read OHEM_DROP_LABEL; the relabelled target is what a training head then reads.
 
 The crop belongs to the stride (32: CROP, reference models.py:147; 8: CROP_UP8, FCN8s' upscore8).  A call without a `Workspace`
 allocates its scratch and builds the embedding tables itself (the predict methods); TrainStep keeps one `Workspace` across steps.
@@ -338,6 +340,82 @@ def pseudo(stride, fmap, emb, H, W, target, unseen, gamma=0.0, keep=0.3, conf_fl
     buf = _scratch(pseudo_workspace_bytes(stride, fmap, emb, H, W), dev)
     pseudo_call(stride, fmap, emb, H, W, tgt, L.class_set(unseen), gamma, permille, conf_floor, cand_label, out, buf, L.stream_ptr(),
                 **extra)
+    return (out, extra) if want else out
+
+
+# ---- hard-pixel mining: keep the hardest labelled pixels of every image -----------------------------------------------------------
+OHEM_DROP_LABEL = -1        # the label a mined-out pixel reads: every loss and metric kernel ignores it
+_OHEM_EXTRAS = ("conf", "qhist", "cut", "counts")
+
+
+def ohem_permille(keep):
+    """the share of an image's labelled pixels to keep, a number in (0, 1], as the integer permille szn_ohem_head takes (rounded; at
+    least 1)"""
+    try:
+        k = float(keep)
+    except (TypeError, ValueError):
+        raise L.SznError("ohem: keep must be a number in (0, 1], got %r" % (keep,))
+    if not 0.0 < k <= 1.0:
+        raise L.SznError("ohem: keep must lie in (0, 1], got %r" % (keep,))
+    return max(1, int(round(k * 1000.0)))
+
+
+def ohem_call(stride, fmap, emb, H, W, target, skip_cs, permille, thresh, drop_label, target_out, ws_buf, stream, conf=None, qhist=None,
+              cut=None, counts=None):
+    """szn_ohem_head with every buffer supplied by the caller (engine.TrainStep: no allocation on the step path); skip_cs: a
+    _lib.class_set or None"""
+    B, h, w, ld = fmap.shape
+    K, E = emb.shape
+    L.call("szn_ohem_head", stride, B, h, w, E, ld, 0, H, W, _CROP[stride], K, L.ptr(fmap), L.ptr(emb), L.ptr(target), skip_cs,
+           int(permille), float(thresh), int(drop_label), L.ptr(target_out), L.ptr(conf), L.ptr(qhist), L.ptr(cut), L.ptr(counts),
+           L.ptr(ws_buf), stream)
+
+
+def ohem_workspace_bytes(stride, fmap, emb, H, W):
+    B, h, w, _ = fmap.shape
+    K, E = emb.shape
+    nbytes = L.load().szn_ohem_head_workspace_bytes(stride, B, h, w, E, K, H, W)
+    if nbytes == 0:
+        raise L.SznError("ohem: bad geometry (stride %d, B %d, map %d x %d, E %d, K %d, image %d x %d)" % (stride, B, h, w, E, K, H, W))
+    return nbytes
+
+
+def ohem(stride, fmap, emb, H, W, target, keep, thresh=None, skip=None, drop_label=OHEM_DROP_LABEL, want=()):
+    """szn_ohem_head on the contiguous fp32 NHWC map `fmap` (the E embedding channels first): per image the `keep` of the labelled
+    pixels (label in [0, K), not in `skip`) whose cosine to their own class embedding is lowest, and every pixel whose cosine lies below
+    `thresh` (None: no threshold; rounded down to a multiple of 1/512), keep their label; the others read drop_label.
+    -> target_out (B,H,W) int64, or (target_out, {name: tensor}) with want = names among conf, qhist, cut, counts."""
+    import math
+    K, E = emb.shape
+    B = fmap.shape[0]
+    if fmap.dtype != torch.float32 or not fmap.is_contiguous() or fmap.dim() != 4:
+        raise L.SznError("ohem: the map must be a contiguous fp32 (B,h,w,C) tensor")
+    permille = ohem_permille(keep)
+    thresh = -2.0 if thresh is None else float(thresh)
+    if not math.isfinite(thresh):
+        raise L.SznError("ohem: thresh must be finite or None (got %r)" % (thresh,))
+    if int(drop_label) >= 0:
+        raise L.SznError("ohem: drop_label must be negative (got %r): a class label cannot mark the dropped pixels" % (drop_label,))
+    skip = sorted(set(int(k) for k in (skip or ())))
+    if skip and (skip[0] < 0 or skip[-1] >= K or len(skip) >= K):
+        raise L.SznError("ohem: skip must name some, not all, classes of [0, %d) (got %r)" % (K, skip))
+    want = (want,) if isinstance(want, str) else tuple(want)
+    bad = [n for n in want if n not in _OHEM_EXTRAS]
+    if bad:
+        raise L.SznError("ohem: want names %r; known: %s" % (bad, ", ".join(_OHEM_EXTRAS)))
+    if target is None:
+        raise L.SznError("ohem: the target is required")
+    dev = fmap.device
+    tgt = target.to(device=dev, dtype=torch.int64).contiguous()
+    if tuple(tgt.shape) != (B, H, W):
+        raise L.SznError("ohem: target shape %r, expected %r" % (tuple(tgt.shape), (B, H, W)))
+    out = torch.empty(B, H, W, dtype=torch.int64, device=dev)
+    shapes = dict(conf=((B, H, W), torch.float32), qhist=((B, L.OHEM_BINS), torch.int64), cut=((B,), torch.int32),
+                  counts=((B, 2), torch.int64))
+    extra = {n: torch.empty(shapes[n][0], dtype=shapes[n][1], device=dev) for n in want}
+    buf = _scratch(ohem_workspace_bytes(stride, fmap, emb, H, W), dev)
+    ohem_call(stride, fmap, emb, H, W, tgt, L.class_set(skip) if skip else None, permille, thresh, drop_label, out, buf, L.stream_ptr(),
+              **extra)
     return (out, extra) if want else out
 
 

@@ -26,6 +26,10 @@ Added for this implementation (none change the reference flags):
                        the hidden pixels per unseen class with its own calibrated prediction (szn_pseudo_head) and trains on them;
                        --pseudo-gamma G (default: --calibration, else 0), --pseudo-floor C (smallest similarity a label may have,
                        default none), --pseudo-start-epoch N (default 0); counts per epoch and class in <log_dir>/pseudo_log.csv
+  --ohem KEEP          hard-pixel mining for the embedding losses: every training step trains on the KEEP (0 < KEEP <= 1) of each image's
+                       labelled pixels whose cosine to their own class embedding is lowest (szn_ohem_head) and ignores the rest;
+                       --ohem-thresh C also keeps every pixel whose cosine lies below C (bins of 1/512), --ohem-start-epoch N
+                       (default 0); pixel counts per epoch in <log_dir>/ohem_log.csv.  Validation is never mined
   --init synthetic|vgg path handling: without the caffe VGG16 file the backbone starts from synth weights
   torchrun: RANK / LOCAL_RANK / WORLD_SIZE are honoured (one process per GPU, RCCL gradient all-reduce).
 """
@@ -114,6 +118,15 @@ def build_parser():
                    help="with --pseudo-label: the smallest cosine similarity a pseudo label may have (default: none)")
     p.add_argument('--pseudo-start-epoch', type=int, default=None, metavar='N',
                    help="with --pseudo-label: the first epoch that self-trains (default 0)")
+    p.add_argument('--ohem', type=float, default=None, metavar='KEEP',
+                   help="hard-pixel mining: every training step trains on the KEEP (0 < KEEP <= 1) of each image's labelled pixels whose "
+                        "cosine to their own class embedding is lowest and ignores the others; needs an embedding configuration.  KEEP "
+                        "has no default: it is a hyper-parameter nobody has tuned here.  Default: off")
+    p.add_argument('--ohem-thresh', type=float, default=None, metavar='C',
+                   help="with --ohem: also keep every pixel whose own-class cosine lies below C, rounded down to a multiple of 1/512 "
+                        "(default: none)")
+    p.add_argument('--ohem-start-epoch', type=int, default=None, metavar='N',
+                   help="with --ohem: the first epoch that mines (default 0)")
     p.add_argument('--hide-unseen', action='store_true',
                    help="the FCN phase trains on every image 'train_seen' would drop for an unseen class as well, with the pixels of "
                         "the unseen classes hidden from every loss and metric (label -3)")
@@ -313,6 +326,26 @@ def check_pseudo(keep, gamma, floor, start_epoch, hide_unseen, cfg):
         raise Exception("--pseudo-label: " + why)
 
 
+def check_ohem(keep, thresh, start_epoch, cfg):
+    """--ohem / --ohem-thresh / --ohem-start-epoch: KEEP in (0, 1], a finite C, N >= 0; the satellites only with --ohem; an embedding
+    configuration (trainer_fcn.ohem_refused)"""
+    import math
+    if keep is None:
+        if thresh is not None or start_epoch is not None:
+            raise Exception("--ohem-thresh / --ohem-start-epoch need --ohem")
+        return
+    if not 0.0 < keep <= 1.0:
+        raise Exception("--ohem: KEEP must lie in (0, 1] (got %r)" % (keep,))
+    if thresh is not None and not math.isfinite(thresh):
+        raise Exception("--ohem-thresh must be finite (got %r)" % (thresh,))
+    if start_epoch is not None and start_epoch < 0:
+        raise Exception("--ohem-start-epoch: N must not be negative (got %r)" % (start_epoch,))
+    n_class = 21 if cfg['dataset'] == 'pascal' else 33
+    why = trainer_fcn.ohem_refused(bool(cfg['embed_dim']) and cfg['fcn_loss'] in _EMBED_LOSSES, n_class)
+    if why:
+        raise Exception("--ohem: " + why)
+
+
 def check_sim_temperature(temperature, cfg):
     """--sim-temperature: only with fcn_loss 'sim_ce', positive and finite"""
     if temperature is None:
@@ -332,6 +365,7 @@ def main(argv=None):
     check_eval_views(args.eval_scales, args.eval_flip, cfg)
     check_calibration(args.calibration, args.calib_sweep, cfg, args.eval_scales, args.eval_flip)
     check_pseudo(args.pseudo_label, args.pseudo_gamma, args.pseudo_floor, args.pseudo_start_epoch, args.hide_unseen, cfg)
+    check_ohem(args.ohem, args.ohem_thresh, args.ohem_start_epoch, cfg)
     hide_unseen = args.hide_unseen or args.pseudo_label is not None
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -455,7 +489,9 @@ def main(argv=None):
         sim_temperature=args.sim_temperature,
         pseudo=None if args.pseudo_label is None else dict(keep=args.pseudo_label, gamma=args.pseudo_gamma,
                                                            conf_floor=-2.0 if args.pseudo_floor is None else args.pseudo_floor),
-        pseudo_start_epoch=args.pseudo_start_epoch or 0, calibration=args.calibration, calib_sweep=calib_sweep_values(args.calib_sweep), eval_scales=args.eval_scales,
+        pseudo_start_epoch=args.pseudo_start_epoch or 0,
+        ohem=None if args.ohem is None else dict(keep=args.ohem, thresh=args.ohem_thresh), ohem_start_epoch=args.ohem_start_epoch or 0,
+        calibration=args.calibration, calib_sweep=calib_sweep_values(args.calib_sweep), eval_scales=args.eval_scales,
         eval_flip=args.eval_flip)
     fcn_trainer.epoch, fcn_trainer.iteration = start_epoch, start_iteration
 

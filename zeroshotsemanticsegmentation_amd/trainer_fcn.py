@@ -75,6 +75,16 @@ def pseudo_refused(has_unseen, embed_cfg, n_class):
     return None
 
 
+def ohem_refused(embed_cfg, n_class):
+    """why a configuration cannot mine hard pixels (ohem=, train.py --ohem), or None: hardness is the cosine to the pixel's own class
+    embedding, a quantity of the fused embedding head"""
+    if not embed_cfg:
+        return "ohem needs an embedding configuration (loss 'cos' | 'mse' | 'sim_ce'): a softmax network has no class embeddings"
+    if n_class > 256:
+        return "ohem: the fused head holds at most 256 classes, got %d" % n_class
+    return None
+
+
 class _NullWriter(object):
     def add_scalar(self, *a, **k): pass
     def add_text(self, *a, **k): pass
@@ -86,8 +96,8 @@ class Trainer(object):
     def __init__(self, cuda, model, optimizer, train_loader, val_loader, log_dir, dataset, max_epoch, tb_writer,
                  pixel_embeddings=None, loss_func=None, unseen=None, val_unseen=None, label_names=None,
                  forced_unseen=False, embed_arr=None, precision=torch.float32, fused_step=True, rank=0, visualize=0, augment=None,
-                 sim_temperature=None, pseudo=None, pseudo_start_epoch=0, calibration=None, calib_sweep=None, eval_scales=None,
-                 eval_flip=False):
+                 sim_temperature=None, pseudo=None, pseudo_start_epoch=0, ohem=None, ohem_start_epoch=0, calibration=None,
+                 calib_sweep=None, eval_scales=None, eval_flip=False):
         if not cuda:
             raise RuntimeError("this implementation runs on the GPU only (cuda=False has no CPU fallback)")
         self.cuda = cuda
@@ -187,6 +197,26 @@ class Trainer(object):
                 if not osp.exists(osp.join(self.log_dir, 'pseudo_log.csv')):
                     with open(osp.join(self.log_dir, 'pseudo_log.csv'), 'w') as f:
                         f.write('epoch,class,candidates,selected\n')
+
+        # hard-pixel mining (engine.TrainStep ohem=): from epoch ohem_start_epoch on every training step trains on the hardest `keep` of
+        # each image's labelled pixels (lowest cosine to their own class embedding) and on every pixel below `thresh`.
+        # ohem = dict(keep=, thresh=None).  Validation is never mined.  Per epoch one row in ohem_log.csv: evaluated and kept pixels
+        self.ohem = None
+        self.ohem_start_epoch = int(ohem_start_epoch)
+        if ohem is not None:
+            from ._lib import SznError
+            why = ohem_refused(bool(pixel_embeddings) and loss_func in _EMBED_LOSSES, self.n_class)
+            if why:
+                raise SznError(why)
+            if not fused_step:
+                raise SznError("ohem runs inside the fused training step (fused_step=True)")
+            _engine.TrainStep._check_ohem(ohem, loss_func)
+            self.ohem = dict(ohem)
+            if self.rank == 0:
+                os.makedirs(self.log_dir, exist_ok=True)
+                if not osp.exists(osp.join(self.log_dir, 'ohem_log.csv')):
+                    with open(osp.join(self.log_dir, 'ohem_log.csv'), 'w') as f:
+                        f.write('epoch,evaluated,kept,fraction\n')
 
         if self.pixel_embeddings:
             arr = np.asarray(embed_arr, dtype=np.float32) if embed_arr is not None else \
@@ -314,6 +344,8 @@ class Trainer(object):
                 kw.update(sim_exclude=self.unseen, sim_temperature=self.sim_temperature)
             if self.pseudo is not None:
                 kw.update(pseudo=self.pseudo)
+            if self.ohem is not None:
+                kw.update(ohem=self.ohem)
         self._step = _engine.TrainStep(self.model, lr=gw['lr'], bias_lr=gb['lr'],
                                        bias_weight_decay=gb.get('weight_decay', 0.0), precision=self.precision,
                                        fused_head=True, keep_grads=os.environ.get("SZN_KEEP_GRADS", "0") == "1", **kw)
@@ -332,6 +364,12 @@ class Trainer(object):
                 raise SznError("pseudo labels run inside the fused training step, which this optimizer wiring does not allow")
             step.set_pseudo_active(self.epoch >= self.pseudo_start_epoch)
             step.pseudo_counts.zero_()
+        if self.ohem is not None:
+            if step is None:
+                from ._lib import SznError
+                raise SznError("ohem runs inside the fused training step, which this optimizer wiring does not allow")
+            step.set_ohem_active(self.epoch >= self.ohem_start_epoch)
+            step.ohem_counts.zero_()
         if step is None and self.model._engine.dtype == torch.float16:
             # IEEE-half gradients need loss scaling, which only engine.TrainStep applies (d(coarse) is multiplied in fp32 before
             # it enters the 16-bit backward pass); the autograd paths (non-reference optimizer wiring, more than 256 classes)
@@ -395,6 +433,20 @@ class Trainer(object):
             self.iteration += 1
         if self.pseudo is not None:
             self._pseudo_report(step)
+        if self.ohem is not None:
+            self._ohem_report(step)
+
+    def _ohem_report(self, step):
+        """once per epoch: the step's {evaluated, kept} pixel counts, summed over the ranks, as one ohem_log.csv row (rank 0)"""
+        import torch.distributed as dist
+        counts = step.ohem_counts.clone()
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            dist.all_reduce(counts)
+        n, kept = (int(v) for v in counts.cpu().numpy())
+        self.last_ohem_counts = (n, kept)
+        if self.rank == 0:
+            with open(osp.join(self.log_dir, 'ohem_log.csv'), 'a') as f:
+                f.write('%d,%d,%d,%.6f\n' % (self.epoch, n, kept, kept / n if n else 1.0))
 
     def _pseudo_report(self, step):
         """once per epoch: the step's {candidates, selected} counts per class, summed over the ranks, as pseudo_log.csv rows (rank 0)"""
