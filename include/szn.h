@@ -382,6 +382,15 @@ int szn_seenmask_head_k(int B, int h, int w, int ldc, int c0, int H, int W, int 
                         const float* weight, const int64_t* target, int n_class, const szn_class_set* seen, float* loss,
                         float* stats, int64_t* conf, int64_t* pred, float* dscore2, float* dweight, void* workspace,
                         szn_stream_t stream);
+/* szn_seenmask_margin: the pred-only call with the decision left open.  margin (B,H,W) f32 = s1 - s0 per pixel, where s0 and s1 are the
+ * two seen-mask scores from exactly the chain szn_seenmask_head_k runs (ci outer, then di, then dj, one fmaf per tap and channel, cells
+ * outside the map contribute exact zeros) and the difference is one fp32 subtraction with denormals kept: margin > 0 exactly where that
+ * head's pred is 1 (s1 > s0), a tie or a NaN gives "not seen" in both.  The caller thresholds it (szn_seen_sweep_head); 4 B per pixel,
+ * half of the int64 group map.  coarse, weight, ldc, c0, crop: szn_seenmask_head_k's.  No workspace.  szn_last_kernel():
+ * smh_margin_kernel.  SZN_ERR_ARG, before any launch: a size below 1, a negative crop, a NULL pointer, an output (+ crop) that does not
+ * fit the map at stride 32 (szn_seenmask_head_k's checks).                                                                          */
+int szn_seenmask_margin(int B, int h, int w, int ldc, int c0, int H, int W, int crop,
+                        const float* coarse, const float* weight, float* margin, szn_stream_t stream);
 /* seenmask_score = Conv2d(4096, 2, 1) (models.py:97,149) backward from the compact gradient above:
  * dw[c][k] = sum_m dscore2[m][c] * feat[m][k], db[c] = sum_m dscore2[m][c]; feat [M][ldf] of `dtype` (relu7 after
  * Dropout2d), F a multiple of 8.  Fixed-order slabs in `workspace` (szn_seenmask_score_wgrad_workspace_bytes).     */
@@ -790,6 +799,46 @@ int szn_calib_head(int stride, int B, int h, int w, int E, int ldc, int c0, int 
                    const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
                    int n_gammas, const float* gammas, int64_t* hist, int pred_index, int64_t* pred,
                    void* workspace, szn_stream_t stream);
+
+/* ---- full SZN inference with a seen-mask threshold ------------------------------------------------------------------------------
+ * szn_seen_sweep_head: szn_fused_head_grouped's class assignment (group mode 1) with the group decided by a threshold on the seen-mask
+ * logit margin (szn_seenmask_margin) instead of s1 > s0, for n_taus thresholds in one pass over the pixels: per threshold a confusion
+ * histogram, and for one of them the prediction.  coarse, embed, stride (32 | 8), crop, ldc and c0 are szn_fused_head_strided's; margin
+ * (B,H,W) f32 device; taus: HOST memory, read during the call, finite and strictly ascending.  Per pixel and per g:
+ *   pred_g = what szn_fused_head_grouped (group mode 1) writes for the pixel when group_map[pix] = (margin[pix] > taus[g]) ? 1 : 0, bit
+ *            for bit: the classes outside the pixel's group score 0 / (sn * 1) and still compete, the first index wins a tie, a
+ *            zero-norm pixel gives class 0.  A NaN margin compares false: the unseen group at every g, as s1 > s0 does.
+ * tau = 0 is szn_seenmask_head_k's decision; p(seen) > sigmoid(tau) in general.  With ascending taus the g at which a pixel takes the
+ * unseen group are upward closed, so a pixel is described by (t, a, b, bin): a = the grouped head's answer in the seen group, b = in the
+ * unseen group (one trip through the classes, two running bests that each see the grouped head's own sequence of values), bin = the
+ * first g with !(margin > taus[g]) (n_taus: never).  From there on the call is szn_calib_head: XA[t][a][bin] and XB[t][b][bin] in the
+ * workspace, one 64-bit integer atomic add per distinct key of a wave and table, calib_hist_kernel adds the prefix sums to
+ *   hist [n_taus][K][K] int64 (device, or NULL):  hist[g][t][pred_g] += 1 for every pixel whose target t has 0 <= t < K;
+ *   pred (B,H,W) int64 (device, or NULL): pred_g for g = pred_index.
+ * The cost does not grow with n_taus; integer counts, two calls are bit-equal.
+ * szn_last_kernel(): calib_hist_kernel when hist is given (szn_prev_kernel(): the pixel kernel), else the pixel kernel --
+ * sweep_cell_kernel (stride 32) or sweep_cell_tab_kernel (stride 8).
+ * workspace: szn_seen_sweep_head_workspace_bytes (0 for sizes the call refuses), 16-byte aligned, szn_calib_head's layout: the prepared
+ * embedding image written by the call, the stride-8 position tables, the crossing tables, 2 * K^2 * (n_taus + 1) int64.
+ * SZN_ERR_ARG, before any launch: everything szn_calib_head refuses, with taus for gammas (stride, n_taus outside
+ * [1, SZN_SEEN_SWEEP_MAX_TAUS], a tau that is not finite or taus not strictly ascending, hist and pred both NULL, hist without target,
+ * pred_index outside [0, n_taus), NULL coarse / embed / workspace / taus, `unseen` NULL, empty, holding every class below K or a class
+ * >= K, K > SZN_MAX_CLASSES, sizes, ldc < c0 + E, the crop window, the workspace alignment), and a NULL margin.                        */
+#define SZN_SEEN_SWEEP_MAX_TAUS 64
+size_t szn_seen_sweep_head_workspace_bytes(int stride, int B, int h, int w, int E, int K, int n_taus);
+int szn_seen_sweep_head(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                        const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
+                        const float* margin, int n_taus, const float* taus, int64_t* hist, int pred_index, int64_t* pred,
+                        void* workspace, szn_stream_t stream);
+/* the same for a caller that has just run a fused embedding head (szn_fused_head_strided / _grouped / _mse_head / _simce_head or their
+ * _prepared forms) with this stride, B, h, w, E, K, coarse, ldc, c0 and embed on the head of THIS workspace, earlier on this stream: the
+ * prepared embedding image and the stride-8 position tables that call left there are exactly what this one would build, so it builds
+ * neither (full SZN validation runs the plain head for the loss first; at stride 8 the tables are the larger part of either call).  The
+ * caller vouches for that; nothing else differs: arguments, refusals, results and szn_last_kernel() are szn_seen_sweep_head's.        */
+int szn_seen_sweep_head_tabled(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                               const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
+                               const float* margin, int n_taus, const float* taus, int64_t* hist, int pred_index, int64_t* pred,
+                               void* workspace, szn_stream_t stream);
 
 /* ---- self-training on the hidden pixels: top-p% pseudo labels ------------------------------------------------------------------
  * szn_pseudo_head: the network's own calibrated prediction labels the most confident keep_permille / 1000 of the pixels whose label is

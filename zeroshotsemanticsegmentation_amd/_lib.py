@@ -77,6 +77,7 @@ def class_set(classes):
 
 MS_MAX_VIEWS = 16           # SZN_MS_MAX_VIEWS
 CALIB_MAX_GAMMAS = 64       # SZN_CALIB_MAX_GAMMAS
+SEEN_SWEEP_MAX_TAUS = 64    # SZN_SEEN_SWEEP_MAX_TAUS
 PSEUDO_BINS = 1024          # SZN_PSEUDO_BINS
 OHEM_BINS = 1024            # SZN_OHEM_BINS
 
@@ -150,6 +151,7 @@ SIGNATURES = {
     "szn_seenmask_head_workspace_bytes": (_SZ, [_I] * 6),
     "szn_seenmask_head": (_I, [_I] * 8 + [_P, _P, _P, _I, _U64] + [_P] * 8),
     "szn_seenmask_head_k": (_I, [_I] * 8 + [_P, _P, _P, _I, _CS] + [_P] * 8),
+    "szn_seenmask_margin": (_I, [_I] * 8 + [_P, _P, _P, _P]),
     "szn_seenmask_score_wgrad_workspace_bytes": (_SZ, [_L, _I]),
     "szn_seenmask_score_wgrad": (_I, [_I, _L, _I, _I, _P, _P, _P, _P, _P, _P]),
     "szn_loss_workspace_bytes": (_SZ, [_I, _I, _I]),
@@ -200,6 +202,9 @@ SIGNATURES = {
     "szn_ms_head": (_I, [_I] * 8 + [_MV, _P, _CS, _I, _P, _P, _P, _P, _P, _P]),
     "szn_calib_head_workspace_bytes": (_SZ, [_I] * 7),
     "szn_calib_head": (_I, [_I] * 11 + [_P, _P, _P, _CS, _I, _FP, _P, _I, _P, _P, _P]),
+    "szn_seen_sweep_head_workspace_bytes": (_SZ, [_I] * 7),
+    "szn_seen_sweep_head": (_I, [_I] * 11 + [_P, _P, _P, _CS, _P, _I, _FP, _P, _I, _P, _P, _P]),
+    "szn_seen_sweep_head_tabled": (_I, [_I] * 11 + [_P, _P, _P, _CS, _P, _I, _FP, _P, _I, _P, _P, _P]),
     "szn_pseudo_head_workspace_bytes": (_SZ, [_I] * 8),
     "szn_pseudo_head": (_I, [_I] * 11 + [_P, _P, _P, _CS, _F, _F, _I, _I64] + [_P] * 8),
     "szn_ohem_head_workspace_bytes": (_SZ, [_I] * 8),

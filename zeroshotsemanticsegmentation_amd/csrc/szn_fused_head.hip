@@ -22,6 +22,8 @@
 //   fh_gather_kernel     one block per coarse position sums the <= 4 cells that use it as a tap and writes dcoarse
 //   calib_cell_kernel / calib_cell_tab_kernel / calib_hist_kernel   szn_calib_head (calibrated stacking): the cell kernels' G and Q (fh_load_taps,
 //                        fh_build_GQ, fh_lookup_GQ), two running bests per pixel (fh_two_best), crossing tables, prefix sums -> hist
+//   sweep_cell_kernel / sweep_cell_tab_kernel   szn_seen_sweep_head (seen-mask threshold sweep): the calibrated kernels with the grouped
+//                        head's two answers per pixel (fh_group_bests) and the seen-mask margin as the switch; then calib_hist_kernel
 //   pseudo_cell_kernel / pseudo_cell_tab_kernel / pseudo_thr_kernel / pseudo_relabel_kernel   szn_pseudo_head (self-training): the same G, Q
 //                        and fh_two_best on the pixels labelled cand_label, a per-class confidence histogram, thresholds, the relabelled target
 //   ohem_cell_kernel / ohem_cell_tab_kernel / ohem_cut_kernel / ohem_relabel_kernel   szn_ohem_head (hard-pixel mining), in launch order: the
@@ -146,6 +148,27 @@ __device__ __forceinline__ FhTwoBest fh_two_best(const FhArgs& a, const float (&
         const bool take = first || sim > (u ? r.vb : r.va);
         if (take && u) { r.vb = sim; r.ib = k; }
         if (take && !u) { r.va = sim; r.ia = k; }
+    }
+    return r;
+}
+
+// Both answers of the GROUPED fh_argmax in one trip (szn_seen_sweep_head): ia = what it returns for a pixel that takes the seen group,
+// ib = for one that takes the unseen group.  Each running best sees fh_argmax's own sequence of values -- the similarity for a class of
+// its group, zero_sim for every other class -- and replaces on k == 0 or a strictly larger value, so the two agree with it bit for bit,
+// zeroed rows, ties, NaN and zero norms included.  One division per class serves both.
+struct FhGroupBest { int ia, ib; };
+template <int KP>
+__device__ __forceinline__ FhGroupBest fh_group_bests(const FhArgs& a, const float (&wt)[4], const float* G, float sn,
+                                                      const float* __restrict__ en) {
+    const float zero_sim = 0.f / (sn * 1.f);
+    FhGroupBest r = {0, 0};
+    float va = 0.f, vb = 0.f;
+    for (int k = 0; k < a.K; ++k) {
+        const bool u = (bool)((class_word(a.unseen, k >> 6) >> (k & 63)) & 1ull);
+        const float sim = fh_sim<KP>(wt, G, sn, en, k);
+        const float sa = u ? zero_sim : sim, sb = u ? sim : zero_sim;
+        if (k == 0 || sa > va) { va = sa; r.ia = k; }
+        if (k == 0 || sb > vb) { vb = sb; r.ib = k; }
     }
     return r;
 }
@@ -892,10 +915,34 @@ __device__ __forceinline__ void calib_count(const FhArgs& a, const CalArgs& c, i
     }
 }
 
-template <int KP>
-__global__ __launch_bounds__(256) void calib_cell_kernel(FhArgs a, CalArgs c) {      // stride 32: one block per (image, cell)
+// ---- seen-mask threshold sweep (szn_seen_sweep_head): the calibrated head's cells, tables and crossing scheme with another switch ------
+// The thresholds travel in CalArgs::gamma.  A pixel takes the seen group at g iff margin[pix] > tau[g]; a is the grouped head's answer in
+// the seen group, b in the unseen group (fh_group_bests), bin = the first g at which the comparison fails (a NaN margin: 0).
+template <int KP, int S>
+__device__ __forceinline__ int sweep_pixel(const FhArgs& a, const CalArgs& c, const float* __restrict__ margin, int b, int I, int J,
+                                           int ty, int tx, bool live, const float* G, const float* Q, const float* __restrict__ en) {
+    const int y = S * I + ty - a.crop, x = S * J + tx - a.crop;
+    if (!(live && y >= 0 && y < a.H && x >= 0 && x < a.W)) return -1;
+    float wt[4];
+    cell_weights<S>(ty, tx, wt);
+    const float sn = sqrtf(fh_ss(wt, Q));
+    const FhGroupBest r = fh_group_bests<KP>(a, wt, G, sn, en);
+    const size_t pix = ((size_t)b * a.H + y) * a.W + x;
+    const float m = margin[pix];
+    int bin = 0;
+    for (int g = 0; g < c.n; ++g) bin += (m > c.gamma[g]) ? 1 : 0;        // ascending: a prefix
+    if (c.pred) c.pred[pix] = bin > c.pred_index ? r.ia : r.ib;
+    if (!c.XA) return -1;
+    const long t = a.target[pix];
+    if (t < 0 || t >= a.K) return -1;
+    return (int)t | r.ia << 8 | r.ib << 16 | bin << 24;
+}
+
+// The two walks over the pixels that the calibrated head and the threshold sweep share: px(b, I, J, ty, tx, live, G, Q, en) is the head's
+// per-pixel body (calib_pixel, sweep_pixel) and returns the pixel's key.  Stride 32: one block per (image, cell), G and Q built in `sm`.
+template <int KP, typename Px>
+__device__ __forceinline__ void calib_cell_walk(const FhArgs& a, const CalArgs& c, float* sm, Px px) {
     constexpr int S = 32;
-    extern __shared__ __attribute__((aligned(16))) float sm[];
     const FhLds L = fh_lds(a.E, KP, false);
     float* Ct = sm + L.Ct;
     float* G = sm + L.G;
@@ -911,16 +958,14 @@ __global__ __launch_bounds__(256) void calib_cell_kernel(FhArgs a, CalArgs c) { 
     __syncthreads();
     fh_build_GQ<KP>(a, embT, Ct, lane, wave, G, Q);
     __syncthreads();
-    for (int q = tid; q < S * S; q += 256)
-        calib_count(a, c, calib_pixel<KP, S>(a, c, b, I, J, q / S, q % S, true, G, Q, en), lane);
+    for (int q = tid; q < S * S; q += 256) calib_count(a, c, px(b, I, J, q / S, q % S, true, G, Q, en), lane);
 }
 
-template <int KP>
-__global__ __launch_bounds__(256) void calib_cell_tab_kernel(FhArgs a, CalArgs c, const float* __restrict__ D,
-                                                             const float* __restrict__ N) {      // stride 8: one wave per cell
+// Stride 8: one wave per cell, G and Q looked up from the position tables into the wave's rows of Gs [4][4 KP] and Qs [4][16] (LDS)
+template <int KP, typename Px>
+__device__ __forceinline__ void calib_cell_tab_walk(const FhArgs& a, const CalArgs& c, const float* __restrict__ D,
+                                                    const float* __restrict__ N, float* Gs, float* Qs, Px px) {
     constexpr int S = 8;
-    __shared__ float Gs[4][4 * KP];
-    __shared__ float Qs[4][16];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int cells_w = a.w + 1, cells = (a.h + 1) * cells_w;
@@ -931,12 +976,50 @@ __global__ __launch_bounds__(256) void calib_cell_tab_kernel(FhArgs a, CalArgs c
     const int b = (int)(cc / cells), cell = (int)(cc % cells);
     const int I = cell / cells_w, J = cell % cells_w;
     const float* en = a.ws_f + (size_t)a.E * KP;
+    float* G = Gs + wave * 4 * KP;
+    float* Q = Qs + wave * 16;
     long tp[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) tp[t] = tap_pos(b, a.h, a.w, I, J, t);
-    fh_lookup_GQ<KP>(tp, D, N, lane, Gs[wave], Qs[wave]);
+    fh_lookup_GQ<KP>(tp, D, N, lane, G, Q);
     __syncthreads();
-    calib_count(a, c, calib_pixel<KP, S>(a, c, b, I, J, lane / S, lane % S, ok && lane < S * S, Gs[wave], Qs[wave], en), lane);
+    calib_count(a, c, px(b, I, J, lane / S, lane % S, ok && lane < S * S, G, Q, en), lane);
+}
+
+template <int KP>
+__global__ __launch_bounds__(256) void calib_cell_kernel(FhArgs a, CalArgs c) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    calib_cell_walk<KP>(a, c, sm, [&](int b, int I, int J, int ty, int tx, bool live, const float* G, const float* Q, const float* en) {
+        return calib_pixel<KP, 32>(a, c, b, I, J, ty, tx, live, G, Q, en);
+    });
+}
+
+template <int KP>
+__global__ __launch_bounds__(256) void calib_cell_tab_kernel(FhArgs a, CalArgs c, const float* __restrict__ D,
+                                                             const float* __restrict__ N) {
+    __shared__ float Gs[4 * 4 * KP];
+    __shared__ float Qs[4 * 16];
+    calib_cell_tab_walk<KP>(a, c, D, N, Gs, Qs, [&](int b, int I, int J, int ty, int tx, bool live, const float* G, const float* Q, const float* en) {
+        return calib_pixel<KP, 8>(a, c, b, I, J, ty, tx, live, G, Q, en);
+    });
+}
+
+template <int KP>
+__global__ __launch_bounds__(256) void sweep_cell_kernel(FhArgs a, CalArgs c, const float* __restrict__ margin) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    calib_cell_walk<KP>(a, c, sm, [&](int b, int I, int J, int ty, int tx, bool live, const float* G, const float* Q, const float* en) {
+        return sweep_pixel<KP, 32>(a, c, margin, b, I, J, ty, tx, live, G, Q, en);
+    });
+}
+
+template <int KP>
+__global__ __launch_bounds__(256) void sweep_cell_tab_kernel(FhArgs a, CalArgs c, const float* __restrict__ margin,
+                                                             const float* __restrict__ D, const float* __restrict__ N) {
+    __shared__ float Gs[4 * 4 * KP];
+    __shared__ float Qs[4 * 16];
+    calib_cell_tab_walk<KP>(a, c, D, N, Gs, Qs, [&](int b, int I, int J, int ty, int tx, bool live, const float* G, const float* Q, const float* en) {
+        return sweep_pixel<KP, 8>(a, c, margin, b, I, J, ty, tx, live, G, Q, en);
+    });
 }
 
 // hist[g][t][k] += sum_{bin > g} XA[t][k][bin] + sum_{bin <= g} XB[t][k][bin]: one thread per (t, k), running prefixes over the bins
@@ -956,19 +1039,28 @@ __global__ __launch_bounds__(256) void calib_hist_kernel(const unsigned long lon
     }
 }
 
+// margin == nullptr: szn_calib_head's pixel kernels; else szn_seen_sweep_head's, same grids and LDS.  tabled: the stride-8 position tables
+// are in the workspace already (szn_seen_sweep_head_tabled)
 template <int KP>
-void calib_launch(int stride, const FhArgs& a, const CalArgs& c, float* tabD, float* tabN, hipStream_t st) {
+void calib_launch(int stride, const FhArgs& a, const CalArgs& c, const float* margin, bool tabled, float* tabD, float* tabN, hipStream_t st) {
     const int cells = (a.h + 1) * (a.w + 1);
     if (stride == 8) {
-        hipLaunchKernelGGL(fh_tables_kernel<KP>, dim3((unsigned)(((long)a.B * a.h * a.w + 3) / 4)), dim3(256),
-                           (size_t)4 * a.E * sizeof(float), st, a, tabD, tabN);
-        hipLaunchKernelGGL(calib_cell_tab_kernel<KP>, dim3((unsigned)(((long)a.B * cells + 3) / 4)), dim3(256), 0, st, a, c,
-                           (const float*)tabD, (const float*)tabN);
+        const dim3 grid((unsigned)(((long)a.B * cells + 3) / 4));
+        if (!tabled) hipLaunchKernelGGL(fh_tables_kernel<KP>, dim3((unsigned)(((long)a.B * a.h * a.w + 3) / 4)), dim3(256),
+                                        (size_t)4 * a.E * sizeof(float), st, a, tabD, tabN);
+        if (margin) hipLaunchKernelGGL(sweep_cell_tab_kernel<KP>, grid, dim3(256), 0, st, a, c, margin, (const float*)tabD, (const float*)tabN);
+        else hipLaunchKernelGGL(calib_cell_tab_kernel<KP>, grid, dim3(256), 0, st, a, c, (const float*)tabD, (const float*)tabN);
     } else {
         const size_t lds = (size_t)(fh_lds(a.E, KP, false).Q + 16) * sizeof(float);       // Ct | G | Q
-        auto kern = calib_cell_kernel<KP>;
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kern, dim3(a.B * cells), dim3(256), lds, st, a, c);
+        if (margin) {
+            auto kern = sweep_cell_kernel<KP>;
+            if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(kern, dim3(a.B * cells), dim3(256), lds, st, a, c, margin);
+        } else {
+            auto kern = calib_cell_kernel<KP>;
+            if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(kern, dim3(a.B * cells), dim3(256), lds, st, a, c);
+        }
     }
 }
 
@@ -1685,29 +1777,37 @@ extern "C" size_t szn_calib_head_workspace_bytes(int stride, int B, int h, int w
     return calib_workspace(B, h, w, E, K, n_gammas).bytes;
 }
 
-extern "C" int szn_calib_head(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
-                              const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
-                              int n_gammas, const float* gammas, int64_t* hist, int pred_index, int64_t* pred, void* workspace,
-                              szn_stream_t stream) {
-    if (const char* why = calib_bad_geometry(stride, B, h, w, E, K, n_gammas)) SZN_FAIL(SZN_ERR_ARG, "calib_head: %s", why);
-    if (!coarse || !embed || !workspace || !gammas) SZN_FAIL(SZN_ERR_ARG, "calib_head: coarse, embed, workspace and gammas are required");
+namespace {
+// szn_calib_head (sweep == false, margin unused) and szn_seen_sweep_head (sweep == true: `gammas` are its taus, the switch is `margin`):
+// the same refusals, workspace and launch sequence, another pixel kernel.  tabled: the workspace already holds the prepared embedding image
+// and the stride-8 position tables of this map (szn_seen_sweep_head_tabled): neither is rebuilt
+int calib_head_impl(const char* who, const char* vals, bool sweep, bool tabled, int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W,
+                    int crop, int K, const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
+                    const float* margin, int n_gammas, const float* gammas, int64_t* hist, int pred_index, int64_t* pred, void* workspace,
+                    szn_stream_t stream) {
+    if (const char* why = calib_bad_geometry(stride, B, h, w, E, K, n_gammas)) SZN_FAIL(SZN_ERR_ARG, "%s: %s", who, why);
+    if (!coarse || !embed || !workspace || !gammas) SZN_FAIL(SZN_ERR_ARG, "%s: coarse, embed, workspace and %s are required", who, vals);
+    if (sweep && !margin) SZN_FAIL(SZN_ERR_ARG, "%s: margin is required", who);
+    if (!sweep) margin = nullptr;
     const ClassBits ubits = class_bits(unseen);
-    if (int rc = calib_check_shared("calib_head", stride, h, w, E, ldc, c0, H, W, crop, K, ubits, workspace)) return rc;
+    if (int rc = calib_check_shared(who, stride, h, w, E, ldc, c0, H, W, crop, K, ubits, workspace)) return rc;
     for (int g = 0; g < n_gammas; ++g) {
-        if (!isfinite(gammas[g])) SZN_FAIL(SZN_ERR_ARG, "calib_head: gammas[%d] is not finite", g);
-        if (g && !(gammas[g] > gammas[g - 1])) SZN_FAIL(SZN_ERR_ARG, "calib_head: gammas must be strictly ascending (at %d)", g);
+        if (!isfinite(gammas[g])) SZN_FAIL(SZN_ERR_ARG, "%s: %s[%d] is not finite", who, vals, g);
+        if (g && !(gammas[g] > gammas[g - 1])) SZN_FAIL(SZN_ERR_ARG, "%s: %s must be strictly ascending (at %d)", who, vals, g);
     }
-    if (!hist && !pred) SZN_FAIL(SZN_ERR_ARG, "calib_head: hist and pred are both NULL");
-    if (hist && !target) SZN_FAIL(SZN_ERR_ARG, "calib_head: hist needs target");
-    if (pred && (pred_index < 0 || pred_index >= n_gammas)) SZN_FAIL(SZN_ERR_ARG, "calib_head: pred_index %d outside [0, %d)", pred_index, n_gammas);
+    if (!hist && !pred) SZN_FAIL(SZN_ERR_ARG, "%s: hist and pred are both NULL", who);
+    if (hist && !target) SZN_FAIL(SZN_ERR_ARG, "%s: hist needs target", who);
+    if (pred && (pred_index < 0 || pred_index >= n_gammas)) SZN_FAIL(SZN_ERR_ARG, "%s: pred_index %d outside [0, %d)", who, pred_index, n_gammas);
     const int KP = kp_of(K);
 
     hipStream_t st = (hipStream_t)stream;
     const FhWorkspace wl = fh_workspace(B, h, w, E, KP);
     const CalWorkspace cl = calib_workspace(B, h, w, E, K, n_gammas);
     char* ws = (char*)workspace;
-    hipLaunchKernelGGL(fh_prep_kernel, dim3(szn_div_up((long)E * KP, 256)), dim3(256), 0, st, embed, (float*)ws, E, K, KP);
-    SZN_CHECK_LAUNCH("fh_prep_kernel");
+    if (!tabled) {
+        hipLaunchKernelGGL(fh_prep_kernel, dim3(szn_div_up((long)E * KP, 256)), dim3(256), 0, st, embed, (float*)ws, E, K, KP);
+        SZN_CHECK_LAUNCH("fh_prep_kernel");
+    }
     FhArgs a{};
     a.coarse = coarse; a.embed = embed; a.target = target; a.ws_f = (float*)ws;
     a.B = B; a.h = h; a.w = w; a.E = E; a.ldc = ldc; a.c0 = c0; a.H = H; a.W = W; a.crop = crop; a.K = K; a.KP = KP;
@@ -1717,25 +1817,60 @@ extern "C" int szn_calib_head(int stride, int B, int h, int w, int E, int ldc, i
     c.n = n_gammas; c.pred = pred; c.pred_index = pred ? pred_index : 0;
     if (hist) {
         c.XA = (unsigned long long*)(ws + cl.XA); c.XB = (unsigned long long*)(ws + cl.XB);
-        if (hipMemsetAsync(ws + cl.XA, 0, cl.bytes - cl.XA, st) != hipSuccess) SZN_FAIL(SZN_ERR_LAUNCH, "calib_head: clearing the crossing tables failed");
+        if (hipMemsetAsync(ws + cl.XA, 0, cl.bytes - cl.XA, st) != hipSuccess) SZN_FAIL(SZN_ERR_LAUNCH, "%s: clearing the crossing tables failed", who);
     }
     float* tabD = (float*)(ws + wl.tabD);
     float* tabN = (float*)(ws + wl.tabN);
     switch (KP) {
-        case 24: calib_launch<24>(stride, a, c, tabD, tabN, st); break;
-        case 40: calib_launch<40>(stride, a, c, tabD, tabN, st); break;
-        case 64: calib_launch<64>(stride, a, c, tabD, tabN, st); break;
-        case 128: calib_launch<128>(stride, a, c, tabD, tabN, st); break;
-        case 192: calib_launch<192>(stride, a, c, tabD, tabN, st); break;
-        default: calib_launch<256>(stride, a, c, tabD, tabN, st); break;
+        case 24: calib_launch<24>(stride, a, c, margin, tabled, tabD, tabN, st); break;
+        case 40: calib_launch<40>(stride, a, c, margin, tabled, tabD, tabN, st); break;
+        case 64: calib_launch<64>(stride, a, c, margin, tabled, tabD, tabN, st); break;
+        case 128: calib_launch<128>(stride, a, c, margin, tabled, tabD, tabN, st); break;
+        case 192: calib_launch<192>(stride, a, c, margin, tabled, tabD, tabN, st); break;
+        default: calib_launch<256>(stride, a, c, margin, tabled, tabD, tabN, st); break;
     }
-    SZN_CHECK_LAUNCH(stride == 8 ? "calib_cell_tab_kernel" : "calib_cell_kernel");
+    if (sweep) SZN_CHECK_LAUNCH(stride == 8 ? "sweep_cell_tab_kernel" : "sweep_cell_kernel");
+    else SZN_CHECK_LAUNCH(stride == 8 ? "calib_cell_tab_kernel" : "calib_cell_kernel");
     if (hist) {
         hipLaunchKernelGGL(calib_hist_kernel, dim3(szn_div_up((long)K * K, 256)), dim3(256), 0, st, (const unsigned long long*)c.XA,
                            (const unsigned long long*)c.XB, K, n_gammas, hist);
         SZN_CHECK_LAUNCH("calib_hist_kernel");
     }
     return SZN_OK;
+}
+}  // namespace
+
+extern "C" int szn_calib_head(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                              const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
+                              int n_gammas, const float* gammas, int64_t* hist, int pred_index, int64_t* pred, void* workspace,
+                              szn_stream_t stream) {
+    return calib_head_impl("calib_head", "gammas", false, false, stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, unseen, nullptr,
+                           n_gammas, gammas, hist, pred_index, pred, workspace, stream);
+}
+
+// Seen-mask threshold sweep (include/szn.h): the grouped head's class rule with the group decided by margin > tau, n_taus thresholds in
+// one pass over the pixels.  Sizes and workspace are szn_calib_head's.
+static_assert(SZN_SEEN_SWEEP_MAX_TAUS == SZN_CALIB_MAX_GAMMAS, "the taus travel in CalArgs::gamma");
+extern "C" size_t szn_seen_sweep_head_workspace_bytes(int stride, int B, int h, int w, int E, int K, int n_taus) {
+    return szn_calib_head_workspace_bytes(stride, B, h, w, E, K, n_taus);
+}
+
+extern "C" int szn_seen_sweep_head(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                                   const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
+                                   const float* margin, int n_taus, const float* taus, int64_t* hist, int pred_index, int64_t* pred,
+                                   void* workspace, szn_stream_t stream) {
+    return calib_head_impl("seen_sweep_head", "taus", true, false, stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, unseen, margin,
+                           n_taus, taus, hist, pred_index, pred, workspace, stream);
+}
+
+// The same on a workspace in whose head a fused embedding head has just run on this map (include/szn.h): its embedding image and its
+// stride-8 position tables are the ones this call would build, so it builds neither.
+extern "C" int szn_seen_sweep_head_tabled(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                                          const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
+                                          const float* margin, int n_taus, const float* taus, int64_t* hist, int pred_index, int64_t* pred,
+                                          void* workspace, szn_stream_t stream) {
+    return calib_head_impl("seen_sweep_head_tabled", "taus", true, true, stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, unseen,
+                           margin, n_taus, taus, hist, pred_index, pred, workspace, stream);
 }
 
 // Self-training pseudo labels (include/szn.h): the calibrated rule at one gamma picks the candidates among the pixels labelled cand_label,

@@ -165,6 +165,61 @@ __global__ __launch_bounds__(256) void smh_cell_kernel(const float* __restrict__
     if (t < 6) part[(long)blockIdx.x * 6 + t] = combine4(dred[0][t], dred[1][t], dred[2][t], dred[3][t]);
 }
 
+// margin[pix] = s1 - s0 (szn_seenmask_margin): smh_cell_kernel's walk over the pixel cells and its fmaf chain for s0 and s1, nothing
+// else -- no target, no loss, no reduction; one fp32 subtraction and one store per pixel
+__global__ __launch_bounds__(256) void smh_margin_kernel(const float* __restrict__ coarse, const float* __restrict__ wt,
+                                                         float* __restrict__ margin, SmhGeom g) {
+    const int t = threadIdx.x, tx = t & 31, ty0 = t >> 5;
+    float wr[4][2][2][2][2];                   // [r][ci][co][di][dj]: the taps of this thread's pixel positions
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int ci = 0; ci < 2; ++ci)
+#pragma unroll
+            for (int co = 0; co < 2; ++co)
+#pragma unroll
+                for (int di = 0; di < 2; ++di)
+#pragma unroll
+                    for (int dj = 0; dj < 2; ++dj) {
+                        const int ky = ty0 + 8 * r + 32 - 32 * di, kx = tx + 32 - 32 * dj;
+                        wr[r][ci][co][di][dj] = wt[((ci * 2 + co) * 64 + ky) * 64 + kx];
+                    }
+    const int ncell = g.B * g.nci * g.ncj;
+    for (int cell = blockIdx.x; cell < ncell; cell += gridDim.x) {
+        const int jc = cell % g.ncj;
+        const int tt = cell / g.ncj;
+        const int ic = tt % g.nci, b = tt / g.nci;
+        const int i1 = g.i1lo + ic, j1 = g.j1lo + jc;
+        float c[2][2][2];                      // [di][dj][ci]; cells outside the map contribute exact zeros
+#pragma unroll
+        for (int di = 0; di < 2; ++di)
+#pragma unroll
+            for (int dj = 0; dj < 2; ++dj) {
+                const int i = i1 - 1 + di, j = j1 - 1 + dj;
+                const bool ok = i >= 0 && i < g.h && j >= 0 && j < g.w;
+                const float* p = coarse + (((long)b * g.h + (ok ? i : 0)) * g.w + (ok ? j : 0)) * g.ldc + g.c0;
+                c[di][dj][0] = ok ? p[0] : 0.f;
+                c[di][dj][1] = ok ? p[1] : 0.f;
+            }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int y = 32 * i1 + ty0 + 8 * r - g.crop, x = 32 * j1 + tx - g.crop;
+            if (y < 0 || y >= g.H || x < 0 || x >= g.W) continue;
+            float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+            for (int ci = 0; ci < 2; ++ci)
+#pragma unroll
+                for (int di = 0; di < 2; ++di)
+#pragma unroll
+                    for (int dj = 0; dj < 2; ++dj) {
+                        s0 = fmaf(c[di][dj][ci], wr[r][ci][0][di][dj], s0);
+                        s1 = fmaf(c[di][dj][ci], wr[r][ci][1][di][dj], s1);
+                    }
+            margin[((long)b * g.H + y) * g.W + x] = s1 - s0;
+        }
+    }
+}
+
 // every block re-derives S = sum of loss terms and N = valid pixels in the same fixed order, then takes its share of the
 // outputs: weight gradient (kTaps elements), d(coarse) gather (B*h*w*2 elements).  Block 0 also writes loss / stats / conf.
 __global__ __launch_bounds__(256) void smh_finalize_kernel(const double* __restrict__ part, int G,
@@ -365,6 +420,19 @@ extern "C" int szn_seenmask_head_k(int B, int h, int w, int ldc, int c0, int H, 
                                    szn_stream_t stream) {
     return seenmask_head_impl(B, h, w, ldc, c0, H, W, crop, coarse, weight, target, n_class, class_bits(seen), loss, stats, conf, pred,
                               dscore2, dweight, workspace, stream);
+}
+
+// The seen-mask logit margin s1 - s0 per pixel (include/szn.h): the pred-only call above with the decision left to the caller.
+extern "C" int szn_seenmask_margin(int B, int h, int w, int ldc, int c0, int H, int W, int crop, const float* coarse,
+                                   const float* weight, float* margin, szn_stream_t stream) {
+    if (B < 1 || h < 1 || w < 1 || H < 1 || W < 1 || crop < 0) SZN_FAIL(SZN_ERR_ARG, "szn_seenmask_margin: bad geometry");
+    if (!coarse || !weight || !margin) SZN_FAIL(SZN_ERR_ARG, "szn_seenmask_margin: null pointer");
+    if (((crop + H - 1) >> 5) > h || ((crop + W - 1) >> 5) > w)
+        SZN_FAIL(SZN_ERR_ARG, "szn_seenmask_margin: %dx%d output (+crop %d) does not fit a %dx%d map at stride 32", H, W, crop, h, w);
+    const SmhGeom g = make_geom(B, h, w, ldc, c0, H, W, crop);
+    smh_margin_kernel<<<smh_grid(g), 256, 0, (hipStream_t)stream>>>(coarse, weight, margin, g);
+    SZN_CHECK_LAUNCH("smh_margin_kernel");
+    return SZN_OK;
 }
 
 extern "C" size_t szn_seenmask_score_wgrad_workspace_bytes(long M, int F) {

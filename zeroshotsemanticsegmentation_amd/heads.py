@@ -15,6 +15,8 @@ szn_fused_ce_head and szn_seenmask_head_k goes through here (models.FCN32s / FCN
             which reads the maps of all views and writes one prediction.
   calib     calibrated stacking (szn_calib_head): a penalty gamma on every seen class, swept over up to 64 values in one pass --
             per gamma a confusion histogram, for one of them the prediction.
+  seen_sweep  full SZN inference with a threshold on the seen-mask logit margin (szn_seenmask_margin, szn_seen_sweep_head): the grouped
+            head's class assignment with the group decided by margin > tau, up to 64 taus in one pass.
   pseudo    self-training pseudo labels (szn_pseudo_head): the calibrated prediction labels the most confident share of the hidden
             pixels per unseen class; the relabelled target is what a training head then reads.
   ohem      hard-pixel mining (szn_ohem_head): per image the labelled pixels with the lowest own-class cosine keep their label, the
@@ -36,18 +38,24 @@ _CROP = {32: CROP, 8: CROP_UP8}
 class Workspace(object):
     """a head workspace kept across calls, plus the embedding tables szn_fused_head_prepare wrote to its head.  The tables are
     rebuilt for a new buffer, a new embedding tensor or an in-place torch write into it (_version), and after invalidate() (a raw
-    kernel writing into the tensor does not bump _version, and a new tensor may reuse the old one's address)."""
+    kernel writing into the tensor does not bump _version, and a new tensor may reuse the old one's address).  `tables` names the map
+    whose embedding head ran here last (embed() records it): seen_sweep(ws=) reuses that call's tables for the same map only."""
 
     def __init__(self, device):
-        self.device, self.buf, self.prep = device, None, None
+        self.device, self.buf, self.prep, self.tables = device, None, None, None
 
     def get(self, nbytes):
         if self.buf is None or self.buf.numel() < nbytes:
             self.buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self.tables = None
         return self.buf
 
     def invalidate(self):
-        self.prep = None
+        self.prep = self.tables = None
+
+    @staticmethod
+    def map_key(stride, fmap):
+        return (stride, fmap.data_ptr(), fmap._version, tuple(fmap.shape))
 
     def prepared(self, nbytes, emb, K, E, stream):
         ws = self.get(nbytes)
@@ -131,6 +139,8 @@ def embed(kind, stride, fmap, emb, H, W, pred, target=None, loss=None, stats=Non
     code = L.dtype_code(dmap.dtype) if dmap is not None else L.SZN_F32
     L.call(fn, stride, B, h, w, E, ld, 0, H, W, _CROP[stride], K, L.ptr(fmap), L.ptr(emb), L.ptr(target), classes, mode,
            L.ptr(gmap), *(sim + (L.ptr(loss), L.ptr(stats), L.ptr(pred), code, L.ptr(dmap), L.ptr(buf), st)))
+    if ws is not None:
+        ws.tables = Workspace.map_key(stride, fmap)
 
 
 def embed_predict(kind, stride, fmap, emb, H, W, target=None, mode=0, unseen=None, gmap=None, exclude=None, temperature=None):
@@ -141,6 +151,16 @@ def embed_predict(kind, stride, fmap, emb, H, W, target=None, mode=0, unseen=Non
     embed(kind, stride, fmap, emb, H, W, pred, tgt, loss, stats, mode=mode, classes=L.class_set(unseen), gmap=gmap, exclude=exclude,
           temperature=temperature)
     return (loss.reshape(()) if loss is not None else None), pred
+
+
+def embed_loss(kind, stride, fmap, emb, H, W, target, exclude=None, temperature=None, ws=None):
+    """the loss of embed_predict alone, bit for bit (the same kernels without the prediction: no trip through the classes per pixel)
+    -> loss 0-dim tensor.  ws: a Workspace or None, as in embed()"""
+    B = fmap.shape[0]
+    tgt = target.to(device=fmap.device, dtype=torch.int64).contiguous()
+    loss, stats = torch.empty(1, device=fmap.device), torch.empty(B, 2, device=fmap.device)
+    embed(kind, stride, fmap, emb, H, W, None, tgt, loss, stats, ws=ws, exclude=exclude, temperature=temperature)
+    return loss.reshape(())
 
 
 def cosine(*args, **kw):
@@ -271,6 +291,71 @@ def calib(stride, fmap, emb, H, W, unseen, gammas, target=None, hist=None, pred_
     L.call("szn_calib_head", stride, B, h, w, E, ld, 0, H, W, _CROP[stride], K, L.ptr(fmap), L.ptr(emb), L.ptr(tgt),
            L.class_set(unseen), G, g.ctypes.data_as(C.POINTER(C.c_float)), L.ptr(hist), -1 if pred_index is None else int(pred_index),
            L.ptr(pred), L.ptr(buf), L.stream_ptr())
+    return hist, pred
+
+
+# ---- full SZN inference with a seen-mask threshold: one-pass sweep ---------------------------------------------------------------
+def seen_sweep_taus(taus):
+    """the candidate thresholds (logit units) as the float32 HOST array szn_seen_sweep_head reads: 1 to SEEN_SWEEP_MAX_TAUS finite,
+    strictly ascending values"""
+    import numpy as np
+    t = np.ascontiguousarray(np.asarray(taus, dtype=np.float32).reshape(-1))
+    if not 1 <= t.size <= L.SEEN_SWEEP_MAX_TAUS:
+        raise L.SznError("seen sweep: %d taus, between 1 and %d are taken" % (t.size, L.SEEN_SWEEP_MAX_TAUS))
+    if not np.isfinite(t).all() or not (np.diff(t) > 0).all():
+        raise L.SznError("seen sweep: the taus must be finite and strictly ascending as float32 (got %r)" % (t.tolist(),))
+    return t
+
+
+def seen_sweep_workspace_bytes(stride, fmap, emb, n_taus):
+    """szn_seen_sweep_head_workspace_bytes for a map and an embedding matrix (0: a geometry the head refuses)"""
+    B, h, w, _ = fmap.shape
+    K, E = emb.shape
+    return L.load().szn_seen_sweep_head_workspace_bytes(stride, B, h, w, E, K, int(n_taus))
+
+
+def seen_sweep(stride, fmap, emb, H, W, unseen, margin, taus, target=None, hist=None, pred_index=None, ws=None):
+    """szn_seen_sweep_head on the contiguous fp32 NHWC map `fmap` (the E embedding channels first): the grouped head's class assignment
+    with a pixel in the seen group iff margin > tau (margin: seenmask_margin's (B,H,W) f32 map), for every tau of `taus` (ascending) in
+    one pass.  target given: hist (G,K,K) int64 += the confusion counts of every tau (allocated as zeros when None).  pred_index given:
+    pred (B,H,W) int64 at taus[pred_index].  -> (hist or None, pred or None).  ws: None, or the Workspace in which embed() / embed_loss()
+    has just run on this very map and embedding matrix, already as large as seen_sweep_workspace_bytes says: the embedding tables and the
+    stride-8 position tables that call left there are reused (szn_seen_sweep_head_tabled)"""
+    import ctypes as C
+    B, h, w, ld = fmap.shape
+    K, E = emb.shape
+    if fmap.dtype != torch.float32 or not fmap.is_contiguous():
+        raise L.SznError("seen_sweep: the map must be a contiguous fp32 (B,h,w,C) tensor")
+    dev = fmap.device
+    if margin is None or margin.dtype != torch.float32 or tuple(margin.shape) != (B, H, W) or not margin.is_contiguous() or margin.device != dev:
+        raise L.SznError("seen_sweep: margin must be a contiguous fp32 (%d,%d,%d) tensor on %s" % (B, H, W, dev))
+    t = seen_sweep_taus(taus)
+    G = int(t.size)
+    if target is None and hist is not None:
+        raise L.SznError("seen_sweep: a histogram needs the target")
+    if target is None and pred_index is None:
+        raise L.SznError("seen_sweep: nothing to compute (no target for a histogram, no pred_index for a prediction)")
+    if pred_index is not None and not 0 <= int(pred_index) < G:
+        raise L.SznError("seen_sweep: pred_index %r outside [0, %d)" % (pred_index, G))
+    tgt = None
+    if target is not None:
+        tgt = target.to(device=dev, dtype=torch.int64).contiguous()
+        if hist is None:
+            hist = torch.zeros(G, K, K, dtype=torch.int64, device=dev)
+        elif hist.dtype != torch.int64 or tuple(hist.shape) != (G, K, K) or not hist.is_contiguous() or hist.device != dev:
+            raise L.SznError("seen_sweep: hist must be a contiguous int64 (%d,%d,%d) tensor on %s" % (G, K, K, dev))
+    pred = torch.empty(B, H, W, dtype=torch.int64, device=dev) if pred_index is not None else None
+    nbytes = seen_sweep_workspace_bytes(stride, fmap, emb, G)
+    if nbytes == 0:
+        raise L.SznError("seen_sweep: bad geometry (stride %d, B %d, map %d x %d, E %d, K %d, %d taus)" % (stride, B, h, w, E, K, G))
+    if ws is not None and (ws.buf is None or ws.buf.numel() < nbytes or ws.tables != Workspace.map_key(stride, fmap)
+                           or ws.prep != (ws.buf.data_ptr(), emb.data_ptr(), emb._version, K, E)):
+        raise L.SznError("seen_sweep: ws must be the Workspace in which the embedding head last ran on this very map and embedding "
+                         "matrix, %d bytes or more" % nbytes)
+    buf = _scratch(nbytes, dev) if ws is None else ws.buf
+    L.call("szn_seen_sweep_head" if ws is None else "szn_seen_sweep_head_tabled", stride, B, h, w, E, ld, 0, H, W, _CROP[stride], K, L.ptr(fmap), L.ptr(emb), L.ptr(tgt),
+           L.class_set(unseen), L.ptr(margin), G, t.ctypes.data_as(C.POINTER(C.c_float)), L.ptr(hist),
+           -1 if pred_index is None else int(pred_index), L.ptr(pred), L.ptr(buf), L.stream_ptr())
     return hist, pred
 
 
@@ -473,3 +558,12 @@ def seenmask_group(coarse, E, up_w, H, W):
     gmap = torch.empty(coarse.shape[0], H, W, dtype=torch.int64, device=coarse.device)
     seenmask(coarse, E, up_w, gmap)
     return gmap
+
+
+def seenmask_margin(coarse, E, up_w, H, W):
+    """the seen-mask logit margin s1 - s0 per pixel (szn_seenmask_margin) -> (B,H,W) f32; margin > 0 is seenmask_group's map bit for
+    bit, margin > tau the group map of seen_sweep() at threshold tau"""
+    B, h, w, CP = coarse.shape
+    margin = torch.empty(B, H, W, dtype=torch.float32, device=coarse.device)
+    L.call("szn_seenmask_margin", B, h, w, CP, E, H, W, CROP, L.ptr(coarse), L.ptr(up_w), L.ptr(margin), L.stream_ptr())
+    return margin

@@ -1317,6 +1317,7 @@ class FCN32s(nn.Module):
         object.__setattr__(self, "_last_ctx", None)
         object.__setattr__(self, "_last_pred", None)
         object.__setattr__(self, "_last_group", None)         # the seen-mask group map of the last szn_predict
+        object.__setattr__(self, "_last_margin", None)        # the seen-mask logit margin of the last seen_sweep_predict
 
     def _initialize_weights(self):
         # only the transposed convolutions are (re)initialised -- bilinear kernels (models.py:102-112)
@@ -1522,6 +1523,41 @@ class FCN32s(nn.Module):
                 hist, cpred = heads.calib(stride, fmap32, emb, ctx.H, ctx.W, unseen, gammas, target, hist, pred_index)
                 if pred_index is not None:
                     pred = cpred
+            self._last_pred = pred
+        return loss_t, pred, hist
+
+    def seen_sweep_predict(self, x, embeddings, unseen, taus, target=None, hist=None, pred_index=None, loss="cos"):
+        """the full SZN network's class assignment with a threshold on the seen-mask decision: one forward pass, then on the same map
+        the plain head for the loss, the seen-mask logit margin s1 - s0 (szn_seenmask_margin on the 1/32 map; FCN8s keeps the x32
+        seen-mask geometry) and szn_seen_sweep_head, which classifies a pixel among the seen classes iff margin > tau and among
+        `unseen` otherwise -- szn_predict's rule, which is tau = 0 -- for every value of `taus` (ascending, at most 64) in one pass.
+        -> (loss, pred, hist): the loss is embed_predict's on that map, bit for bit (None without a target), and so szn_predict's; pred
+        (B,H,W) int64 is the prediction at taus[pred_index], or embed_predict's own when pred_index is None; hist (G,K,K) int64 holds
+        the confusion counts of every tau: `hist` accumulated in place when given; a fresh one with a target and no pred_index; None
+        with a pred_index and no `hist` (a prediction-only call: no crossing tables, no histogram kernel).  The margin is left in
+        self._last_margin."""
+        kind = heads.embed_kind(loss)
+        with torch.no_grad():
+            ctx, stride, fmap = self._head_map(x)
+            emb = heads.embeddings(embeddings, self.n_class, fmap.device)
+            ws = None
+            if target is not None and pred_index is not None and fmap.dtype == torch.float32:
+                # the sweep head writes the prediction: the plain head runs for the loss alone (no class loop per pixel), in the sweep
+                # head's workspace, which then finds the embedding tables and the stride-8 position tables of this map in place
+                ws = heads.Workspace(fmap.device)
+                ws.get(heads.seen_sweep_workspace_bytes(stride, fmap, emb, len(heads.seen_sweep_taus(taus))))
+                loss_t, pred = heads.embed_loss(kind, stride, fmap, emb, ctx.H, ctx.W, target, ws=ws, **self._sim_kw(kind)), None
+            else:
+                loss_t, pred = heads.embed_predict(kind, stride, fmap, emb, ctx.H, ctx.W, target, **self._sim_kw(kind))
+            self._last_margin = None
+            if target is not None or pred_index is not None:
+                self._last_margin = heads.seenmask_margin(ctx.coarse, self.n_class, self._engine._images["up.w"], ctx.H, ctx.W)
+                fmap32 = fmap if fmap.dtype == torch.float32 else fmap.to(torch.float32)
+                counted = target if (hist is not None or pred_index is None) else None
+                hist, spred = heads.seen_sweep(stride, fmap32, emb, ctx.H, ctx.W, unseen, self._last_margin, taus, counted, hist, pred_index,
+                                               ws=ws)
+                if pred_index is not None:
+                    pred = spred
             self._last_pred = pred
         return loss_t, pred, hist
 

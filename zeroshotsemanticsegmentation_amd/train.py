@@ -18,6 +18,10 @@ Added for this implementation (none change the reference flags):
                        class before the argmax (szn_calib_head); --calib-sweep LO HI N also writes the metrics of N penalties between
                        LO and HI, and their harmonic mean of seen and unseen mIoU, to <log_dir>/calib_log.csv at one extra head launch
                        per validation batch
+  --seen-threshold TAU with -m test_all: a pixel takes the seen class group iff its seen-mask logit margin s1 - s0 exceeds TAU, that
+                       is p(seen) > sigmoid(TAU) (szn_seen_sweep_head; 0 = the plain decision); --seen-sweep LO HI N also writes the
+                       metrics of N thresholds between LO and HI, and their harmonic mean of seen and unseen mIoU, to
+                       <log_dir>/seen_sweep_log.csv from the same head launch
   -loss sim_ce         similarity cross-entropy: softmax over the seen classes' cosine similarities to the pixel embedding, cross
                        entropy against the label (szn_fused_simce_head; the unseen classes do not compete); --sim-temperature T
                        (default 0.1, a hyper-parameter default, not a tuned value) divides the similarities
@@ -104,6 +108,13 @@ def build_parser():
     p.add_argument('--calib-sweep', type=float, nargs=3, metavar=('LO', 'HI', 'N'), default=None,
                    help="every validation also evaluates N penalties (2 to 64) evenly spaced from LO to HI in one extra pass of the "
                         "head and appends their metrics and the harmonic mean of seen and unseen mIoU to <log_dir>/calib_log.csv")
+    p.add_argument('--seen-threshold', type=float, default=None, metavar='TAU',
+                   help="with -m test_all: threshold on the seen-mask logit margin s1 - s0, in logit units -- a pixel is classified "
+                        "among the seen classes iff the margin exceeds TAU, that is p(seen) > sigmoid(TAU).  Default: the plain "
+                        "decision s1 > s0, which is TAU = 0")
+    p.add_argument('--seen-sweep', type=float, nargs=3, metavar=('LO', 'HI', 'N'), default=None,
+                   help="with -m test_all: also evaluates N thresholds (2 to 64) evenly spaced from LO to HI in the same pass of the "
+                        "head and appends their metrics and the harmonic mean of seen and unseen mIoU to <log_dir>/seen_sweep_log.csv")
     p.add_argument('--sim-temperature', type=float, default=None, metavar='T',
                    help="with -loss sim_ce (softmax over the seen classes' cosine similarities to the pixel embedding, cross entropy "
                         "against the label): the temperature the similarities are divided by.  Default %g: a hyper-parameter default, "
@@ -269,20 +280,44 @@ def check_eval_views(scales, flip, cfg):
         raise Exception("--eval-scales must contain 1 (got %r)" % (scales,))
 
 
-def calib_sweep_values(sweep):
+def calib_sweep_values(sweep, flag="--calib-sweep"):
     """--calib-sweep LO HI N -> the N float32 penalties numpy.linspace(LO, HI, N), or None without the flag"""
     if sweep is None:
         return None
     import numpy as np
     lo, hi, n = sweep
     if n != int(n) or not 2 <= int(n) <= 64:
-        raise Exception("--calib-sweep: N must be an integer from 2 to 64 (got %r)" % (n,))
+        raise Exception("%s: N must be an integer from 2 to 64 (got %r)" % (flag, n))
     if not (np.isfinite([lo, hi]).all() and lo < hi):
-        raise Exception("--calib-sweep: LO < HI, both finite (got %r, %r)" % (lo, hi))
+        raise Exception("%s: LO < HI, both finite (got %r, %r)" % (flag, lo, hi))
     vals = np.linspace(lo, hi, int(n)).astype(np.float32)
     if not (np.diff(vals) > 0).all():
-        raise Exception("--calib-sweep: %d values between %r and %r are not distinct in float32" % (int(n), lo, hi))
+        raise Exception("%s: %d values between %r and %r are not distinct in float32" % (flag, int(n), lo, hi))
     return vals
+
+
+def seen_sweep_values(sweep):
+    """--seen-sweep LO HI N -> the N float32 thresholds numpy.linspace(LO, HI, N), or None without the flag"""
+    return calib_sweep_values(sweep, "--seen-sweep")
+
+
+def check_seen_threshold(threshold, sweep, cfg, calibration=None, calib_sweep=None, eval_scales=None, eval_flip=False):
+    """--seen-threshold / --seen-sweep: -m test_all only, never together with --calibration / --calib-sweep (another class-assignment
+    rule, refused under test_all anyway); otherwise trainer_fcn.seen_threshold_refused"""
+    if threshold is None and sweep is None:
+        return
+    seen_sweep_values(sweep)
+    if threshold is not None and (threshold != threshold or threshold in (float('inf'), float('-inf'))):
+        raise Exception("--seen-threshold: TAU must be finite (got %r)" % (threshold,))
+    if calibration is not None or calib_sweep is not None:
+        raise Exception("--seen-threshold / --seen-sweep: not together with --calibration / --calib-sweep (two class-assignment rules)")
+    n_class = 21 if cfg['dataset'] == 'pascal' else 33
+    why = trainer_fcn.seen_threshold_refused(bool(cfg['train_unseen'] or cfg['val_unseen']),
+                                             bool(cfg['embed_dim']) and cfg['fcn_loss'] in _EMBED_LOSSES, bool(cfg['forced_unseen']),
+                                             cfg['mode'] == 'test_all', bool(eval_scales or eval_flip), n_class,
+                                             os.environ.get("SZN_VERBOSE_VAL", "0") == "1")
+    if why:
+        raise Exception("--seen-threshold / --seen-sweep: " + why)
 
 
 def check_calibration(calibration, sweep, cfg, eval_scales=None, eval_flip=False):
@@ -364,6 +399,7 @@ def main(argv=None):
     check_precision(args.precision, cfg)
     check_eval_views(args.eval_scales, args.eval_flip, cfg)
     check_calibration(args.calibration, args.calib_sweep, cfg, args.eval_scales, args.eval_flip)
+    check_seen_threshold(args.seen_threshold, args.seen_sweep, cfg, args.calibration, args.calib_sweep, args.eval_scales, args.eval_flip)
     check_pseudo(args.pseudo_label, args.pseudo_gamma, args.pseudo_floor, args.pseudo_start_epoch, args.hide_unseen, cfg)
     check_ohem(args.ohem, args.ohem_thresh, args.ohem_start_epoch, cfg)
     hide_unseen = args.hide_unseen or args.pseudo_label is not None
@@ -486,7 +522,7 @@ def main(argv=None):
         dataset=cfg['dataset'], max_epoch=cfg['fcn_epochs'], pixel_embeddings=cfg['embed_dim'], loss_func=cfg['fcn_loss'],
         tb_writer=tb_writer, unseen=all_unseen, val_unseen=cfg['val_unseen'], label_names=label_names,
         forced_unseen=cfg['forced_unseen'], precision=precision, rank=rank, visualize=args.viz, augment=augment,
-        sim_temperature=args.sim_temperature,
+        seen_threshold=args.seen_threshold, seen_sweep=seen_sweep_values(args.seen_sweep), sim_temperature=args.sim_temperature,
         pseudo=None if args.pseudo_label is None else dict(keep=args.pseudo_label, gamma=args.pseudo_gamma,
                                                            conf_floor=-2.0 if args.pseudo_floor is None else args.pseudo_floor),
         pseudo_start_epoch=args.pseudo_start_epoch or 0,

@@ -63,6 +63,27 @@ def calibration_refused(has_unseen, embed_cfg, forced_unseen, test_all, eval_vie
     return None
 
 
+def seen_threshold_refused(has_unseen, embed_cfg, forced_unseen, test_all, eval_views, n_class, verbose_val=False):
+    """why a configuration cannot threshold the seen-mask decision (seen_threshold= / seen_sweep=, train.py --seen-threshold /
+    --seen-sweep), or None: the threshold moves the operating point of the full SZN network (validate(True), -m test_all), whose
+    seen-mask classifier picks the class group per pixel inside the fused embedding head"""
+    if not has_unseen:
+        return "a seen-mask threshold needs unseen classes (train_unseen / val_unseen): without them there is one class group"
+    if not embed_cfg:
+        return "a seen-mask threshold needs an embedding configuration (loss 'cos' | 'mse' | 'sim_ce'): a softmax network has no class groups"
+    if forced_unseen:
+        return "a seen-mask threshold and forced_unseen are two different class-assignment rules: pick one"
+    if not test_all:
+        return "a seen-mask threshold acts on the full SZN network only: validate(both_fcn_and_seenmask=True), -m test_all"
+    if eval_views:
+        return "a seen-mask threshold with eval_scales / eval_flip is not built (the view-ensemble head takes its own group map)"
+    if n_class > 256:
+        return "a seen-mask threshold: the fused head holds at most 256 classes, got %d" % n_class
+    if verbose_val:
+        return "a seen-mask threshold: SZN_VERBOSE_VAL needs the materialised score, which the sweep head never forms"
+    return None
+
+
 def pseudo_refused(has_unseen, embed_cfg, n_class):
     """why a configuration cannot self-train on pseudo labels (pseudo=, train.py --pseudo-label), or None: the labels are the unseen
     classes' calibrated predictions of the fused embedding head"""
@@ -96,6 +117,7 @@ class Trainer(object):
     def __init__(self, cuda, model, optimizer, train_loader, val_loader, log_dir, dataset, max_epoch, tb_writer,
                  pixel_embeddings=None, loss_func=None, unseen=None, val_unseen=None, label_names=None,
                  forced_unseen=False, embed_arr=None, precision=torch.float32, fused_step=True, rank=0, visualize=0, augment=None,
+                 seen_threshold=None, seen_sweep=None,
                  sim_temperature=None, pseudo=None, pseudo_start_epoch=0, ohem=None, ohem_start_epoch=0, calibration=None,
                  calib_sweep=None, eval_scales=None, eval_flip=False):
         if not cuda:
@@ -151,6 +173,16 @@ class Trainer(object):
             self.calib_sweep = calib_gammas(calib_sweep)
         self.best_gamma = None
         self.best_harmonic_mean_iu = None
+        # the seen-mask threshold of the full SZN network (models.seen_sweep_predict), validate(True) only: a pixel takes the seen group
+        # iff its seen-mask logit margin s1 - s0 exceeds `seen_threshold` (None: the plain route, which is tau = 0); `seen_sweep` =
+        # ascending candidate taus whose metrics validate(True) writes to seen_sweep_log.csv from the same head launch
+        self.seen_threshold = None if seen_threshold is None else float(np.float32(seen_threshold))
+        self.seen_sweep = None
+        if seen_sweep is not None:
+            from .heads import seen_sweep_taus
+            self.seen_sweep = seen_sweep_taus(seen_sweep)
+        self.best_seen_tau = None
+        self.best_seen_harmonic_mean_iu = None
 
         self.epoch = 0
         self.iteration = 0
@@ -172,6 +204,14 @@ class Trainer(object):
             if self.calibration is not None and not np.isfinite(self.calibration):
                 from ._lib import SznError
                 raise SznError("calibration: gamma must be finite (got %r)" % (calibration,))
+        if self.seen_threshold is not None or self.seen_sweep is not None:
+            from ._lib import SznError
+            why = seen_threshold_refused(bool(self.unseen), bool(pixel_embeddings) and loss_func in _EMBED_LOSSES, forced_unseen,
+                                         True, bool(self.eval_scales), self.n_class, self.verbose_val)
+            if why:
+                raise SznError(why)
+            if self.seen_threshold is not None and not np.isfinite(self.seen_threshold):
+                raise SznError("seen_threshold: tau must be finite (got %r)" % (seen_threshold,))
 
         # self-training (engine.TrainStep pseudo=): from epoch pseudo_start_epoch on every training step labels the most confident
         # `keep` of the hidden pixels (datasets.HIDDEN_LABEL: a hide_unseen training set) per unseen class with the step's own
@@ -491,10 +531,19 @@ class Trainer(object):
                 loss, pred = self.model.ms_predict(data, self.embeddings, self.eval_scales, self.eval_flip, target, unseen=self.unseen,
                                                    group='seenmask' if szn else 'target', loss=self.loss_func)
                 return None, loss, pred, target
+            if szn and (self.seen_threshold is not None or self._seen_hist is not None):
+                # the seen-mask decision at a threshold: one forward pass; the sweep's histogram and the reported prediction come from
+                # one szn_seen_sweep_head launch on the map the loss used
+                loss, pred, _ = self.model.seen_sweep_predict(data, self.embeddings, self.unseen, self._seen_taus(), target,
+                                                              hist=self._seen_hist, pred_index=self._seen_index(), loss=self.loss_func)
+                return None, loss, pred, target
             predict = {"cos": self.model.szn_predict, "mse": self.model.szn_predict_mse,
                        "sim_ce": self.model.szn_predict_sim_ce}[self.loss_func]
             loss, pred = predict(data, self.embeddings, self.unseen, target, group='seenmask' if szn else 'target')
             return None, loss, pred, target
+        if szn and (self.seen_threshold is not None or self._seen_hist is not None):
+            from ._lib import SznError
+            raise SznError("a seen-mask threshold runs on the fused head: dense target embeddings keep the materialised score")
         if self.eval_scales and not self._ms_warned:
             # dense target embeddings, SZN_VERBOSE_VAL and more than 256 classes keep the materialised-score route: one view
             self._ms_warned = True
@@ -534,22 +583,27 @@ class Trainer(object):
             return None
         return 0 if self._calib_hist is None else int(np.searchsorted(self._calib_all, np.float32(self.calibration)))
 
-    def _calib_report(self, hist_all):
-        """rank 0, once per epoch: one calib_log.csv row per gamma of the sweep, and the gamma with the largest harmonic mean"""
-        keep = np.searchsorted(self._calib_all, self.calib_sweep)
-        path = osp.join(self.log_dir, 'calib_log.csv')
+    def _sweep_report(self, hist_all, all_vals, sweep, fname, column):
+        """one <fname> row per value of the sweep (hist_all follows all_vals) -> (value, harmonic mean) of the largest harmonic mean, or
+        None; ties go to the value nearest 0 (a NaN never wins)"""
+        keep = np.searchsorted(all_vals, sweep)
+        path = osp.join(self.log_dir, fname)
         if not osp.exists(path):
             with open(path, 'w') as f:
-                f.write('epoch,iteration,gamma,val/pxl_acc,val/mean_iu,val/seen/mean_iu,val/unseen/mean_iu,val/harmonic_mean_iu\n')
+                f.write('epoch,iteration,%s,val/pxl_acc,val/mean_iu,val/seen/mean_iu,val/unseen/mean_iu,val/harmonic_mean_iu\n' % column)
         best = None
         with open(path, 'a') as f:
-            for gamma, g in zip(self.calib_sweep, keep):
+            for val, g in zip(sweep, keep):
                 m, ms, mu = utils.calib_rows(hist_all[g], self.n_class, self.val_unseen)
                 hm = utils.harmonic_mean_iu(ms, mu)
-                f.write(','.join(map(str, [self.epoch, self.iteration, float(gamma), m[0], m[2], ms[2], mu[2], hm])) + '\n')
-                # the largest harmonic mean; ties go to the gamma nearest 0 (a NaN never wins)
-                if not np.isnan(hm) and (best is None or hm > best[1] or (hm == best[1] and abs(float(gamma)) < abs(best[0]))):
-                    best = (float(gamma), hm)
+                f.write(','.join(map(str, [self.epoch, self.iteration, float(val), m[0], m[2], ms[2], mu[2], hm])) + '\n')
+                if not np.isnan(hm) and (best is None or hm > best[1] or (hm == best[1] and abs(float(val)) < abs(best[0]))):
+                    best = (float(val), hm)
+        return best
+
+    def _calib_report(self, hist_all):
+        """rank 0, once per epoch: one calib_log.csv row per gamma of the sweep, and the gamma with the largest harmonic mean"""
+        best = self._sweep_report(hist_all, self._calib_all, self.calib_sweep, 'calib_log.csv', 'gamma')
         if best is not None:
             self.best_gamma, self.best_harmonic_mean_iu = best
             print('calibration: best gamma %g, harmonic mean IU %.3f' % best)
@@ -557,6 +611,29 @@ class Trainer(object):
             self.tb_writer.add_scalar('fcn/val/calib/best_harmonic_mean_iu', best[1], self.epoch)
         else:
             print('calibration: no gamma has a harmonic mean IU (the validation set holds no seen or no unseen pixels)')
+
+    # the seen-mask threshold: as above, the threshold in use (tau = 0 without one: the plain route's decision) joins the sweep's taus
+    _seen_hist = None                           # the (G,K,K) device histogram of the running validate(True), None outside a sweep
+
+    def _seen_taus(self):
+        if self._seen_hist is None:
+            return [self.seen_threshold]
+        return self._seen_all
+
+    def _seen_index(self):
+        tau = 0.0 if self.seen_threshold is None else self.seen_threshold
+        return 0 if self._seen_hist is None else int(np.searchsorted(self._seen_all, np.float32(tau)))
+
+    def _seen_report(self, hist_all):
+        """rank 0, once per validate(True): one seen_sweep_log.csv row per tau of the sweep, and the tau with the largest harmonic mean"""
+        best = self._sweep_report(hist_all, self._seen_all, self.seen_sweep, 'seen_sweep_log.csv', 'tau')
+        if best is not None:
+            self.best_seen_tau, self.best_seen_harmonic_mean_iu = best
+            print('seen-mask threshold: best tau %g, harmonic mean IU %.3f' % best)
+            self.tb_writer.add_scalar('fcn/val/seen_sweep/best_tau', best[0], self.epoch)
+            self.tb_writer.add_scalar('fcn/val/seen_sweep/best_harmonic_mean_iu', best[1], self.epoch)
+        else:
+            print('seen-mask threshold: no tau has a harmonic mean IU (the validation set holds no seen or no unseen pixels)')
 
     def validate(self, both_fcn_and_seenmask=False):
         """reference :182-292.  The {all, seen, unseen} K x K histograms and the loss sum are accumulated on the GPU
@@ -577,6 +654,16 @@ class Trainer(object):
                 from ._lib import SznError
                 raise SznError("calibration: a 64-gamma sweep has no room for a calibration value that is not one of its gammas")
             self._calib_hist = torch.zeros(self._calib_all.size, self.n_class, self.n_class, dtype=torch.int64, device=self.device)
+        if not both_fcn_and_seenmask and (self.seen_threshold is not None or self.seen_sweep is not None):
+            from ._lib import SznError
+            raise SznError(seen_threshold_refused(True, True, False, False, False, self.n_class))
+        if both_fcn_and_seenmask and self.seen_sweep is not None:
+            extra = [np.float32(0.0 if self.seen_threshold is None else self.seen_threshold)]
+            self._seen_all = np.unique(np.concatenate([self.seen_sweep, np.asarray(extra, dtype=np.float32)]))
+            if self._seen_all.size > 64:
+                from ._lib import SznError
+                raise SznError("seen sweep: a 64-tau sweep has no room for a reported threshold (seen_threshold, else 0) that is not one of its taus")
+            self._seen_hist = torch.zeros(self._seen_all.size, self.n_class, self.n_class, dtype=torch.int64, device=self.device)
         n_viz = self.visualize if self.rank == 0 else 0                        # rank 0 renders the first images of its own shard
         tiles = []                                                             # device pictures, kept there until the epoch ends
         mean_bgr = vis_utils.dataset_mean_bgr(getattr(self.val_loader, 'dataset', None)) if n_viz else None
@@ -597,16 +684,23 @@ class Trainer(object):
                     print("Test Epoch {:<5} | Iteration {:<5} | Loss {:5.5f} | Score Sum {:10.5f}".format(
                         int(self.epoch), int(batch_idx), float(loss.item()), float(score.sum().item())))
         calib_hist, self._calib_hist = self._calib_hist, None
+        seen_hist, self._seen_hist = self._seen_hist, None
         if world > 1:
             dist.all_reduce(hist)
             dist.all_reduce(acc)
             if calib_hist is not None:
                 dist.all_reduce(calib_hist)
+            if seen_hist is not None:
+                dist.all_reduce(seen_hist)
         h = hist.cpu().numpy()
         if calib_hist is not None:
             calib_hist = calib_hist.cpu().numpy()
             if self.rank == 0:
                 self._calib_report(calib_hist)
+        if seen_hist is not None:
+            seen_hist = seen_hist.cpu().numpy()
+            if self.rank == 0:
+                self._seen_report(seen_hist)
         accn = acc.cpu().numpy()
         if np.isnan(accn[0]):
             raise ValueError('loss is nan while validating')
