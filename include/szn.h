@@ -549,6 +549,35 @@ int szn_fused_simce_head_prepared(int stride, int B, int h, int w, int E, int ld
                                   const szn_class_set* exclude, float temperature, float* loss, float* stats, int64_t* pred,
                                   int dcoarse_dtype, void* dcoarse, void* workspace, szn_stream_t stream);
 
+/* ---- fused hinge ranking head (train.py -loss rank, DeViSE): the label's cosine against the other seen classes', without the score ----
+ * Equivalent to szn_bilinear_up_crop_fwd(stride) -> utils.rank_loss (forward and autograd backward) -> szn_embed_argmax_k ->
+ * szn_bilinear_up_crop_bwd(stride).  Arguments, strides (32 | 8), group modes, NULL rules (pred-only, loss-only, no dcoarse), error
+ * codes, workspace (szn_fused_head_workspace_bytes) and prepare step (szn_fused_head_prepare for _prepared) are those of
+ * szn_fused_mse_head[_prepared]; pred is szn_fused_head_grouped's pred bit for bit.  For a pixel with upsampled score s (fp32
+ * arithmetic), cos_k and n_k as szn_fused_simce_head defines them (n_k = 1 where |e_k| = 0):
+ *   S = the classes of [0, K) not in `exclude` (NULL: all K compete);  v_k = margin - cos_label + cos_k for k in S, k != label;
+ *   hardest = 0 (sum of hinges):  term = sum_k max(0, v_k),  c_k = 1[v_k > 0];
+ *   hardest = 1 (hardest negative):  k* = argmax_k v_k (the lowest index on an exact tie),  term = max(0, v_k*),  c_k* = 1[v_k* > 0],
+ *   every other c_k = 0;   c_label = -sum_{k != label} c_k.
+ * A pixel counts when 0 <= label < K and label is in S (sim_ce's rule): -1, -2, -3 (hidden), labels >= K and labels in `exclude` are
+ * ignored.  stats f32 [B][2] = {sum of terms, number of counted px}; loss = mean_b S_b / N_b.  dcoarse = d loss / d coarse with
+ *   d term / d s = sum_k c_k (e_k / (|s| n_k) - cos_k s / |s|^2)
+ * (at v_k = 0 exactly the coefficient is 0: the hinge is flat there as far as this head is concerned), scaled by 1 / (B N_b) and carried back through the
+ * upsample, channels [c0, c0+E) only, in dcoarse_dtype.  A pred-only call (target NULL) evaluates no hinge.  Errors, all before any
+ * launch: margin < 0 or not finite, hardest not 0 | 1, a class in `exclude` >= K, and an `exclude` that leaves fewer than two classes
+ * competing (the loss would be identically zero) are SZN_ERR_ARG.  Fixed-order reductions, no atomics: two calls give bitwise-equal
+ * outputs.                                                                                                                             */
+int szn_fused_rank_head(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                        const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
+                        int group_mode, const int64_t* group_map, const szn_class_set* exclude, float margin, int hardest,
+                        float* loss, float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
+                        szn_stream_t stream);
+int szn_fused_rank_head_prepared(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                                 const float* coarse, const float* embed, const int64_t* target,
+                                 const szn_class_set* unseen, int group_mode, const int64_t* group_map,
+                                 const szn_class_set* exclude, float margin, int hardest, float* loss, float* stats, int64_t* pred,
+                                 int dcoarse_dtype, void* dcoarse, void* workspace, szn_stream_t stream);
+
 /* ---- fused softmax cross-entropy head: coarse -> (loss, stats, prediction, dcoarse) without the (B,C,H,W) score ---------
  * Equivalent to szn_bilinear_up_crop_fwd(stride) -> szn_ce2d_fwd (pred = channel argmax) -> szn_ce2d_bwd (gout NULL) ->
  * szn_bilinear_up_crop_bwd(stride) (models.py:94,146-147 upscore + crop, utils.py:19-48 cross_entropy2d, trainer_fcn.py:117

@@ -31,6 +31,7 @@
 //                        (a prefix scan), the target with the easy pixels dropped
 //   sce_cell_kernel / sce_cell_tab_kernel   szn_fused_simce_head (similarity cross-entropy): the same G and Q, a softmax over the classes per
 //                        pixel (sce_pixel) and a dense A through a per-wave LDS tile (sce_dense_A); sums, finalize and gather as above
+//                        The same two kernels over RankArgs: szn_fused_rank_head (hinge ranking loss), one walk over the classes per pixel
 // Both cell kernels run the same per-pixel body (fh_pixel) and the same label loop (fh_scatter_A), and write per cell: pred, the
 // loss partial, A and Bm.
 //
@@ -642,27 +643,35 @@ __device__ __forceinline__ ScePx sce_pixel(const FhArgs& a, const SceArgs& s, in
     return px;
 }
 
-// A[t][k] += sum over the wave's 64 pixels of w_t (y_k - p_k) / (T |s| n_k), every k < K.  wl: this wave's kSceWave floats of LDS.
-// Block-uniform control flow (the barriers order the tile writes before the column reads, and the reads before the next writes).
+// The per-pixel coefficient of class k that sim_ce hands to the dense-A pass: (y_k - p_k) / (T |s| n_k), 0 for a pixel that does not
+// count and a class that does not compete.
 template <int KP>
-__device__ __forceinline__ void sce_dense_A(const FhArgs& a, const SceArgs& s, const ScePx& px, const float* G,
-                                            const float* __restrict__ en, int lane, float* wl, float* myA) {
+struct SceCoef {
+    const SceArgs& s; const ScePx& px; const float* G; const float* __restrict__ en; float aco;
+    __device__ __forceinline__ SceCoef(const SceArgs& s_, const ScePx& px_, const float* G_, const float* __restrict__ en_)
+        : s(s_), px(px_), G(G_), en(en_), aco(s_.inv_t * px_.rsn) {}
+    __device__ __forceinline__ float operator()(int k) const {
+        float c = 0.f;
+        if (px.counted && sce_competes(s, k)) {
+            const float p = expf(sce_cos<KP>(px.wt, G, px.rsn, en, k) * s.inv_t - px.m) * px.rsum;
+            c = (((long)k == px.lbl ? 1.f : 0.f) - p) * (aco * __builtin_amdgcn_rcpf(en[k]));
+        }
+        return c;
+    }
+};
+
+// A[t][k] += sum over the wave's 64 pixels of w_t coef(k), every k < K; coef(k) is this lane's pixel's coefficient of class k (SceCoef,
+// RankCoef), wt its tap weights.  wl: this wave's kSceWave floats of LDS.
+// Block-uniform control flow (the barriers order the tile writes before the column reads, and the reads before the next writes).
+template <int KP, class Coef>
+__device__ __forceinline__ void sce_dense_A(const FhArgs& a, const float (&wt)[4], const Coef& coef, int lane, float* wl, float* myA) {
     float* tile = wl;
     float* wpx = wl + 64 * kSceRow;
 #pragma unroll
-    for (int t = 0; t < 4; ++t) wpx[lane * 4 + t] = px.wt[t];
-    const float aco = s.inv_t * px.rsn;
+    for (int t = 0; t < 4; ++t) wpx[lane * 4 + t] = wt[t];
     for (int k0 = 0; k0 < a.K; k0 += 64) {
         const int nk = min(64, a.K - k0);
-        for (int kk = 0; kk < nk; ++kk) {
-            const int k = k0 + kk;
-            float c = 0.f;
-            if (px.counted && sce_competes(s, k)) {
-                const float p = expf(sce_cos<KP>(px.wt, G, px.rsn, en, k) * s.inv_t - px.m) * px.rsum;
-                c = (((long)k == px.lbl ? 1.f : 0.f) - p) * (aco * __builtin_amdgcn_rcpf(en[k]));
-            }
-            tile[lane * kSceRow + kk] = c;
-        }
+        for (int kk = 0; kk < nk; ++kk) tile[lane * kSceRow + kk] = coef(k0 + kk);
         __syncthreads();
         if (lane < nk) {
             float acc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -677,14 +686,101 @@ __device__ __forceinline__ void sce_dense_A(const FhArgs& a, const SceArgs& s, c
         __syncthreads();
     }
 }
+template <int KP>
+__device__ __forceinline__ SceCoef<KP> sce_coef(const SceArgs& s, const ScePx& px, const float* G, const float* __restrict__ en) {
+    return SceCoef<KP>(s, px, G, en);
+}
+
+// ---- hinge ranking loss (szn_fused_rank_head, DeViSE): the pixel's own class must beat every other competing class by a margin ---------
+// v_k = margin - cos_label + cos_k, k in S \ {label}.  Sum of hinges: term = sum_k max(0, v_k), c_k = 1[v_k > 0]; hardest negative:
+// term = max(0, v_k*), k* = the lowest index of the largest v_k, c_k* = 1[v_k* > 0]; c_label = -sum_k c_k.  The gradient has sim_ce's
+// shape with c_k in the place of (p_k - y_k) / T, so the cell kernels, the tile and everything downstream are sim_ce's:
+//     A[t][k] = -sum_px w_t c_k / (|s| n_k),      Bm[t][u] = -sum_px w_t w_u sum_k c_k cos_k / |s|^2
+// One walk over the classes per pixel (term, number of violators, sum of their cosines | the best negative); no exponential, no
+// logarithm.  The dense-A pass re-derives 1[v_k > 0] from the same sce_cos and the same rank_v > 0 as that walk (hardest: from the
+// stored k*), so A and Bm describe one sub-gradient.  v_k = 0 exactly: coefficient 0.
+struct RankArgs { ClassBits excl; float margin; int hardest; };
+// mcl = margin - cos_label; nv = -c_label (the number of violators, 0 | 1 for hardest); kstar: hardest only, -1 without a violator
+struct RankPx { float wt[4]; long lbl; bool counted; float rsn, mcl, nv; int kstar; };
+
+__device__ __forceinline__ bool sce_competes(const RankArgs& s, int k) { return !((class_word(s.excl, k >> 6) >> (k & 63)) & 1ull); }
+__device__ __forceinline__ float rank_v(float mcl, float c) { return mcl + c; }
+
+template <int KP, int S, bool GROUPED>
+__device__ __forceinline__ RankPx sce_pixel(const FhArgs& a, const RankArgs& s, int b, int I, int J, int ty, int tx, bool live,
+                                            const float* G, const float* Q, const float* __restrict__ en, float (&bm)[16],
+                                            double& term_sum, double& cnt) {
+    RankPx px = {{0.f, 0.f, 0.f, 0.f}, -1, false, 0.f, 0.f, 0.f, -1};
+    const int y = S * I + ty - a.crop, x = S * J + tx - a.crop;
+    if (live && y >= 0 && y < a.H && x >= 0 && x < a.W) {
+        cell_weights<S>(ty, tx, px.wt);
+        const float (&wt)[4] = px.wt;
+        const float ss = fh_ss(wt, Q);
+        const float sn = sqrtf(ss);
+        const size_t pix = ((size_t)b * a.H + y) * a.W + x;
+        px.lbl = a.target ? a.target[pix] : -1;
+        if (GROUPED || a.pred) a.pred[pix] = fh_argmax<KP, GROUPED>(a, wt, G, sn, en, pix, px.lbl);
+        if (px.lbl >= 0 && px.lbl < a.K && !in_set(s.excl, px.lbl)) {
+            const float rsn = 1.f / sn;
+            const float cl = sce_cos<KP>(wt, G, rsn, en, (int)px.lbl);
+            const float mcl = s.margin - cl;
+            float term = 0.f, nv = 0.f, sc = 0.f;
+            if (s.hardest) {
+                float best = -INFINITY, cbest = 0.f;
+                int kb = -1;
+                for (int k = 0; k < a.K; ++k)
+                    if ((long)k != px.lbl && sce_competes(s, k)) {
+                        const float c = sce_cos<KP>(wt, G, rsn, en, k);
+                        const float v = rank_v(mcl, c);
+                        if (v > best) { best = v; cbest = c; kb = k; }      // strict: the lowest index on a tie
+                    }
+                if (best > 0.f) { term = best; nv = 1.f; sc = cbest; px.kstar = kb; }
+            } else {
+                for (int k = 0; k < a.K; ++k)
+                    if ((long)k != px.lbl && sce_competes(s, k)) {
+                        const float c = sce_cos<KP>(wt, G, rsn, en, k);
+                        const float v = rank_v(mcl, c);
+                        if (v > 0.f) { term += v; nv += 1.f; sc += c; }
+                    }
+            }
+            term_sum += (double)term;
+            cnt += 1.0;
+            px.counted = true; px.rsn = rsn; px.mcl = mcl; px.nv = nv;
+            const float bco = (nv * cl - sc) / ss;
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int u = 0; u < 4; ++u) bm[t * 4 + u] = fmaf(wt[t] * wt[u], bco, bm[t * 4 + u]);
+        }
+    }
+    return px;
+}
+
+// -c_k / (|s| n_k): nv for the label, -1 for a violator (hardest: for k*), 0 elsewhere
+template <int KP>
+struct RankCoef {
+    const RankArgs& s; const RankPx& px; const float* G; const float* __restrict__ en;
+    __device__ __forceinline__ float operator()(int k) const {
+        if (!px.counted || px.nv == 0.f) return 0.f;
+        float c = 0.f;
+        if ((long)k == px.lbl) c = px.nv;
+        else if (s.hardest ? k == px.kstar : sce_competes(s, k) && rank_v(px.mcl, sce_cos<KP>(px.wt, G, px.rsn, en, k)) > 0.f) c = -1.f;
+        return c == 0.f ? 0.f : c * (px.rsn * __builtin_amdgcn_rcpf(en[k]));
+    }
+};
+template <int KP>
+__device__ __forceinline__ RankCoef<KP> sce_coef(const RankArgs& s, const RankPx& px, const float* G, const float* __restrict__ en) {
+    return RankCoef<KP>{s, px, G, en};
+}
 
 // dynamic LDS in floats: stride 32 fh_lds(E, KP, false) | 4 waves' tiles; stride 8 G [4][4 KP] | A [4][4 KP] | Q [4][16] | the tiles
 __host__ __device__ inline size_t sce_lds_floats(int stride, int E, int KP) {
     return (stride == 8 ? (size_t)32 * KP + 64 : (size_t)fh_lds(E, KP, false).end) + 4 * kSceWave;
 }
 
-template <int KP, bool GROUPED>
-__global__ __launch_bounds__(256) void sce_cell_kernel(FhArgs a, SceArgs s) {        // stride 32: one block per (image, cell)
+// LA: SceArgs (sim_ce) | RankArgs (rank); sce_pixel and sce_coef are overloaded on it
+template <int KP, bool GROUPED, class LA>
+__global__ __launch_bounds__(256) void sce_cell_kernel(FhArgs a, LA s) {        // stride 32: one block per (image, cell)
     constexpr int S = 32;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const FhLds L = fh_lds(a.E, KP, false);
@@ -715,8 +811,8 @@ __global__ __launch_bounds__(256) void sce_cell_kernel(FhArgs a, SceArgs s) {   
     double term_sum = 0.0, cnt = 0.0;
     float* myA = Aw + wave * 4 * KP;
     for (int q = tid; q < S * S; q += 256) {         // four rounds for every thread: the barriers of sce_dense_A are block-uniform
-        const ScePx px = sce_pixel<KP, S, GROUPED>(a, s, b, I, J, q / S, q % S, true, G, Q, en, bm, term_sum, cnt);
-        if (a.target) sce_dense_A<KP>(a, s, px, G, en, lane, wl, myA);
+        const auto px = sce_pixel<KP, S, GROUPED>(a, s, b, I, J, q / S, q % S, true, G, Q, en, bm, term_sum, cnt);
+        if (a.target) sce_dense_A<KP>(a, px.wt, sce_coef<KP>(s, px, G, en), lane, wl, myA);
     }
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
@@ -735,8 +831,8 @@ __global__ __launch_bounds__(256) void sce_cell_kernel(FhArgs a, SceArgs s) {   
     }
 }
 
-template <int KP, bool GROUPED>
-__global__ __launch_bounds__(256) void sce_cell_tab_kernel(FhArgs a, SceArgs s, const float* __restrict__ D,
+template <int KP, bool GROUPED, class LA>
+__global__ __launch_bounds__(256) void sce_cell_tab_kernel(FhArgs a, LA s, const float* __restrict__ D,
                                                            const float* __restrict__ N) {      // stride 8: one wave per cell
     constexpr int S = 8;
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -765,8 +861,8 @@ __global__ __launch_bounds__(256) void sce_cell_tab_kernel(FhArgs a, SceArgs s, 
 #pragma unroll
     for (int u = 0; u < 16; ++u) bm[u] = 0.f;
     double term_sum = 0.0, cnt = 0.0;
-    const ScePx px = sce_pixel<KP, S, GROUPED>(a, s, b, I, J, lane / S, lane % S, ok && lane < S * S, G, Q, en, bm, term_sum, cnt);
-    if (a.target) sce_dense_A<KP>(a, s, px, G, en, lane, wl, myA);
+    const auto px = sce_pixel<KP, S, GROUPED>(a, s, b, I, J, lane / S, lane % S, ok && lane < S * S, G, Q, en, bm, term_sum, cnt);
+    if (a.target) sce_dense_A<KP>(a, px.wt, sce_coef<KP>(s, px, G, en), lane, wl, myA);
     float bs[16];
 #pragma unroll
     for (int u = 0; u < 16; ++u) bs[u] = wave_sum(bm[u]);
@@ -1545,27 +1641,38 @@ void fh_launch_kp(bool grouped, bool mse, int stride, const FhArgs& a, float* ta
     else mse ? fh_launch<KP, false, true>(stride, a, tabD, tabN, st) : fh_launch<KP, false, false>(stride, a, tabD, tabN, st);
 }
 
-// the similarity cross-entropy cell pass: the same two shapes; the LDS is dynamic at both strides (the tiles take it past 48 KB)
-template <int KP, bool GROUPED>
-void sce_launch(int stride, const FhArgs& a, const SceArgs& s, float* tabD, float* tabN, hipStream_t st) {
+// the similarity cross-entropy and ranking cell pass: the same two shapes; the LDS is dynamic at both strides (the tiles take it past 48 KB)
+template <int KP, bool GROUPED, class LA>
+void sce_launch(int stride, const FhArgs& a, const LA& s, float* tabD, float* tabN, hipStream_t st) {
     const int cells = (a.h + 1) * (a.w + 1);
     const size_t lds = sce_lds_floats(stride, a.E, KP) * sizeof(float);
     if (stride == 8) {
         hipLaunchKernelGGL(fh_tables_kernel<KP>, dim3((unsigned)(((long)a.B * a.h * a.w + 3) / 4)), dim3(256),
                            (size_t)4 * a.E * sizeof(float), st, a, tabD, tabN);
-        auto kern = sce_cell_tab_kernel<KP, GROUPED>;
+        auto kern = sce_cell_tab_kernel<KP, GROUPED, LA>;
         (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(kern, dim3((unsigned)(((long)a.B * cells + 3) / 4)), dim3(256), lds, st, a, s, (const float*)tabD,
                            (const float*)tabN);
     } else {
-        auto kern = sce_cell_kernel<KP, GROUPED>;
+        auto kern = sce_cell_kernel<KP, GROUPED, LA>;
         (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(kern, dim3(a.B * cells), dim3(256), lds, st, a, s);
     }
 }
-template <int KP>
-void sce_launch_kp(bool grouped, int stride, const FhArgs& a, const SceArgs& s, float* tabD, float* tabN, hipStream_t st) {
+template <int KP, class LA>
+void sce_launch_kp(bool grouped, int stride, const FhArgs& a, const LA& s, float* tabD, float* tabN, hipStream_t st) {
     grouped ? sce_launch<KP, true>(stride, a, s, tabD, tabN, st) : sce_launch<KP, false>(stride, a, s, tabD, tabN, st);
+}
+template <class LA>
+void sce_launch_k(int KP, bool grouped, int stride, const FhArgs& a, const LA& s, float* tabD, float* tabN, hipStream_t st) {
+    switch (KP) {
+        case 24: sce_launch_kp<24>(grouped, stride, a, s, tabD, tabN, st); break;
+        case 40: sce_launch_kp<40>(grouped, stride, a, s, tabD, tabN, st); break;
+        case 64: sce_launch_kp<64>(grouped, stride, a, s, tabD, tabN, st); break;
+        case 128: sce_launch_kp<128>(grouped, stride, a, s, tabD, tabN, st); break;
+        case 192: sce_launch_kp<192>(grouped, stride, a, s, tabD, tabN, st); break;
+        default: sce_launch_kp<256>(grouped, stride, a, s, tabD, tabN, st); break;
+    }
 }
 
 template <typename T, bool MSE>
@@ -1579,13 +1686,15 @@ void fh_launch_gather_t(bool mse, const FhArgs& a, const float* stats, void* dco
 }
 
 // every szn_fused_*head* entry point: prep = build the embedding tables first; unseen / group_mode / group_map as in
-// szn_fused_head_grouped (NULL, 0, NULL: ungrouped); kind = the loss; exclude / temperature: FH_SIMCE only
-enum FhKind { FH_COS, FH_MSE, FH_SIMCE };
+// szn_fused_head_grouped (NULL, 0, NULL: ungrouped); kind = the loss; exclude: FH_SIMCE and FH_RANK; temperature: FH_SIMCE only;
+// margin / hardest: FH_RANK only
+enum FhKind { FH_COS, FH_MSE, FH_SIMCE, FH_RANK };
 int fused_head_impl(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
                     const float* coarse, const float* embed, const int64_t* target, float* loss,
                     float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
                     szn_stream_t stream, bool prep, const szn_class_set* unseen, int group_mode,
-                    const int64_t* group_map, FhKind kind, const szn_class_set* exclude = nullptr, float temperature = 1.f) {
+                    const int64_t* group_map, FhKind kind, const szn_class_set* exclude = nullptr, float temperature = 1.f,
+                    float margin = 0.f, int hardest = 0) {
     const bool mse = kind == FH_MSE;
     if (stride != 32 && stride != 8) SZN_FAIL(SZN_ERR_UNSUPPORTED, "fused_head: stride %d (32 and 8 are built)", stride);
     if (!coarse || !embed || !workspace || B <= 0 || h <= 0 || w <= 0 || E <= 0 || c0 < 0 || ldc < c0 + E || H <= 0 ||
@@ -1613,11 +1722,23 @@ int fused_head_impl(int stride, int B, int h, int w, int E, int ldc, int c0, int
         if (n_excl >= K) SZN_FAIL(SZN_ERR_ARG, "fused_simce_head: the exclude set leaves none of the %d classes competing", K);
         sce.inv_t = 1.f / temperature;
     }
+    RankArgs rank{};
+    if (kind == FH_RANK) {
+        if (!(margin >= 0.f) || !isfinite(margin)) SZN_FAIL(SZN_ERR_ARG, "fused_rank_head: margin %g is not a finite number >= 0", (double)margin);
+        if (hardest != 0 && hardest != 1) SZN_FAIL(SZN_ERR_ARG, "fused_rank_head: hardest %d is neither 0 nor 1", hardest);
+        rank.excl = class_bits(exclude);
+        if (!class_bits_fit(rank.excl, K)) SZN_FAIL(SZN_ERR_ARG, "fused_rank_head: the exclude set names a class >= K = %d", K);
+        int n_excl = 0;
+        for (int i = 0; i < 4; ++i) n_excl += __builtin_popcountll(rank.excl.w[i]);
+        if (K - n_excl < 2) SZN_FAIL(SZN_ERR_ARG, "fused_rank_head: the exclude set leaves %d of the %d classes competing (two are needed)", K - n_excl, K);
+        rank.margin = margin; rank.hardest = hardest;
+    }
+    const bool dense = kind == FH_SIMCE || kind == FH_RANK;
     const bool grouped = group_mode != 0;
     hipStream_t st = (hipStream_t)stream;
     const int KP = kp_of(K);
     const int cells = (h + 1) * (w + 1);
-    if (fh_lds(E, KP, mse).bytes() > 150 * 1024 || (kind == FH_SIMCE && sce_lds_floats(stride, E, KP) * sizeof(float) > 150 * 1024))
+    if (fh_lds(E, KP, mse).bytes() > 150 * 1024 || (dense && sce_lds_floats(stride, E, KP) * sizeof(float) > 150 * 1024))
         SZN_FAIL(SZN_ERR_UNSUPPORTED, "fused_head: E=%d too large for LDS", E);
     const FhWorkspace wl = fh_workspace(B, h, w, E, KP);
     char* ws = (char*)workspace;
@@ -1634,14 +1755,8 @@ int fused_head_impl(int stride, int B, int h, int w, int E, int ldc, int c0, int
     a.coarse = coarse; a.embed = embed; a.target = target; a.pred = pred; a.ws_f = ws_f; a.part = part;
     a.B = B; a.h = h; a.w = w; a.E = E; a.ldc = ldc; a.c0 = c0; a.H = H; a.W = W; a.crop = crop; a.K = K; a.KP = KP;
     a.gmap = group_map; a.gmode = group_mode; a.unseen = ubits;
-    if (kind == FH_SIMCE) switch (KP) {
-        case 24: sce_launch_kp<24>(grouped, stride, a, sce, tabD, tabN, st); break;
-        case 40: sce_launch_kp<40>(grouped, stride, a, sce, tabD, tabN, st); break;
-        case 64: sce_launch_kp<64>(grouped, stride, a, sce, tabD, tabN, st); break;
-        case 128: sce_launch_kp<128>(grouped, stride, a, sce, tabD, tabN, st); break;
-        case 192: sce_launch_kp<192>(grouped, stride, a, sce, tabD, tabN, st); break;
-        default: sce_launch_kp<256>(grouped, stride, a, sce, tabD, tabN, st); break;
-    }
+    if (kind == FH_SIMCE) sce_launch_k(KP, grouped, stride, a, sce, tabD, tabN, st);
+    else if (kind == FH_RANK) sce_launch_k(KP, grouped, stride, a, rank, tabD, tabN, st);
     else switch (KP) {
         case 24: fh_launch_kp<24>(grouped, mse, stride, a, tabD, tabN, st); break;
         case 40: fh_launch_kp<40>(grouped, mse, stride, a, tabD, tabN, st); break;
@@ -1769,6 +1884,26 @@ extern "C" int szn_fused_simce_head_prepared(int stride, int B, int h, int w, in
                                              int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace, szn_stream_t stream) {
     return fused_head_impl(stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype, dcoarse,
                            workspace, stream, false, unseen, group_mode, group_map, FH_SIMCE, exclude, temperature);
+}
+
+// The hinge ranking loss (train.py -loss rank; utils.rank_loss) through the same head: the label's cosine against the cosines of the
+// other classes outside `exclude`, sum of hinges (hardest = 0) or the hardest negative alone (hardest = 1) (include/szn.h).
+extern "C" int szn_fused_rank_head(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                                   const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
+                                   int group_mode, const int64_t* group_map, const szn_class_set* exclude, float margin, int hardest,
+                                   float* loss, float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
+                                   szn_stream_t stream) {
+    return fused_head_impl(stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype, dcoarse,
+                           workspace, stream, true, unseen, group_mode, group_map, FH_RANK, exclude, 1.f, margin, hardest);
+}
+
+extern "C" int szn_fused_rank_head_prepared(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                                            const float* coarse, const float* embed, const int64_t* target,
+                                            const szn_class_set* unseen, int group_mode, const int64_t* group_map,
+                                            const szn_class_set* exclude, float margin, int hardest, float* loss, float* stats,
+                                            int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace, szn_stream_t stream) {
+    return fused_head_impl(stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype, dcoarse,
+                           workspace, stream, false, unseen, group_mode, group_map, FH_RANK, exclude, 1.f, margin, hardest);
 }
 
 // Calibrated stacking (include/szn.h): the seen-class penalty gamma swept over n_gammas values in one pass over the pixels.

@@ -375,7 +375,8 @@ class TrainStep(object):
                  adam_weight_decay=0.0, grad_comm_dtype=None, loss_scale=None, dynamic_loss_scale=None,
                  scale_growth=2.0, scale_backoff=0.5, scale_growth_interval=2000, force_comm=None, reserved_cus=None,
                  fused_adam=None, keep_grads=True, exchange=None, direct_wire=None, sharded=None, forced_unseen=None,
-                 class_weight=None, size_average=False, sim_exclude=None, sim_temperature=None, pseudo=None, ohem=None):
+                 class_weight=None, size_average=False, sim_exclude=None, sim_temperature=None, pseudo=None, ohem=None,
+                 rank_margin=None, rank_hardest=False):
         """Data-parallel knobs (the reference is single-GPU): grad_comm_dtype (SZN_GRAD_COMM = fp32 | bf16) = the
         wire format of the gradient buckets; exchange=False (SZN_GRAD_COMM=off) = no exchange at all (bench.py's comm-off timing);
         direct_wire (default: on for a 16-bit wire with keep_grads=False; SZN_WIRE_DIRECT=0 turns it off) = the weight-gradient
@@ -392,12 +393,16 @@ class TrainStep(object):
         loss="sim_ce" (utils.sim_ce_loss; szn_fused_simce_head): a softmax over the cosines of the classes outside sim_exclude (a list
         of class indices, the trainer's unseen classes; None: all compete) divided by sim_temperature (None: heads.SIM_TEMPERATURE),
         cross entropy against the label.  Fused head only: fused_head=False raises (no materialised kernels were built for it).
+        loss="rank" (utils.rank_loss; szn_fused_rank_head): the hinge ranking loss -- the label's cosine must exceed the cosine of every
+        other class outside sim_exclude (the same exclude set as sim_ce's) by rank_margin (None: heads.RANK_MARGIN); rank_hardest
+        keeps the hardest negative alone instead of the sum of hinges.  Fused head only, like sim_ce; wherever the step treats
+        sim_ce's exclude set specially (pseudo labels, ohem) it treats this one the same.
         pseudo=dict(unseen=[...], gamma=0.0, keep=0.3, conf_floor=-2.0) (embedding losses only): self-training on the pixels a
         hide_unseen dataset hides (label datasets.HIDDEN_LABEL).  After the forward pass szn_pseudo_head runs on the step's own head map
         (the 1/32 map, FCN8s: the 1/8 fused map) and stream: the calibrated rule at gamma picks the hidden pixels it gives to an unseen
         class with a similarity of at least conf_floor, per class the most confident `keep` of them take that class as their label, and
         the head -- fused or the fused_head=False referee -- trains on the relabelled target.  The train-metric histogram keeps the
-        caller's target.  set_pseudo_active(False) makes the step the plain step again, launch for launch; with loss "sim_ce" the active
+        caller's target.  set_pseudo_active(False) makes the step the plain step again, launch for launch; with loss "sim_ce" or "rank" the active
         step empties sim_exclude (the unseen classes now have positives), the inactive one restores it.  pseudo_counts, a device (K,2) int64
         tensor, accumulates {candidates, selected} per class until the caller zeroes it; with keep_ctx the relabelled target of the last
         step stays in last_pseudo_target.  Under data parallelism the thresholds are those of each rank's own batch: nothing is
@@ -407,19 +412,25 @@ class TrainStep(object):
         image the `keep` (a share in (0, 1]) of the labelled pixels whose cosine to their own class embedding is lowest, and every pixel
         whose cosine lies below `thresh` (None: no threshold; bins of 1/512), keep their label, the others read heads.OHEM_DROP_LABEL,
         and the head -- fused or the fused_head=False referee -- trains on that target.  Hardness is the own-class cosine for all three
-        losses; with loss "sim_ce" the labels in the exclude set the step is using at that moment are neither counted nor dropped.  The
+        losses; with loss "sim_ce" or "rank" the labels in the exclude set the step is using at that moment are neither counted nor dropped.  The
         caller's target tensor is never written and the train-metric histogram keeps it (with forced_unseen the dropped pixels of the
         train prediction compete in the seen group, like every ignored pixel).  set_ohem_active(False) makes the step the plain step
         again, launch for launch.  ohem_counts, a device (2,) int64 tensor, accumulates {evaluated, kept} over images and steps until the
         caller zeroes it; with keep_ctx the mined target of the last step stays in last_ohem_target.  Under data parallelism the cuts
         belong to each rank's own images: nothing is exchanged."""
-        if loss not in ("cos", "mse", "sim_ce", "cross_entropy"):
-            raise L.SznError("TrainStep: loss must be 'cos', 'mse', 'sim_ce' or 'cross_entropy', got %r" % (loss,))
-        if loss != "sim_ce" and (sim_exclude is not None or sim_temperature is not None):
-            raise L.SznError("TrainStep: sim_exclude / sim_temperature belong to loss 'sim_ce', not %r" % (loss,))
+        if loss not in ("cos", "mse", "sim_ce", "rank", "cross_entropy"):
+            raise L.SznError("TrainStep: loss must be 'cos', 'mse', 'sim_ce', 'rank' or 'cross_entropy', got %r" % (loss,))
+        if (loss not in ("sim_ce", "rank") and sim_exclude is not None) or (loss != "sim_ce" and sim_temperature is not None):
+            raise L.SznError("TrainStep: sim_exclude belongs to loss 'sim_ce' or 'rank' and sim_temperature to loss 'sim_ce', not %r"
+                             % (loss,))
+        if loss != "rank" and (rank_margin is not None or rank_hardest):
+            raise L.SznError("TrainStep: rank_margin / rank_hardest belong to loss 'rank', not %r" % (loss,))
         if loss == "sim_ce" and not fused_head:
             raise L.SznError("TrainStep: the sim_ce loss runs on the fused head only; the materialised score goes through autograd "
                              "(utils.sim_ce_loss)")
+        if loss == "rank" and not fused_head:
+            raise L.SznError("TrainStep: the rank loss runs on the fused head only; the materialised score goes through autograd "
+                             "(utils.rank_loss)")
         if pseudo is not None:
             pseudo = self._check_pseudo(pseudo, loss)
         if ohem is not None:
@@ -478,7 +489,7 @@ class TrainStep(object):
             raise L.SznError("TrainStep: forced_unseen names a class outside [0, %d)" % self.K)
         self._unseen_cs = L.class_set(self.forced_unseen) if self.forced_unseen is not None else None
         self._group = 0 if self.forced_unseen is None else 2          # heads.embed group mode: plain / forced unseen
-        self._sim_kw = {}                                             # heads.embed's extra keywords of loss "sim_ce"
+        self._sim_kw = {}                                             # heads.embed's extra keywords of loss "sim_ce" / "rank"
         if loss == "sim_ce":
             excl = sorted(set(int(k) for k in (sim_exclude or [])))
             if any(not 0 <= k < self.K for k in excl) or len(excl) >= self.K:
@@ -487,6 +498,14 @@ class TrainStep(object):
             if not 0 < temp < float("inf"):
                 raise L.SznError("TrainStep: sim_temperature must be positive and finite, got %r" % (sim_temperature,))
             self._sim_kw = dict(exclude=excl, temperature=temp)
+        if loss == "rank":
+            excl = sorted(set(int(k) for k in (sim_exclude or [])))
+            if any(not 0 <= k < self.K for k in excl) or self.K - len(excl) < 2:
+                raise L.SznError("TrainStep: sim_exclude must name classes of [0, %d) and leave two competing for loss 'rank'" % self.K)
+            margin = float(heads.RANK_MARGIN if rank_margin is None else rank_margin)
+            if not 0 <= margin < float("inf"):
+                raise L.SznError("TrainStep: rank_margin must be finite and >= 0, got %r" % (rank_margin,))
+            self._sim_kw = dict(exclude=excl, margin=margin, hardest=bool(rank_hardest))
         self._pseudo = None                                           # szn_pseudo_head's arguments, see set_pseudo_active
         self._pseudo_active = False
         self.last_pseudo_target = None                                # (keep_ctx) the relabelled target the last step's head read
@@ -518,6 +537,9 @@ class TrainStep(object):
         # 4096 x 2 / (T |s|) stays under 65504 once |s| > 0.07 at the worst shape above (B N_b / S^2 = 18), and the scores of a fresh
         # or trained head are orders above that.  Should a batch overflow all the same, the dynamic scale pays log2(2 / T) ~ 5
         # skipped steps at the very start (x 1/2 per overflowing step) and nothing afterwards.
+        # The rank head starts there too: |dL/ds| <= 2 V / |s| for a pixel with V violated hinges (V <= 1 with rank_hardest), the
+        # cosine bound times 2 V.  A fresh head violates most of its up to K - 2 hinges, so the sum form may exceed sim_ce's 2 / T
+        # at first; the dynamic scale pays for that with a few halvings at the start and grows back as the hinges clear.
         fp16_scale0 = 1.0 if self.ce else (512.0 if loss == "mse" else 4096.0)
         self._loss_scale0 = float(loss_scale) if loss_scale is not None else (fp16_scale0 if precision == torch.float16 else 1.0)
         # dynamic loss scaling (default for fp16): the scale, the overflow flag and the count of APPLIED optimizer steps live
@@ -581,7 +603,7 @@ class TrainStep(object):
         """pseudo= checked as far as the host alone can (before anything touches a device) -> (unseen, gamma, permille, conf_floor)"""
         import math
         if loss == "cross_entropy":
-            raise L.SznError("TrainStep: pseudo labels need an embedding loss ('cos' | 'mse' | 'sim_ce'): the cross-entropy head has "
+            raise L.SznError("TrainStep: pseudo labels need an embedding loss ('cos' | 'mse' | 'sim_ce' | 'rank'): the cross-entropy head has "
                              "no unseen-class scores")
         if not isinstance(cfg, dict):
             raise L.SznError("TrainStep: pseudo must be a dict(unseen=, gamma=, keep=, conf_floor=), got %r" % (cfg,))
@@ -615,7 +637,7 @@ class TrainStep(object):
                 raise L.SznError("TrainStep: set_pseudo_active(True) on a step built without pseudo=")
             return
         self._pseudo_active = bool(active)
-        if self.loss_kind == "sim_ce":
+        if self.loss_kind in ("sim_ce", "rank"):
             self._sim_kw["exclude"] = [] if self._pseudo_active else self._sim_exclude
 
     def _head_target(self, stride, fmap, target, H, W, st):
@@ -643,7 +665,7 @@ class TrainStep(object):
         """ohem= checked as far as the host alone can (before anything touches a device) -> (permille, thresh; -2.0: no threshold)"""
         import math
         if loss == "cross_entropy":
-            raise L.SznError("TrainStep: ohem needs an embedding loss ('cos' | 'mse' | 'sim_ce'): hardness is the cosine to the "
+            raise L.SznError("TrainStep: ohem needs an embedding loss ('cos' | 'mse' | 'sim_ce' | 'rank'): hardness is the cosine to the "
                              "pixel's own class embedding, which the cross-entropy head does not have")
         if not isinstance(cfg, dict):
             raise L.SznError("TrainStep: ohem must be a dict(keep=, thresh=None), got %r" % (cfg,))
@@ -689,7 +711,7 @@ class TrainStep(object):
             self._ohem_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
         if self._ohem_step_counts is None or self._ohem_step_counts.shape[0] != B:
             self._ohem_step_counts = torch.zeros(B, 2, dtype=torch.int64, device=self.dev)
-        excl = self._sim_kw.get("exclude") if self.loss_kind == "sim_ce" else None      # the set the head uses in this very step
+        excl = self._sim_kw.get("exclude") if self.loss_kind in ("sim_ce", "rank") else None      # the set the head uses in this very step
         if excl is not self._ohem_skip[0]:
             self._ohem_skip = (excl, L.class_set(excl))
         out = torch.empty_like(target)

@@ -1,7 +1,8 @@
 """heads.py -- the host side of the fused heads: every call into szn_fused_head_grouped[_prepared], szn_fused_mse_head[_prepared],
 szn_fused_ce_head and szn_seenmask_head_k goes through here (models.FCN32s / FCN8s predict methods, engine.TrainStep, engine.SeenmaskStep).
 
-  embed     the embedding head, kind "cos" | "mse" | "sim_ce" (wrappers cosine / cosine_predict, mse / mse_predict, sim_ce / sim_ce_predict):
+  embed     the embedding head, kind "cos" | "mse" | "sim_ce" | "rank" (wrappers cosine / cosine_predict, mse / mse_predict,
+            sim_ce / sim_ce_predict, rank / rank_predict):
   cosine    loss, stats, nearest-embedding prediction and d(map) from an NHWC map: stride 32 on the 1/32 map, stride 8 on FCN8s'
             1/8 fused map (fp32).  Group mode 0 = plain (szn_fused_head_grouped launches exactly what szn_fused_head_strided
             launches, bit for bit), 1 = seen / unseen group from the seen-mask prediction, 2 = forced unseen (group from the target).
@@ -9,6 +10,8 @@ szn_fused_ce_head and szn_seenmask_head_k goes through here (models.FCN32s / FCN
             Workspace tables; loss, stats and d(map) are those of sum |s - e_label|^2 / N_b.
   sim_ce    the same head with the similarity cross-entropy loss (szn_fused_simce_head): a softmax over the cosines of the classes
             outside `exclude`, divided by `temperature`; same prediction bit for bit, same Workspace tables.
+  rank      the same head with the hinge ranking loss (szn_fused_rank_head, DeViSE): the label's cosine must beat the cosine of every
+            other class outside `exclude` by `margin`; `hardest` keeps the hardest negative alone.  Same prediction, same tables.
   ce        the softmax cross-entropy head, stride 32 or 8.
   seenmask  the x32 seen-mask head on the 1/32 map: training, predict and pred-only (group map) calls.
   ms        multi-scale / mirrored inference: the views of an input (szn_resize_flip_f32) and the view-ensemble head (szn_ms_head),
@@ -97,16 +100,17 @@ def _outputs(B, H, W, device, target):
     return pred, target.to(device=device, dtype=torch.int64).contiguous(), torch.empty(1, device=device)
 
 
-# ---- embedding heads (cosine | mse | sim_ce) --------------------------------------------------------------------------------
+# ---- embedding heads (cosine | mse | sim_ce | rank) -------------------------------------------------------------------------
 _EMBED_ENTRY = {"cos": "szn_fused_head_grouped", "mse": "szn_fused_mse_head",      # all share workspace and prepare step
-                "sim_ce": "szn_fused_simce_head"}
+                "sim_ce": "szn_fused_simce_head", "rank": "szn_fused_rank_head"}
 SIM_TEMPERATURE = 0.1        # the default of train.py --sim-temperature: a hyper-parameter default, not a tuned value
+RANK_MARGIN = 0.1            # the default of train.py --rank-margin: DeViSE's value, a hyper-parameter default, not a tuned value
 
 
 def embed_kind(loss):
-    """the embedding heads' loss argument checked: "cos" | "mse" | "sim_ce" """
+    """the embedding heads' loss argument checked: "cos" | "mse" | "sim_ce" | "rank" """
     if loss not in _EMBED_ENTRY:
-        raise L.SznError("embedding head: loss must be 'cos', 'mse' or 'sim_ce', got %r" % (loss,))
+        raise L.SznError("embedding head: loss must be 'cos', 'mse', 'sim_ce' or 'rank', got %r" % (loss,))
     return loss
 
 
@@ -120,10 +124,29 @@ def _sim_args(kind, exclude, temperature):
     return (L.class_set(exclude), float(SIM_TEMPERATURE if temperature is None else temperature))
 
 
+def _rank_args(kind, exclude, margin, hardest):
+    """the three extra C arguments of kind "rank" (exclude: None or an iterable of classes; margin: None = RANK_MARGIN; hardest:
+    None = False); margin / hardest are an error for the other kinds (their exclude is _sim_args' business)"""
+    if kind != "rank":
+        if margin is not None or hardest is not None:
+            raise L.SznError("embedding head: margin / hardest belong to loss 'rank', not %r" % (kind,))
+        return ()
+    return (L.class_set(exclude), float(RANK_MARGIN if margin is None else margin), int(bool(hardest)))
+
+
+def _loss_args(kind, exclude, temperature, margin, hardest):
+    """the extra C arguments of `kind` between group_map and loss; a setting that belongs to another kind is an error"""
+    if kind == "rank":
+        if temperature is not None:
+            raise L.SznError("embedding head: temperature belongs to loss 'sim_ce', not 'rank'")
+        return _rank_args(kind, exclude, margin, hardest)
+    return _sim_args(kind, exclude, temperature) + _rank_args(kind, exclude, margin, hardest)
+
+
 def embed(kind, stride, fmap, emb, H, W, pred, target=None, loss=None, stats=None, dmap=None, mode=0, classes=None, gmap=None,
-          ws=None, stream=None, exclude=None, temperature=None):
+          ws=None, stream=None, exclude=None, temperature=None, margin=None, hardest=None):
     """szn_fused_head_grouped (kind "cos") / szn_fused_mse_head (kind "mse") / szn_fused_simce_head (kind "sim_ce", with exclude = the
-    classes that do not compete and temperature) on the contiguous NHWC map `fmap` (the E embedding channels first).  target / loss / stats go together; dmap (zero-padded, [E, ld) stays untouched) receives d loss / d fmap in its
+    classes that do not compete and temperature) / szn_fused_rank_head (kind "rank", with exclude, margin and hardest) on the contiguous NHWC map `fmap` (the E embedding channels first).  target / loss / stats go together; dmap (zero-padded, [E, ld) stays untouched) receives d loss / d fmap in its
     dtype.  classes = the unseen class set (L.class_set) of modes 1 / 2, gmap the group map of mode 1.  ws: a Workspace (its
     embedding tables are reused, whichever kind wrote them) or None."""
     B, h, w, ld = fmap.shape
@@ -131,7 +154,7 @@ def embed(kind, stride, fmap, emb, H, W, pred, target=None, loss=None, stats=Non
     st = L.stream_ptr() if stream is None else stream
     nbytes = L.load().szn_fused_head_workspace_bytes(B, h, w, E, K)
     fn = _EMBED_ENTRY[kind]
-    sim = _sim_args(kind, exclude, temperature)
+    sim = _loss_args(kind, exclude, temperature, margin, hardest)
     if ws is None:
         buf = _scratch(nbytes, fmap.device)
     else:
@@ -143,23 +166,25 @@ def embed(kind, stride, fmap, emb, H, W, pred, target=None, loss=None, stats=Non
         ws.tables = Workspace.map_key(stride, fmap)
 
 
-def embed_predict(kind, stride, fmap, emb, H, W, target=None, mode=0, unseen=None, gmap=None, exclude=None, temperature=None):
+def embed_predict(kind, stride, fmap, emb, H, W, target=None, mode=0, unseen=None, gmap=None, exclude=None, temperature=None,
+                  margin=None, hardest=None):
     """forward-only embedding head -> (loss 0-dim tensor or None, pred (B,H,W) int64)"""
     B = fmap.shape[0]
     pred, tgt, loss = _outputs(B, H, W, fmap.device, target)
     stats = None if loss is None else torch.empty(B, 2, device=fmap.device)
     embed(kind, stride, fmap, emb, H, W, pred, tgt, loss, stats, mode=mode, classes=L.class_set(unseen), gmap=gmap, exclude=exclude,
-          temperature=temperature)
+          temperature=temperature, margin=margin, hardest=hardest)
     return (loss.reshape(()) if loss is not None else None), pred
 
 
-def embed_loss(kind, stride, fmap, emb, H, W, target, exclude=None, temperature=None, ws=None):
+def embed_loss(kind, stride, fmap, emb, H, W, target, exclude=None, temperature=None, ws=None, margin=None, hardest=None):
     """the loss of embed_predict alone, bit for bit (the same kernels without the prediction: no trip through the classes per pixel)
     -> loss 0-dim tensor.  ws: a Workspace or None, as in embed()"""
     B = fmap.shape[0]
     tgt = target.to(device=fmap.device, dtype=torch.int64).contiguous()
     loss, stats = torch.empty(1, device=fmap.device), torch.empty(B, 2, device=fmap.device)
-    embed(kind, stride, fmap, emb, H, W, None, tgt, loss, stats, ws=ws, exclude=exclude, temperature=temperature)
+    embed(kind, stride, fmap, emb, H, W, None, tgt, loss, stats, ws=ws, exclude=exclude, temperature=temperature, margin=margin,
+          hardest=hardest)
     return loss.reshape(())
 
 
@@ -188,6 +213,15 @@ def sim_ce(*args, **kw):
 
 def sim_ce_predict(*args, **kw):
     return embed_predict("sim_ce", *args, **kw)
+
+
+def rank(*args, **kw):
+    """embed("rank", ...): the hinge ranking loss (utils.rank_loss) -- same arguments plus exclude / margin / hardest, same pred"""
+    embed("rank", *args, **kw)
+
+
+def rank_predict(*args, **kw):
+    return embed_predict("rank", *args, **kw)
 
 
 # ---- view-ensemble embedding head (multi-scale / mirrored inference) ---------------------------------------------------------

@@ -1403,6 +1403,22 @@ class FCN32s(nn.Module):
         """the extra keywords of heads.embed / embed_predict for `kind`"""
         return dict(exclude=self._sim_ce[0], temperature=self._sim_ce[1]) if kind == "sim_ce" else {}
 
+    # loss="rank" (hinge ranking loss, szn_fused_rank_head) keeps its three settings on the model for the same reason
+    _rank = (None, None, False)
+
+    def set_rank(self, exclude=None, margin=None, hardest=False):
+        """the settings every loss="rank" call of this model uses: `exclude` = the classes that are no negatives and whose pixels
+        do not count (the trainer passes its unseen classes; None: all compete), `margin` (None: heads.RANK_MARGIN), `hardest` =
+        the hardest negative alone instead of the sum of hinges.  -> self"""
+        self._rank = (None if exclude is None else [int(k) for k in exclude], None if margin is None else float(margin), bool(hardest))
+        return self
+
+    def _head_kw(self, kind):
+        """the extra keywords of heads.embed / embed_predict / embed_loss for `kind`: _sim_kw's, or the rank settings"""
+        if kind == "rank":
+            return dict(exclude=self._rank[0], margin=self._rank[1], hardest=self._rank[2])
+        return self._sim_kw(kind)
+
     def embed_predict(self, x, embeddings, target=None, loss="cos"):
         """forward pass + nearest-class-embedding prediction (+ cosine loss when `target` is given) WITHOUT materialising the
         (B,E,H,W) score: the fused-from-coarse head (szn_fused_head) evaluates upscore + crop (models.py:146-147), cosine_loss
@@ -1411,12 +1427,13 @@ class FCN32s(nn.Module):
         Same numbers as `forward` + utils up to rounding order (class assignment differs only on pixels whose top-2 cosine margin
         is < 1e-5).  loss="mse": the loss is utils.mse_loss's (utils.py:50-73, szn_fused_mse_head); the prediction is the same, bit
         for bit.  loss="sim_ce": utils.sim_ce_loss's with the model's set_sim_ce settings (szn_fused_simce_head), same prediction.
+        loss="rank": utils.rank_loss's with the model's set_rank settings (szn_fused_rank_head), same prediction.
         Used by Trainer.validate."""
         kind = heads.embed_kind(loss)
         with torch.no_grad():
             ctx, stride, fmap = self._head_map(x)
             emb = heads.embeddings(embeddings, self.n_class, fmap.device)
-            loss, self._last_pred = heads.embed_predict(kind, stride, fmap, emb, ctx.H, ctx.W, target, **self._sim_kw(kind))
+            loss, self._last_pred = heads.embed_predict(kind, stride, fmap, emb, ctx.H, ctx.W, target, **self._head_kw(kind))
         return loss, self._last_pred
 
     def softmax_predict(self, x, target=None, weight=None):
@@ -1462,6 +1479,11 @@ class FCN32s(nn.Module):
         for bit, the loss is utils.sim_ce_loss's with the model's set_sim_ce settings (szn_fused_simce_head)."""
         return self._szn_predict(x, embeddings, unseen, target, group, "sim_ce")
 
+    def szn_predict_rank(self, x, embeddings, unseen, target=None, group='seenmask'):
+        """szn_predict for a network trained with the hinge ranking loss (train.py -loss rank): the same class assignment bit for
+        bit, the loss is utils.rank_loss's with the model's set_rank settings (szn_fused_rank_head)."""
+        return self._szn_predict(x, embeddings, unseen, target, group, "rank")
+
     def _szn_predict(self, x, embeddings, unseen, target, group, kind):
         mode = self._szn_group(group, target)
         with torch.no_grad():
@@ -1471,7 +1493,7 @@ class FCN32s(nn.Module):
             if mode == 1:
                 self._last_group = heads.seenmask_group(ctx.coarse, self.n_class, self._engine._images["up.w"], ctx.H, ctx.W)
             return heads.embed_predict(kind, stride, fmap, emb, ctx.H, ctx.W, target, mode, unseen, self._last_group,
-                                       **self._sim_kw(kind))
+                                       **self._head_kw(kind))
 
     def ms_predict(self, x, embeddings, scales, flip=False, target=None, unseen=None, group=None, loss="cos"):
         """multi-scale (and mirrored) inference: the network runs once per view of `x` -- every scale of `scales`, which must contain
@@ -1483,7 +1505,7 @@ class FCN32s(nn.Module):
         szn_predict[_mse] return for x, bit for bit (that view's pass is shared with them); only the prediction comes from the
         ensemble.  The class assignment is the cosine argmax whatever the loss.  Softmax models have no such head: SznError."""
         if embeddings is None or loss == "cross_entropy":
-            raise L.SznError("ms_predict: multi-scale inference is built for the embedding heads (loss 'cos' | 'mse' | 'sim_ce'); averaging "
+            raise L.SznError("ms_predict: multi-scale inference is built for the embedding heads (loss 'cos' | 'mse' | 'sim_ce' | 'rank'); averaging "
                              "softmax probabilities over views is not")
         kind = heads.embed_kind(loss)
         mode = 0 if group is None else self._szn_group(group, target)
@@ -1496,7 +1518,7 @@ class FCN32s(nn.Module):
             if mode == 1:
                 self._last_group = heads.seenmask_group(ctx.coarse, self.n_class, self._engine._images["up.w"], H, W)
             loss_t, _ = heads.embed_predict(kind, stride, fmap, emb, H, W, target, mode, unseen if mode else None, self._last_group,
-                                            **self._sim_kw(kind))
+                                            **self._head_kw(kind))
             # every view's map is copied out before the next forward pass reuses the engine's buffers
             maps = {(H, W, False): fmap.to(torch.float32, copy=True)}
             for key in plan:
@@ -1517,7 +1539,7 @@ class FCN32s(nn.Module):
         with torch.no_grad():
             ctx, stride, fmap = self._head_map(x)
             emb = heads.embeddings(embeddings, self.n_class, fmap.device)
-            loss_t, pred = heads.embed_predict(kind, stride, fmap, emb, ctx.H, ctx.W, target, **self._sim_kw(kind))
+            loss_t, pred = heads.embed_predict(kind, stride, fmap, emb, ctx.H, ctx.W, target, **self._head_kw(kind))
             if target is not None or pred_index is not None:
                 fmap32 = fmap if fmap.dtype == torch.float32 else fmap.to(torch.float32)
                 hist, cpred = heads.calib(stride, fmap32, emb, ctx.H, ctx.W, unseen, gammas, target, hist, pred_index)
@@ -1546,9 +1568,9 @@ class FCN32s(nn.Module):
                 # head's workspace, which then finds the embedding tables and the stride-8 position tables of this map in place
                 ws = heads.Workspace(fmap.device)
                 ws.get(heads.seen_sweep_workspace_bytes(stride, fmap, emb, len(heads.seen_sweep_taus(taus))))
-                loss_t, pred = heads.embed_loss(kind, stride, fmap, emb, ctx.H, ctx.W, target, ws=ws, **self._sim_kw(kind)), None
+                loss_t, pred = heads.embed_loss(kind, stride, fmap, emb, ctx.H, ctx.W, target, ws=ws, **self._head_kw(kind)), None
             else:
-                loss_t, pred = heads.embed_predict(kind, stride, fmap, emb, ctx.H, ctx.W, target, **self._sim_kw(kind))
+                loss_t, pred = heads.embed_predict(kind, stride, fmap, emb, ctx.H, ctx.W, target, **self._head_kw(kind))
             self._last_margin = None
             if target is not None or pred_index is not None:
                 self._last_margin = heads.seenmask_margin(ctx.coarse, self.n_class, self._engine._images["up.w"], ctx.H, ctx.W)
@@ -1712,7 +1734,7 @@ class _FusedHead8(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, x, emb, target, H, W, want_grad, kind="cos"):
-        # (kind "sim_ce": exclude / temperature are the model's set_sim_ce settings)
+        # (kind "sim_ce": exclude / temperature are the model's set_sim_ce settings; kind "rank": the set_rank settings)
         x = x.contiguous()
         B, h, w, ld = x.shape
         dev = x.device
@@ -1720,7 +1742,7 @@ class _FusedHead8(torch.autograd.Function):
         loss = torch.empty(1, device=dev)
         stats = torch.empty(B, 2, device=dev)
         dx = torch.zeros(B, h, w, ld, device=dev, dtype=torch.float32) if want_grad else None
-        heads.embed(kind, 8, x, emb, H, W, pred, target, loss, stats, dx, **model._sim_kw(kind))
+        heads.embed(kind, 8, x, emb, H, W, pred, target, loss, stats, dx, **model._head_kw(kind))
         ctx.dx = dx
         model._last_pred = pred
         return loss.reshape(())
@@ -1811,7 +1833,8 @@ class FCN8s(FCN32s):
         """training-time fused head: -> (cosine loss with autograd history, pred (B,H,W) int64).  Same numbers as
         utils.cosine_loss(self(x), target, embeddings) / utils.infer_lbl_device up to rounding order, without the
         (B,E,H,W) score or its gradient in HBM.  loss="mse": utils.mse_loss instead (szn_fused_mse_head); loss="sim_ce":
-        utils.sim_ce_loss with the model's set_sim_ce settings (szn_fused_simce_head)."""
+        utils.sim_ce_loss with the model's set_sim_ce settings (szn_fused_simce_head); loss="rank": utils.rank_loss with the
+        model's set_rank settings (szn_fused_rank_head)."""
         kind = heads.embed_kind(loss)
         emb = heads.embeddings(embeddings, self.n_class, x.device)
         _, fuse3 = self._fuse(x, self.training, dropout_masks)

@@ -25,6 +25,10 @@ Added for this implementation (none change the reference flags):
   -loss sim_ce         similarity cross-entropy: softmax over the seen classes' cosine similarities to the pixel embedding, cross
                        entropy against the label (szn_fused_simce_head; the unseen classes do not compete); --sim-temperature T
                        (default 0.1, a hyper-parameter default, not a tuned value) divides the similarities
+  -loss rank           hinge ranking loss (DeViSE): a pixel's cosine to its own class embedding must exceed its cosine to every other
+                       seen class by a margin (szn_fused_rank_head; the unseen classes are no negatives); --rank-margin M (default 0.1,
+                       DeViSE's value: a hyper-parameter default, not a tuned value), --rank-hardest keeps the hardest negative alone
+                       instead of the sum of hinges
   --pseudo-label KEEP  self-training on the unseen classes: the training set keeps the images 'train_seen' drops for their unseen classes,
                        with those pixels hidden (--hide-unseen, implied), and every step labels the most confident KEEP (0 < KEEP <= 1) of
                        the hidden pixels per unseen class with its own calibrated prediction (szn_pseudo_head) and trains on them;
@@ -49,7 +53,7 @@ import yaml
 from . import engine as _engine
 from . import models, trainer_fcn, trainer_seenmask
 from .configs import configurations
-from .heads import SIM_TEMPERATURE
+from .heads import RANK_MARGIN, SIM_TEMPERATURE
 from .optim import FusedAdam, FusedSGD
 from .synthetic_dataset import SyntheticSegmentation
 
@@ -70,7 +74,7 @@ def build_parser():
     p.add_argument('-e', '--embed_dim', type=int, choices=[2, 5, 10, 20, 21, 50, 100, 200, 300])
     p.add_argument('-ve', '--fcn_epochs', type=int)
     p.add_argument('-lr', '--fcn_learning_rate', type=float)
-    p.add_argument('-loss', '--fcn_loss', type=str, choices=['cos', 'mse', 'sim_ce', 'cross_entropy'])
+    p.add_argument('-loss', '--fcn_loss', type=str, choices=['cos', 'mse', 'sim_ce', 'rank', 'cross_entropy'])
     p.add_argument('-o', '--fcn_optim', type=str, choices=['sgd', 'adam'])
     p.add_argument('-se', '--seenmask_epochs', type=int)
     p.add_argument('-slr', '--seenmask_learning_rate', type=float)
@@ -119,6 +123,13 @@ def build_parser():
                    help="with -loss sim_ce (softmax over the seen classes' cosine similarities to the pixel embedding, cross entropy "
                         "against the label): the temperature the similarities are divided by.  Default %g: a hyper-parameter default, "
                         "not a tuned value.  An error without -loss sim_ce" % SIM_TEMPERATURE)
+    p.add_argument('--rank-margin', type=float, default=None, metavar='M',
+                   help="with -loss rank (hinge ranking loss: the pixel embedding's cosine to its own class must exceed its cosine to "
+                        "every other seen class by M): the margin.  Default %g, DeViSE's value: a hyper-parameter default, not a tuned "
+                        "value.  An error without -loss rank" % RANK_MARGIN)
+    p.add_argument('--rank-hardest', action='store_true',
+                   help="with -loss rank: the hardest negative class alone carries the hinge, not the sum over all seen classes.  An "
+                        "error without -loss rank")
     p.add_argument('--pseudo-label', type=float, default=None, metavar='KEEP',
                    help="self-training: every training step labels the most confident KEEP (0 < KEEP <= 1) of the hidden pixels per "
                         "unseen class with its own calibrated prediction and trains on them; implies --hide-unseen; needs unseen "
@@ -161,7 +172,7 @@ def update_cfg_with_args(cfg, args):
     return cfg
 
 
-_EMBED_LOSSES = trainer_fcn._EMBED_LOSSES          # 'cos' | 'mse' | 'sim_ce': the losses of an embedding configuration
+_EMBED_LOSSES = trainer_fcn._EMBED_LOSSES          # 'cos' | 'mse' | 'sim_ce' | 'rank': the losses of an embedding configuration
 
 
 # configuration sanity rules (the reference's checks, train.py:232-251, with its messages: the CLI contract): (broken?, message)
@@ -261,10 +272,11 @@ def freeze_for_seenmask(model):
 
 def check_precision(precision, cfg):
     """--precision fp16 trains only where loss scaling exists: the fused steps (engine.TrainStep / SeenmaskStep; see
-    trainer_fcn.Trainer.train_epoch) -- an embedding configuration with fcn_loss 'cos', 'mse' or 'sim_ce', or the softmax configuration"""
+    trainer_fcn.Trainer.train_epoch) -- an embedding configuration with fcn_loss 'cos', 'mse', 'sim_ce' or 'rank', or the softmax
+    configuration"""
     fused_cfg = (cfg['fcn_loss'] in _EMBED_LOSSES and cfg['embed_dim']) or (cfg['fcn_loss'] == 'cross_entropy' and not cfg['embed_dim'])
     if precision == 'fp16' and cfg['mode'] == 'train' and cfg['fcn_epochs'] > 0 and not fused_cfg:
-        raise Exception("--precision fp16 needs the fused training step: embedding configuration with fcn_loss 'cos', 'mse' or 'sim_ce', or "
+        raise Exception("--precision fp16 needs the fused training step: embedding configuration with fcn_loss 'cos', 'mse', 'sim_ce' or 'rank', or "
                         "the softmax configuration (fcn_loss 'cross_entropy', no embedding) (got loss %r, embed_dim %r); use bf16 "
                         "or fp32" % (cfg['fcn_loss'], cfg['embed_dim']))
 
@@ -274,7 +286,7 @@ def check_eval_views(scales, flip, cfg):
     if not scales and not flip:
         return
     if not (cfg['embed_dim'] and cfg['fcn_loss'] in _EMBED_LOSSES):
-        raise Exception("--eval-scales / --eval-flip need an embedding configuration with fcn_loss 'cos', 'mse' or 'sim_ce' (got loss %r, "
+        raise Exception("--eval-scales / --eval-flip need an embedding configuration with fcn_loss 'cos', 'mse', 'sim_ce' or 'rank' (got loss %r, "
                         "embed_dim %r)" % (cfg['fcn_loss'], cfg['embed_dim']))
     if scales and 1.0 not in [float(s) for s in scales]:
         raise Exception("--eval-scales must contain 1 (got %r)" % (scales,))
@@ -391,11 +403,22 @@ def check_sim_temperature(temperature, cfg):
         raise Exception("--sim-temperature: T must be positive and finite (got %r)" % (temperature,))
 
 
+def check_rank(margin, hardest, cfg):
+    """--rank-margin / --rank-hardest: only with fcn_loss 'rank'; the margin finite and >= 0"""
+    if margin is None and not hardest:
+        return
+    if cfg['fcn_loss'] != 'rank':
+        raise Exception("--rank-margin / --rank-hardest need -loss rank (got loss %r)" % (cfg['fcn_loss'],))
+    if margin is not None and not 0 <= margin < float('inf'):
+        raise Exception("--rank-margin: M must be finite and >= 0 (got %r)" % (margin,))
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     cfg = update_cfg_with_args(configurations[args.config], args)
     validate_cfg(cfg)
     check_sim_temperature(args.sim_temperature, cfg)
+    check_rank(args.rank_margin, args.rank_hardest, cfg)
     check_precision(args.precision, cfg)
     check_eval_views(args.eval_scales, args.eval_flip, cfg)
     check_calibration(args.calibration, args.calib_sweep, cfg, args.eval_scales, args.eval_flip)
@@ -523,6 +546,7 @@ def main(argv=None):
         tb_writer=tb_writer, unseen=all_unseen, val_unseen=cfg['val_unseen'], label_names=label_names,
         forced_unseen=cfg['forced_unseen'], precision=precision, rank=rank, visualize=args.viz, augment=augment,
         seen_threshold=args.seen_threshold, seen_sweep=seen_sweep_values(args.seen_sweep), sim_temperature=args.sim_temperature,
+        rank_margin=args.rank_margin, rank_hardest=args.rank_hardest,
         pseudo=None if args.pseudo_label is None else dict(keep=args.pseudo_label, gamma=args.pseudo_gamma,
                                                            conf_floor=-2.0 if args.pseudo_floor is None else args.pseudo_floor),
         pseudo_start_epoch=args.pseudo_start_epoch or 0,

@@ -35,7 +35,7 @@ def load_embeddings(dataset, dim):
     raise IOError("no embedding matrix for dataset=%s dim=%s (looked for %s.pkl and %s)" % (dataset, dim, pkl, npy))
 
 
-_EMBED_LOSSES = ("cos", "mse", "sim_ce")          # the embedding losses: each has a fused head (heads.embed)
+_EMBED_LOSSES = ("cos", "mse", "sim_ce", "rank")          # the embedding losses: each has a fused head (heads.embed)
 
 
 def _now():
@@ -49,7 +49,7 @@ def calibration_refused(has_unseen, embed_cfg, forced_unseen, test_all, eval_vie
     if not has_unseen:
         return "calibration needs unseen classes (train_unseen / val_unseen): without them there is no seen group to penalise"
     if not embed_cfg:
-        return "calibration needs an embedding configuration (loss 'cos' | 'mse' | 'sim_ce'): a softmax network has no unseen-class scores"
+        return "calibration needs an embedding configuration (loss 'cos' | 'mse' | 'sim_ce' | 'rank'): a softmax network has no unseen-class scores"
     if forced_unseen:
         return "calibration and forced_unseen are two different class-assignment rules: pick one"
     if test_all:
@@ -70,7 +70,7 @@ def seen_threshold_refused(has_unseen, embed_cfg, forced_unseen, test_all, eval_
     if not has_unseen:
         return "a seen-mask threshold needs unseen classes (train_unseen / val_unseen): without them there is one class group"
     if not embed_cfg:
-        return "a seen-mask threshold needs an embedding configuration (loss 'cos' | 'mse' | 'sim_ce'): a softmax network has no class groups"
+        return "a seen-mask threshold needs an embedding configuration (loss 'cos' | 'mse' | 'sim_ce' | 'rank'): a softmax network has no class groups"
     if forced_unseen:
         return "a seen-mask threshold and forced_unseen are two different class-assignment rules: pick one"
     if not test_all:
@@ -90,7 +90,7 @@ def pseudo_refused(has_unseen, embed_cfg, n_class):
     if not has_unseen:
         return "pseudo labels need unseen classes (train_unseen / val_unseen): there is nothing hidden to label"
     if not embed_cfg:
-        return "pseudo labels need an embedding configuration (loss 'cos' | 'mse' | 'sim_ce'): a softmax network has no unseen-class scores"
+        return "pseudo labels need an embedding configuration (loss 'cos' | 'mse' | 'sim_ce' | 'rank'): a softmax network has no unseen-class scores"
     if n_class > 256:
         return "pseudo labels: the fused head holds at most 256 classes, got %d" % n_class
     return None
@@ -100,7 +100,7 @@ def ohem_refused(embed_cfg, n_class):
     """why a configuration cannot mine hard pixels (ohem=, train.py --ohem), or None: hardness is the cosine to the pixel's own class
     embedding, a quantity of the fused embedding head"""
     if not embed_cfg:
-        return "ohem needs an embedding configuration (loss 'cos' | 'mse' | 'sim_ce'): a softmax network has no class embeddings"
+        return "ohem needs an embedding configuration (loss 'cos' | 'mse' | 'sim_ce' | 'rank'): a softmax network has no class embeddings"
     if n_class > 256:
         return "ohem: the fused head holds at most 256 classes, got %d" % n_class
     return None
@@ -118,7 +118,7 @@ class Trainer(object):
                  pixel_embeddings=None, loss_func=None, unseen=None, val_unseen=None, label_names=None,
                  forced_unseen=False, embed_arr=None, precision=torch.float32, fused_step=True, rank=0, visualize=0, augment=None,
                  seen_threshold=None, seen_sweep=None,
-                 sim_temperature=None, pseudo=None, pseudo_start_epoch=0, ohem=None, ohem_start_epoch=0, calibration=None,
+                 sim_temperature=None, rank_margin=None, rank_hardest=False, pseudo=None, pseudo_start_epoch=0, ohem=None, ohem_start_epoch=0, calibration=None,
                  calib_sweep=None, eval_scales=None, eval_flip=False):
         if not cuda:
             raise RuntimeError("this implementation runs on the GPU only (cuda=False has no CPU fallback)")
@@ -152,6 +152,15 @@ class Trainer(object):
         self.sim_temperature = float(SIM_TEMPERATURE if sim_temperature is None else sim_temperature)
         if loss_func == "sim_ce" and pixel_embeddings:
             model.set_sim_ce(self.unseen, self.sim_temperature)
+        # loss_func "rank" (utils.rank_loss, szn_fused_rank_head): the hinges run over the seen classes -- `exclude` is self.unseen --
+        # at this margin (None: heads.RANK_MARGIN), summed or (rank_hardest) the hardest negative alone; the model carries all three
+        if (rank_margin is not None or rank_hardest) and loss_func != "rank":
+            from ._lib import SznError
+            raise SznError("rank_margin / rank_hardest belong to loss 'rank' (got loss %r)" % (loss_func,))
+        from .heads import RANK_MARGIN
+        self.rank_margin, self.rank_hardest = float(RANK_MARGIN if rank_margin is None else rank_margin), bool(rank_hardest)
+        if loss_func == "rank" and pixel_embeddings:
+            model.set_rank(self.unseen, self.rank_margin, self.rank_hardest)
         # multi-scale / mirrored validation (models.ms_predict): the scales every validation image is evaluated at (None: once, as
         # stored) and whether each is also evaluated mirrored.  Training steps never see them.
         self.eval_scales = tuple(float(s) for s in eval_scales) if eval_scales else None
@@ -159,7 +168,7 @@ class Trainer(object):
         self._ms_warned = False
         if (self.eval_scales or self.eval_flip) and not (pixel_embeddings and loss_func in _EMBED_LOSSES):
             from ._lib import SznError
-            raise SznError("eval_scales / eval_flip need an embedding configuration (loss 'cos' | 'mse' | 'sim_ce'): averaging softmax "
+            raise SznError("eval_scales / eval_flip need an embedding configuration (loss 'cos' | 'mse' | 'sim_ce' | 'rank'): averaging softmax "
                            "probabilities over views is not built")
         if self.eval_flip and not self.eval_scales:
             self.eval_scales = (1.0,)
@@ -310,6 +319,8 @@ class Trainer(object):
             return utils.mse_loss(score, target, te)
         if self.loss_func == "sim_ce":
             return utils.sim_ce_loss(score, target, self.embeddings, self.unseen, self.sim_temperature)
+        if self.loss_func == "rank":
+            return utils.rank_loss(score, target, self.embeddings, self.unseen, self.rank_margin, self.rank_hardest)
         if self.loss_func == "cross_entropy":
             return utils.cross_entropy2d(score, target, size_average=False)
         raise ValueError("unknown loss_func %r" % (self.loss_func,))
@@ -341,7 +352,7 @@ class Trainer(object):
 
     # ---- training --------------------------------------------------------------------------------------------
     def _embed_cfg(self):
-        """an embedding configuration whose loss has a fused head: cosine, mse or sim_ce (train.py -loss cos | mse | sim_ce)"""
+        """an embedding configuration whose loss has a fused head: cosine, mse, sim_ce or rank (train.py -loss cos | mse | sim_ce | rank)"""
         return bool(self.pixel_embeddings) and self.loss_func in _EMBED_LOSSES
 
     def _ce_cfg(self):
@@ -382,6 +393,8 @@ class Trainer(object):
             kw.update(embeddings=self.embeddings, forced_unseen=self.unseen if self.forced_unseen else None, loss=self.loss_func)
             if self.loss_func == "sim_ce":
                 kw.update(sim_exclude=self.unseen, sim_temperature=self.sim_temperature)
+            if self.loss_func == "rank":
+                kw.update(sim_exclude=self.unseen, rank_margin=self.rank_margin, rank_hardest=self.rank_hardest)
             if self.pseudo is not None:
                 kw.update(pseudo=self.pseudo)
             if self.ohem is not None:
@@ -538,7 +551,7 @@ class Trainer(object):
                                                               hist=self._seen_hist, pred_index=self._seen_index(), loss=self.loss_func)
                 return None, loss, pred, target
             predict = {"cos": self.model.szn_predict, "mse": self.model.szn_predict_mse,
-                       "sim_ce": self.model.szn_predict_sim_ce}[self.loss_func]
+                       "sim_ce": self.model.szn_predict_sim_ce, "rank": self.model.szn_predict_rank}[self.loss_func]
             loss, pred = predict(data, self.embeddings, self.unseen, target, group='seenmask' if szn else 'target')
             return None, loss, pred, target
         if szn and (self.seen_threshold is not None or self._seen_hist is not None):

@@ -8,6 +8,7 @@ There is no CPU fallback: tensors must live on the GPU.
   cross_entropy2d(score, target, ...)      utils.py:19-48
   mse_loss / cosine_loss                   utils.py:50-102
   sim_ce_loss                              similarity cross-entropy in torch ops (no reference counterpart)
+  rank_loss                                hinge ranking loss (DeViSE) in torch ops (no reference counterpart)
   label_accuracy_score                     utils.py:104-154
   infer_lbl / infer_lbl_forced_unseen / infer_lbl_szn / stich_seen_unseen_with_mask   utils.py:159-205
 
@@ -185,6 +186,51 @@ def sim_ce_loss(score, target, embed, exclude=None, temperature=0.1):
     lbl = torch.where(in_range, target, torch.zeros_like(target))
     counted = in_range & competes[lbl]
     term = torch.logsumexp(z, dim=3) - zall.gather(3, lbl.unsqueeze(3)).squeeze(3)
+    term = torch.where(counted, term, torch.zeros_like(term))
+    per_image = term.sum(dim=(1, 2)) / counted.sum(dim=(1, 2)).to(score.dtype)
+    return per_image.mean()
+
+
+def rank_loss(score, target, embed, exclude=None, margin=0.1, hardest=False):
+    """Hinge ranking loss (include/szn.h, szn_fused_rank_head; DeViSE): per pixel sum_k max(0, margin - cos(s, e_label) + cos(s, e_k))
+    over the classes k != label NOT in `exclude` -- with `hardest` the largest of these hinges alone (the lowest class index on an
+    exact tie); labels < 0, >= K or in `exclude` are ignored; per image the sum of the terms over its counted pixels divided by
+    their number, the loss is the mean over images.  Plain differentiable torch ops on the materialised score (n,c,h,w), in the score's
+    own dtype (float32 or float64) and on its device: the autograd route and the in-suite referee of the fused head.
+    embed: the (K,c) class-embedding matrix; a zero row counts with norm 1."""
+    if score.dim() != 4:
+        raise L.SznError("rank_loss: score must be (n,c,h,w), got %s" % (tuple(score.shape),))
+    if not float(margin) >= 0 or not np.isfinite(float(margin)):
+        raise L.SznError("rank_loss: margin must be finite and >= 0, got %r" % (margin,))
+    B, E, H, W = score.shape
+    emb = torch.as_tensor(embed).detach().to(device=score.device, dtype=score.dtype)
+    K = emb.shape[0]
+    if emb.dim() != 2 or emb.shape[1] != E:
+        raise L.SznError("rank_loss: embedding matrix %s does not match the score's %d channels" % (tuple(emb.shape), E))
+    excl = sorted(set(int(k) for k in (exclude if exclude is not None else [])))
+    if any(not 0 <= k < K for k in excl):
+        raise L.SznError("rank_loss: exclude names a class outside [0, %d)" % K)
+    if K - len(excl) < 2:
+        raise L.SznError("rank_loss: exclude leaves fewer than two classes competing")
+    competes = torch.ones(K, dtype=torch.bool, device=score.device)
+    if excl:
+        competes[torch.tensor(excl, device=score.device)] = False
+    target = target.to(device=score.device, dtype=torch.int64)
+    en = emb.norm(dim=1)
+    en = torch.where(en == 0, torch.ones_like(en), en)
+    s = score.permute(0, 2, 3, 1)                                        # (B,H,W,E)
+    cos = (s @ emb.t()) / (s.norm(dim=3, keepdim=True) * en)             # (B,H,W,K)
+    in_range = (target >= 0) & (target < K)
+    lbl = torch.where(in_range, target, torch.zeros_like(target))
+    counted = in_range & competes[lbl]
+    v = float(margin) - cos.gather(3, lbl.unsqueeze(3)) + cos            # (B,H,W,K)
+    negative = competes.expand_as(v).clone()
+    negative.scatter_(3, lbl.unsqueeze(3), False)                        # the label is no negative of its own pixel
+    if hardest:
+        # max() sends the gradient to the first maximal index: the lowest class index on a tie
+        term = v.masked_fill(~negative, float("-inf")).max(dim=3)[0].clamp(min=0)
+    else:
+        term = torch.where(negative, v, torch.zeros_like(v)).clamp(min=0).sum(dim=3)
     term = torch.where(counted, term, torch.zeros_like(term))
     per_image = term.sum(dim=(1, 2)) / counted.sum(dim=(1, 2)).to(score.dtype)
     return per_image.mean()
