@@ -578,6 +578,38 @@ int szn_fused_rank_head_prepared(int stride, int B, int h, int w, int E, int ldc
                                  const szn_class_set* exclude, float margin, int hardest, float* loss, float* stats, int64_t* pred,
                                  int dcoarse_dtype, void* dcoarse, void* workspace, szn_stream_t stream);
 
+/* ---- fused sim_ce head with the unseen-bias term (train.py -loss sim_ce --bias-loss, QFSL): hidden pixels pull towards the unseen set --
+ * Equivalent to szn_bilinear_up_crop_fwd(stride) -> utils.sim_ce_bias_loss (forward and autograd backward) -> szn_embed_argmax_k ->
+ * szn_bilinear_up_crop_bwd(stride).  szn_fused_simce_head[_prepared]'s arguments, strides, group modes, NULL rules, error codes,
+ * workspace, prepare step and dcoarse_dtype codes, with (bias_unseen, weight, hidden_label) after `temperature`; pred is
+ * szn_fused_head_grouped's pred bit for bit.  cos_k, n_k, z_k = cos_k / temperature as szn_fused_simce_head defines them; X = `exclude`,
+ * U = `bias_unseen` (non-empty, not all K classes; independent of the `unseen` of the group modes), lambda = `weight` > 0,
+ * hl = `hidden_label` < -1 (datasets.HIDDEN_LABEL).
+ *   A labelled pixel (0 <= label < K, label not in X): term = logsumexp_{k not in X} z_k - z_label, szn_fused_simce_head's term, its
+ *   gradient and its bits.
+ *   A hidden pixel (label == hl): the softmax runs over ALL K classes whatever X holds, p_k = softmax_k(z_k), and
+ *     term = lambda * -log sum_{u in U} p_u = lambda * (logsumexp_{all k} z_k - logsumexp_{u in U} z_u),
+ *   each log-sum-exp with its own maximum subtracted (m over all k, m_U over U), so the term and the gradient are finite where
+ *   P_U = sum_U p_u itself underflows;  q_k = 1[k in U] exp(z_k - m_U) / sum_{u in U} exp(z_u - m_U)  (= p_k / P_U), and
+ *     d term / d s = (lambda / temperature) sum_k (p_k - q_k) (e_k / (|s| n_k) - cos_k s / |s|^2).
+ *   Every other pixel (-1, -2, other negative labels, labels >= K, labels in X) is ignored.
+ * stats f32 [B][2] = {S_b = sum of all terms, N_b = labelled + hidden px}; loss = mean_b S_b / N_b: one joint mean per image, not
+ * QFSL's separate means over labelled and unlabelled data.  dcoarse is scaled by 1 / (B N_b).  With no hidden pixel in `target` every
+ * output is szn_fused_simce_head's bit for bit.  Errors, all before any launch (SZN_ERR_ARG): U empty or all K classes or naming a
+ * class >= K, weight not finite or <= 0, hidden_label >= -1, and the temperature and `exclude` szn_fused_simce_head refuses.
+ * Fixed-order reductions, no atomics: two calls give bitwise-equal outputs. */
+int szn_fused_simce_bias_head(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                              const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
+                              int group_mode, const int64_t* group_map, const szn_class_set* exclude, float temperature,
+                              const szn_class_set* bias_unseen, float weight, int64_t hidden_label, float* loss, float* stats,
+                              int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace, szn_stream_t stream);
+int szn_fused_simce_bias_head_prepared(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                                       const float* coarse, const float* embed, const int64_t* target,
+                                       const szn_class_set* unseen, int group_mode, const int64_t* group_map,
+                                       const szn_class_set* exclude, float temperature, const szn_class_set* bias_unseen,
+                                       float weight, int64_t hidden_label, float* loss, float* stats, int64_t* pred,
+                                       int dcoarse_dtype, void* dcoarse, void* workspace, szn_stream_t stream);
+
 /* ---- fused softmax cross-entropy head: coarse -> (loss, stats, prediction, dcoarse) without the (B,C,H,W) score ---------
  * Equivalent to szn_bilinear_up_crop_fwd(stride) -> szn_ce2d_fwd (pred = channel argmax) -> szn_ce2d_bwd (gout NULL) ->
  * szn_bilinear_up_crop_bwd(stride) (models.py:94,146-147 upscore + crop, utils.py:19-48 cross_entropy2d, trainer_fcn.py:117

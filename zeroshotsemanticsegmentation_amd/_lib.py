@@ -178,6 +178,8 @@ SIGNATURES = {
     "szn_fused_simce_head_prepared": (_I, [_I] * 11 + [_P, _P, _P, _CS, _I, _P, _CS, _F, _P, _P, _P, _I, _P, _P, _P]),
     "szn_fused_rank_head": (_I, [_I] * 11 + [_P, _P, _P, _CS, _I, _P, _CS, _F, _I, _P, _P, _P, _I, _P, _P, _P]),
     "szn_fused_rank_head_prepared": (_I, [_I] * 11 + [_P, _P, _P, _CS, _I, _P, _CS, _F, _I, _P, _P, _P, _I, _P, _P, _P]),
+    "szn_fused_simce_bias_head": (_I, [_I] * 11 + [_P, _P, _P, _CS, _I, _P, _CS, _F, _CS, _F, _I64, _P, _P, _P, _I, _P, _P, _P]),
+    "szn_fused_simce_bias_head_prepared": (_I, [_I] * 11 + [_P, _P, _P, _CS, _I, _P, _CS, _F, _CS, _F, _I64, _P, _P, _P, _I, _P, _P, _P]),
     "szn_fused_ce_head_workspace_bytes": (_SZ, [_I] * 5),
     "szn_fused_ce_head": (_I, [_I] * 10 + [_P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P]),
     "szn_adam_step": (_I, [_L, _P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _F, _P, _I, _P]),

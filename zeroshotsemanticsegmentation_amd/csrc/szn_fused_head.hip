@@ -32,6 +32,7 @@
 //   sce_cell_kernel / sce_cell_tab_kernel   szn_fused_simce_head (similarity cross-entropy): the same G and Q, a softmax over the classes per
 //                        pixel (sce_pixel) and a dense A through a per-wave LDS tile (sce_dense_A); sums, finalize and gather as above
 //                        The same two kernels over RankArgs: szn_fused_rank_head (hinge ranking loss), one walk over the classes per pixel
+//                        and over BiasArgs: szn_fused_simce_bias_head (sim_ce plus the unseen-bias term on hidden pixels)
 // Both cell kernels run the same per-pixel body (fh_pixel) and the same label loop (fh_scatter_A), and write per cell: pred, the
 // loss partial, A and Bm.
 //
@@ -773,12 +774,117 @@ __device__ __forceinline__ RankCoef<KP> sce_coef(const RankArgs& s, const RankPx
     return RankCoef<KP>{s, px, G, en};
 }
 
+// ---- sim_ce with the unseen-bias term on hidden pixels (szn_fused_simce_bias_head, QFSL) ---------------------------------------------
+// A labelled pixel (0 <= lbl < K, lbl outside `excl`) is sim_ce's pixel: the same passes, the same expressions, the same bits.  A hidden
+// pixel (lbl == hidden) is known to carry some class of `unseen`: its softmax runs over all K classes, z_k = cos_k / T, and its term is
+//     weight * -log sum_{u in U} p_u = weight * ((m - m_U) + log sum_k e^{z_k - m} - log sum_u e^{z_u - m_U})
+// with m = max_k z_k and m_U = max_u z_u: each sum holds a term equal to 1, so neither logarithm sees 0 where P_U itself (e^{-200} at
+// T = 0.01) is no float.  q_k = 1[k in U] e^{z_k - m_U} / sum_U for the same reason, never p_k / P_U.  The gradient has sim_ce's shape
+// with q_k in the place of y_k:
+//     A[t][k] += w_t weight (q_k - p_k) / (T |s| n_k),      Bm[t][u] += w_t w_u weight (sum_k q_k cos_k - sum_k p_k cos_k) / (T |s|^2)
+// Both kinds count 1 in N_b; sums, finalize and gather are sim_ce's.  Per pixel: |q_k - p_k| summed over k is at most 2, so the
+// pixel's d(score) is bounded by 2 weight / (T |s|), sim_ce's 2 / (T |s|) times weight.
+struct BiasArgs { ClassBits excl, unseen; float inv_t, weight; long hidden; };
+// kind: 0 the pixel does not count, 1 labelled (m, rsum over the competing classes; mu, rsumu unused), 2 hidden (m, rsum over all
+// classes, mu, rsumu over `unseen`)
+struct BiasPx { float wt[4]; long lbl; int kind; float rsn, m, rsum, mu, rsumu; };
+
+__device__ __forceinline__ bool sce_competes(const BiasArgs& s, int k) { return !((class_word(s.excl, k >> 6) >> (k & 63)) & 1ull); }
+__device__ __forceinline__ bool bias_unseen(const BiasArgs& s, int k) { return (class_word(s.unseen, k >> 6) >> (k & 63)) & 1ull; }
+
+template <int KP, int S, bool GROUPED>
+__device__ __forceinline__ BiasPx sce_pixel(const FhArgs& a, const BiasArgs& s, int b, int I, int J, int ty, int tx, bool live,
+                                            const float* G, const float* Q, const float* __restrict__ en, float (&bm)[16],
+                                            double& term_sum, double& cnt) {
+    BiasPx px = {{0.f, 0.f, 0.f, 0.f}, -1, 0, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const int y = S * I + ty - a.crop, x = S * J + tx - a.crop;
+    if (live && y >= 0 && y < a.H && x >= 0 && x < a.W) {
+        cell_weights<S>(ty, tx, px.wt);
+        const float (&wt)[4] = px.wt;
+        const float ss = fh_ss(wt, Q);
+        const float sn = sqrtf(ss);
+        const size_t pix = ((size_t)b * a.H + y) * a.W + x;
+        px.lbl = a.target ? a.target[pix] : -1;
+        if (GROUPED || a.pred) a.pred[pix] = fh_argmax<KP, GROUPED>(a, wt, G, sn, en, pix, px.lbl);
+        const bool lab = px.lbl >= 0 && px.lbl < a.K && !in_set(s.excl, px.lbl);
+        const bool hid = px.lbl == s.hidden;             // hidden < -1: never the -1 of a call without target
+        if (lab || hid) {
+            // one walk per pass for both kinds, so a wave that holds both does not pay for two: a labelled lane skips the classes of
+            // `excl` and never enters the U branch, and what it computes is sim_ce's sequence of operations
+            const float rsn = 1.f / sn;
+            float m = -INFINITY, mu = -INFINITY;
+            for (int k = 0; k < a.K; ++k)
+                if (hid || sce_competes(s, k)) {
+                    const float z = sce_cos<KP>(wt, G, rsn, en, k) * s.inv_t;
+                    m = fmaxf(m, z);
+                    if (hid && bias_unseen(s, k)) mu = fmaxf(mu, z);
+                }
+            float sum = 0.f, sc = 0.f, sumu = 0.f, scu = 0.f;
+            for (int k = 0; k < a.K; ++k)
+                if (hid || sce_competes(s, k)) {
+                    const float c = sce_cos<KP>(wt, G, rsn, en, k);
+                    const float z = c * s.inv_t;
+                    const float e = expf(z - m);
+                    sum += e;
+                    sc = fmaf(e, c, sc);
+                    if (hid && bias_unseen(s, k)) {
+                        const float eu = expf(z - mu);
+                        sumu += eu;
+                        scu = fmaf(eu, c, scu);
+                    }
+                }
+            cnt += 1.0;
+            px.rsn = rsn; px.m = m; px.rsum = 1.f / sum;
+            float bco;
+            if (lab) {
+                const float cl = sce_cos<KP>(wt, G, rsn, en, (int)px.lbl);
+                term_sum += (double)((m - cl * s.inv_t) + logf(sum));
+                px.kind = 1;
+                bco = (cl - sc * px.rsum) * s.inv_t / ss;
+            } else {
+                term_sum += (double)(s.weight * ((m - mu) + (logf(sum) - logf(sumu))));
+                px.kind = 2; px.mu = mu; px.rsumu = 1.f / sumu;
+                bco = s.weight * (scu * px.rsumu - sc * px.rsum) * s.inv_t / ss;
+            }
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int u = 0; u < 4; ++u) bm[t * 4 + u] = fmaf(wt[t] * wt[u], bco, bm[t * 4 + u]);
+        }
+    }
+    return px;
+}
+
+// labelled: SceCoef's (y_k - p_k) / (T |s| n_k) over the competing classes; hidden: weight (q_k - p_k) / (T |s| n_k) over all classes
+template <int KP>
+struct BiasCoef {
+    const BiasArgs& s; const BiasPx& px; const float* G; const float* __restrict__ en; float aco;
+    __device__ __forceinline__ BiasCoef(const BiasArgs& s_, const BiasPx& px_, const float* G_, const float* __restrict__ en_)
+        : s(s_), px(px_), G(G_), en(en_), aco(s_.inv_t * px_.rsn * (px_.kind == 2 ? s_.weight : 1.f)) {}      // x 1: exact
+    __device__ __forceinline__ float operator()(int k) const {
+        float c = 0.f;
+        const bool hid = px.kind == 2;
+        if (px.kind != 0 && (hid || sce_competes(s, k))) {                  // one walk for both kinds, as in sce_pixel
+            const float z = sce_cos<KP>(px.wt, G, px.rsn, en, k) * s.inv_t;
+            const float p = expf(z - px.m) * px.rsum;
+            float tk = (long)k == px.lbl ? 1.f : 0.f;                       // y_k; a hidden pixel's label is no class
+            if (hid && bias_unseen(s, k)) tk = expf(z - px.mu) * px.rsumu;  // q_k
+            c = (tk - p) * (aco * __builtin_amdgcn_rcpf(en[k]));
+        }
+        return c;
+    }
+};
+template <int KP>
+__device__ __forceinline__ BiasCoef<KP> sce_coef(const BiasArgs& s, const BiasPx& px, const float* G, const float* __restrict__ en) {
+    return BiasCoef<KP>(s, px, G, en);
+}
+
 // dynamic LDS in floats: stride 32 fh_lds(E, KP, false) | 4 waves' tiles; stride 8 G [4][4 KP] | A [4][4 KP] | Q [4][16] | the tiles
 __host__ __device__ inline size_t sce_lds_floats(int stride, int E, int KP) {
     return (stride == 8 ? (size_t)32 * KP + 64 : (size_t)fh_lds(E, KP, false).end) + 4 * kSceWave;
 }
 
-// LA: SceArgs (sim_ce) | RankArgs (rank); sce_pixel and sce_coef are overloaded on it
+// LA: SceArgs (sim_ce) | RankArgs (rank) | BiasArgs (sim_ce with the bias term); sce_pixel and sce_coef are overloaded on it
 template <int KP, bool GROUPED, class LA>
 __global__ __launch_bounds__(256) void sce_cell_kernel(FhArgs a, LA s) {        // stride 32: one block per (image, cell)
     constexpr int S = 32;
@@ -1686,15 +1792,16 @@ void fh_launch_gather_t(bool mse, const FhArgs& a, const float* stats, void* dco
 }
 
 // every szn_fused_*head* entry point: prep = build the embedding tables first; unseen / group_mode / group_map as in
-// szn_fused_head_grouped (NULL, 0, NULL: ungrouped); kind = the loss; exclude: FH_SIMCE and FH_RANK; temperature: FH_SIMCE only;
-// margin / hardest: FH_RANK only
-enum FhKind { FH_COS, FH_MSE, FH_SIMCE, FH_RANK };
+// szn_fused_head_grouped (NULL, 0, NULL: ungrouped); kind = the loss; exclude: FH_SIMCE, FH_RANK and FH_BIAS; temperature: FH_SIMCE and
+// FH_BIAS; margin / hardest: FH_RANK only; bias_unseen / bias_weight / hidden_label: FH_BIAS only
+enum FhKind { FH_COS, FH_MSE, FH_SIMCE, FH_RANK, FH_BIAS };
 int fused_head_impl(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
                     const float* coarse, const float* embed, const int64_t* target, float* loss,
                     float* stats, int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace,
                     szn_stream_t stream, bool prep, const szn_class_set* unseen, int group_mode,
                     const int64_t* group_map, FhKind kind, const szn_class_set* exclude = nullptr, float temperature = 1.f,
-                    float margin = 0.f, int hardest = 0) {
+                    float margin = 0.f, int hardest = 0, const szn_class_set* bias_unseen = nullptr, float bias_weight = 0.f,
+                    int64_t hidden_label = 0) {
     const bool mse = kind == FH_MSE;
     if (stride != 32 && stride != 8) SZN_FAIL(SZN_ERR_UNSUPPORTED, "fused_head: stride %d (32 and 8 are built)", stride);
     if (!coarse || !embed || !workspace || B <= 0 || h <= 0 || w <= 0 || E <= 0 || c0 < 0 || ldc < c0 + E || H <= 0 ||
@@ -1733,7 +1840,22 @@ int fused_head_impl(int stride, int B, int h, int w, int E, int ldc, int c0, int
         if (K - n_excl < 2) SZN_FAIL(SZN_ERR_ARG, "fused_rank_head: the exclude set leaves %d of the %d classes competing (two are needed)", K - n_excl, K);
         rank.margin = margin; rank.hardest = hardest;
     }
-    const bool dense = kind == FH_SIMCE || kind == FH_RANK;
+    BiasArgs bias{};
+    if (kind == FH_BIAS) {
+        if (!(temperature > 0.f) || !isfinite(temperature)) SZN_FAIL(SZN_ERR_ARG, "fused_simce_bias_head: temperature %g is not a positive finite number", (double)temperature);
+        bias.excl = class_bits(exclude);
+        if (!class_bits_fit(bias.excl, K)) SZN_FAIL(SZN_ERR_ARG, "fused_simce_bias_head: the exclude set names a class >= K = %d", K);
+        bias.unseen = class_bits(bias_unseen);
+        if (!class_bits_fit(bias.unseen, K)) SZN_FAIL(SZN_ERR_ARG, "fused_simce_bias_head: the bias set names a class >= K = %d", K);
+        int n_excl = 0, n_u = 0;
+        for (int i = 0; i < 4; ++i) { n_excl += __builtin_popcountll(bias.excl.w[i]); n_u += __builtin_popcountll(bias.unseen.w[i]); }
+        if (n_excl >= K) SZN_FAIL(SZN_ERR_ARG, "fused_simce_bias_head: the exclude set leaves none of the %d classes competing", K);
+        if (n_u == 0 || n_u >= K) SZN_FAIL(SZN_ERR_ARG, "fused_simce_bias_head: the bias set holds %d of the %d classes (at least one, not all)", n_u, K);
+        if (!(bias_weight > 0.f) || !isfinite(bias_weight)) SZN_FAIL(SZN_ERR_ARG, "fused_simce_bias_head: weight %g is not a positive finite number", (double)bias_weight);
+        if (hidden_label >= -1) SZN_FAIL(SZN_ERR_ARG, "fused_simce_bias_head: hidden label %lld is not below -1", (long long)hidden_label);
+        bias.inv_t = 1.f / temperature; bias.weight = bias_weight; bias.hidden = (long)hidden_label;
+    }
+    const bool dense = kind == FH_SIMCE || kind == FH_RANK || kind == FH_BIAS;
     const bool grouped = group_mode != 0;
     hipStream_t st = (hipStream_t)stream;
     const int KP = kp_of(K);
@@ -1757,6 +1879,7 @@ int fused_head_impl(int stride, int B, int h, int w, int E, int ldc, int c0, int
     a.gmap = group_map; a.gmode = group_mode; a.unseen = ubits;
     if (kind == FH_SIMCE) sce_launch_k(KP, grouped, stride, a, sce, tabD, tabN, st);
     else if (kind == FH_RANK) sce_launch_k(KP, grouped, stride, a, rank, tabD, tabN, st);
+    else if (kind == FH_BIAS) sce_launch_k(KP, grouped, stride, a, bias, tabD, tabN, st);
     else switch (KP) {
         case 24: fh_launch_kp<24>(grouped, mse, stride, a, tabD, tabN, st); break;
         case 40: fh_launch_kp<40>(grouped, mse, stride, a, tabD, tabN, st); break;
@@ -1904,6 +2027,29 @@ extern "C" int szn_fused_rank_head_prepared(int stride, int B, int h, int w, int
                                             int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace, szn_stream_t stream) {
     return fused_head_impl(stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype, dcoarse,
                            workspace, stream, false, unseen, group_mode, group_map, FH_RANK, exclude, 1.f, margin, hardest);
+}
+
+// sim_ce with QFSL's unseen-bias term (train.py -loss sim_ce --bias-loss; utils.sim_ce_bias_loss): a pixel labelled `hidden_label` adds
+// weight * -log sum_{u in bias_unseen} softmax_u over all K classes; every other pixel is szn_fused_simce_head's (include/szn.h).
+extern "C" int szn_fused_simce_bias_head(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                                         const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
+                                         int group_mode, const int64_t* group_map, const szn_class_set* exclude, float temperature,
+                                         const szn_class_set* bias_unseen, float weight, int64_t hidden_label, float* loss, float* stats,
+                                         int64_t* pred, int dcoarse_dtype, void* dcoarse, void* workspace, szn_stream_t stream) {
+    return fused_head_impl(stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype, dcoarse,
+                           workspace, stream, true, unseen, group_mode, group_map, FH_BIAS, exclude, temperature, 0.f, 0, bias_unseen, weight,
+                           hidden_label);
+}
+
+extern "C" int szn_fused_simce_bias_head_prepared(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                                                  const float* coarse, const float* embed, const int64_t* target,
+                                                  const szn_class_set* unseen, int group_mode, const int64_t* group_map,
+                                                  const szn_class_set* exclude, float temperature, const szn_class_set* bias_unseen,
+                                                  float weight, int64_t hidden_label, float* loss, float* stats, int64_t* pred,
+                                                  int dcoarse_dtype, void* dcoarse, void* workspace, szn_stream_t stream) {
+    return fused_head_impl(stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, loss, stats, pred, dcoarse_dtype, dcoarse,
+                           workspace, stream, false, unseen, group_mode, group_map, FH_BIAS, exclude, temperature, 0.f, 0, bias_unseen, weight,
+                           hidden_label);
 }
 
 // Calibrated stacking (include/szn.h): the seen-class penalty gamma swept over n_gammas values in one pass over the pixels.

@@ -376,7 +376,7 @@ class TrainStep(object):
                  scale_growth=2.0, scale_backoff=0.5, scale_growth_interval=2000, force_comm=None, reserved_cus=None,
                  fused_adam=None, keep_grads=True, exchange=None, direct_wire=None, sharded=None, forced_unseen=None,
                  class_weight=None, size_average=False, sim_exclude=None, sim_temperature=None, pseudo=None, ohem=None,
-                 rank_margin=None, rank_hardest=False):
+                 rank_margin=None, rank_hardest=False, bias=None):
         """Data-parallel knobs (the reference is single-GPU): grad_comm_dtype (SZN_GRAD_COMM = fp32 | bf16) = the
         wire format of the gradient buckets; exchange=False (SZN_GRAD_COMM=off) = no exchange at all (bench.py's comm-off timing);
         direct_wire (default: on for a 16-bit wire with keep_grads=False; SZN_WIRE_DIRECT=0 turns it off) = the weight-gradient
@@ -417,7 +417,15 @@ class TrainStep(object):
         train prediction compete in the seen group, like every ignored pixel).  set_ohem_active(False) makes the step the plain step
         again, launch for launch.  ohem_counts, a device (2,) int64 tensor, accumulates {evaluated, kept} over images and steps until the
         caller zeroes it; with keep_ctx the mined target of the last step stays in last_ohem_target.  Under data parallelism the cuts
-        belong to each rank's own images: nothing is exchanged."""
+        belong to each rank's own images: nothing is exchanged.
+        bias=dict(unseen=[...], weight=lambda, hidden=datasets.HIDDEN_LABEL) (loss "sim_ce" only; utils.sim_ce_bias_loss;
+        szn_fused_simce_bias_head): QFSL's unseen-bias term.  A pixel the dataset hides (label `hidden`) adds weight * -log of the
+        probability mass its softmax over ALL classes puts on `unseen`; labelled pixels keep sim_ce's term, and the image's mean runs over
+        both kinds.  The head reads the target the pseudo-label and mining passes leave: pixels that pseudo labelling relabels get the
+        supervised term and only the still-hidden ones the bias term; mining neither counts nor drops hidden pixels (it evaluates labels
+        in [0, K) only and copies every other label through).  `unseen` stays as given when active pseudo labels empty sim_exclude.
+        set_bias_active(False) makes the step the plain sim_ce step again, launch for launch.  Under data parallelism nothing is
+        exchanged: the term is per pixel."""
         if loss not in ("cos", "mse", "sim_ce", "rank", "cross_entropy"):
             raise L.SznError("TrainStep: loss must be 'cos', 'mse', 'sim_ce', 'rank' or 'cross_entropy', got %r" % (loss,))
         if (loss not in ("sim_ce", "rank") and sim_exclude is not None) or (loss != "sim_ce" and sim_temperature is not None):
@@ -431,6 +439,12 @@ class TrainStep(object):
         if loss == "rank" and not fused_head:
             raise L.SznError("TrainStep: the rank loss runs on the fused head only; the materialised score goes through autograd "
                              "(utils.rank_loss)")
+        if bias is not None:
+            if loss != "sim_ce":
+                raise L.SznError("TrainStep: the bias loss belongs to loss 'sim_ce', not %r" % (loss,))
+            if not isinstance(bias, dict) or embeddings is None:
+                raise L.SznError("TrainStep: bias must be a dict(unseen=, weight=[, hidden=]) next to the class embeddings, got %r" % (bias,))
+            heads.bias_args(loss, bias, len(embeddings))              # host checks only: nothing has touched a device yet
         if pseudo is not None:
             pseudo = self._check_pseudo(pseudo, loss)
         if ohem is not None:
@@ -506,6 +520,9 @@ class TrainStep(object):
             if not 0 <= margin < float("inf"):
                 raise L.SznError("TrainStep: rank_margin must be finite and >= 0, got %r" % (rank_margin,))
             self._sim_kw = dict(exclude=excl, margin=margin, hardest=bool(rank_hardest))
+        self._bias = None if bias is None else dict(bias)             # heads.embed's bias keyword, see set_bias_active
+        self._bias_active = False
+        self.set_bias_active(bias is not None)
         self._pseudo = None                                           # szn_pseudo_head's arguments, see set_pseudo_active
         self._pseudo_active = False
         self.last_pseudo_target = None                                # (keep_ctx) the relabelled target the last step's head read
@@ -540,6 +557,8 @@ class TrainStep(object):
         # The rank head starts there too: |dL/ds| <= 2 V / |s| for a pixel with V violated hinges (V <= 1 with rank_hardest), the
         # cosine bound times 2 V.  A fresh head violates most of its up to K - 2 hinges, so the sum form may exceed sim_ce's 2 / T
         # at first; the dynamic scale pays for that with a few halvings at the start and grows back as the hinges clear.
+        # The bias term of sim_ce keeps sim_ce's start: a hidden pixel's gradient is (weight / T) sum_k (p_k - q_k) d cos_k / d s with
+        # sum_k |p_k - q_k| <= 2 (two distributions), so |dL/ds| <= 2 weight / (T |s|), sim_ce's bound times weight.
         fp16_scale0 = 1.0 if self.ce else (512.0 if loss == "mse" else 4096.0)
         self._loss_scale0 = float(loss_scale) if loss_scale is not None else (fp16_scale0 if precision == torch.float16 else 1.0)
         # dynamic loss scaling (default for fp16): the scale, the overflow flag and the count of APPLIED optimizer steps live
@@ -596,6 +615,18 @@ class TrainStep(object):
         self.keep_ctx = False        # tests: keep the forward state of the last step (activations stay alive one step longer)
         self.last_ctx = None
         self.last_fuse3 = None           # (FCN8s, keep_ctx) the 1/8 fused map of the last step
+
+    def set_bias_active(self, active):
+        """turn the unseen-bias term of a step built with bias= on or off; off, the step is the plain sim_ce step launch for launch"""
+        if self._bias is None:
+            if active:
+                raise L.SznError("TrainStep: set_bias_active(True) on a step built without bias=")
+            return
+        self._bias_active = bool(active)
+        if self._bias_active:
+            self._sim_kw["bias"] = self._bias
+        else:
+            self._sim_kw.pop("bias", None)
 
     # ---- self-training pseudo labels ----------------------------------------------------------------------------------------
     @staticmethod

@@ -12,6 +12,8 @@ szn_fused_ce_head and szn_seenmask_head_k goes through here (models.FCN32s / FCN
             outside `exclude`, divided by `temperature`; same prediction bit for bit, same Workspace tables.
   rank      the same head with the hinge ranking loss (szn_fused_rank_head, DeViSE): the label's cosine must beat the cosine of every
             other class outside `exclude` by `margin`; `hardest` keeps the hardest negative alone.  Same prediction, same tables.
+  sim_ce_bias  sim_ce with QFSL's unseen-bias term (szn_fused_simce_bias_head): embed("sim_ce", ..., bias=dict(unseen=, weight=,
+            hidden=HIDDEN_LABEL)); a pixel labelled `hidden` adds weight * -log sum_{u in unseen} softmax_u over all classes.
   ce        the softmax cross-entropy head, stride 32 or 8.
   seenmask  the x32 seen-mask head on the 1/32 map: training, predict and pred-only (group map) calls.
   ms        multi-scale / mirrored inference: the views of an input (szn_resize_flip_f32) and the view-ensemble head (szn_ms_head),
@@ -143,18 +145,47 @@ def _loss_args(kind, exclude, temperature, margin, hardest):
     return _sim_args(kind, exclude, temperature) + _rank_args(kind, exclude, margin, hardest)
 
 
+def bias_args(kind, bias, K):
+    """the three extra C arguments of the bias term after sim_ce's (bias: None | dict(unseen=classes, weight=lambda, hidden=label,
+    default HIDDEN_LABEL)), checked on the host: kind "sim_ce" only, unseen some but not all of [0, K), weight finite > 0, hidden < -1"""
+    import math
+    if bias is None:
+        return ()
+    if kind != "sim_ce":
+        raise L.SznError("embedding head: the bias term belongs to loss 'sim_ce', not %r" % (kind,))
+    unknown = sorted(set(bias) - {"unseen", "weight", "hidden"})
+    if unknown or "unseen" not in bias or "weight" not in bias:
+        raise L.SznError("bias loss: bias = dict(unseen=classes, weight=lambda[, hidden=label]), got keys %r" % (sorted(bias),))
+    try:
+        unseen = sorted(set(int(k) for k in bias["unseen"]))
+        weight = float(bias["weight"])
+        hidden = int(bias.get("hidden", HIDDEN_LABEL))
+    except (TypeError, ValueError):
+        raise L.SznError("bias loss: unseen must be class indices, weight a number, hidden an integer (got %r)" % (bias,))
+    if not unseen or unseen[0] < 0 or unseen[-1] >= K or len(unseen) >= K:
+        raise L.SznError("bias loss: unseen must name some, not all, classes of [0, %d) (got %r)" % (K, unseen))
+    if not (math.isfinite(weight) and weight > 0.0):
+        raise L.SznError("bias loss: weight must be a finite number > 0 (got %r)" % (bias["weight"],))
+    if hidden >= -1:
+        raise L.SznError("bias loss: the hidden label must lie below -1 (got %r): -1 and the class labels are taken" % (hidden,))
+    return (L.class_set(unseen), weight, hidden)
+
+
 def embed(kind, stride, fmap, emb, H, W, pred, target=None, loss=None, stats=None, dmap=None, mode=0, classes=None, gmap=None,
-          ws=None, stream=None, exclude=None, temperature=None, margin=None, hardest=None):
+          ws=None, stream=None, exclude=None, temperature=None, bias=None, margin=None, hardest=None):
     """szn_fused_head_grouped (kind "cos") / szn_fused_mse_head (kind "mse") / szn_fused_simce_head (kind "sim_ce", with exclude = the
     classes that do not compete and temperature) / szn_fused_rank_head (kind "rank", with exclude, margin and hardest) on the contiguous NHWC map `fmap` (the E embedding channels first).  target / loss / stats go together; dmap (zero-padded, [E, ld) stays untouched) receives d loss / d fmap in its
     dtype.  classes = the unseen class set (L.class_set) of modes 1 / 2, gmap the group map of mode 1.  ws: a Workspace (its
-    embedding tables are reused, whichever kind wrote them) or None."""
+    embedding tables are reused, whichever kind wrote them) or None.  bias (kind "sim_ce" only): dict(unseen=, weight=, hidden=) routes
+    to szn_fused_simce_bias_head (bias_args)."""
     B, h, w, ld = fmap.shape
     K, E = emb.shape
     st = L.stream_ptr() if stream is None else stream
     nbytes = L.load().szn_fused_head_workspace_bytes(B, h, w, E, K)
     fn = _EMBED_ENTRY[kind]
     sim = _loss_args(kind, exclude, temperature, margin, hardest)
+    if bias is not None:
+        fn, sim = "szn_fused_simce_bias_head", sim + bias_args(kind, bias, K)
     if ws is None:
         buf = _scratch(nbytes, fmap.device)
     else:
@@ -167,24 +198,24 @@ def embed(kind, stride, fmap, emb, H, W, pred, target=None, loss=None, stats=Non
 
 
 def embed_predict(kind, stride, fmap, emb, H, W, target=None, mode=0, unseen=None, gmap=None, exclude=None, temperature=None,
-                  margin=None, hardest=None):
+                  bias=None, margin=None, hardest=None):
     """forward-only embedding head -> (loss 0-dim tensor or None, pred (B,H,W) int64)"""
     B = fmap.shape[0]
     pred, tgt, loss = _outputs(B, H, W, fmap.device, target)
     stats = None if loss is None else torch.empty(B, 2, device=fmap.device)
     embed(kind, stride, fmap, emb, H, W, pred, tgt, loss, stats, mode=mode, classes=L.class_set(unseen), gmap=gmap, exclude=exclude,
-          temperature=temperature, margin=margin, hardest=hardest)
+          temperature=temperature, margin=margin, hardest=hardest, bias=bias)
     return (loss.reshape(()) if loss is not None else None), pred
 
 
-def embed_loss(kind, stride, fmap, emb, H, W, target, exclude=None, temperature=None, ws=None, margin=None, hardest=None):
+def embed_loss(kind, stride, fmap, emb, H, W, target, exclude=None, temperature=None, ws=None, bias=None, margin=None, hardest=None):
     """the loss of embed_predict alone, bit for bit (the same kernels without the prediction: no trip through the classes per pixel)
     -> loss 0-dim tensor.  ws: a Workspace or None, as in embed()"""
     B = fmap.shape[0]
     tgt = target.to(device=fmap.device, dtype=torch.int64).contiguous()
     loss, stats = torch.empty(1, device=fmap.device), torch.empty(B, 2, device=fmap.device)
     embed(kind, stride, fmap, emb, H, W, None, tgt, loss, stats, ws=ws, exclude=exclude, temperature=temperature, margin=margin,
-          hardest=hardest)
+          hardest=hardest, bias=bias)
     return loss.reshape(())
 
 
@@ -213,6 +244,12 @@ def sim_ce(*args, **kw):
 
 def sim_ce_predict(*args, **kw):
     return embed_predict("sim_ce", *args, **kw)
+
+
+def sim_ce_bias(stride, fmap, emb, H, W, pred, unseen, weight, hidden=HIDDEN_LABEL, **kw):
+    """embed("sim_ce", ..., bias=dict(unseen=, weight=, hidden=)): sim_ce plus the unseen-bias term on the pixels labelled `hidden`
+    (utils.sim_ce_bias_loss) -- sim_ce's other arguments, same pred"""
+    embed("sim_ce", stride, fmap, emb, H, W, pred, bias=dict(unseen=unseen, weight=weight, hidden=hidden), **kw)
 
 
 def rank(*args, **kw):

@@ -34,6 +34,10 @@ Added for this implementation (none change the reference flags):
                        the hidden pixels per unseen class with its own calibrated prediction (szn_pseudo_head) and trains on them;
                        --pseudo-gamma G (default: --calibration, else 0), --pseudo-floor C (smallest similarity a label may have,
                        default none), --pseudo-start-epoch N (default 0); counts per epoch and class in <log_dir>/pseudo_log.csv
+  --bias-loss LAMBDA   with -loss sim_ce: the unseen-bias loss of QFSL on the pixels the training set hides (--hide-unseen, implied): each
+                       adds LAMBDA * -log of the probability its softmax over all classes gives the unseen ones
+                       (szn_fused_simce_bias_head); no class is committed to.  LAMBDA has no default; --bias-start-epoch N (default 0).
+                       Combines with --pseudo-label: relabelled pixels get the supervised term, the still-hidden ones this term
   --ohem KEEP          hard-pixel mining for the embedding losses: every training step trains on the KEEP (0 < KEEP <= 1) of each image's
                        labelled pixels whose cosine to their own class embedding is lowest (szn_ohem_head) and ignores the rest;
                        --ohem-thresh C also keeps every pixel whose cosine lies below C (bins of 1/512), --ohem-start-epoch N
@@ -140,6 +144,12 @@ def build_parser():
                    help="with --pseudo-label: the smallest cosine similarity a pseudo label may have (default: none)")
     p.add_argument('--pseudo-start-epoch', type=int, default=None, metavar='N',
                    help="with --pseudo-label: the first epoch that self-trains (default 0)")
+    p.add_argument('--bias-loss', type=float, default=None, metavar='LAMBDA',
+                   help="with -loss sim_ce: every hidden pixel adds LAMBDA * -log(probability of the unseen classes under the softmax "
+                        "over all classes) to the loss (QFSL's bias loss); implies --hide-unseen; needs unseen classes.  LAMBDA has no "
+                        "default: it is a hyper-parameter nobody has tuned here.  An error without -loss sim_ce.  Default: off")
+    p.add_argument('--bias-start-epoch', type=int, default=None, metavar='N',
+                   help="with --bias-loss: the first epoch that applies the term (default 0)")
     p.add_argument('--ohem', type=float, default=None, metavar='KEEP',
                    help="hard-pixel mining: every training step trains on the KEEP (0 < KEEP <= 1) of each image's labelled pixels whose "
                         "cosine to their own class embedding is lowest and ignores the others; needs an embedding configuration.  KEEP "
@@ -373,6 +383,26 @@ def check_pseudo(keep, gamma, floor, start_epoch, hide_unseen, cfg):
         raise Exception("--pseudo-label: " + why)
 
 
+def check_bias(weight, start_epoch, cfg):
+    """--bias-loss / --bias-start-epoch: only with fcn_loss 'sim_ce'; LAMBDA finite and > 0, N >= 0; the satellite only with
+    --bias-loss; unseen classes (trainer_fcn.bias_refused)"""
+    import math
+    if weight is None:
+        if start_epoch is not None:
+            raise Exception("--bias-start-epoch needs --bias-loss")
+        return
+    if cfg['fcn_loss'] != 'sim_ce':
+        raise Exception("--bias-loss needs -loss sim_ce (got loss %r)" % (cfg['fcn_loss'],))
+    if not (math.isfinite(weight) and weight > 0):
+        raise Exception("--bias-loss: LAMBDA must be finite and > 0 (got %r)" % (weight,))
+    if start_epoch is not None and start_epoch < 0:
+        raise Exception("--bias-start-epoch: N must not be negative (got %r)" % (start_epoch,))
+    n_class = 21 if cfg['dataset'] == 'pascal' else 33
+    why = trainer_fcn.bias_refused(bool(cfg['train_unseen'] or cfg['val_unseen']), bool(cfg['embed_dim']), cfg['fcn_loss'], n_class)
+    if why:
+        raise Exception("--bias-loss: " + why)
+
+
 def check_ohem(keep, thresh, start_epoch, cfg):
     """--ohem / --ohem-thresh / --ohem-start-epoch: KEEP in (0, 1], a finite C, N >= 0; the satellites only with --ohem; an embedding
     configuration (trainer_fcn.ohem_refused)"""
@@ -425,7 +455,8 @@ def main(argv=None):
     check_seen_threshold(args.seen_threshold, args.seen_sweep, cfg, args.calibration, args.calib_sweep, args.eval_scales, args.eval_flip)
     check_pseudo(args.pseudo_label, args.pseudo_gamma, args.pseudo_floor, args.pseudo_start_epoch, args.hide_unseen, cfg)
     check_ohem(args.ohem, args.ohem_thresh, args.ohem_start_epoch, cfg)
-    hide_unseen = args.hide_unseen or args.pseudo_label is not None
+    check_bias(args.bias_loss, args.bias_start_epoch, cfg)
+    hide_unseen = args.hide_unseen or args.pseudo_label is not None or args.bias_loss is not None
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", str(args.gpu)))
@@ -552,7 +583,7 @@ def main(argv=None):
         pseudo_start_epoch=args.pseudo_start_epoch or 0,
         ohem=None if args.ohem is None else dict(keep=args.ohem, thresh=args.ohem_thresh), ohem_start_epoch=args.ohem_start_epoch or 0,
         calibration=args.calibration, calib_sweep=calib_sweep_values(args.calib_sweep), eval_scales=args.eval_scales,
-        eval_flip=args.eval_flip)
+        eval_flip=args.eval_flip, bias_loss=args.bias_loss, bias_start_epoch=args.bias_start_epoch or 0)
     fcn_trainer.epoch, fcn_trainer.iteration = start_epoch, start_iteration
 
     if cfg['mode'] == 'train':

@@ -96,6 +96,18 @@ def pseudo_refused(has_unseen, embed_cfg, n_class):
     return None
 
 
+def bias_refused(has_unseen, pixel_embeddings, loss_func, n_class):
+    """why a configuration cannot train with the unseen-bias loss (bias_loss=, train.py --bias-loss), or None: the term is part of the
+    fused sim_ce head and pulls the hidden pixels towards the unseen classes"""
+    if not (pixel_embeddings and loss_func == "sim_ce"):
+        return "the bias loss belongs to loss 'sim_ce' (got loss %r): it is a term of that head's softmax" % (loss_func,)
+    if not has_unseen:
+        return "the bias loss needs unseen classes (train_unseen / val_unseen): there is nothing hidden to pull towards them"
+    if n_class > 256:
+        return "the bias loss: the fused head holds at most 256 classes, got %d" % n_class
+    return None
+
+
 def ohem_refused(embed_cfg, n_class):
     """why a configuration cannot mine hard pixels (ohem=, train.py --ohem), or None: hardness is the cosine to the pixel's own class
     embedding, a quantity of the fused embedding head"""
@@ -118,7 +130,7 @@ class Trainer(object):
                  pixel_embeddings=None, loss_func=None, unseen=None, val_unseen=None, label_names=None,
                  forced_unseen=False, embed_arr=None, precision=torch.float32, fused_step=True, rank=0, visualize=0, augment=None,
                  seen_threshold=None, seen_sweep=None,
-                 sim_temperature=None, rank_margin=None, rank_hardest=False, pseudo=None, pseudo_start_epoch=0, ohem=None, ohem_start_epoch=0, calibration=None,
+                 sim_temperature=None, rank_margin=None, rank_hardest=False, bias_loss=None, bias_start_epoch=0, pseudo=None, pseudo_start_epoch=0, ohem=None, ohem_start_epoch=0, calibration=None,
                  calib_sweep=None, eval_scales=None, eval_flip=False):
         if not cuda:
             raise RuntimeError("this implementation runs on the GPU only (cuda=False has no CPU fallback)")
@@ -267,6 +279,23 @@ class Trainer(object):
                     with open(osp.join(self.log_dir, 'ohem_log.csv'), 'w') as f:
                         f.write('epoch,evaluated,kept,fraction\n')
 
+        # the unseen-bias loss (engine.TrainStep bias=, QFSL): from epoch bias_start_epoch on every hidden pixel (datasets.HIDDEN_LABEL: a
+        # hide_unseen training set) adds bias_loss * -log P(unseen classes) to the sim_ce loss; the unseen set is self.unseen.
+        # Validation data has no hidden pixels: validation is untouched
+        self.bias_loss = None
+        self.bias_start_epoch = int(bias_start_epoch)
+        if bias_loss is not None:
+            from ._lib import SznError
+            from .heads import bias_args
+            why = bias_refused(bool(self.unseen), bool(pixel_embeddings), loss_func, self.n_class)
+            if why:
+                raise SznError(why)
+            if not fused_step:
+                raise SznError("the bias loss runs inside the fused training step (fused_step=True)")
+            cfg = dict(unseen=list(self.unseen), weight=bias_loss)
+            bias_args(loss_func, cfg, self.n_class)
+            self.bias_loss = cfg
+
         if self.pixel_embeddings:
             arr = np.asarray(embed_arr, dtype=np.float32) if embed_arr is not None else \
                 load_embeddings(dataset, pixel_embeddings)
@@ -399,6 +428,8 @@ class Trainer(object):
                 kw.update(pseudo=self.pseudo)
             if self.ohem is not None:
                 kw.update(ohem=self.ohem)
+            if self.bias_loss is not None:
+                kw.update(bias=self.bias_loss)
         self._step = _engine.TrainStep(self.model, lr=gw['lr'], bias_lr=gb['lr'],
                                        bias_weight_decay=gb.get('weight_decay', 0.0), precision=self.precision,
                                        fused_head=True, keep_grads=os.environ.get("SZN_KEEP_GRADS", "0") == "1", **kw)
@@ -423,6 +454,11 @@ class Trainer(object):
                 raise SznError("ohem runs inside the fused training step, which this optimizer wiring does not allow")
             step.set_ohem_active(self.epoch >= self.ohem_start_epoch)
             step.ohem_counts.zero_()
+        if self.bias_loss is not None:
+            if step is None:
+                from ._lib import SznError
+                raise SznError("the bias loss runs inside the fused training step, which this optimizer wiring does not allow")
+            step.set_bias_active(self.epoch >= self.bias_start_epoch)
         if step is None and self.model._engine.dtype == torch.float16:
             # IEEE-half gradients need loss scaling, which only engine.TrainStep applies (d(coarse) is multiplied in fp32 before
             # it enters the 16-bit backward pass); the autograd paths (non-reference optimizer wiring, more than 256 classes)

@@ -8,6 +8,7 @@ There is no CPU fallback: tensors must live on the GPU.
   cross_entropy2d(score, target, ...)      utils.py:19-48
   mse_loss / cosine_loss                   utils.py:50-102
   sim_ce_loss                              similarity cross-entropy in torch ops (no reference counterpart)
+  sim_ce_bias_loss                         sim_ce plus QFSL's unseen-bias term on hidden pixels, in torch ops (no reference counterpart)
   rank_loss                                hinge ranking loss (DeViSE) in torch ops (no reference counterpart)
   label_accuracy_score                     utils.py:104-154
   infer_lbl / infer_lbl_forced_unseen / infer_lbl_szn / stich_seen_unseen_with_mask   utils.py:159-205
@@ -188,6 +189,57 @@ def sim_ce_loss(score, target, embed, exclude=None, temperature=0.1):
     term = torch.logsumexp(z, dim=3) - zall.gather(3, lbl.unsqueeze(3)).squeeze(3)
     term = torch.where(counted, term, torch.zeros_like(term))
     per_image = term.sum(dim=(1, 2)) / counted.sum(dim=(1, 2)).to(score.dtype)
+    return per_image.mean()
+
+
+def sim_ce_bias_loss(score, target, embed, exclude=None, temperature=0.1, unseen=(), weight=1.0, hidden_label=-3):
+    """sim_ce_loss plus QFSL's unseen-bias term (include/szn.h, szn_fused_simce_bias_head): a labelled pixel (0 <= label < K, label not
+    in `exclude`) has sim_ce_loss's term; a pixel labelled `hidden_label` has weight * -log sum_{u in unseen} softmax_u(cos(s, e_k) / T)
+    with the softmax over ALL K classes, formed as logsumexp_all - logsumexp_unseen so that it stays finite where the unseen
+    probability itself underflows; every other pixel is ignored.  Per image the sum of all terms over the number of labelled plus hidden
+    pixels (one joint mean), the loss is the mean over images.  Plain differentiable torch ops on the materialised score (n,c,h,w), in
+    the score's own dtype (float32 or float64) and on its device: the autograd route and the in-suite referee of the fused head.
+    hidden_label: datasets.HIDDEN_LABEL by default (datasets imports this module, hence the literal)."""
+    if score.dim() != 4:
+        raise L.SznError("sim_ce_bias_loss: score must be (n,c,h,w), got %s" % (tuple(score.shape),))
+    if not float(temperature) > 0 or not np.isfinite(float(temperature)):
+        raise L.SznError("sim_ce_bias_loss: temperature must be positive and finite, got %r" % (temperature,))
+    if not float(weight) > 0 or not np.isfinite(float(weight)):
+        raise L.SznError("sim_ce_bias_loss: weight must be positive and finite, got %r" % (weight,))
+    if int(hidden_label) >= -1:
+        raise L.SznError("sim_ce_bias_loss: the hidden label must lie below -1, got %r" % (hidden_label,))
+    B, E, H, W = score.shape
+    emb = torch.as_tensor(embed).detach().to(device=score.device, dtype=score.dtype)
+    K = emb.shape[0]
+    if emb.dim() != 2 or emb.shape[1] != E:
+        raise L.SznError("sim_ce_bias_loss: embedding matrix %s does not match the score's %d channels" % (tuple(emb.shape), E))
+    excl = sorted(set(int(k) for k in (exclude if exclude is not None else [])))
+    if any(not 0 <= k < K for k in excl):
+        raise L.SznError("sim_ce_bias_loss: exclude names a class outside [0, %d)" % K)
+    if len(excl) >= K:
+        raise L.SznError("sim_ce_bias_loss: exclude leaves no class competing")
+    uns = sorted(set(int(k) for k in unseen))
+    if not uns or uns[0] < 0 or uns[-1] >= K or len(uns) >= K:
+        raise L.SznError("sim_ce_bias_loss: unseen must name some, not all, classes of [0, %d)" % K)
+    competes = torch.ones(K, dtype=torch.bool, device=score.device)
+    if excl:
+        competes[torch.tensor(excl, device=score.device)] = False
+    in_u = torch.zeros(K, dtype=torch.bool, device=score.device)
+    in_u[torch.tensor(uns, device=score.device)] = True
+    target = target.to(device=score.device, dtype=torch.int64)
+    en = emb.norm(dim=1)
+    en = torch.where(en == 0, torch.ones_like(en), en)
+    s = score.permute(0, 2, 3, 1)                                        # (B,H,W,E)
+    cos = (s @ emb.t()) / (s.norm(dim=3, keepdim=True) * en)             # (B,H,W,K)
+    zall = cos / float(temperature)
+    in_range = (target >= 0) & (target < K)
+    lbl = torch.where(in_range, target, torch.zeros_like(target))
+    labelled = in_range & competes[lbl]
+    hidden = target == int(hidden_label)
+    sup = torch.logsumexp(zall.masked_fill(~competes, float("-inf")), dim=3) - zall.gather(3, lbl.unsqueeze(3)).squeeze(3)
+    bias = float(weight) * (torch.logsumexp(zall, dim=3) - torch.logsumexp(zall.masked_fill(~in_u, float("-inf")), dim=3))
+    term = torch.where(labelled, sup, torch.where(hidden, bias, torch.zeros_like(sup)))
+    per_image = term.sum(dim=(1, 2)) / (labelled | hidden).sum(dim=(1, 2)).to(score.dtype)
     return per_image.mean()
 
 
