@@ -976,6 +976,44 @@ int szn_ohem_head(int stride, int B, int h, int w, int E, int ldc, int c0, int H
                   int64_t* target_out, float* conf, int64_t* qhist, int32_t* cut, int64_t* counts,
                   void* workspace, szn_stream_t stream);
 
+/* ---- class prototypes: masked average pooling of the upsampled score, per class (few-shot adaptation of the class embeddings) -----
+ * szn_class_proto: for every class k the sum, over the pixels `labels` gives it, of the pixel's score vector (SZN_PROTO_RAW) or of its
+ * unit vector (SZN_PROTO_UNIT, the mean a cosine classifier wants), and the pixel counts -- without the (B,E,H,W) score in memory.
+ * coarse, stride (32 | 8), crop, ldc, c0, h, w, H and W are szn_fused_head_strided's; labels is any int64 (B,H,W) map (ground truth, a
+ * prediction, szn_pseudo_head's target_out).
+ *   A pixel PARTICIPATES when 0 <= labels[pix] < K and its label is in `classes` (NULL: all K classes).  Every other label -- -1, -2,
+ *   -3, a label >= K, a class outside the set -- is skipped without arithmetic.
+ *   s = the pixel's upsampled, cropped score in fp32: the blend of the four taps of its cell with the weights of get_upsampling_weight
+ *   (models.py:13-24).  |s| is formed as the fused head forms it: |s|^2 = the fmaf chain over the 16 (t, u) pairs of w_t w_u (C_t . C_u),
+ *   each dot product 64 strided fp32 chains + xor butterfly, then sqrtf.
+ *   A participating pixel CONTRIBUTES when |s| is finite and > 0 (UNIT), always (RAW).
+ *   counts[K][2] int64 = { participating pixels, contributing pixels } of every class.
+ *   sums[K][E] double = the sum over the contributing pixels of s (RAW) or s / |s| (UNIT), evaluated as sum_pos T[pos][k] *
+ *   coarse[pos][c0 + e]: T[pos][k] = the sum over the class's contributing pixels that blend position pos of w_t (RAW) or w_t / |s|
+ *   (UNIT).  w_t and |s| are fp32, the quotient, T and everything after are double (RAW: T and every product are exact, only the
+ *   additions over the positions round).  Positions whose coefficient is 0 are skipped: a NaN under no contributing pixel stays out.
+ *   Channels outside [c0, c0 + E) are never read.
+ * accumulate = 0 writes all K rows of sums and counts: rows of classes outside the set, or without a pixel, are exactly 0.
+ * accumulate = 1 adds the value the call would have written to what is there -- one double add per element of sums, one integer add per
+ * count: a support set is pooled batch by batch.
+ * Every reduction runs in a fixed order; the only atomics are integer adds into the count table (zeroed on the stream by the call): two
+ * calls give bit-equal outputs.  Scalar arguments only: no host synchronisation, no allocation, capturable in a hipGraph.
+ * szn_last_kernel(): proto_finalize_kernel; szn_prev_kernel(): proto_reduce_kernel (before them proto_tables_kernel in UNIT mode,
+ * proto_cell_kernel and proto_gather_kernel).
+ * workspace: szn_class_proto_workspace_bytes (0 for shapes szn_class_proto refuses), 16-byte aligned: the Gram table of the positions
+ * (8 floats each), the per-cell coefficient tables [4][K] and the per-position table T [K] in double, up to 64 [K][E] partial sums.
+ * Nothing in it grows with H * W * E or H * W * K.
+ * SZN_ERR_ARG, before any launch: stride not 32 | 8; a size that is not positive; K > SZN_MAX_CLASSES; c0 < 0 or ldc < c0 + E; a crop
+ * window larger than the deconv output; NULL coarse, labels, sums, counts or workspace; a workspace that is not 16-byte aligned; a class
+ * in `classes` >= K; an empty `classes`; mode not SZN_PROTO_RAW | SZN_PROTO_UNIT; accumulate not 0 | 1.  SZN_ERR_UNSUPPORTED: an E too
+ * large for LDS (the table pass stages four position vectors: E > 3840).                                                              */
+#define SZN_PROTO_RAW  0
+#define SZN_PROTO_UNIT 1
+size_t szn_class_proto_workspace_bytes(int stride, int B, int h, int w, int E, int K);
+int szn_class_proto(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                    const float* coarse, const int64_t* labels, const szn_class_set* classes, int mode, int accumulate,
+                    double* sums, int64_t* counts, void* workspace, szn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

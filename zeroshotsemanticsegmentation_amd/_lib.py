@@ -80,6 +80,7 @@ CALIB_MAX_GAMMAS = 64       # SZN_CALIB_MAX_GAMMAS
 SEEN_SWEEP_MAX_TAUS = 64    # SZN_SEEN_SWEEP_MAX_TAUS
 PSEUDO_BINS = 1024          # SZN_PSEUDO_BINS
 OHEM_BINS = 1024            # SZN_OHEM_BINS
+PROTO_RAW, PROTO_UNIT = 0, 1   # SZN_PROTO_RAW, SZN_PROTO_UNIT (szn_class_proto's mode)
 
 
 class MsView(C.Structure):
@@ -213,6 +214,8 @@ SIGNATURES = {
     "szn_pseudo_head": (_I, [_I] * 11 + [_P, _P, _P, _CS, _F, _F, _I, _I64] + [_P] * 8),
     "szn_ohem_head_workspace_bytes": (_SZ, [_I] * 8),
     "szn_ohem_head": (_I, [_I] * 11 + [_P, _P, _P, _CS, _I, _F, _I64] + [_P] * 7),
+    "szn_class_proto_workspace_bytes": (_SZ, [_I] * 6),
+    "szn_class_proto": (_I, [_I] * 11 + [_P, _P, _CS, _I, _I, _P, _P, _P, _P]),
     "szn_viz_segmentation": (_I, [_I, _I, _I, _P, _I, C.POINTER(C.c_double), _P, _P, _I, _CS, _U64, _P, _L, _L, _P]),
     "szn_viz_seenmask": (_I, [_I, _I, _I, _P, _I, C.POINTER(C.c_double), _P, _P, _U64, _P, _L, _L, _P]),
 }

@@ -149,6 +149,14 @@ class _SegmentationDataset(torch.utils.data.Dataset):
         self._presence[key] = [st.st_size, int(st.st_mtime), mask]
         return mask, True
 
+    def class_presence(self, index):
+        """the sorted classes that occur in the label of sample `index`, from the presence cache (the label file is opened only where the
+        cache has no valid record of it; a fresh record is saved)"""
+        mask, fresh = self._presence_of(self.files[index]['lbl'])
+        if fresh:
+            self._save_cache()
+        return [k for k in range(len(self.class_names)) if (mask >> k) & 1]
+
     # ---- samples -------------------------------------------------------------------------------------------------------
     def _load_embeddings(self, embed_arr):
         if embed_arr is not None:
@@ -337,6 +345,61 @@ class Augment(object):
             raise ValueError("Augment needs (images, labels, sizes) batches: build the training loaders with collate_fn=datasets.augment_collate")
         img, lbl, sizes = batch
         return utils.augment_to_device(img, lbl, self.params(sizes, epoch, iteration, rank), self.crop, device, mean_bgr)
+
+
+class SupportSet(torch.utils.data.Dataset):
+    """The strict K-shot support set of few-shot prototype adaptation (SPNet's few-label protocol): for each class of `classes`, in
+    ascending order, the first `shots` samples of `base`, in ascending index, whose label holds at least one pixel of it.  Items are
+    (base index, class) pairs (`items`); item i is base's sample with the label reduced to where(lbl == class, class, -1): a shot
+    reveals one class's mask and nothing else.  `base` must show the classes: a real dataset's split 'train' built with empty unseen
+    lists (class presence then comes from its presence cache, class_presence), SyntheticSegmentation(split='train', unseen=[]) (from
+    the generated label).  `found` maps each class to the number of shots it got (fewer than `shots` where base runs out)."""
+
+    def __init__(self, base, classes, shots):
+        self.base = base
+        self.classes = sorted(set(int(k) for k in classes))
+        self.shots = int(shots)
+        if self.shots < 1:
+            raise ValueError("SupportSet: shots must be at least 1, got %r" % (shots,))
+        if not self.classes or self.classes[0] < 0:
+            raise ValueError("SupportSet: classes must name at least one class index >= 0, got %r" % (classes,))
+        want = set(self.classes)
+        per_class = {k: [] for k in self.classes}
+        for index in range(len(base)):
+            if all(len(v) >= self.shots for v in per_class.values()):
+                break
+            for k in sorted(want & set(self._present(index))):
+                if len(per_class[k]) < self.shots:
+                    per_class[k].append(index)
+        self.items = [(index, k) for k in self.classes for index in per_class[k]]
+        self.found = {k: len(per_class[k]) for k in self.classes}
+
+    def _present(self, index):
+        if hasattr(self.base, 'class_presence'):
+            return self.base.class_presence(index)
+        lbl = self._label_of(self.base[index])
+        return [int(k) for k in np.unique(np.asarray(lbl)) if k >= 0]
+
+    @staticmethod
+    def _label_of(sample):
+        lbl = sample[1]
+        return lbl[0] if isinstance(lbl, (tuple, list)) else lbl
+
+    def __len__(self):
+        return len(self.items)
+
+    def __getitem__(self, i):
+        index, k = self.items[i]
+        sample = self.base[index]
+        lbl = self._label_of(sample)
+        if isinstance(lbl, torch.Tensor):
+            one = torch.where(lbl == k, lbl, torch.full_like(lbl, -1))
+        else:
+            lbl = np.asarray(lbl)
+            one = np.where(lbl == k, lbl, -1).astype(lbl.dtype)
+        rest = sample[1]
+        new_lbl = (one,) + tuple(rest[1:]) if isinstance(rest, (tuple, list)) else one
+        return (sample[0], new_lbl) + tuple(sample[2:])
 
 
 def download(data_dir):

@@ -26,6 +26,8 @@ szn_fused_ce_head and szn_seenmask_head_k goes through here (models.FCN32s / FCN
             pixels per unseen class; the relabelled target is what a training head then reads.
   ohem      hard-pixel mining (szn_ohem_head): per image the labelled pixels with the lowest own-class cosine keep their label, the
             others read OHEM_DROP_LABEL; the relabelled target is what a training head then reads.
+  class_proto  class prototypes by masked average pooling (szn_class_proto): per class the sum of the upsampled score's unit (or raw)
+            vectors over the pixels a label map gives it, and the pixel counts; utils.blend_prototypes turns them into adapted embeddings.
 
 The crop belongs to the stride (32: CROP, reference models.py:147; 8: CROP_UP8, FCN8s' upscore8).  A call without a `Workspace`
 allocates its scratch and builds the embedding tables itself (the predict methods); TrainStep keeps one `Workspace` across steps.
@@ -573,6 +575,73 @@ def ohem(stride, fmap, emb, H, W, target, keep, thresh=None, skip=None, drop_lab
     ohem_call(stride, fmap, emb, H, W, tgt, L.class_set(skip) if skip else None, permille, thresh, drop_label, out, buf, L.stream_ptr(),
               **extra)
     return (out, extra) if want else out
+
+
+# ---- class prototypes: masked average pooling of the upsampled score ------------------------------------------------------------
+_PROTO_MODE = {"raw": L.PROTO_RAW, "unit": L.PROTO_UNIT}
+
+
+def proto_mode(mode):
+    """"unit" | "raw" -> szn_class_proto's mode argument"""
+    if mode not in _PROTO_MODE:
+        raise L.SznError("class_proto: mode must be 'unit' or 'raw', got %r" % (mode,))
+    return _PROTO_MODE[mode]
+
+
+def proto_workspace_bytes(stride, fmap, E, K):
+    B, h, w, _ = fmap.shape
+    nbytes = L.load().szn_class_proto_workspace_bytes(stride, B, h, w, E, K)
+    if nbytes == 0:
+        raise L.SznError("class_proto: bad geometry (stride %d, B %d, map %d x %d, E %d, K %d)" % (stride, B, h, w, E, K))
+    return nbytes
+
+
+def proto_call(stride, fmap, E, H, W, labels, K, classes_cs, mode_code, accumulate, sums, counts, ws_buf, stream):
+    """szn_class_proto with every buffer supplied by the caller; classes_cs: a _lib.class_set or None (all K classes)"""
+    B, h, w, ld = fmap.shape
+    L.call("szn_class_proto", stride, B, h, w, E, ld, 0, H, W, _CROP[stride], K, L.ptr(fmap), L.ptr(labels), classes_cs, int(mode_code),
+           int(accumulate), L.ptr(sums), L.ptr(counts), L.ptr(ws_buf), stream)
+
+
+def class_proto(stride, fmap, H, W, labels, K, classes=None, mode="unit", out=None, E=None):
+    """szn_class_proto on the contiguous fp32 NHWC map `fmap` (the E embedding channels first; E: None = all its channels): per class k
+    of `classes` (None: all K) the sum over the pixels labelled k of the upsampled score's unit vector (mode "unit") or of the score
+    itself ("raw"), and the pixel counts {labelled, summed}.  labels: any (B,H,W) integer map; every label outside [0, K) or outside
+    `classes` is skipped.  out = (sums, counts) of an earlier call: this call's values are added to them (a support set pooled batch by
+    batch).  -> (sums (K,E) float64, counts (K,2) int64) on the map's device."""
+    if fmap.dtype != torch.float32 or not fmap.is_contiguous() or fmap.dim() != 4:
+        raise L.SznError("class_proto: the map must be a contiguous fp32 (B,h,w,C) tensor")
+    B, _, _, ld = fmap.shape
+    E = ld if E is None else int(E)
+    K = int(K)
+    code = proto_mode(mode)
+    if not 1 <= E <= ld:
+        raise L.SznError("class_proto: E = %d outside [1, %d], the map's channels" % (E, ld))
+    if not 1 <= K <= L.MAX_CLASSES:
+        raise L.SznError("class_proto: K = %d outside [1, %d]" % (K, L.MAX_CLASSES))
+    cs = None
+    if classes is not None:
+        classes = sorted(set(int(k) for k in classes))
+        if not classes or classes[0] < 0 or classes[-1] >= K:
+            raise L.SznError("class_proto: classes must name at least one class of [0, %d) (got %r)" % (K, classes))
+        cs = L.class_set(classes)
+    if labels is None:
+        raise L.SznError("class_proto: the label map is required")
+    dev = fmap.device
+    lbl = labels.to(device=dev, dtype=torch.int64).contiguous()
+    if tuple(lbl.shape) != (B, H, W):
+        raise L.SznError("class_proto: labels shape %r, expected %r" % (tuple(lbl.shape), (B, H, W)))
+    if out is None:
+        sums = torch.empty(K, E, dtype=torch.float64, device=dev)
+        counts = torch.empty(K, 2, dtype=torch.int64, device=dev)
+    else:
+        sums, counts = out
+        if (sums.dtype != torch.float64 or tuple(sums.shape) != (K, E) or not sums.is_contiguous() or sums.device != dev
+                or counts.dtype != torch.int64 or tuple(counts.shape) != (K, 2) or not counts.is_contiguous() or counts.device != dev):
+            raise L.SznError("class_proto: out must be (float64 (%d,%d), int64 (%d,2)) contiguous tensors on %s" % (K, E, K, dev))
+    buf = _scratch(proto_workspace_bytes(stride, fmap, E, K), dev)
+    proto_call(stride, fmap, E, H, W, lbl, K, cs, code, out is not None, sums, counts, buf, L.stream_ptr())
+    return sums, counts
 
 
 # ---- softmax cross-entropy head -------------------------------------------------------------------------------------------

@@ -1548,6 +1548,17 @@ class FCN32s(nn.Module):
             self._last_pred = pred
         return loss_t, pred, hist
 
+    def class_prototypes(self, x, labels, K, classes=None, mode="unit", out=None):
+        """class prototypes by masked average pooling (few-shot adaptation of the class embeddings): one inference forward pass, then
+        szn_class_proto on the map the class head reads -- per class k of `classes` (None: all K) the sum over the pixels `labels`
+        (B,H,W) gives it of the upsampled score's unit vector (mode "unit") or of the score ("raw"), WITHOUT the (B,E,H,W) score.
+        -> (sums (K,E) float64, counts (K,2) int64 {labelled, summed pixels}) device tensors; out = an earlier call's pair: this
+        batch is added to it.  utils.blend_prototypes turns them into adapted embeddings."""
+        with torch.no_grad():
+            ctx, stride, fmap = self._head_map(x)
+            fmap32 = fmap if fmap.dtype == torch.float32 else fmap.to(torch.float32)
+            return heads.class_proto(stride, fmap32, ctx.H, ctx.W, labels, K, classes, mode, out, E=self.n_class)
+
     def seen_sweep_predict(self, x, embeddings, unseen, taus, target=None, hist=None, pred_index=None, loss="cos"):
         """the full SZN network's class assignment with a threshold on the seen-mask decision: one forward pass, then on the same map
         the plain head for the loss, the seen-mask logit margin s1 - s0 (szn_seenmask_margin on the 1/32 map; FCN8s keeps the x32

@@ -42,6 +42,12 @@ Added for this implementation (none change the reference flags):
                        labelled pixels whose cosine to their own class embedding is lowest (szn_ohem_head) and ignores the rest;
                        --ohem-thresh C also keeps every pixel whose cosine lies below C (bins of 1/512), --ohem-start-epoch N
                        (default 0); pixel counts per epoch in <log_dir>/ohem_log.csv.  Validation is never mined
+  --proto-shots N      few-shot prototype adaptation of the unseen classes: every validation pools, from N one-class masks per unseen class
+                       (datasets.SupportSet over split 'train'), the mean unit vector of the class's pixels (szn_class_proto) with the
+                       current weights and evaluates with the class embedding's direction moved --proto-alpha A (default 0.5, the
+                       midpoint: a hyper-parameter nobody has tuned) of the way from the word vector to it; --proto-mode unit|raw
+                       (default unit), --proto-min-pixels P (default 1); one row per class in <log_dir>/proto_log.csv.  Training never
+                       sees the adapted rows
   --init synthetic|vgg path handling: without the caffe VGG16 file the backbone starts from synth weights
   torchrun: RANK / LOCAL_RANK / WORLD_SIZE are honoured (one process per GPU, RCCL gradient all-reduce).
 """
@@ -159,6 +165,19 @@ def build_parser():
                         "(default: none)")
     p.add_argument('--ohem-start-epoch', type=int, default=None, metavar='N',
                    help="with --ohem: the first epoch that mines (default 0)")
+    p.add_argument('--proto-shots', type=int, default=None, metavar='N',
+                   help="few-shot prototype adaptation of the unseen classes: every validation pools, from N labelled one-class masks per "
+                        "unseen class (the first N images of split 'train' that show it), the mean unit vector the network gives the "
+                        "class's pixels, and evaluates with the class embedding moved towards it; needs an embedding configuration and "
+                        "unseen classes.  N has no default.  Default: off")
+    p.add_argument('--proto-alpha', type=float, default=None, metavar='A',
+                   help="with --proto-shots: how far the embedding's direction moves from the word vector (0) to the prototype (1), in "
+                        "[0, 1] (default %g: the midpoint, a hyper-parameter nobody has tuned here)" % trainer_fcn.PROTO_ALPHA)
+    p.add_argument('--proto-mode', choices=('unit', 'raw'), default=None,
+                   help="with --proto-shots: pool the pixels' unit vectors (unit, the mean a cosine classifier wants; default) or the raw "
+                        "score vectors (raw)")
+    p.add_argument('--proto-min-pixels', type=int, default=None, metavar='P',
+                   help="with --proto-shots: a class with fewer than P pooled pixels keeps its word vector (default 1)")
     p.add_argument('--hide-unseen', action='store_true',
                    help="the FCN phase trains on every image 'train_seen' would drop for an unseen class as well, with the pixels of "
                         "the unseen classes hidden from every loss and metric (label -3)")
@@ -423,6 +442,25 @@ def check_ohem(keep, thresh, start_epoch, cfg):
         raise Exception("--ohem: " + why)
 
 
+def check_proto(shots, alpha, mode, min_pixels, cfg):
+    """--proto-shots / --proto-alpha / --proto-mode / --proto-min-pixels: N >= 1, A in [0, 1], P >= 1; the satellites only with
+    --proto-shots; an embedding configuration with unseen classes (trainer_fcn.proto_refused) -> the Trainer's proto dict, or None"""
+    if shots is None:
+        if alpha is not None or mode is not None or min_pixels is not None:
+            raise Exception("--proto-alpha / --proto-mode / --proto-min-pixels need --proto-shots")
+        return None
+    n_class = 21 if cfg['dataset'] == 'pascal' else 33
+    why = trainer_fcn.proto_refused(bool(cfg['train_unseen'] or cfg['val_unseen']),
+                                    bool(cfg['embed_dim']) and cfg['fcn_loss'] in _EMBED_LOSSES, n_class, shots)
+    if why:
+        raise Exception("--proto-shots: " + why)
+    if alpha is not None and not 0.0 <= alpha <= 1.0:
+        raise Exception("--proto-alpha: A must lie in [0, 1] (got %r)" % (alpha,))
+    if min_pixels is not None and min_pixels < 1:
+        raise Exception("--proto-min-pixels: P must be at least 1 (got %r)" % (min_pixels,))
+    return trainer_fcn.check_proto(dict(shots=shots, alpha=alpha, mode=mode, min_pixels=min_pixels))
+
+
 def check_sim_temperature(temperature, cfg):
     """--sim-temperature: only with fcn_loss 'sim_ce', positive and finite"""
     if temperature is None:
@@ -456,6 +494,7 @@ def main(argv=None):
     check_pseudo(args.pseudo_label, args.pseudo_gamma, args.pseudo_floor, args.pseudo_start_epoch, args.hide_unseen, cfg)
     check_ohem(args.ohem, args.ohem_thresh, args.ohem_start_epoch, cfg)
     check_bias(args.bias_loss, args.bias_start_epoch, cfg)
+    proto = check_proto(args.proto_shots, args.proto_alpha, args.proto_mode, args.proto_min_pixels, cfg)
     hide_unseen = args.hide_unseen or args.pseudo_label is not None or args.bias_loss is not None
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -544,6 +583,19 @@ def main(argv=None):
     val_loader = loader(val_dataset, 1, False)            # sharded by rank above; Trainer.validate all-reduces the sums
     val_loader.szn_sharded = world > 1                    # tells the trainers not to skip batches by index on top of it
     label_names = train_dataset.class_names
+    support_loader = None
+    if proto is not None:
+        # the strict K-shot support set: one-class masks of the unseen classes from a 'train' split that shows every class.  Every
+        # rank pools the whole (small) set itself: the loader is not sharded
+        from .datasets import SupportSet
+        if args.synthetic:
+            support_base = SyntheticSegmentation(split='train', n_images=n_img, size=(H, W), n_class=n_class,
+                                                 embed_dim=cfg['embed_dim'], unseen=[], seed=1337)
+        else:
+            support_base = cls(split='train', embed_dim=cfg['embed_dim'], one_hot_embed=cfg['one_hot_embed'], data_dir=args.data_dir,
+                               train_unseen=[], val_unseen=[], native=True)
+        support_loader = torch.utils.data.DataLoader(SupportSet(support_base, all_unseen, proto['shots']), batch_size=1, shuffle=False,
+                                                     **kwargs)
     if rank == 0 and not osp.exists(osp.join(log_dir, 'counts.csv')):
         with open(osp.join(log_dir, 'counts.csv'), 'w') as f:
             f.write('train_seen,train_unseen,val\n%d,%d,%d\n' % (len(train_seen_loader), len(train_loader) - len(train_seen_loader),
@@ -576,6 +628,7 @@ def main(argv=None):
         dataset=cfg['dataset'], max_epoch=cfg['fcn_epochs'], pixel_embeddings=cfg['embed_dim'], loss_func=cfg['fcn_loss'],
         tb_writer=tb_writer, unseen=all_unseen, val_unseen=cfg['val_unseen'], label_names=label_names,
         forced_unseen=cfg['forced_unseen'], precision=precision, rank=rank, visualize=args.viz, augment=augment,
+        proto=proto, support_loader=support_loader,
         seen_threshold=args.seen_threshold, seen_sweep=seen_sweep_values(args.seen_sweep), sim_temperature=args.sim_temperature,
         rank_margin=args.rank_margin, rank_hardest=args.rank_hardest,
         pseudo=None if args.pseudo_label is None else dict(keep=args.pseudo_label, gamma=args.pseudo_gamma,

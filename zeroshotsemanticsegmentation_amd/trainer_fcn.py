@@ -8,6 +8,7 @@ tensorboard writer, checkpoints with the reference's dict keys) is host-side and
 The JPEG tile visualisations of validation (reference :198-219,267; drawn there on the host through the third-party `fcn` package) are
 rendered on the GPU by vis_utils from the tensors validate() already holds: Trainer(visualize=N) / train.py --viz N, off by default.
 """
+import contextlib
 import datetime
 import os
 import os.path as osp
@@ -118,6 +119,49 @@ def ohem_refused(embed_cfg, n_class):
     return None
 
 
+PROTO_ALPHA = 0.5          # the default of train.py --proto-alpha: the midpoint between word vector and prototype, nobody has tuned it
+
+
+def proto_refused(has_unseen, embed_cfg, n_class, shots=1):
+    """why a configuration cannot adapt its unseen class embeddings from a few labelled shots (proto=, train.py --proto-shots), or None:
+    the prototypes are pooled by the fused head's masked-pooling call and replace rows of the class-embedding matrix in validation"""
+    if not embed_cfg:
+        return "prototype adaptation needs an embedding configuration (loss 'cos' | 'mse' | 'sim_ce' | 'rank'): a softmax network has no class embeddings"
+    if not has_unseen:
+        return "prototype adaptation needs unseen classes (train_unseen / val_unseen): the seen classes' embeddings are trained against already"
+    try:
+        ok = int(shots) == shots and int(shots) >= 1
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        return "prototype adaptation: shots must be an integer >= 1 (got %r)" % (shots,)
+    if n_class > 256:
+        return "prototype adaptation: the fused head holds at most 256 classes, got %d" % n_class
+    return None
+
+
+def check_proto(proto):
+    """proto = dict(shots=, alpha=PROTO_ALPHA, mode="unit", min_pixels=1) checked -> the dict with every key filled in"""
+    from ._lib import SznError
+    from .heads import proto_mode
+    if not isinstance(proto, dict) or "shots" not in proto or set(proto) - {"shots", "alpha", "mode", "min_pixels"}:
+        raise SznError("proto = dict(shots=N[, alpha=, mode=, min_pixels=]), got %r" % (proto,))
+    cfg = dict(alpha=PROTO_ALPHA, mode="unit", min_pixels=1)
+    cfg.update({k: v for k, v in proto.items() if v is not None})
+    try:
+        cfg["shots"], cfg["alpha"], cfg["min_pixels"] = int(cfg["shots"]), float(cfg["alpha"]), int(cfg["min_pixels"])
+    except (TypeError, ValueError):
+        raise SznError("proto: shots and min_pixels must be integers, alpha a number (got %r)" % (proto,))
+    if cfg["shots"] < 1 or cfg["shots"] != proto["shots"]:
+        raise SznError("proto: shots must be an integer >= 1 (got %r)" % (proto["shots"],))
+    if not 0.0 <= cfg["alpha"] <= 1.0:
+        raise SznError("proto: alpha must lie in [0, 1] (got %r)" % (cfg["alpha"],))
+    if cfg["min_pixels"] < 1:
+        raise SznError("proto: min_pixels must be at least 1 (got %r)" % (cfg["min_pixels"],))
+    proto_mode(cfg["mode"])
+    return cfg
+
+
 class _NullWriter(object):
     def add_scalar(self, *a, **k): pass
     def add_text(self, *a, **k): pass
@@ -129,7 +173,7 @@ class Trainer(object):
     def __init__(self, cuda, model, optimizer, train_loader, val_loader, log_dir, dataset, max_epoch, tb_writer,
                  pixel_embeddings=None, loss_func=None, unseen=None, val_unseen=None, label_names=None,
                  forced_unseen=False, embed_arr=None, precision=torch.float32, fused_step=True, rank=0, visualize=0, augment=None,
-                 seen_threshold=None, seen_sweep=None,
+                 seen_threshold=None, seen_sweep=None, proto=None, support_loader=None,
                  sim_temperature=None, rank_margin=None, rank_hardest=False, bias_loss=None, bias_start_epoch=0, pseudo=None, pseudo_start_epoch=0, ohem=None, ohem_start_epoch=0, calibration=None,
                  calib_sweep=None, eval_scales=None, eval_flip=False):
         if not cuda:
@@ -306,6 +350,31 @@ class Trainer(object):
             unseen_arr[self.unseen, :] = arr[self.unseen, :]
             self.seen_embeddings = torch.from_numpy(seen_arr).to(self.device).float()
             self.unseen_embeddings = torch.from_numpy(unseen_arr).to(self.device).float()
+
+        # few-shot prototype adaptation (models.class_prototypes, utils.blend_prototypes): every validate() pools the prototypes of
+        # self.unseen over `support_loader` (a loader over datasets.SupportSet: `shots` one-class masks per unseen class) with the current
+        # weights and evaluates with those rows of the class embeddings moved `alpha` of the way from the word vector to the prototype.
+        # proto = dict(shots=, alpha=, mode=, min_pixels=).  Training steps never see the adapted rows.  Per validation one row per
+        # unseen class in proto_log.csv
+        self.proto = None
+        self.support_loader = support_loader
+        self.last_proto = None                       # the last validation's (sums, counts) as numpy arrays
+        if proto is not None:
+            from ._lib import SznError
+            why = proto_refused(bool(self.unseen), self._embed_cfg(), self.n_class, proto.get("shots", 1) if isinstance(proto, dict) else 1)
+            if why:
+                raise SznError(why)
+            self.proto = check_proto(proto)
+            if support_loader is None:
+                raise SznError("proto needs support_loader: a loader over datasets.SupportSet(base, unseen classes, shots)")
+            if self.rank == 0:
+                os.makedirs(self.log_dir, exist_ok=True)
+                if not osp.exists(osp.join(self.log_dir, 'proto_log.csv')):
+                    with open(osp.join(self.log_dir, 'proto_log.csv'), 'w') as f:
+                        f.write('epoch,class,name,shots,participating,contributing,cos_word_proto\n')
+        elif support_loader is not None:
+            from ._lib import SznError
+            raise SznError("support_loader belongs to proto= (prototype adaptation), which is off")
 
         base = ['loss', 'pxl_acc', 'class_acc', 'mean_iu', 'fwavacc']
         self.train_log_headers = ['epoch', 'iteration'] + ['train/' + b for b in base] + ['elapsed_time']
@@ -684,10 +753,71 @@ class Trainer(object):
         else:
             print('seen-mask threshold: no tau has a harmonic mean IU (the validation set holds no seen or no unseen pixels)')
 
+    def pool_prototypes(self):
+        """the prototypes of self.unseen pooled over the support loader with the current weights: one inference forward per support
+        batch, accumulated on the device -> (sums (K,E) float64, counts (K,2) int64, shots (K,) int64: support samples that showed the
+        class).  Every rank pools the whole (small) support set itself: nothing is exchanged."""
+        self.model.eval()
+        out = None
+        shots = torch.zeros(self.n_class, dtype=torch.int64, device=self.device)
+        cls = torch.tensor(self.unseen, dtype=torch.int64, device=self.device)
+        with torch.no_grad():
+            for batch in self.support_loader:
+                data, target, _ = self._unpack(batch[0], batch[1])
+                res = self.model.class_prototypes(data, target, self.n_class, self.unseen, self.proto["mode"], out)
+                out = res if out is None else out
+                shots[cls] += (target.reshape(target.shape[0], 1, -1) == cls.reshape(1, -1, 1)).any(dim=2).sum(dim=0)
+        if out is None:
+            E = self.embeddings.shape[1]
+            out = (torch.zeros(self.n_class, E, dtype=torch.float64, device=self.device),
+                   torch.zeros(self.n_class, 2, dtype=torch.int64, device=self.device))
+        return out[0], out[1], shots
+
+    def _proto_report(self, sums, counts, shots):
+        """rank 0, once per validation: one proto_log.csv row per unseen class"""
+        e = self._proto_saved[0].detach().cpu().numpy().astype(np.float64)
+        with open(osp.join(self.log_dir, 'proto_log.csv'), 'a') as f:
+            for k in self.unseen:
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    cosv = float(np.dot(e[k], sums[k]) / (np.linalg.norm(e[k]) * np.linalg.norm(sums[k])))
+                name = str(self.label_names[k]) if self.label_names is not None and k < len(self.label_names) else 'class%d' % k
+                f.write('%d,%d,%s,%d,%d,%d,%r\n' % (self.epoch, k, name.replace(',', ' '), shots[k], counts[k, 0], counts[k, 1], cosv))
+
+    _proto_saved = None                         # (embeddings, seen_embeddings, unseen_embeddings) while the adapted rows are swapped in
+
+    @contextlib.contextmanager
+    def adapted_embeddings(self):
+        """proto=: for the duration of the block self.embeddings (and its row-zeroed companions seen_embeddings / unseen_embeddings)
+        are fresh tensors whose unseen rows are blended with the prototypes pooled just now (pool_prototypes, utils.blend_prototypes);
+        the originals return in a `finally`.  Fresh tensors: heads.Workspace.prepared sees new keys.  Without proto= nothing happens."""
+        if self.proto is None or self._proto_saved is not None:
+            yield
+            return
+        sums, counts, shots = self.pool_prototypes()
+        adapted = utils.blend_prototypes(self.embeddings, sums, counts, self.unseen, self.proto["alpha"], self.proto["min_pixels"])
+        seen_e, unseen_e = torch.zeros_like(adapted), torch.zeros_like(adapted)
+        seen_e[self.seen] = adapted[self.seen]
+        unseen_e[self.unseen] = adapted[self.unseen]
+        self._proto_saved = (self.embeddings, self.seen_embeddings, self.unseen_embeddings)
+        try:
+            self.last_proto = (sums.cpu().numpy(), counts.cpu().numpy())
+            if self.rank == 0:
+                self._proto_report(self.last_proto[0], self.last_proto[1], shots.cpu().numpy())
+            self.embeddings, self.seen_embeddings, self.unseen_embeddings = adapted, seen_e, unseen_e
+            yield
+        finally:
+            self.embeddings, self.seen_embeddings, self.unseen_embeddings = self._proto_saved
+            self._proto_saved = None
+
     def validate(self, both_fcn_and_seenmask=False):
         """reference :182-292.  The {all, seen, unseen} K x K histograms and the loss sum are accumulated on the GPU
         (szn_confusion_hist on the device prediction) and read back ONCE per epoch; under data parallelism the validation
-        images are split across the ranks and the histograms / loss sums are all-reduced before the metrics."""
+        images are split across the ranks and the histograms / loss sums are all-reduced before the metrics.  With proto= the whole
+        validation runs on the adapted class embeddings (adapted_embeddings)."""
+        with self.adapted_embeddings():
+            return self._validate(both_fcn_and_seenmask)
+
+    def _validate(self, both_fcn_and_seenmask):
         import torch.distributed as dist
         self.model.eval()
         world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1

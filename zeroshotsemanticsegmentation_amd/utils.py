@@ -436,6 +436,39 @@ def harmonic_mean_iu(seen_metrics, unseen_metrics):
     return 2.0 * s * u / (s + u)
 
 
+def blend_prototypes(embeddings, sums, counts, classes, alpha, min_pixels=1):
+    """few-shot adaptation of class embeddings: move the rows `classes` of `embeddings` (K,E) from their word vector towards the class
+    prototype sums[k] (heads.class_proto / FCN32s.class_prototypes: the sum of the class's pixel vectors; only its direction matters).
+    For each k in `classes` with counts[k][1] >= min_pixels, |sums[k]| != 0 and |e_k| != 0:
+        d = (1 - alpha) e_k / |e_k| + alpha sums[k] / |sums[k]|,     row k = |e_k| d / |d|       (float64; the row keeps its norm, so the
+    norm-sensitive losses validation reports stay comparable); the row stays when d = 0.  Every other row is the input's, bit for bit,
+    and alpha = 0 returns the input bit for bit.  -> a new (K,E) float32 tensor (on the device of `embeddings` when that is a tensor)."""
+    alpha = float(alpha)
+    if not 0.0 <= alpha <= 1.0:
+        raise L.SznError("blend_prototypes: alpha must lie in [0, 1], got %r" % (alpha,))
+    dev = embeddings.device if isinstance(embeddings, torch.Tensor) else None
+    e32 = np.array(_data(embeddings).detach().cpu().numpy() if isinstance(embeddings, torch.Tensor) else embeddings, dtype=np.float32)
+    s = np.asarray(sums.detach().cpu().numpy() if isinstance(sums, torch.Tensor) else sums, dtype=np.float64)
+    c = np.asarray(counts.detach().cpu().numpy() if isinstance(counts, torch.Tensor) else counts, dtype=np.int64)
+    K, E = e32.shape
+    if s.shape != (K, E) or c.shape != (K, 2):
+        raise L.SznError("blend_prototypes: sums %r / counts %r do not fit embeddings %r" % (s.shape, c.shape, e32.shape))
+    out = e32.copy()
+    for k in sorted(set(int(k) for k in classes)):
+        if not 0 <= k < K:
+            raise L.SznError("blend_prototypes: class %d outside [0, %d)" % (k, K))
+        e = e32[k].astype(np.float64)
+        en, sn = np.sqrt((e * e).sum()), np.sqrt((s[k] * s[k]).sum())
+        if alpha == 0.0 or c[k, 1] < int(min_pixels) or not (np.isfinite(sn) and sn > 0.0 and en > 0.0):
+            continue
+        d = (1.0 - alpha) * (e / en) + alpha * (s[k] / sn)
+        dn = np.sqrt((d * d).sum())
+        if dn > 0.0:
+            out[k] = (en * (d / dn)).astype(np.float32)
+    t = torch.from_numpy(out)
+    return t if dev is None else t.to(dev)
+
+
 def calib_rows(hist, n_class, unseen):
     """one gamma's (K,K) confusion histogram -> (metrics, seen metrics, unseen metrics): the seen / unseen histograms are its rows
     with the target outside / inside `unseen`, the others zero (what szn_confusion_hist_k fills)"""
