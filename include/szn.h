@@ -901,6 +901,47 @@ int szn_seen_sweep_head_tabled(int stride, int B, int h, int w, int E, int ldc, 
                                const float* margin, int n_taus, const float* taus, int64_t* hist, int pred_index, int64_t* pred,
                                void* workspace, szn_stream_t stream);
 
+/* ---- ConSE zero-shot inference for the softmax FCN ---------------------------------------------------------------------------------
+ * szn_conse_head: convex combination of semantic embeddings (Norouzi et al., ICLR 2014) per pixel, from the logit map of a network that
+ * was trained on the seen classes with szn_fused_ce_head, with the seen-class penalty gamma of szn_calib_head swept over n_gammas values
+ * in one pass.  coarse: the fp32 NHWC logit map, the K class channels at [c0, c0 + K) of pixel stride ldc; stride (32 | 8), crop, h, w, H
+ * and W are szn_fused_ce_head's.  embed [K][E] f32 (device).  unseen: as in szn_calib_head, non-empty and not every class.  gammas: HOST
+ * memory, read during the call, finite and strictly ascending.  Per pixel (only the logits are pinned bit for bit, the rest is
+ * mathematics plus tie rules):
+ *   z[c]   = szn_fused_ce_head's logit (the same bilinear weights, the same fmaf chain over the four taps): bit-identical;
+ *   S      = the first min(top_t, n_seen) SEEN classes ordered by (z descending, class index ascending); the channels of unseen classes
+ *            are never read;
+ *   p_t    = exp(z_t - max_S z) / sum_S exp(z - max_S z): the seen-class softmax renormalised over S (ConSE's normalisation; what the
+ *            full seen-class denominator adds cancels);
+ *   sim[k] = (sum_{t in S} p_t G[t][k]) / (|f| * en[k]),  G = embed embed^T (products accumulated in double, stored fp32, built once per
+ *            call), en[k] = sqrt(G[k][k]), |f| = sqrt(sum_{t,u in S} p_t p_u G[t][u]), a zero |f| or en[k] replaced by 1 (the cosine
+ *            heads' rule).  The mixture f = sum_t p_t e_t is never formed: E is not on the per-pixel path;
+ *   a, va  = the first seen class holding the seen maximum of sim;  b, vb = the same over the unseen classes;  m = va - vb;
+ *   pred_g = szn_calib_head's rule: 0 if m is NaN; else a if m > gammas[g], or if m == gammas[g] and a < b; else b.
+ * forced = 0:  hist [n_gammas][K][K] int64 (device, or NULL): hist[g][t][pred_g] += 1 for every pixel whose target t has 0 <= t < K (-1,
+ *            the padding label and labels >= K are skipped);  pred (B,H,W) int64 (device, or NULL): pred_g for g = pred_index.  The pixel's
+ *            (t, a, b, bin) record goes through szn_calib_head's crossing tables and calib_hist_kernel: the cost does not grow with n_gammas.
+ * forced = 1 (the reference's -fu): pred = b where target names an unseen class, a elsewhere (0 where m is NaN); gammas and hist must be
+ *            NULL, n_gammas 0, target and pred given.
+ * No atomics except the crossing tables' integer adds: two calls are bit-equal.  Scalar arguments, no allocation, no host sync.
+ * szn_last_kernel(): calib_hist_kernel when hist is given (szn_prev_kernel(): the pixel kernel), else the pixel kernel -- conse_cell_kernel
+ * (G copied into LDS: taps + en + G within 64 KiB, K <= 119 at stride 8 and K <= 125 at stride 32) or conse_cell_global_kernel (G read
+ * through L2); the launch before the pixel kernel is conse_prep_kernel.
+ * workspace: szn_conse_head_workspace_bytes (0 for sizes the call refuses; n_gammas = 0 sizes the forced call), 16-byte aligned: G
+ * [K][K | 1] and en [K] floats, then the crossing tables, 2 * K^2 * (n_gammas + 1) int64 (none for the forced call).
+ * SZN_ERR_ARG, before any launch: everything szn_calib_head refuses (stride not 8 or 32; n_gammas outside [1, SZN_CALIB_MAX_GAMMAS]; a
+ * gamma that is not finite, or gammas not strictly ascending; hist and pred both NULL; hist without target; pred with pred_index outside
+ * [0, n_gammas); NULL coarse, embed, workspace or gammas; `unseen` NULL, empty, holding every class below K or a class >= K; K >
+ * SZN_MAX_CLASSES; a size that is not positive; a crop window larger than the deconv output; a workspace that is not 16-byte aligned),
+ * with ldc < c0 + K in place of its ldc rule; top_t outside [1, SZN_CONSE_MAX_TOP]; forced not 0 or 1; a forced call with gammas, hist
+ * or n_gammas != 0, or without target or pred.  SZN_ERR_UNSUPPORTED: a cell's taps that do not fit LDS (no K <= SZN_MAX_CLASSES does that). */
+#define SZN_CONSE_MAX_TOP 16
+size_t szn_conse_head_workspace_bytes(int stride, int B, int h, int w, int E, int K, int n_gammas);
+int szn_conse_head(int stride, int B, int h, int w, int K, int ldc, int c0, int H, int W, int crop, int E,
+                   const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
+                   int top_t, int forced, int n_gammas, const float* gammas, int64_t* hist, int pred_index, int64_t* pred,
+                   void* workspace, szn_stream_t stream);
+
 /* ---- self-training on the hidden pixels: top-p% pseudo labels ------------------------------------------------------------------
  * szn_pseudo_head: the network's own calibrated prediction labels the most confident keep_permille / 1000 of the pixels whose label is
  * hidden (target == cand_label, a negative value: datasets.HIDDEN_LABEL), per unseen class, and writes the relabelled target.

@@ -78,6 +78,7 @@ def class_set(classes):
 MS_MAX_VIEWS = 16           # SZN_MS_MAX_VIEWS
 CALIB_MAX_GAMMAS = 64       # SZN_CALIB_MAX_GAMMAS
 SEEN_SWEEP_MAX_TAUS = 64    # SZN_SEEN_SWEEP_MAX_TAUS
+CONSE_MAX_TOP = 16          # SZN_CONSE_MAX_TOP
 PSEUDO_BINS = 1024          # SZN_PSEUDO_BINS
 OHEM_BINS = 1024            # SZN_OHEM_BINS
 PROTO_RAW, PROTO_UNIT = 0, 1   # SZN_PROTO_RAW, SZN_PROTO_UNIT (szn_class_proto's mode)
@@ -210,6 +211,8 @@ SIGNATURES = {
     "szn_seen_sweep_head_workspace_bytes": (_SZ, [_I] * 7),
     "szn_seen_sweep_head": (_I, [_I] * 11 + [_P, _P, _P, _CS, _P, _I, _FP, _P, _I, _P, _P, _P]),
     "szn_seen_sweep_head_tabled": (_I, [_I] * 11 + [_P, _P, _P, _CS, _P, _I, _FP, _P, _I, _P, _P, _P]),
+    "szn_conse_head_workspace_bytes": (_SZ, [_I] * 7),
+    "szn_conse_head": (_I, [_I] * 11 + [_P, _P, _P, _CS, _I, _I, _I, _FP, _P, _I, _P, _P, _P]),
     "szn_pseudo_head_workspace_bytes": (_SZ, [_I] * 8),
     "szn_pseudo_head": (_I, [_I] * 11 + [_P, _P, _P, _CS, _F, _F, _I, _I64] + [_P] * 8),
     "szn_ohem_head_workspace_bytes": (_SZ, [_I] * 8),

@@ -22,6 +22,7 @@
 //   fh_gather_kernel     one block per coarse position sums the <= 4 cells that use it as a tap and writes dcoarse
 //   calib_cell_kernel / calib_cell_tab_kernel / calib_hist_kernel   szn_calib_head (calibrated stacking): the cell kernels' G and Q (fh_load_taps,
 //                        fh_build_GQ, fh_lookup_GQ), two running bests per pixel (fh_two_best), crossing tables, prefix sums -> hist
+//                        (calib_count and calib_hist_kernel live in szn_calib.h, shared with szn_conse_head.hip)
 //   sweep_cell_kernel / sweep_cell_tab_kernel   szn_seen_sweep_head (seen-mask threshold sweep): the calibrated kernels with the grouped
 //                        head's two answers per pixel (fh_group_bests) and the seen-mask margin as the switch; then calib_hist_kernel
 //   pseudo_cell_kernel / pseudo_cell_tab_kernel / pseudo_thr_kernel / pseudo_relabel_kernel   szn_pseudo_head (self-training): the same G, Q
@@ -49,6 +50,7 @@
 // Stride 8: one wave owns the cell and already visits its labels class by class for A, so P_k lives in registers for the duration
 // of that class's turn, read from the coarse vectors themselves (the per-position tables D, N would only give the cancelling form).
 #include "szn_upcell.h"
+#include "szn_calib.h"
 
 namespace {
 
@@ -1070,11 +1072,7 @@ __global__ __launch_bounds__(256) void fh_gather_kernel(const float* __restrict_
 // A pixel is (t, a, b, bin): target, best seen class, best unseen class, first gamma at which it takes b (n: never; include/szn.h).
 // XA [K][K][n + 1] counts (t, a, bin), XB (t, b, bin), both int64, zeroed by the call.  Integer atomics: the result does not depend on
 // their order.  The gammas travel as kernel arguments; the per-pixel search is a wave-uniform loop over them (scalar loads).
-struct CalArgs {
-    float gamma[SZN_CALIB_MAX_GAMMAS];
-    unsigned long long* XA; unsigned long long* XB;
-    int64_t* pred; int n, pred_index;
-};
+// CalArgs, calib_count and calib_hist_kernel: szn_calib.h (szn_conse_head.hip feeds the same tables).
 
 // Pixel (ty, tx) of cell (I, J) of image b: the prediction at gammas[pred_index] (where wanted) and the pixel's key
 // t | a << 8 | b << 16 | bin << 24, or -1 where it is not counted (no histogram, outside the image, label outside [0, K))
@@ -1098,23 +1096,6 @@ __device__ __forceinline__ int calib_pixel(const FhArgs& a, const CalArgs& c, in
     const long t = a.target[pix];
     if (t < 0 || t >= a.K) return -1;
     return (int)t | r.ia << 8 | r.ib << 16 | bin << 24;
-}
-
-// the keys of a wave, equal ones combined: one atomic add of the popcount per distinct key and table
-__device__ __forceinline__ void calib_count(const FhArgs& a, const CalArgs& c, int key, int lane) {
-    unsigned long long todo = __ballot(key >= 0);
-    while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        const int k0 = __shfl(key, src, 64);
-        const unsigned long long same = __ballot(key == k0);
-        if (lane == src) {
-            const unsigned long long cnt = (unsigned long long)__popcll(same);
-            const int t = k0 & 255, ia = (k0 >> 8) & 255, ib = (k0 >> 16) & 255, bin = (k0 >> 24) & 127;
-            atomicAdd(c.XA + ((size_t)t * a.K + ia) * (c.n + 1) + bin, cnt);
-            atomicAdd(c.XB + ((size_t)t * a.K + ib) * (c.n + 1) + bin, cnt);
-        }
-        todo &= ~same;
-    }
 }
 
 // ---- seen-mask threshold sweep (szn_seen_sweep_head): the calibrated head's cells, tables and crossing scheme with another switch ------
@@ -1222,23 +1203,6 @@ __global__ __launch_bounds__(256) void sweep_cell_tab_kernel(FhArgs a, CalArgs c
     calib_cell_tab_walk<KP>(a, c, D, N, Gs, Qs, [&](int b, int I, int J, int ty, int tx, bool live, const float* G, const float* Q, const float* en) {
         return sweep_pixel<KP, 8>(a, c, margin, b, I, J, ty, tx, live, G, Q, en);
     });
-}
-
-// hist[g][t][k] += sum_{bin > g} XA[t][k][bin] + sum_{bin <= g} XB[t][k][bin]: one thread per (t, k), running prefixes over the bins
-__global__ __launch_bounds__(256) void calib_hist_kernel(const unsigned long long* __restrict__ XA,
-                                                         const unsigned long long* __restrict__ XB, int K, int n,
-                                                         int64_t* __restrict__ hist) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= K * K) return;
-    const unsigned long long* xa = XA + (size_t)i * (n + 1);
-    const unsigned long long* xb = XB + (size_t)i * (n + 1);
-    unsigned long long above = 0, below = 0;
-    for (int bin = 0; bin <= n; ++bin) above += xa[bin];
-    for (int g = 0; g < n; ++g) {
-        above -= xa[g];
-        below += xb[g];
-        hist[(size_t)g * K * K + i] += (int64_t)(above + below);
-    }
 }
 
 // margin == nullptr: szn_calib_head's pixel kernels; else szn_seen_sweep_head's, same grids and LDS.  tabled: the stride-8 position tables

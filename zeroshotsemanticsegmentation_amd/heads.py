@@ -20,6 +20,8 @@ szn_fused_ce_head and szn_seenmask_head_k goes through here (models.FCN32s / FCN
             which reads the maps of all views and writes one prediction.
   calib     calibrated stacking (szn_calib_head): a penalty gamma on every seen class, swept over up to 64 values in one pass --
             per gamma a confusion histogram, for one of them the prediction.
+  conse     ConSE zero-shot inference for the softmax network (szn_conse_head): the top-T seen-class softmax mixes class embeddings,
+            the nearest class by cosine wins, calib's gamma between the groups, swept in one pass; or forced by the target.
   seen_sweep  full SZN inference with a threshold on the seen-mask logit margin (szn_seenmask_margin, szn_seen_sweep_head): the grouped
             head's class assignment with the group decided by margin > tau, up to 64 taus in one pass.
   pseudo    self-training pseudo labels (szn_pseudo_head): the calibrated prediction labels the most confident share of the hidden
@@ -364,6 +366,67 @@ def calib(stride, fmap, emb, H, W, unseen, gammas, target=None, hist=None, pred_
     L.call("szn_calib_head", stride, B, h, w, E, ld, 0, H, W, _CROP[stride], K, L.ptr(fmap), L.ptr(emb), L.ptr(tgt),
            L.class_set(unseen), G, g.ctypes.data_as(C.POINTER(C.c_float)), L.ptr(hist), -1 if pred_index is None else int(pred_index),
            L.ptr(pred), L.ptr(buf), L.stream_ptr())
+    return hist, pred
+
+
+# ---- ConSE: zero-shot inference for the softmax FCN ---------------------------------------------------------------------------
+def conse_top(top_t):
+    """ConSE's T as szn_conse_head takes it: an integer in [1, CONSE_MAX_TOP]"""
+    if isinstance(top_t, bool) or int(top_t) != top_t or not 1 <= int(top_t) <= L.CONSE_MAX_TOP:
+        raise L.SznError("conse: top_t must be an integer in [1, %d], got %r" % (L.CONSE_MAX_TOP, top_t))
+    return int(top_t)
+
+
+def conse(stride, fmap, emb, H, W, unseen, top_t, gammas=None, target=None, hist=None, pred_index=None, forced=False):
+    """szn_conse_head on the contiguous fp32 NHWC LOGIT map `fmap` of a softmax network (the K class channels first) with the (K,E)
+    class embeddings `emb`: per pixel the softmax over the classes NOT in `unseen`, its top `top_t`, the probability-weighted mean of
+    their embeddings, and the nearest class by cosine among all classes, with calib()'s penalty gamma on the seen classes -- for
+    every gamma of `gammas` (ascending) in one pass.  target given: hist (G,K,K) int64 += the confusion counts of every gamma
+    (allocated as zeros when None).  pred_index given: pred (B,H,W) int64 at gammas[pred_index].  forced=True (the reference's -fu):
+    pred = the best unseen class where `target` names an unseen class, the best seen class elsewhere; no gammas, no hist.
+    -> (hist or None, pred or None)"""
+    import ctypes as C
+    B, h, w, ld = fmap.shape
+    K, E = emb.shape
+    if fmap.dtype != torch.float32 or not fmap.is_contiguous():
+        raise L.SznError("conse: the map must be a contiguous fp32 (B,h,w,C) tensor")
+    if emb.dtype != torch.float32 or not emb.is_contiguous() or emb.device != fmap.device:
+        raise L.SznError("conse: the embeddings must be a contiguous fp32 (K,E) tensor on the map's device")
+    top_t = conse_top(top_t)
+    dev = fmap.device
+    tgt = None if target is None else target.to(device=dev, dtype=torch.int64).contiguous()
+    if forced:
+        if gammas is not None or hist is not None or pred_index is not None:
+            raise L.SznError("conse: a forced call takes no gammas, hist or pred_index")
+        if tgt is None:
+            raise L.SznError("conse: a forced call needs the target")
+        G, gp, pidx = 0, None, 0
+        pred = torch.empty(B, H, W, dtype=torch.int64, device=dev)
+    else:
+        if gammas is None:
+            raise L.SznError("conse: gammas are required (forced=False)")
+        g = calib_gammas(gammas)
+        G = int(g.size)
+        gp = g.ctypes.data_as(C.POINTER(C.c_float))
+        if tgt is None and hist is not None:
+            raise L.SznError("conse: a histogram needs the target")
+        if tgt is None and pred_index is None:
+            raise L.SznError("conse: nothing to compute (no target for a histogram, no pred_index for a prediction)")
+        if pred_index is not None and not 0 <= int(pred_index) < G:
+            raise L.SznError("conse: pred_index %r outside [0, %d)" % (pred_index, G))
+        if tgt is not None:
+            if hist is None:
+                hist = torch.zeros(G, K, K, dtype=torch.int64, device=dev)
+            elif hist.dtype != torch.int64 or tuple(hist.shape) != (G, K, K) or not hist.is_contiguous() or hist.device != dev:
+                raise L.SznError("conse: hist must be a contiguous int64 (%d,%d,%d) tensor on %s" % (G, K, K, dev))
+        pidx = -1 if pred_index is None else int(pred_index)
+        pred = torch.empty(B, H, W, dtype=torch.int64, device=dev) if pred_index is not None else None
+    nbytes = L.load().szn_conse_head_workspace_bytes(stride, B, h, w, E, K, G)
+    if nbytes == 0:
+        raise L.SznError("conse: bad geometry (stride %d, B %d, map %d x %d, E %d, K %d, %d gammas)" % (stride, B, h, w, E, K, G))
+    buf = _scratch(nbytes, dev)
+    L.call("szn_conse_head", stride, B, h, w, K, ld, 0, H, W, _CROP[stride], E, L.ptr(fmap), L.ptr(emb), L.ptr(tgt),
+           L.class_set(unseen), top_t, int(bool(forced)), G, gp, L.ptr(hist), pidx, L.ptr(pred), L.ptr(buf), L.stream_ptr())
     return hist, pred
 
 

@@ -1548,6 +1548,29 @@ class FCN32s(nn.Module):
             self._last_pred = pred
         return loss_t, pred, hist
 
+    def conse_predict(self, x, embeddings, unseen, top_t, gammas=None, target=None, hist=None, pred_index=None, forced=False):
+        """ConSE zero-shot inference for the softmax network (Norouzi et al., ICLR 2014): one forward pass, then on the same logit map
+        szn_fused_ce_head for the loss and szn_conse_head, which mixes the (K,E) class `embeddings` of the top `top_t` SEEN classes
+        with their renormalised softmax probabilities per pixel and takes the nearest class by cosine among all K = n_class classes
+        -- with calibrated stacking's penalty gamma on the seen classes, for every value of `gammas` (ascending, at most 64) in one
+        pass; forced=True (the reference's -fu) picks the group from the target instead.  No (B,K,H,W) score, softmax, mixture or
+        cosine in HBM.  -> (loss, pred, hist): the loss is softmax_predict's on that map, bit for bit (None without a target); pred
+        (B,H,W) int64 is the ConSE prediction at gammas[pred_index] (forced: the forced one), None when neither is asked for; hist
+        (G,K,K) int64 holds the confusion counts of every gamma: `hist` accumulated in place when given, a fresh one with a target
+        (not forced), else None."""
+        with torch.no_grad():
+            ctx, stride, fmap = self._head_map(x)
+            emb = torch.as_tensor(embeddings).to(fmap.device, torch.float32).contiguous()
+            if emb.dim() != 2 or emb.shape[0] != self.n_class:
+                raise L.SznError("conse_predict: embeddings must be (n_class = %d, E), got %r" % (self.n_class, tuple(emb.shape)))
+            loss_t = None
+            if target is not None:
+                loss_t, _ = heads.ce_predict(stride, fmap, self.n_class, ctx.H, ctx.W, target)
+            fmap32 = fmap if fmap.dtype == torch.float32 else fmap.to(torch.float32)
+            hist, pred = heads.conse(stride, fmap32, emb, ctx.H, ctx.W, unseen, top_t, gammas, target, hist, pred_index, forced)
+            self._last_pred = pred
+        return loss_t, pred, hist
+
     def class_prototypes(self, x, labels, K, classes=None, mode="unit", out=None):
         """class prototypes by masked average pooling (few-shot adaptation of the class embeddings): one inference forward pass, then
         szn_class_proto on the map the class head reads -- per class k of `classes` (None: all K) the sum over the pixels `labels`

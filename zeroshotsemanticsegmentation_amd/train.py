@@ -14,6 +14,10 @@ Added for this implementation (none change the reference flags):
                        (vis_utils; 25 = the reference's behaviour, 0 = off)
   --crop-size H W      train on randomly scaled, cropped and mirrored images at a fixed H x W network input (datasets.Augment; one
                        kernel on the GPU, szn_augment_u8); --scale-range LO HI (default 0.5 2.0), --no-flip.  Validation is untouched
+  --conse T            ConSE zero-shot inference for the softmax network (-c 1): validation and -m test_fcn -r <ckpt> mix the class
+                       embeddings (--conse-dim E, default 300) of the top T seen classes with their softmax probabilities per pixel and
+                       name the nearest class by cosine (szn_conse_head); --conse-gamma G penalises the seen classes, --conse-sweep LO
+                       HI N writes the metrics of N penalties to <log_dir>/conse_log.csv from the same head launch
   --calibration GAMMA  calibrated stacking in validation and -m test_fcn: GAMMA is subtracted from the cosine similarity of every seen
                        class before the argmax (szn_calib_head); --calib-sweep LO HI N also writes the metrics of N penalties between
                        LO and HI, and their harmonic mean of seen and unseen mIoU, to <log_dir>/calib_log.csv at one extra head launch
@@ -63,6 +67,7 @@ import yaml
 from . import engine as _engine
 from . import models, trainer_fcn, trainer_seenmask
 from .configs import configurations
+from ._lib import CONSE_MAX_TOP
 from .heads import RANK_MARGIN, SIM_TEMPERATURE
 from .optim import FusedAdam, FusedSGD
 from .synthetic_dataset import SyntheticSegmentation
@@ -122,6 +127,21 @@ def build_parser():
     p.add_argument('--calib-sweep', type=float, nargs=3, metavar=('LO', 'HI', 'N'), default=None,
                    help="every validation also evaluates N penalties (2 to 64) evenly spaced from LO to HI in one extra pass of the "
                         "head and appends their metrics and the harmonic mean of seen and unseen mIoU to <log_dir>/calib_log.csv")
+    p.add_argument('--conse', type=int, default=None, metavar='T',
+                   help="ConSE zero-shot inference for the softmax network (-c 1: fcn_loss cross_entropy, no embedding): validation "
+                        "(and -m test_fcn -r <ckpt>, on any such checkpoint, without retraining) mixes the class embeddings of the top "
+                        "T (1 to %d) seen classes with their softmax probabilities per pixel and names the nearest class by cosine "
+                        "among all classes; needs unseen classes.  T has no default: nobody has tuned it here (the paper uses 1, 10 "
+                        "and 1000).  Default: off" % CONSE_MAX_TOP)
+    p.add_argument('--conse-dim', type=int, default=None, choices=[2, 5, 10, 20, 21, 50, 100, 200, 300], metavar='E',
+                   help="with --conse: the width of the dataset's class embeddings (default 300)")
+    p.add_argument('--conse-gamma', type=float, default=None, metavar='G',
+                   help="with --conse: the penalty subtracted from the cosine of every seen class before the two groups are compared "
+                        "(calibrated stacking; default 0, at which ConSE almost never names an unseen class)")
+    p.add_argument('--conse-sweep', type=float, nargs=3, metavar=('LO', 'HI', 'N'), default=None,
+                   help="with --conse: every validation also evaluates N penalties (2 to 64) evenly spaced from LO to HI in the same "
+                        "pass of the head and appends their metrics and the harmonic mean of seen and unseen mIoU to "
+                        "<log_dir>/conse_log.csv")
     p.add_argument('--seen-threshold', type=float, default=None, metavar='TAU',
                    help="with -m test_all: threshold on the seen-mask logit margin s1 - s0, in logit units -- a pixel is classified "
                         "among the seen classes iff the margin exceeds TAU, that is p(seen) > sigmoid(TAU).  Default: the plain "
@@ -378,6 +398,31 @@ def check_calibration(calibration, sweep, cfg, eval_scales=None, eval_flip=False
         raise Exception("--calibration / --calib-sweep: " + why)
 
 
+def check_conse(top, dim, gamma, sweep, cfg, eval_scales=None, eval_flip=False):
+    """--conse / --conse-dim / --conse-gamma / --conse-sweep: T in [1, CONSE_MAX_TOP], a finite G, the satellites only with --conse;
+    unseen classes, the softmax configuration, and none of -m test_all, multi-scale views, or -fu together with a gamma or a sweep
+    (trainer_fcn.conse_refused).  -> the Trainer's conse= dict, or None without the flag"""
+    if top is None:
+        if dim is not None or gamma is not None or sweep is not None:
+            raise Exception("--conse-dim / --conse-gamma / --conse-sweep belong to --conse T")
+        return None
+    if not 1 <= top <= CONSE_MAX_TOP:
+        raise Exception("--conse: T must be from 1 to %d (got %r)" % (CONSE_MAX_TOP, top))
+    if gamma is not None and (gamma != gamma or gamma in (float('inf'), float('-inf'))):
+        raise Exception("--conse-gamma: G must be finite (got %r)" % (gamma,))
+    calib_sweep_values(sweep, "--conse-sweep")
+    why = trainer_fcn.conse_refused(bool(cfg['train_unseen'] or cfg['val_unseen']),
+                                    not cfg['embed_dim'] and cfg['fcn_loss'] == 'cross_entropy', bool(cfg['forced_unseen']),
+                                    cfg['mode'] == 'test_all', bool(eval_scales or eval_flip), bool(gamma) or sweep is not None)
+    if why:
+        raise Exception("--conse: " + why)
+    if sweep is not None and os.environ.get("SZN_VERBOSE_VAL", "0") == "1":
+        raise Exception("--conse-sweep: SZN_VERBOSE_VAL needs the materialised score, which the fused head never forms")
+    if cfg['dataset'] != 'pascal':
+        raise Exception("--conse: the softmax network has 21 channels (the reference's -c 1): dataset 'pascal' only (got %r)" % (cfg['dataset'],))
+    return dict(top=int(top), dim=300 if dim is None else int(dim), gamma=0.0 if gamma is None else float(gamma))
+
+
 def check_pseudo(keep, gamma, floor, start_epoch, hide_unseen, cfg):
     """--pseudo-label / --pseudo-gamma / --pseudo-floor / --pseudo-start-epoch / --hide-unseen: KEEP in (0, 1], finite G and C, N >= 0;
     the satellites only with --pseudo-label; unseen classes and an embedding configuration (trainer_fcn.pseudo_refused)"""
@@ -491,6 +536,7 @@ def main(argv=None):
     check_eval_views(args.eval_scales, args.eval_flip, cfg)
     check_calibration(args.calibration, args.calib_sweep, cfg, args.eval_scales, args.eval_flip)
     check_seen_threshold(args.seen_threshold, args.seen_sweep, cfg, args.calibration, args.calib_sweep, args.eval_scales, args.eval_flip)
+    conse = check_conse(args.conse, args.conse_dim, args.conse_gamma, args.conse_sweep, cfg, args.eval_scales, args.eval_flip)
     check_pseudo(args.pseudo_label, args.pseudo_gamma, args.pseudo_floor, args.pseudo_start_epoch, args.hide_unseen, cfg)
     check_ohem(args.ohem, args.ohem_thresh, args.ohem_start_epoch, cfg)
     check_bias(args.bias_loss, args.bias_start_epoch, cfg)
@@ -636,7 +682,8 @@ def main(argv=None):
         pseudo_start_epoch=args.pseudo_start_epoch or 0,
         ohem=None if args.ohem is None else dict(keep=args.ohem, thresh=args.ohem_thresh), ohem_start_epoch=args.ohem_start_epoch or 0,
         calibration=args.calibration, calib_sweep=calib_sweep_values(args.calib_sweep), eval_scales=args.eval_scales,
-        eval_flip=args.eval_flip, bias_loss=args.bias_loss, bias_start_epoch=args.bias_start_epoch or 0)
+        eval_flip=args.eval_flip, bias_loss=args.bias_loss, bias_start_epoch=args.bias_start_epoch or 0,
+        conse=conse, conse_sweep=calib_sweep_values(args.conse_sweep, "--conse-sweep"))
     fcn_trainer.epoch, fcn_trainer.iteration = start_epoch, start_iteration
 
     if cfg['mode'] == 'train':

@@ -85,6 +85,23 @@ def seen_threshold_refused(has_unseen, embed_cfg, forced_unseen, test_all, eval_
     return None
 
 
+def conse_refused(has_unseen, softmax_cfg, forced_unseen, test_all, eval_views, tuned):
+    """why a configuration cannot run ConSE zero-shot inference (conse= / conse_sweep=, train.py --conse / --conse-sweep), or None: ConSE
+    mixes class embeddings with the softmax network's seen-class probabilities, so it needs unseen classes and the softmax
+    configuration (cross entropy, no embedding); `tuned` = a gamma other than 0 or a sweep was asked for"""
+    if not has_unseen:
+        return "conse needs unseen classes (train_unseen / val_unseen): without them the channel argmax already names every class"
+    if not softmax_cfg:
+        return "conse needs the softmax configuration (fcn_loss 'cross_entropy', embed_dim 0): an embedding network has heads of its own"
+    if test_all:
+        return "conse on the full SZN network (-m test_all, seen-mask grouping) is not built: use -m test_fcn"
+    if eval_views:
+        return "conse with eval_scales / eval_flip is not built (averaging softmax probabilities over views is not)"
+    if forced_unseen and tuned:
+        return "conse: forced_unseen picks the class group from the target, a gamma or a sweep picks it from the margin: pick one"
+    return None
+
+
 def pseudo_refused(has_unseen, embed_cfg, n_class):
     """why a configuration cannot self-train on pseudo labels (pseudo=, train.py --pseudo-label), or None: the labels are the unseen
     classes' calibrated predictions of the fused embedding head"""
@@ -173,7 +190,7 @@ class Trainer(object):
     def __init__(self, cuda, model, optimizer, train_loader, val_loader, log_dir, dataset, max_epoch, tb_writer,
                  pixel_embeddings=None, loss_func=None, unseen=None, val_unseen=None, label_names=None,
                  forced_unseen=False, embed_arr=None, precision=torch.float32, fused_step=True, rank=0, visualize=0, augment=None,
-                 seen_threshold=None, seen_sweep=None, proto=None, support_loader=None,
+                 seen_threshold=None, seen_sweep=None, proto=None, support_loader=None, conse=None, conse_sweep=None,
                  sim_temperature=None, rank_margin=None, rank_hardest=False, bias_loss=None, bias_start_epoch=0, pseudo=None, pseudo_start_epoch=0, ohem=None, ohem_start_epoch=0, calibration=None,
                  calib_sweep=None, eval_scales=None, eval_flip=False):
         if not cuda:
@@ -277,6 +294,43 @@ class Trainer(object):
                 raise SznError(why)
             if self.seen_threshold is not None and not np.isfinite(self.seen_threshold):
                 raise SznError("seen_threshold: tau must be finite (got %r)" % (seen_threshold,))
+
+        # ConSE zero-shot inference for the softmax configuration (models.conse_predict): conse = dict(top=, dim=, gamma=) -- validation
+        # mixes the dataset's `dim`-wide class embeddings of the top `top` seen classes with their softmax probabilities and names the
+        # nearest class, with the penalty `gamma` (default 0) on the seen classes; `conse_sweep` = ascending candidate gammas whose
+        # metrics validate() writes to conse_log.csv from the same head launch.  Training steps never see them.
+        self.conse = None
+        self.conse_sweep = None
+        self.conse_embeddings = None
+        self.best_conse_gamma = None
+        self.best_conse_harmonic_mean_iu = None
+        if conse_sweep is not None and conse is None:
+            from ._lib import SznError
+            raise SznError("conse_sweep belongs to conse= (ConSE inference), which is off")
+        if conse is not None:
+            from ._lib import SznError
+            from .heads import calib_gammas, conse_top
+            cfg = dict(conse)
+            if set(cfg) - {"top", "dim", "gamma"} or "top" not in cfg:
+                raise SznError("conse = dict(top=, dim=300, gamma=0.0), got %r" % (conse,))
+            gamma = float(np.float32(cfg.get("gamma") or 0.0))
+            if not np.isfinite(gamma):
+                raise SznError("conse: gamma must be finite (got %r)" % (cfg.get("gamma"),))
+            if conse_sweep is not None:
+                self.conse_sweep = calib_gammas(conse_sweep)
+            why = conse_refused(bool(self.unseen), not pixel_embeddings and loss_func == "cross_entropy", forced_unseen, False,
+                                bool(self.eval_scales), gamma != 0.0 or self.conse_sweep is not None)
+            if why:
+                raise SznError(why)
+            if self.conse_sweep is not None and (self.verbose_val or self.n_class > 256):
+                raise SznError("conse: a sweep runs on the fused head (at most 256 classes, no SZN_VERBOSE_VAL)")
+            if model.n_class != self.n_class:
+                raise SznError("conse: the network has %d class channels, the dataset %d classes" % (model.n_class, self.n_class))
+            self.conse = dict(top=conse_top(cfg["top"]), dim=int(cfg.get("dim") or 300), gamma=gamma)
+            arr = np.asarray(embed_arr, dtype=np.float32) if embed_arr is not None else load_embeddings(dataset, self.conse["dim"])
+            if arr.ndim != 2 or arr.shape[0] != self.n_class:
+                raise SznError("conse: the class embeddings must be (%d, E), got %r" % (self.n_class, arr.shape))
+            self.conse_embeddings = torch.from_numpy(np.ascontiguousarray(arr)).to(self.device).float()
 
         # self-training (engine.TrainStep pseudo=): from epoch pseudo_start_epoch on every training step labels the most confident
         # `keep` of the hidden pixels (datasets.HIDDEN_LABEL: a hide_unseen training set) per unseen class with the step's own
@@ -666,16 +720,37 @@ class Trainer(object):
             # dense target embeddings, SZN_VERBOSE_VAL and more than 256 classes keep the materialised-score route: one view
             self._ms_warned = True
             print("warning: eval_scales / eval_flip ignored: this validation route materialises the score and evaluates one view")
+        if self.conse is not None and szn:
+            from ._lib import SznError
+            raise SznError(conse_refused(True, True, False, True, False, False))
         if self._ce_cfg() and self._fused_step and not szn and not self.verbose_val:
+            if self.conse is not None:
+                # ConSE: the loss is softmax_predict's; the class comes from szn_conse_head on the same map (no score, softmax,
+                # mixture or cosine in HBM), forced by the target under forced_unseen, else at the gamma in use with the sweep's histogram
+                if self.forced_unseen:
+                    loss, pred, _ = self.model.conse_predict(data, self.conse_embeddings, self.unseen, self.conse["top"], target=target,
+                                                             forced=True)
+                else:
+                    loss, pred, _ = self.model.conse_predict(data, self.conse_embeddings, self.unseen, self.conse["top"],
+                                                             self._conse_gammas(), target, hist=self._conse_hist,
+                                                             pred_index=self._conse_index())
+                return None, loss, pred, target
             # softmax inference: summed cross entropy + channel argmax straight from the coarse map (no (n,C,h,w) score in HBM)
             loss, pred = self.model.softmax_predict(data, target)
             return None, loss, pred, target
+        if self.conse is not None and self._conse_hist is not None:
+            from ._lib import SznError
+            raise SznError("conse: a sweep runs on the fused head; this validation route materialises the score")
         if szn:
             score, seen_mask_score = self.model(data, mode='both')
         else:
             score = self.model(data, mode='fcn')
         loss = self._loss(score, target, target_embed)
-        if not self.pixel_embeddings:
+        if self.conse is not None:
+            # the materialised route (more than 256 classes, SZN_VERBOSE_VAL, fused_step off): the torch-op referee on the score
+            pred = utils.conse_infer(score, self.conse_embeddings, self.unseen, self.conse["top"], self.conse["gamma"],
+                                     target if self.forced_unseen else None)
+        elif not self.pixel_embeddings:
             pred = utils.channel_argmax(score)
         elif szn:
             full = self.seen_embeddings + self.unseen_embeddings
@@ -729,6 +804,28 @@ class Trainer(object):
             self.tb_writer.add_scalar('fcn/val/calib/best_harmonic_mean_iu', best[1], self.epoch)
         else:
             print('calibration: no gamma has a harmonic mean IU (the validation set holds no seen or no unseen pixels)')
+
+    # ConSE: as above, the gamma in use (0 without one) joins the sweep's gammas for the call
+    _conse_hist = None                          # the (G,K,K) device histogram of the running validate(), None outside a sweep
+
+    def _conse_gammas(self):
+        if self._conse_hist is None:
+            return [self.conse["gamma"]]
+        return self._conse_all
+
+    def _conse_index(self):
+        return 0 if self._conse_hist is None else int(np.searchsorted(self._conse_all, np.float32(self.conse["gamma"])))
+
+    def _conse_report(self, hist_all):
+        """rank 0, once per epoch: one conse_log.csv row per gamma of the sweep, and the gamma with the largest harmonic mean"""
+        best = self._sweep_report(hist_all, self._conse_all, self.conse_sweep, 'conse_log.csv', 'gamma')
+        if best is not None:
+            self.best_conse_gamma, self.best_conse_harmonic_mean_iu = best
+            print('conse: best gamma %g, harmonic mean IU %.3f' % best)
+            self.tb_writer.add_scalar('fcn/val/conse/best_gamma', best[0], self.epoch)
+            self.tb_writer.add_scalar('fcn/val/conse/best_harmonic_mean_iu', best[1], self.epoch)
+        else:
+            print('conse: no gamma has a harmonic mean IU (the validation set holds no seen or no unseen pixels)')
 
     # the seen-mask threshold: as above, the threshold in use (tau = 0 without one: the plain route's decision) joins the sweep's taus
     _seen_hist = None                           # the (G,K,K) device histogram of the running validate(True), None outside a sweep
@@ -833,6 +930,15 @@ class Trainer(object):
                 from ._lib import SznError
                 raise SznError("calibration: a 64-gamma sweep has no room for a calibration value that is not one of its gammas")
             self._calib_hist = torch.zeros(self._calib_all.size, self.n_class, self.n_class, dtype=torch.int64, device=self.device)
+        if both_fcn_and_seenmask and self.conse is not None:
+            from ._lib import SznError
+            raise SznError(conse_refused(True, True, False, True, False, False))
+        if self.conse_sweep is not None:
+            self._conse_all = np.unique(np.concatenate([self.conse_sweep, np.asarray([self.conse["gamma"]], dtype=np.float32)]))
+            if self._conse_all.size > 64:
+                from ._lib import SznError
+                raise SznError("conse: a 64-gamma sweep has no room for a gamma in use that is not one of its gammas")
+            self._conse_hist = torch.zeros(self._conse_all.size, self.n_class, self.n_class, dtype=torch.int64, device=self.device)
         if not both_fcn_and_seenmask and (self.seen_threshold is not None or self.seen_sweep is not None):
             from ._lib import SznError
             raise SznError(seen_threshold_refused(True, True, False, False, False, self.n_class))
@@ -864,9 +970,12 @@ class Trainer(object):
                         int(self.epoch), int(batch_idx), float(loss.item()), float(score.sum().item())))
         calib_hist, self._calib_hist = self._calib_hist, None
         seen_hist, self._seen_hist = self._seen_hist, None
+        conse_hist, self._conse_hist = self._conse_hist, None
         if world > 1:
             dist.all_reduce(hist)
             dist.all_reduce(acc)
+            if conse_hist is not None:
+                dist.all_reduce(conse_hist)
             if calib_hist is not None:
                 dist.all_reduce(calib_hist)
             if seen_hist is not None:
@@ -880,6 +989,10 @@ class Trainer(object):
             seen_hist = seen_hist.cpu().numpy()
             if self.rank == 0:
                 self._seen_report(seen_hist)
+        if conse_hist is not None:
+            conse_hist = conse_hist.cpu().numpy()
+            if self.rank == 0:
+                self._conse_report(conse_hist)
         accn = acc.cpu().numpy()
         if np.isnan(accn[0]):
             raise ValueError('loss is nan while validating')

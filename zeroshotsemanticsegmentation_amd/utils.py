@@ -480,6 +480,58 @@ def calib_rows(hist, n_class, unseen):
     return _hist_to_metrics(hist), _hist_to_metrics(seen_h), _hist_to_metrics(unseen_h)
 
 
+def _first_max(vals, members):
+    """(class, value) of the first class of `members` (ascending) holding the maximum of vals (B,K,H,W) over them"""
+    sub = vals[:, members]
+    best = sub.max(dim=1, keepdim=True).values
+    pos = torch.arange(len(members), device=vals.device).view(1, -1, 1, 1)
+    first = torch.where(sub == best, pos, len(members)).min(dim=1).values.clamp(max=len(members) - 1)
+    return members[first], best[:, 0]
+
+
+def conse_infer(score, embeddings, unseen, top_t, gamma=0.0, target=None):
+    """ConSE (Norouzi et al., ICLR 2014) on a materialised (B,K,H,W) softmax-network score with torch operations: the referee of
+    szn_conse_head (heads.conse, FCN32s.conse_predict) and the route for configurations the fused head does not take (more than 256
+    classes, SZN_VERBOSE_VAL).  Runs on the score's device, CPU included.  Per pixel: the top `top_t` SEEN classes (not in `unseen`)
+    by (score descending, class ascending), their softmax p, the mixture f = sum p_t e_t of the rows of `embeddings` (K,E), the cosine
+    of f with every row (a zero norm counts as 1); a / b = the first best seen / unseen class, m = their cosine difference.
+    target None: a where m > gamma, or m == gamma and a < b; else b (0 where m is NaN).  target given: the reference's forced rule
+    -- b where the target names an unseen class, a elsewhere; gamma is not used.  -> int64 (B,H,W) tensor on the score's device."""
+    score = _data(score).detach().float()
+    dev = score.device
+    emb = _data(embeddings).to(device=dev, dtype=torch.float32)
+    B, K, H, W = score.shape
+    if emb.dim() != 2 or emb.shape[0] != K:
+        raise L.SznError("conse_infer: embeddings must be (%d,E), got %s" % (K, tuple(emb.shape)))
+    uns = sorted(set(int(k) for k in unseen))
+    if not uns or len(uns) >= K or uns[0] < 0 or uns[-1] >= K:
+        raise L.SznError("conse_infer: the unseen classes must be a non-empty proper subset of range(%d)" % K)
+    if int(top_t) < 1:
+        raise L.SznError("conse_infer: top_t must be at least 1, got %r" % (top_t,))
+    is_unseen = torch.zeros(K, dtype=torch.bool, device=dev)
+    is_unseen[uns] = True
+    seen_idx, unseen_idx = torch.nonzero(~is_unseen)[:, 0], torch.nonzero(is_unseen)[:, 0]
+    n = min(int(top_t), int(seen_idx.numel()))
+    vals, order = torch.sort(score[:, seen_idx], dim=1, descending=True, stable=True)       # stable: ties keep the class order
+    p = torch.softmax(vals[:, :n], dim=1)
+    probs = torch.zeros_like(score).scatter_(1, seen_idx[order[:, :n]], p)                   # (B,K,H,W), zero outside S
+    f = torch.einsum('bkhw,ke->behw', probs, emb)
+    fn = f.norm(dim=1, keepdim=True)
+    en = emb.norm(dim=1)
+    sim = torch.einsum('behw,ke->bkhw', f, emb) / (torch.where(fn == 0, torch.ones_like(fn), fn)
+                                                   * torch.where(en == 0, torch.ones_like(en), en).view(1, K, 1, 1))
+    a, va = _first_max(sim, seen_idx)
+    b, vb = _first_max(sim, unseen_idx)
+    m = va - vb
+    if target is not None:
+        tgt = _data(target).to(device=dev, dtype=torch.int64)
+        pred = torch.where(torch.isin(tgt, unseen_idx), b, a)
+    else:
+        g = float(np.float32(gamma))
+        pred = torch.where((m > g) | ((m == g) & (a < b)), a, b)
+    return torch.where(torch.isnan(m), torch.zeros_like(pred), pred)
+
+
 def _fast_hist(label_true, label_pred, n_class, target='all', unseen=None):
     """host restatement of utils.py:104-119 for numpy label maps (validation logs on the host)"""
     label_true = np.asarray(label_true)
