@@ -901,6 +901,44 @@ int szn_seen_sweep_head_tabled(int stride, int B, int h, int w, int E, int ldc, 
                                const float* margin, int n_taus, const float* taus, int64_t* hist, int pred_index, int64_t* pred,
                                void* workspace, szn_stream_t stream);
 
+/* ---- full SZN inference with a soft seen/unseen gate --------------------------------------------------------------------------------
+ * szn_soft_gate_head: the probabilistic form of the seen-mask route (a novelty detector in front of two classifiers, Socher et al. 2013;
+ * Atzmon & Chechik 2019): p(k | x) = p(group(k) | x) p(k | group(k), x) with p(seen | x) = sigmoid(m - tau), m = margin[pix], and inside
+ * each group a softmax over the cosines at `temperature`.  With a / b the best seen / best unseen class, the pixel takes a iff
+ * m - tau > log P_U(b) - log P_S(a): a per-pixel adaptive threshold on the margin, so the call is szn_seen_sweep_head with another
+ * per-pixel body.  Arguments, workspace layout (szn_soft_gate_head_workspace_bytes == szn_seen_sweep_head_workspace_bytes), refusals and
+ * the _tabled form are szn_seen_sweep_head's.  Per pixel:
+ *   sim[k]   = szn_calib_head's ungrouped similarity, the same operations in the same order;
+ *   a, va / b, vb = the TRUE argmax inside the seen / the unseen group, the first index winning (szn_calib_head's two running bests).
+ *              This is NOT szn_seen_sweep_head's pair: there a class outside the group competes with 0 / (sn * 1), the reference's
+ *              zeroed-row quirk, which has no probabilistic meaning.  The two agree where each group's best cosine is positive;
+ *   inv_t    = 1.0f / temperature (one fp32 division on the host);
+ *   l_S      = logf(sum_{k seen} expf((sim[k] - va) * inv_t)) = -log P_S(a), l_U likewise over `unseen` with vb: 0 <= l_G <= log n_G, each
+ *              sum shifted by its own group's maximum (an online sum, rescaled when the running best moves: one expf per class, every
+ *              exponent <= 0); a group of one class gives exactly 0.0f;
+ *   D        = l_S - l_U,  e = fmaf(-weight, D, m);
+ *   the pixel takes a at g iff e > taus[g]; bin = the first g at which that fails (n_taus: never).
+ * D NaN (a zero-norm pixel): a = b = 0, class 0 at every tau (szn_calib_head's rule).  A NaN margin compares false: b at every tau.
+ * weight = 0 is the hard threshold on the true groups (e == m bit for bit), weight = 1 the probabilistic rule, larger weights trust the
+ * two experts more.  hist, pred, the crossing tables and calib_hist_kernel are szn_seen_sweep_head's: integer counts, two calls bit-equal.
+ *   eff (B,H,W) f32 (device, or NULL): e per pixel (NaN where D or the margin is NaN).
+ * szn_last_kernel(): calib_hist_kernel when hist is given (szn_prev_kernel(): the pixel kernel), else the pixel kernel --
+ * gate_cell_kernel (stride 32) or gate_cell_tab_kernel (stride 8).
+ * SZN_ERR_ARG, before any launch: everything szn_seen_sweep_head refuses, except that hist and pred may both be NULL when eff is given
+ * (hist, pred and eff all NULL is refused); a temperature that is not finite or <= 0; a weight that is not finite or < 0.             */
+size_t szn_soft_gate_head_workspace_bytes(int stride, int B, int h, int w, int E, int K, int n_taus);
+int szn_soft_gate_head(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                       const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
+                       const float* margin, float temperature, float weight,
+                       int n_taus, const float* taus, int64_t* hist, int pred_index, int64_t* pred, float* eff,
+                       void* workspace, szn_stream_t stream);
+/* on a workspace in whose head a fused embedding head has just run on this map: szn_seen_sweep_head_tabled's vouching rule            */
+int szn_soft_gate_head_tabled(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                              const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
+                              const float* margin, float temperature, float weight,
+                              int n_taus, const float* taus, int64_t* hist, int pred_index, int64_t* pred, float* eff,
+                              void* workspace, szn_stream_t stream);
+
 /* ---- ConSE zero-shot inference for the softmax FCN ---------------------------------------------------------------------------------
  * szn_conse_head: convex combination of semantic embeddings (Norouzi et al., ICLR 2014) per pixel, from the logit map of a network that
  * was trained on the seen classes with szn_fused_ce_head, with the seen-class penalty gamma of szn_calib_head swept over n_gammas values

@@ -211,6 +211,9 @@ SIGNATURES = {
     "szn_seen_sweep_head_workspace_bytes": (_SZ, [_I] * 7),
     "szn_seen_sweep_head": (_I, [_I] * 11 + [_P, _P, _P, _CS, _P, _I, _FP, _P, _I, _P, _P, _P]),
     "szn_seen_sweep_head_tabled": (_I, [_I] * 11 + [_P, _P, _P, _CS, _P, _I, _FP, _P, _I, _P, _P, _P]),
+    "szn_soft_gate_head_workspace_bytes": (_SZ, [_I] * 7),
+    "szn_soft_gate_head": (_I, [_I] * 11 + [_P, _P, _P, _CS, _P, _F, _F, _I, _FP, _P, _I, _P, _P, _P, _P]),
+    "szn_soft_gate_head_tabled": (_I, [_I] * 11 + [_P, _P, _P, _CS, _P, _F, _F, _I, _FP, _P, _I, _P, _P, _P, _P]),
     "szn_conse_head_workspace_bytes": (_SZ, [_I] * 7),
     "szn_conse_head": (_I, [_I] * 11 + [_P, _P, _P, _CS, _I, _I, _I, _FP, _P, _I, _P, _P, _P]),
     "szn_pseudo_head_workspace_bytes": (_SZ, [_I] * 8),

@@ -25,6 +25,8 @@
 //                        (calib_count and calib_hist_kernel live in szn_calib.h, shared with szn_conse_head.hip)
 //   sweep_cell_kernel / sweep_cell_tab_kernel   szn_seen_sweep_head (seen-mask threshold sweep): the calibrated kernels with the grouped
 //                        head's two answers per pixel (fh_group_bests) and the seen-mask margin as the switch; then calib_hist_kernel
+//   gate_cell_kernel / gate_cell_tab_kernel   szn_soft_gate_head (soft seen/unseen gating): the sweep kernels with the true in-group bests and
+//                        an online log-sum-exp per group (fh_gate_bests); the switch is margin - weight * (l_S - l_U); then calib_hist_kernel
 //   pseudo_cell_kernel / pseudo_cell_tab_kernel / pseudo_thr_kernel / pseudo_relabel_kernel   szn_pseudo_head (self-training): the same G, Q
 //                        and fh_two_best on the pixels labelled cand_label, a per-class confidence histogram, thresholds, the relabelled target
 //   ohem_cell_kernel / ohem_cell_tab_kernel / ohem_cut_kernel / ohem_relabel_kernel   szn_ohem_head (hard-pixel mining), in launch order: the
@@ -1121,8 +1123,68 @@ __device__ __forceinline__ int sweep_pixel(const FhArgs& a, const CalArgs& c, co
     return (int)t | r.ia << 8 | r.ib << 16 | bin << 24;
 }
 
+// ---- soft seen/unseen gating (szn_soft_gate_head): the sweep's cells, tables and crossing scheme with a per-pixel adaptive switch --------
+// p(k | x) = p(group(k) | x) p(k | group(k), x) with p(seen) = sigmoid(margin - tau) and a softmax over the cosines at temperature T
+// inside each group collapses to: the pixel takes a iff e = margin - weight * (l_S - l_U) > tau, l_G = -log P_G(best of G) (include/szn.h).
+// a, b are the TRUE in-group argmaxes (fh_two_best's rule), not fh_group_bests' zeroed-row answers.
+struct GateArgs {
+    const float* margin;         // (B,H,W)
+    float* eff;                  // (B,H,W) or null: e per pixel
+    float inv_t, weight;
+};
+
+// One trip through the classes: fh_two_best's two running bests, and next to each the sum of exp((sim - best) / T) over its group,
+// rescaled when the best moves (an online log-sum-exp).  One expf per class: its argument is -|sim - best| / T <= 0 either way -- the
+// factor that rescales the old sum when sim takes over, the new term when it does not -- so nothing overflows, and the class that holds
+// the maximum contributes exactly 1: sum >= 1, a group of one class gives exactly 1 and logf(1) = 0.  The group bit is wave-uniform as in
+// fh_two_best: scalar selects.  A NaN similarity (zero-norm pixel) makes both sums NaN.
+struct FhGateBest { int ia, ib; float ls, lu; };
+template <int KP>
+__device__ __forceinline__ FhGateBest fh_gate_bests(const FhArgs& a, const float (&wt)[4], const float* G, float sn,
+                                                    const float* __restrict__ en, float inv_t) {
+    int ia = -1, ib = -1;
+    float va = 0.f, vb = 0.f, sa = 0.f, sb = 0.f;
+    for (int k = 0; k < a.K; ++k) {
+        const bool u = (bool)((class_word(a.unseen, k >> 6) >> (k & 63)) & 1ull);
+        const float sim = fh_sim<KP>(wt, G, sn, en, k);
+        const bool first = u ? ib < 0 : ia < 0;
+        const float v = first ? sim : (u ? vb : va), s = u ? sb : sa;
+        const bool take = first || sim > v;
+        const float d = sim - v;                                  // the group's first class: 0, or NaN for a NaN similarity
+        const float ex = expf((take ? -d : d) * inv_t);
+        const float s2 = first ? 1.f + d : (take ? fmaf(s, ex, 1.f) : s + ex);
+        if (u) { sb = s2; if (take) { vb = sim; ib = k; } }
+        else { sa = s2; if (take) { va = sim; ia = k; } }
+    }
+    return {ia, ib, logf(sa), logf(sb)};
+}
+
+template <int KP, int S>
+__device__ __forceinline__ int gate_pixel(const FhArgs& a, const CalArgs& c, const GateArgs& g, int b, int I, int J,
+                                          int ty, int tx, bool live, const float* G, const float* Q, const float* __restrict__ en) {
+    const int y = S * I + ty - a.crop, x = S * J + tx - a.crop;
+    if (!(live && y >= 0 && y < a.H && x >= 0 && x < a.W)) return -1;
+    float wt[4];
+    cell_weights<S>(ty, tx, wt);
+    const float sn = sqrtf(fh_ss(wt, Q));
+    FhGateBest r = fh_gate_bests<KP>(a, wt, G, sn, en, g.inv_t);
+    const size_t pix = ((size_t)b * a.H + y) * a.W + x;
+    const float D = r.ls - r.lu;
+    const float e = fmaf(-g.weight, D, g.margin[pix]);
+    int bin = 0;
+    if (D != D) { r.ia = 0; r.ib = 0; bin = c.n; }        // NaN (a zero-norm pixel): class 0 at every tau, calib_pixel's rule
+    else
+        for (int t = 0; t < c.n; ++t) bin += (e > c.gamma[t]) ? 1 : 0;     // ascending: a prefix; a NaN margin: the unseen group
+    if (g.eff) g.eff[pix] = e;
+    if (c.pred) c.pred[pix] = bin > c.pred_index ? r.ia : r.ib;
+    if (!c.XA) return -1;
+    const long t = a.target[pix];
+    if (t < 0 || t >= a.K) return -1;
+    return (int)t | r.ia << 8 | r.ib << 16 | bin << 24;
+}
+
 // The two walks over the pixels that the calibrated head and the threshold sweep share: px(b, I, J, ty, tx, live, G, Q, en) is the head's
-// per-pixel body (calib_pixel, sweep_pixel) and returns the pixel's key.  Stride 32: one block per (image, cell), G and Q built in `sm`.
+// per-pixel body (calib_pixel, sweep_pixel, gate_pixel) and returns the pixel's key.  Stride 32: one block per (image, cell), G and Q built in `sm`.
 template <int KP, typename Px>
 __device__ __forceinline__ void calib_cell_walk(const FhArgs& a, const CalArgs& c, float* sm, Px px) {
     constexpr int S = 32;
@@ -1205,20 +1267,44 @@ __global__ __launch_bounds__(256) void sweep_cell_tab_kernel(FhArgs a, CalArgs c
     });
 }
 
-// margin == nullptr: szn_calib_head's pixel kernels; else szn_seen_sweep_head's, same grids and LDS.  tabled: the stride-8 position tables
-// are in the workspace already (szn_seen_sweep_head_tabled)
 template <int KP>
-void calib_launch(int stride, const FhArgs& a, const CalArgs& c, const float* margin, bool tabled, float* tabD, float* tabN, hipStream_t st) {
+__global__ __launch_bounds__(256) void gate_cell_kernel(FhArgs a, CalArgs c, GateArgs g) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    calib_cell_walk<KP>(a, c, sm, [&](int b, int I, int J, int ty, int tx, bool live, const float* G, const float* Q, const float* en) {
+        return gate_pixel<KP, 32>(a, c, g, b, I, J, ty, tx, live, G, Q, en);
+    });
+}
+
+template <int KP>
+__global__ __launch_bounds__(256) void gate_cell_tab_kernel(FhArgs a, CalArgs c, GateArgs g, const float* __restrict__ D,
+                                                            const float* __restrict__ N) {
+    __shared__ float Gs[4 * 4 * KP];
+    __shared__ float Qs[4 * 16];
+    calib_cell_tab_walk<KP>(a, c, D, N, Gs, Qs, [&](int b, int I, int J, int ty, int tx, bool live, const float* G, const float* Q, const float* en) {
+        return gate_pixel<KP, 8>(a, c, g, b, I, J, ty, tx, live, G, Q, en);
+    });
+}
+
+// gate: szn_soft_gate_head's pixel kernels; else margin == nullptr: szn_calib_head's; else szn_seen_sweep_head's -- same grids and LDS.
+// tabled: the stride-8 position tables are in the workspace already (szn_seen_sweep_head_tabled, szn_soft_gate_head_tabled)
+template <int KP>
+void calib_launch(int stride, const FhArgs& a, const CalArgs& c, const float* margin, const GateArgs* gate, bool tabled, float* tabD,
+                  float* tabN, hipStream_t st) {
     const int cells = (a.h + 1) * (a.w + 1);
     if (stride == 8) {
         const dim3 grid((unsigned)(((long)a.B * cells + 3) / 4));
         if (!tabled) hipLaunchKernelGGL(fh_tables_kernel<KP>, dim3((unsigned)(((long)a.B * a.h * a.w + 3) / 4)), dim3(256),
                                         (size_t)4 * a.E * sizeof(float), st, a, tabD, tabN);
-        if (margin) hipLaunchKernelGGL(sweep_cell_tab_kernel<KP>, grid, dim3(256), 0, st, a, c, margin, (const float*)tabD, (const float*)tabN);
+        if (gate) hipLaunchKernelGGL(gate_cell_tab_kernel<KP>, grid, dim3(256), 0, st, a, c, *gate, (const float*)tabD, (const float*)tabN);
+        else if (margin) hipLaunchKernelGGL(sweep_cell_tab_kernel<KP>, grid, dim3(256), 0, st, a, c, margin, (const float*)tabD, (const float*)tabN);
         else hipLaunchKernelGGL(calib_cell_tab_kernel<KP>, grid, dim3(256), 0, st, a, c, (const float*)tabD, (const float*)tabN);
     } else {
         const size_t lds = (size_t)(fh_lds(a.E, KP, false).Q + 16) * sizeof(float);       // Ct | G | Q
-        if (margin) {
+        if (gate) {
+            auto kern = gate_cell_kernel<KP>;
+            if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(kern, dim3(a.B * cells), dim3(256), lds, st, a, c, *gate);
+        } else if (margin) {
             auto kern = sweep_cell_kernel<KP>;
             if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             hipLaunchKernelGGL(kern, dim3(a.B * cells), dim3(256), lds, st, a, c, margin);
@@ -2025,11 +2111,12 @@ extern "C" size_t szn_calib_head_workspace_bytes(int stride, int B, int h, int w
 namespace {
 // szn_calib_head (sweep == false, margin unused) and szn_seen_sweep_head (sweep == true: `gammas` are its taus, the switch is `margin`):
 // the same refusals, workspace and launch sequence, another pixel kernel.  tabled: the workspace already holds the prepared embedding image
-// and the stride-8 position tables of this map (szn_seen_sweep_head_tabled): neither is rebuilt
+// and the stride-8 position tables of this map (szn_seen_sweep_head_tabled): neither is rebuilt.  gate: szn_soft_gate_head (sweep == true
+// with the gate's pixel kernels; its eff output counts as a result)
 int calib_head_impl(const char* who, const char* vals, bool sweep, bool tabled, int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W,
                     int crop, int K, const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
                     const float* margin, int n_gammas, const float* gammas, int64_t* hist, int pred_index, int64_t* pred, void* workspace,
-                    szn_stream_t stream) {
+                    szn_stream_t stream, GateArgs* gate = nullptr) {
     if (const char* why = calib_bad_geometry(stride, B, h, w, E, K, n_gammas)) SZN_FAIL(SZN_ERR_ARG, "%s: %s", who, why);
     if (!coarse || !embed || !workspace || !gammas) SZN_FAIL(SZN_ERR_ARG, "%s: coarse, embed, workspace and %s are required", who, vals);
     if (sweep && !margin) SZN_FAIL(SZN_ERR_ARG, "%s: margin is required", who);
@@ -2040,7 +2127,10 @@ int calib_head_impl(const char* who, const char* vals, bool sweep, bool tabled, 
         if (!isfinite(gammas[g])) SZN_FAIL(SZN_ERR_ARG, "%s: %s[%d] is not finite", who, vals, g);
         if (g && !(gammas[g] > gammas[g - 1])) SZN_FAIL(SZN_ERR_ARG, "%s: %s must be strictly ascending (at %d)", who, vals, g);
     }
-    if (!hist && !pred) SZN_FAIL(SZN_ERR_ARG, "%s: hist and pred are both NULL", who);
+    if (gate) {
+        if (!hist && !pred && !gate->eff) SZN_FAIL(SZN_ERR_ARG, "%s: hist, pred and eff are all NULL", who);
+        gate->margin = margin;
+    } else if (!hist && !pred) SZN_FAIL(SZN_ERR_ARG, "%s: hist and pred are both NULL", who);
     if (hist && !target) SZN_FAIL(SZN_ERR_ARG, "%s: hist needs target", who);
     if (pred && (pred_index < 0 || pred_index >= n_gammas)) SZN_FAIL(SZN_ERR_ARG, "%s: pred_index %d outside [0, %d)", who, pred_index, n_gammas);
     const int KP = kp_of(K);
@@ -2067,14 +2157,15 @@ int calib_head_impl(const char* who, const char* vals, bool sweep, bool tabled, 
     float* tabD = (float*)(ws + wl.tabD);
     float* tabN = (float*)(ws + wl.tabN);
     switch (KP) {
-        case 24: calib_launch<24>(stride, a, c, margin, tabled, tabD, tabN, st); break;
-        case 40: calib_launch<40>(stride, a, c, margin, tabled, tabD, tabN, st); break;
-        case 64: calib_launch<64>(stride, a, c, margin, tabled, tabD, tabN, st); break;
-        case 128: calib_launch<128>(stride, a, c, margin, tabled, tabD, tabN, st); break;
-        case 192: calib_launch<192>(stride, a, c, margin, tabled, tabD, tabN, st); break;
-        default: calib_launch<256>(stride, a, c, margin, tabled, tabD, tabN, st); break;
+        case 24: calib_launch<24>(stride, a, c, margin, gate, tabled, tabD, tabN, st); break;
+        case 40: calib_launch<40>(stride, a, c, margin, gate, tabled, tabD, tabN, st); break;
+        case 64: calib_launch<64>(stride, a, c, margin, gate, tabled, tabD, tabN, st); break;
+        case 128: calib_launch<128>(stride, a, c, margin, gate, tabled, tabD, tabN, st); break;
+        case 192: calib_launch<192>(stride, a, c, margin, gate, tabled, tabD, tabN, st); break;
+        default: calib_launch<256>(stride, a, c, margin, gate, tabled, tabD, tabN, st); break;
     }
-    if (sweep) SZN_CHECK_LAUNCH(stride == 8 ? "sweep_cell_tab_kernel" : "sweep_cell_kernel");
+    if (gate) SZN_CHECK_LAUNCH(stride == 8 ? "gate_cell_tab_kernel" : "gate_cell_kernel");
+    else if (sweep) SZN_CHECK_LAUNCH(stride == 8 ? "sweep_cell_tab_kernel" : "sweep_cell_kernel");
     else SZN_CHECK_LAUNCH(stride == 8 ? "calib_cell_tab_kernel" : "calib_cell_kernel");
     if (hist) {
         hipLaunchKernelGGL(calib_hist_kernel, dim3(szn_div_up((long)K * K, 256)), dim3(256), 0, st, (const unsigned long long*)c.XA,
@@ -2116,6 +2207,42 @@ extern "C" int szn_seen_sweep_head_tabled(int stride, int B, int h, int w, int E
                                           void* workspace, szn_stream_t stream) {
     return calib_head_impl("seen_sweep_head_tabled", "taus", true, true, stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, unseen,
                            margin, n_taus, taus, hist, pred_index, pred, workspace, stream);
+}
+
+// Soft seen/unseen gating (include/szn.h): the threshold sweep with the per-pixel effective margin e = margin - weight * (l_S - l_U) as the
+// switch and the true in-group argmaxes as the two answers.  Sizes, workspace, refusals and launch sequence are szn_seen_sweep_head's.
+extern "C" size_t szn_soft_gate_head_workspace_bytes(int stride, int B, int h, int w, int E, int K, int n_taus) {
+    return szn_calib_head_workspace_bytes(stride, B, h, w, E, K, n_taus);
+}
+
+namespace {
+int soft_gate_impl(const char* who, bool tabled, int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                   const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen, const float* margin,
+                   float temperature, float weight, int n_taus, const float* taus, int64_t* hist, int pred_index, int64_t* pred, float* eff,
+                   void* workspace, szn_stream_t stream) {
+    if (!isfinite(temperature) || !(temperature > 0.f)) SZN_FAIL(SZN_ERR_ARG, "%s: temperature must be finite and > 0", who);
+    if (!isfinite(weight) || !(weight >= 0.f)) SZN_FAIL(SZN_ERR_ARG, "%s: weight must be finite and >= 0", who);
+    GateArgs g{};
+    g.eff = eff; g.inv_t = 1.0f / temperature; g.weight = weight;
+    return calib_head_impl(who, "taus", true, tabled, stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, unseen, margin, n_taus,
+                           taus, hist, pred_index, pred, workspace, stream, &g);
+}
+}  // namespace
+
+extern "C" int szn_soft_gate_head(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                                  const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
+                                  const float* margin, float temperature, float weight, int n_taus, const float* taus, int64_t* hist,
+                                  int pred_index, int64_t* pred, float* eff, void* workspace, szn_stream_t stream) {
+    return soft_gate_impl("soft_gate_head", false, stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, unseen, margin, temperature,
+                          weight, n_taus, taus, hist, pred_index, pred, eff, workspace, stream);
+}
+
+extern "C" int szn_soft_gate_head_tabled(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                                         const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
+                                         const float* margin, float temperature, float weight, int n_taus, const float* taus, int64_t* hist,
+                                         int pred_index, int64_t* pred, float* eff, void* workspace, szn_stream_t stream) {
+    return soft_gate_impl("soft_gate_head_tabled", true, stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, unseen, margin,
+                          temperature, weight, n_taus, taus, hist, pred_index, pred, eff, workspace, stream);
 }
 
 // Self-training pseudo labels (include/szn.h): the calibrated rule at one gamma picks the candidates among the pixels labelled cand_label,

@@ -24,6 +24,8 @@ szn_fused_ce_head and szn_seenmask_head_k goes through here (models.FCN32s / FCN
             the nearest class by cosine wins, calib's gamma between the groups, swept in one pass; or forced by the target.
   seen_sweep  full SZN inference with a threshold on the seen-mask logit margin (szn_seenmask_margin, szn_seen_sweep_head): the grouped
             head's class assignment with the group decided by margin > tau, up to 64 taus in one pass.
+  soft_gate   the same route with a probabilistic gate (szn_soft_gate_head): p(seen) = sigmoid(margin - tau) times a softmax over the cosines
+            inside each group, which is a per-pixel adaptive threshold on the margin; same sweep, same workspace.
   pseudo    self-training pseudo labels (szn_pseudo_head): the calibrated prediction labels the most confident share of the hidden
             pixels per unseen class; the relabelled target is what a training head then reads.
   ohem      hard-pixel mining (szn_ohem_head): per image the labelled pixels with the lowest own-class cosine keep their label, the
@@ -493,6 +495,84 @@ def seen_sweep(stride, fmap, emb, H, W, unseen, margin, taus, target=None, hist=
            L.class_set(unseen), L.ptr(margin), G, t.ctypes.data_as(C.POINTER(C.c_float)), L.ptr(hist),
            -1 if pred_index is None else int(pred_index), L.ptr(pred), L.ptr(buf), L.stream_ptr())
     return hist, pred
+
+
+# ---- full SZN inference with a soft seen/unseen gate ----------------------------------------------------------------------------
+GATE_TEMPERATURE = 0.1       # the default of train.py --gate-temperature: a hyper-parameter default, not a tuned value
+
+
+def gate_params(gate):
+    """a gate description dict(weight=, temperature=) checked -> (weight, temperature) as the float32 values szn_soft_gate_head reads:
+    weight finite and >= 0 (required), temperature finite and > 0 (None or absent: GATE_TEMPERATURE)"""
+    import numpy as np
+    if not isinstance(gate, dict) or set(gate) - {"weight", "temperature"} or "weight" not in gate:
+        raise L.SznError("soft gate: gate must be dict(weight=, temperature=) with a weight, got %r" % (gate,))
+    temperature = gate.get("temperature")
+    try:
+        w = float(np.float32(gate["weight"]))
+        t = float(np.float32(GATE_TEMPERATURE if temperature is None else temperature))
+    except (TypeError, ValueError):
+        raise L.SznError("soft gate: weight and temperature must be numbers, got %r" % (gate,))
+    if not np.isfinite(w) or w < 0:
+        raise L.SznError("soft gate: weight must be finite and >= 0 (got %r)" % (gate["weight"],))
+    if not np.isfinite(t) or t <= 0:
+        raise L.SznError("soft gate: temperature must be finite and > 0 (got %r)" % (temperature,))
+    return w, t
+
+
+def soft_gate_workspace_bytes(stride, fmap, emb, n_taus):
+    """szn_soft_gate_head_workspace_bytes for a map and an embedding matrix (0: a geometry the head refuses)"""
+    B, h, w, _ = fmap.shape
+    K, E = emb.shape
+    return L.load().szn_soft_gate_head_workspace_bytes(stride, B, h, w, E, K, int(n_taus))
+
+
+def soft_gate(stride, fmap, emb, H, W, unseen, margin, taus, temperature, weight, target=None, hist=None, pred_index=None,
+              want_eff=False, ws=None):
+    """szn_soft_gate_head on the contiguous fp32 NHWC map `fmap` (the E embedding channels first): seen_sweep() with the probabilistic
+    gate p(k|x) = p(group|x) p(k|group,x) -- a pixel takes its best seen class iff e = margin - weight * (l_S - l_U) > tau, l_G = -log of
+    the best class's softmax probability inside its group at `temperature`, and its best unseen class otherwise; the two candidates are
+    the true in-group argmaxes.  Every tau of `taus` (ascending) in one pass.  target given: hist (G,K,K) int64 += the confusion counts of
+    every tau (allocated as zeros when None).  pred_index given: pred (B,H,W) int64 at taus[pred_index].  want_eff: eff (B,H,W) f32 = e.
+    -> (hist or None, pred or None, eff or None).  ws: as in seen_sweep() (szn_soft_gate_head_tabled)"""
+    import ctypes as C
+    B, h, w, ld = fmap.shape
+    K, E = emb.shape
+    if fmap.dtype != torch.float32 or not fmap.is_contiguous():
+        raise L.SznError("soft_gate: the map must be a contiguous fp32 (B,h,w,C) tensor")
+    dev = fmap.device
+    if margin is None or margin.dtype != torch.float32 or tuple(margin.shape) != (B, H, W) or not margin.is_contiguous() or margin.device != dev:
+        raise L.SznError("soft_gate: margin must be a contiguous fp32 (%d,%d,%d) tensor on %s" % (B, H, W, dev))
+    wgt, temp = gate_params(dict(weight=weight, temperature=temperature))
+    t = seen_sweep_taus(taus)
+    G = int(t.size)
+    if target is None and hist is not None:
+        raise L.SznError("soft_gate: a histogram needs the target")
+    if target is None and pred_index is None and not want_eff:
+        raise L.SznError("soft_gate: nothing to compute (no target for a histogram, no pred_index for a prediction, no eff)")
+    if pred_index is not None and not 0 <= int(pred_index) < G:
+        raise L.SznError("soft_gate: pred_index %r outside [0, %d)" % (pred_index, G))
+    tgt = None
+    if target is not None:
+        tgt = target.to(device=dev, dtype=torch.int64).contiguous()
+        if hist is None:
+            hist = torch.zeros(G, K, K, dtype=torch.int64, device=dev)
+        elif hist.dtype != torch.int64 or tuple(hist.shape) != (G, K, K) or not hist.is_contiguous() or hist.device != dev:
+            raise L.SznError("soft_gate: hist must be a contiguous int64 (%d,%d,%d) tensor on %s" % (G, K, K, dev))
+    pred = torch.empty(B, H, W, dtype=torch.int64, device=dev) if pred_index is not None else None
+    eff = torch.empty(B, H, W, dtype=torch.float32, device=dev) if want_eff else None
+    nbytes = soft_gate_workspace_bytes(stride, fmap, emb, G)
+    if nbytes == 0:
+        raise L.SznError("soft_gate: bad geometry (stride %d, B %d, map %d x %d, E %d, K %d, %d taus)" % (stride, B, h, w, E, K, G))
+    if ws is not None and (ws.buf is None or ws.buf.numel() < nbytes or ws.tables != Workspace.map_key(stride, fmap)
+                           or ws.prep != (ws.buf.data_ptr(), emb.data_ptr(), emb._version, K, E)):
+        raise L.SznError("soft_gate: ws must be the Workspace in which the embedding head last ran on this very map and embedding "
+                         "matrix, %d bytes or more" % nbytes)
+    buf = _scratch(nbytes, dev) if ws is None else ws.buf
+    L.call("szn_soft_gate_head" if ws is None else "szn_soft_gate_head_tabled", stride, B, h, w, E, ld, 0, H, W, _CROP[stride], K,
+           L.ptr(fmap), L.ptr(emb), L.ptr(tgt), L.class_set(unseen), L.ptr(margin), temp, wgt, G, t.ctypes.data_as(C.POINTER(C.c_float)),
+           L.ptr(hist), -1 if pred_index is None else int(pred_index), L.ptr(pred), L.ptr(eff), L.ptr(buf), L.stream_ptr())
+    return hist, pred, eff
 
 
 # ---- self-training: top-p% pseudo labels on the hidden pixels ------------------------------------------------------------------

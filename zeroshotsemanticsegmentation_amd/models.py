@@ -1592,6 +1592,19 @@ class FCN32s(nn.Module):
         the confusion counts of every tau: `hist` accumulated in place when given; a fresh one with a target and no pred_index; None
         with a pred_index and no `hist` (a prediction-only call: no crossing tables, no histogram kernel).  The margin is left in
         self._last_margin."""
+        return self._seen_route_predict(x, embeddings, unseen, taus, None, target, hist, pred_index, loss)
+
+    def seen_gate_predict(self, x, embeddings, unseen, taus, gate, target=None, hist=None, pred_index=None, loss="cos"):
+        """seen_sweep_predict with the soft seen/unseen gate gate = dict(weight=, temperature=) (heads.gate_params): the same forward
+        pass, loss head, margin and workspace reuse, with szn_soft_gate_head in place of szn_seen_sweep_head -- a pixel takes its best
+        seen class iff margin - weight * (l_S - l_U) > tau, l_G = -log of the best class's softmax probability inside its group at
+        `temperature`, and its best unseen class otherwise (the candidates are the true in-group argmaxes).  Same results tuple, the
+        loss bit for bit seen_sweep_predict's; the margin is left in self._last_margin.  (A method of its own: seen_sweep_predict's
+        parameter list is pinned.)"""
+        return self._seen_route_predict(x, embeddings, unseen, taus, heads.gate_params(gate), target, hist, pred_index, loss)
+
+    def _seen_route_predict(self, x, embeddings, unseen, taus, gate, target, hist, pred_index, loss):
+        """seen_sweep_predict (gate None) and seen_gate_predict (gate = (weight, temperature)): one launch sequence, another sweep head"""
         kind = heads.embed_kind(loss)
         with torch.no_grad():
             ctx, stride, fmap = self._head_map(x)
@@ -1610,8 +1623,12 @@ class FCN32s(nn.Module):
                 self._last_margin = heads.seenmask_margin(ctx.coarse, self.n_class, self._engine._images["up.w"], ctx.H, ctx.W)
                 fmap32 = fmap if fmap.dtype == torch.float32 else fmap.to(torch.float32)
                 counted = target if (hist is not None or pred_index is None) else None
-                hist, spred = heads.seen_sweep(stride, fmap32, emb, ctx.H, ctx.W, unseen, self._last_margin, taus, counted, hist, pred_index,
-                                               ws=ws)
+                if gate is None:
+                    hist, spred = heads.seen_sweep(stride, fmap32, emb, ctx.H, ctx.W, unseen, self._last_margin, taus, counted, hist,
+                                                   pred_index, ws=ws)
+                else:
+                    hist, spred, _ = heads.soft_gate(stride, fmap32, emb, ctx.H, ctx.W, unseen, self._last_margin, taus, gate[1], gate[0],
+                                                     counted, hist, pred_index, ws=ws)
                 if pred_index is not None:
                     pred = spred
             self._last_pred = pred

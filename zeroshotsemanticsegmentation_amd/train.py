@@ -26,6 +26,10 @@ Added for this implementation (none change the reference flags):
                        is p(seen) > sigmoid(TAU) (szn_seen_sweep_head; 0 = the plain decision); --seen-sweep LO HI N also writes the
                        metrics of N thresholds between LO and HI, and their harmonic mean of seen and unseen mIoU, to
                        <log_dir>/seen_sweep_log.csv from the same head launch
+  --seen-gate WEIGHT   with -m test_all: the soft seen/unseen gate p(k|x) = p(group|x) p(k|group,x) (szn_soft_gate_head) -- the cut acts on
+                       the margin minus WEIGHT * (log P_U(best unseen) - log P_S(best seen)), the experts' softmaxes over the cosines at
+                       --gate-temperature T (default 0.1, a hyper-parameter default, not a tuned value).  0 = the hard cut, 1 = the
+                       probabilistic rule.  Composes with --seen-threshold / --seen-sweep; the sweep's rows go to seen_gate_log.csv
   -loss sim_ce         similarity cross-entropy: softmax over the seen classes' cosine similarities to the pixel embedding, cross
                        entropy against the label (szn_fused_simce_head; the unseen classes do not compete); --sim-temperature T
                        (default 0.1, a hyper-parameter default, not a tuned value) divides the similarities
@@ -68,7 +72,7 @@ from . import engine as _engine
 from . import models, trainer_fcn, trainer_seenmask
 from .configs import configurations
 from ._lib import CONSE_MAX_TOP
-from .heads import RANK_MARGIN, SIM_TEMPERATURE
+from .heads import GATE_TEMPERATURE, RANK_MARGIN, SIM_TEMPERATURE
 from .optim import FusedAdam, FusedSGD
 from .synthetic_dataset import SyntheticSegmentation
 
@@ -149,6 +153,15 @@ def build_parser():
     p.add_argument('--seen-sweep', type=float, nargs=3, metavar=('LO', 'HI', 'N'), default=None,
                    help="with -m test_all: also evaluates N thresholds (2 to 64) evenly spaced from LO to HI in the same pass of the "
                         "head and appends their metrics and the harmonic mean of seen and unseen mIoU to <log_dir>/seen_sweep_log.csv")
+    p.add_argument('--seen-gate', type=float, default=None, metavar='WEIGHT',
+                   help="with -m test_all: soft seen/unseen gating -- p(class) = p(group) * p(class | group) with p(seen) = "
+                        "sigmoid(margin - TAU) and a softmax over the cosines inside each class group, which cuts the margin minus WEIGHT * "
+                        "(log P_U(best unseen class) - log P_S(best seen class)) at TAU instead of the margin.  0 = the hard cut between "
+                        "the two groups' best classes, 1 = the probabilistic rule, larger values trust the class experts more.  No "
+                        "default.  With --seen-sweep the rows go to <log_dir>/seen_gate_log.csv")
+    p.add_argument('--gate-temperature', type=float, default=None, metavar='T',
+                   help="with --seen-gate: the temperature the cosines are divided by in the two class experts' softmaxes.  Default "
+                        "%g: a hyper-parameter default, not a tuned value.  An error without --seen-gate" % GATE_TEMPERATURE)
     p.add_argument('--sim-temperature', type=float, default=None, metavar='T',
                    help="with -loss sim_ce (softmax over the seen classes' cosine similarities to the pixel embedding, cross entropy "
                         "against the label): the temperature the similarities are divided by.  Default %g: a hyper-parameter default, "
@@ -381,6 +394,29 @@ def check_seen_threshold(threshold, sweep, cfg, calibration=None, calib_sweep=No
         raise Exception("--seen-threshold / --seen-sweep: " + why)
 
 
+def check_seen_gate(weight, temperature, cfg, calibration=None, calib_sweep=None, eval_scales=None, eval_flip=False):
+    """--seen-gate / --gate-temperature -> the Trainer's seen_gate dict, or None without the flags: the temperature belongs to the gate;
+    otherwise check_seen_threshold's rules (trainer_fcn.seen_gate_refused)"""
+    if weight is None:
+        if temperature is not None:
+            raise Exception("--gate-temperature: belongs to --seen-gate, which is off")
+        return None
+    if not (weight == weight and 0 <= weight < float('inf')):
+        raise Exception("--seen-gate: WEIGHT must be finite and >= 0 (got %r)" % (weight,))
+    if temperature is not None and not (temperature == temperature and 0 < temperature < float('inf')):
+        raise Exception("--gate-temperature: T must be finite and > 0 (got %r)" % (temperature,))
+    if calibration is not None or calib_sweep is not None:
+        raise Exception("--seen-gate: not together with --calibration / --calib-sweep (two class-assignment rules)")
+    n_class = 21 if cfg['dataset'] == 'pascal' else 33
+    why = trainer_fcn.seen_gate_refused(bool(cfg['train_unseen'] or cfg['val_unseen']),
+                                        bool(cfg['embed_dim']) and cfg['fcn_loss'] in _EMBED_LOSSES, bool(cfg['forced_unseen']),
+                                        cfg['mode'] == 'test_all', bool(eval_scales or eval_flip), n_class,
+                                        os.environ.get("SZN_VERBOSE_VAL", "0") == "1")
+    if why:
+        raise Exception("--seen-gate: " + why)
+    return dict(weight=weight, temperature=GATE_TEMPERATURE if temperature is None else temperature)
+
+
 def check_calibration(calibration, sweep, cfg, eval_scales=None, eval_flip=False):
     """--calibration / --calib-sweep: unseen classes, an embedding configuration, and none of the other class-assignment rules
     (forced unseen, -m test_all, multi-scale views); more than 256 classes and SZN_VERBOSE_VAL keep the materialised score"""
@@ -536,6 +572,7 @@ def main(argv=None):
     check_eval_views(args.eval_scales, args.eval_flip, cfg)
     check_calibration(args.calibration, args.calib_sweep, cfg, args.eval_scales, args.eval_flip)
     check_seen_threshold(args.seen_threshold, args.seen_sweep, cfg, args.calibration, args.calib_sweep, args.eval_scales, args.eval_flip)
+    seen_gate = check_seen_gate(args.seen_gate, args.gate_temperature, cfg, args.calibration, args.calib_sweep, args.eval_scales, args.eval_flip)
     conse = check_conse(args.conse, args.conse_dim, args.conse_gamma, args.conse_sweep, cfg, args.eval_scales, args.eval_flip)
     check_pseudo(args.pseudo_label, args.pseudo_gamma, args.pseudo_floor, args.pseudo_start_epoch, args.hide_unseen, cfg)
     check_ohem(args.ohem, args.ohem_thresh, args.ohem_start_epoch, cfg)
@@ -675,7 +712,8 @@ def main(argv=None):
         tb_writer=tb_writer, unseen=all_unseen, val_unseen=cfg['val_unseen'], label_names=label_names,
         forced_unseen=cfg['forced_unseen'], precision=precision, rank=rank, visualize=args.viz, augment=augment,
         proto=proto, support_loader=support_loader,
-        seen_threshold=args.seen_threshold, seen_sweep=seen_sweep_values(args.seen_sweep), sim_temperature=args.sim_temperature,
+        seen_threshold=args.seen_threshold, seen_sweep=seen_sweep_values(args.seen_sweep), seen_gate=seen_gate,
+        sim_temperature=args.sim_temperature,
         rank_margin=args.rank_margin, rank_hardest=args.rank_hardest,
         pseudo=None if args.pseudo_label is None else dict(keep=args.pseudo_label, gamma=args.pseudo_gamma,
                                                            conf_floor=-2.0 if args.pseudo_floor is None else args.pseudo_floor),

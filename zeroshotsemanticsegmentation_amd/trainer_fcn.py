@@ -85,6 +85,13 @@ def seen_threshold_refused(has_unseen, embed_cfg, forced_unseen, test_all, eval_
     return None
 
 
+def seen_gate_refused(has_unseen, embed_cfg, forced_unseen, test_all, eval_views, n_class, verbose_val=False):
+    """why a configuration cannot run the soft seen/unseen gate (seen_gate=, train.py --seen-gate), or None: the gate replaces the cut on
+    the seen-mask margin by a per-pixel one inside the same sweep head, so seen_threshold_refused's reasons are its reasons"""
+    why = seen_threshold_refused(has_unseen, embed_cfg, forced_unseen, test_all, eval_views, n_class, verbose_val)
+    return None if why is None else why.replace("a seen-mask threshold", "the soft seen/unseen gate")
+
+
 def conse_refused(has_unseen, softmax_cfg, forced_unseen, test_all, eval_views, tuned):
     """why a configuration cannot run ConSE zero-shot inference (conse= / conse_sweep=, train.py --conse / --conse-sweep), or None: ConSE
     mixes class embeddings with the softmax network's seen-class probabilities, so it needs unseen classes and the softmax
@@ -190,7 +197,7 @@ class Trainer(object):
     def __init__(self, cuda, model, optimizer, train_loader, val_loader, log_dir, dataset, max_epoch, tb_writer,
                  pixel_embeddings=None, loss_func=None, unseen=None, val_unseen=None, label_names=None,
                  forced_unseen=False, embed_arr=None, precision=torch.float32, fused_step=True, rank=0, visualize=0, augment=None,
-                 seen_threshold=None, seen_sweep=None, proto=None, support_loader=None, conse=None, conse_sweep=None,
+                 seen_threshold=None, seen_sweep=None, proto=None, support_loader=None, conse=None, conse_sweep=None, seen_gate=None,
                  sim_temperature=None, rank_margin=None, rank_hardest=False, bias_loss=None, bias_start_epoch=0, pseudo=None, pseudo_start_epoch=0, ohem=None, ohem_start_epoch=0, calibration=None,
                  calib_sweep=None, eval_scales=None, eval_flip=False):
         if not cuda:
@@ -265,6 +272,13 @@ class Trainer(object):
             self.seen_sweep = seen_sweep_taus(seen_sweep)
         self.best_seen_tau = None
         self.best_seen_harmonic_mean_iu = None
+        # the soft seen/unseen gate (models.seen_gate_predict), validate(True) only: seen_gate = dict(weight=, temperature=) -- the cut
+        # acts on margin - weight * (l_S - l_U), the margin corrected per pixel by how sure the two class experts are, instead of on the
+        # margin; seen_threshold / seen_sweep keep their meaning (tau is a cut on that value), the sweep's rows go to seen_gate_log.csv
+        self.seen_gate = None
+        if seen_gate is not None:
+            from .heads import gate_params
+            self.seen_gate = dict(zip(("weight", "temperature"), gate_params(seen_gate)))
 
         self.epoch = 0
         self.iteration = 0
@@ -294,6 +308,12 @@ class Trainer(object):
                 raise SznError(why)
             if self.seen_threshold is not None and not np.isfinite(self.seen_threshold):
                 raise SznError("seen_threshold: tau must be finite (got %r)" % (seen_threshold,))
+        if self.seen_gate is not None:
+            from ._lib import SznError
+            why = seen_gate_refused(bool(self.unseen), bool(pixel_embeddings) and loss_func in _EMBED_LOSSES, forced_unseen,
+                                    True, bool(self.eval_scales), self.n_class, self.verbose_val)
+            if why:
+                raise SznError(why)
 
         # ConSE zero-shot inference for the softmax configuration (models.conse_predict): conse = dict(top=, dim=, gamma=) -- validation
         # mixes the dataset's `dim`-wide class embeddings of the top `top` seen classes with their softmax probabilities and names the
@@ -703,6 +723,11 @@ class Trainer(object):
                 loss, pred = self.model.ms_predict(data, self.embeddings, self.eval_scales, self.eval_flip, target, unseen=self.unseen,
                                                    group='seenmask' if szn else 'target', loss=self.loss_func)
                 return None, loss, pred, target
+            if szn and self.seen_gate is not None:
+                # the soft gate: the same route with szn_soft_gate_head; without a threshold the reported prediction is tau = 0's
+                loss, pred, _ = self.model.seen_gate_predict(data, self.embeddings, self.unseen, self._seen_taus(), self.seen_gate, target,
+                                                             hist=self._seen_hist, pred_index=self._seen_index(), loss=self.loss_func)
+                return None, loss, pred, target
             if szn and (self.seen_threshold is not None or self._seen_hist is not None):
                 # the seen-mask decision at a threshold: one forward pass; the sweep's histogram and the reported prediction come from
                 # one szn_seen_sweep_head launch on the map the loss used
@@ -713,7 +738,7 @@ class Trainer(object):
                        "sim_ce": self.model.szn_predict_sim_ce, "rank": self.model.szn_predict_rank}[self.loss_func]
             loss, pred = predict(data, self.embeddings, self.unseen, target, group='seenmask' if szn else 'target')
             return None, loss, pred, target
-        if szn and (self.seen_threshold is not None or self._seen_hist is not None):
+        if szn and (self.seen_threshold is not None or self._seen_hist is not None or self.seen_gate is not None):
             from ._lib import SznError
             raise SznError("a seen-mask threshold runs on the fused head: dense target embeddings keep the materialised score")
         if self.eval_scales and not self._ms_warned:
@@ -776,20 +801,21 @@ class Trainer(object):
             return None
         return 0 if self._calib_hist is None else int(np.searchsorted(self._calib_all, np.float32(self.calibration)))
 
-    def _sweep_report(self, hist_all, all_vals, sweep, fname, column):
+    def _sweep_report(self, hist_all, all_vals, sweep, fname, column, extra=()):
         """one <fname> row per value of the sweep (hist_all follows all_vals) -> (value, harmonic mean) of the largest harmonic mean, or
-        None; ties go to the value nearest 0 (a NaN never wins)"""
+        None; ties go to the value nearest 0 (a NaN never wins).  extra: (column, value) pairs appended to every row"""
         keep = np.searchsorted(all_vals, sweep)
         path = osp.join(self.log_dir, fname)
         if not osp.exists(path):
             with open(path, 'w') as f:
-                f.write('epoch,iteration,%s,val/pxl_acc,val/mean_iu,val/seen/mean_iu,val/unseen/mean_iu,val/harmonic_mean_iu\n' % column)
+                f.write(','.join(['epoch,iteration,%s,val/pxl_acc,val/mean_iu,val/seen/mean_iu,val/unseen/mean_iu,val/harmonic_mean_iu' % column]
+                                 + [k for k, _ in extra]) + '\n')
         best = None
         with open(path, 'a') as f:
             for val, g in zip(sweep, keep):
                 m, ms, mu = utils.calib_rows(hist_all[g], self.n_class, self.val_unseen)
                 hm = utils.harmonic_mean_iu(ms, mu)
-                f.write(','.join(map(str, [self.epoch, self.iteration, float(val), m[0], m[2], ms[2], mu[2], hm])) + '\n')
+                f.write(','.join(map(str, [self.epoch, self.iteration, float(val), m[0], m[2], ms[2], mu[2], hm] + [v for _, v in extra])) + '\n')
                 if not np.isnan(hm) and (best is None or hm > best[1] or (hm == best[1] and abs(float(val)) < abs(best[0]))):
                     best = (float(val), hm)
         return best
@@ -832,7 +858,7 @@ class Trainer(object):
 
     def _seen_taus(self):
         if self._seen_hist is None:
-            return [self.seen_threshold]
+            return [0.0 if self.seen_threshold is None else self.seen_threshold]      # (None: the gate alone)
         return self._seen_all
 
     def _seen_index(self):
@@ -841,6 +867,8 @@ class Trainer(object):
 
     def _seen_report(self, hist_all):
         """rank 0, once per validate(True): one seen_sweep_log.csv row per tau of the sweep, and the tau with the largest harmonic mean"""
+        if self.seen_gate is not None:
+            return self._gate_report(hist_all)
         best = self._sweep_report(hist_all, self._seen_all, self.seen_sweep, 'seen_sweep_log.csv', 'tau')
         if best is not None:
             self.best_seen_tau, self.best_seen_harmonic_mean_iu = best
@@ -849,6 +877,19 @@ class Trainer(object):
             self.tb_writer.add_scalar('fcn/val/seen_sweep/best_harmonic_mean_iu', best[1], self.epoch)
         else:
             print('seen-mask threshold: no tau has a harmonic mean IU (the validation set holds no seen or no unseen pixels)')
+
+    def _gate_report(self, hist_all):
+        """the same with the soft gate on: the rows go to seen_gate_log.csv, which also names the gate's weight and temperature"""
+        g = self.seen_gate
+        best = self._sweep_report(hist_all, self._seen_all, self.seen_sweep, 'seen_gate_log.csv', 'tau',
+                                  (('weight', g["weight"]), ('temperature', g["temperature"])))
+        if best is not None:
+            self.best_seen_tau, self.best_seen_harmonic_mean_iu = best
+            print('soft gate (weight %g, temperature %g): best tau %g, harmonic mean IU %.3f' % ((g["weight"], g["temperature"]) + best))
+            self.tb_writer.add_scalar('fcn/val/seen_gate/best_tau', best[0], self.epoch)
+            self.tb_writer.add_scalar('fcn/val/seen_gate/best_harmonic_mean_iu', best[1], self.epoch)
+        else:
+            print('soft gate: no tau has a harmonic mean IU (the validation set holds no seen or no unseen pixels)')
 
     def pool_prototypes(self):
         """the prototypes of self.unseen pooled over the support loader with the current weights: one inference forward per support
@@ -942,6 +983,9 @@ class Trainer(object):
         if not both_fcn_and_seenmask and (self.seen_threshold is not None or self.seen_sweep is not None):
             from ._lib import SznError
             raise SznError(seen_threshold_refused(True, True, False, False, False, self.n_class))
+        if not both_fcn_and_seenmask and self.seen_gate is not None:
+            from ._lib import SznError
+            raise SznError(seen_gate_refused(True, True, False, False, False, self.n_class))
         if both_fcn_and_seenmask and self.seen_sweep is not None:
             extra = [np.float32(0.0 if self.seen_threshold is None else self.seen_threshold)]
             self._seen_all = np.unique(np.concatenate([self.seen_sweep, np.asarray(extra, dtype=np.float32)]))

@@ -532,6 +532,39 @@ def conse_infer(score, embeddings, unseen, top_t, gamma=0.0, target=None):
     return torch.where(torch.isnan(m), torch.zeros_like(pred), pred)
 
 
+def soft_gate_infer(score, seen_mask_score, embeddings, unseen, tau, temperature, weight):
+    """the soft seen/unseen gate on a materialised (B,E,H,W) embedding score and (B,2,H,W) seen-mask score with torch operations: the
+    referee of szn_soft_gate_head (heads.soft_gate, FCN32s.seen_gate_predict).  Runs on the score's device, CPU included.  Per pixel:
+    the cosine of the score with every row of `embeddings` (K,E) (a zero-norm pixel: NaN); a / b = the first best seen / unseen class;
+    l_S = log sum_{k seen} exp((cos_k - cos_a) / temperature) = -log P_S(a), l_U likewise; e = (s1 - s0) - weight * (l_S - l_U).
+    a where e > tau, else b (a NaN margin: b); class 0 where l_S - l_U is NaN.  -> int64 (B,H,W) tensor on the score's device."""
+    score = _data(score).detach().float()
+    dev = score.device
+    sm = _data(seen_mask_score).detach().to(device=dev, dtype=torch.float32)
+    emb = _data(embeddings).to(device=dev, dtype=torch.float32)
+    K = emb.shape[0]
+    if emb.dim() != 2 or emb.shape[1] != score.shape[1]:
+        raise L.SznError("soft_gate_infer: embeddings must be (K,%d), got %s" % (score.shape[1], tuple(emb.shape)))
+    uns = sorted(set(int(k) for k in unseen))
+    if not uns or len(uns) >= K or uns[0] < 0 or uns[-1] >= K:
+        raise L.SznError("soft_gate_infer: the unseen classes must be a non-empty proper subset of range(%d)" % K)
+    t, w = float(np.float32(temperature)), float(np.float32(weight))
+    if not (np.isfinite(t) and t > 0 and np.isfinite(w) and w >= 0):
+        raise L.SznError("soft_gate_infer: temperature must be finite and > 0, weight finite and >= 0")
+    is_unseen = torch.zeros(K, dtype=torch.bool, device=dev)
+    is_unseen[uns] = True
+    seen_idx, unseen_idx = torch.nonzero(~is_unseen)[:, 0], torch.nonzero(is_unseen)[:, 0]
+    sim = torch.einsum('behw,ke->bkhw', score, emb) / (score.norm(dim=1, keepdim=True) * emb.norm(dim=1).view(1, K, 1, 1))
+    a, va = _first_max(sim, seen_idx)
+    b, vb = _first_max(sim, unseen_idx)
+    ls = torch.log(torch.exp((sim[:, seen_idx] - va.unsqueeze(1)) / t).sum(dim=1))
+    lu = torch.log(torch.exp((sim[:, unseen_idx] - vb.unsqueeze(1)) / t).sum(dim=1))
+    d = ls - lu
+    e = (sm[:, 1] - sm[:, 0]) - w * d
+    pred = torch.where(e > float(np.float32(tau)), a, b)
+    return torch.where(torch.isnan(d), torch.zeros_like(pred), pred)
+
+
 def _fast_hist(label_true, label_pred, n_class, target='all', unseen=None):
     """host restatement of utils.py:104-119 for numpy label maps (validation logs on the host)"""
     label_true = np.asarray(label_true)
