@@ -939,6 +939,55 @@ int szn_soft_gate_head_tabled(int stride, int B, int h, int w, int E, int ldc, i
                               int n_taus, const float* taus, int64_t* hist, int pred_index, int64_t* pred, float* eff,
                               void* workspace, szn_stream_t stream);
 
+/* ---- hubness correction for zero-shot inference ---------------------------------------------------------------------------------------
+ * A few class vectors end up near a large share of all projected pixels and take their predictions (hubness: Radovanovic et al. 2010; Dinu
+ * et al. 2015).  The label-free answers act per class: centering subtracts from each class's similarity its mean similarity to the queries
+ * (Suzuki et al. 2013), standardising divides by the spread as well.  The queries are the pixels of the image being segmented.
+ *
+ * szn_hub_stats writes per image and class a pair (scale, shift): table [B][K][2] f32 (device).  coarse, embed, stride (32 | 8), crop, ldc and
+ * c0 are szn_fused_head_strided's.  A pixel of image b counts when it lies inside H x W, target is NULL or target[pix] != SZN_PAD_LABEL, and
+ * its norm sn is finite and > 0; unlabelled (-1) and hidden pixels count: the statistics are label-free.  For a counted pixel and class k:
+ *   sim[k] = szn_calib_head's similarity, the same operations in the same order;
+ *   q      = clamp((long long)rintf(sim[k] * 1048576.f), -2^21, 2^21);   S1[b][k] += q;  S2[b][k] += q * q;  n[b] += 1 once per pixel,
+ * all int64: any accumulation order gives the same bits, two calls are bit-equal, and a batch's composition changes nothing.  A second
+ * kernel (one thread per (b, k), double arithmetic) forms mean = S1 / (n 2^20), sd = sqrt(max(S2 / (n 2^40) - mean^2, 0)) and the row
+ *   mode SZN_HUB_MEAN:    scale = 1,                        shift = (float)(beta * mean);
+ *   mode SZN_HUB_ZSCORE:  f = max(sd, min_sd),  scale = (float)(1 / f),  shift = (float)(beta * mean / f);
+ *   n[b] == 0:            the identity row (1, 0).
+ * beta = 1 is the textbook form, beta = 0 in mean mode the identity.  sums [B][K][2] int64 (S1, S2) and counts [B] int64 (device, or NULL)
+ * are inspection copies, written, not accumulated.  No host synchronisation; the call can be captured into a graph.
+ * Pixel pass: classes outermost, each thread adds its own pixels for class k, a wave reduction, one LDS slot per wave, class and moment, and
+ * one 64-bit integer atomic add per block (stride 8: per image present in the block), class and moment.
+ * szn_last_kernel(): hub_table_kernel (szn_prev_kernel(): hub_stats_cell_kernel at stride 32, hub_stats_cell_tab_kernel at stride 8).
+ * workspace: szn_hub_stats_workspace_bytes (0 for sizes the call refuses), 16-byte aligned: the fused head's (prepared embedding image,
+ * stride-8 position tables), then S1 / S2 and n.
+ * SZN_ERR_ARG, before any launch: everything szn_fused_head_strided refuses (stride not 8 or 32, a size that is not positive,
+ * K > SZN_MAX_CLASSES, ldc < c0 + E, the crop window, NULL coarse / embed / workspace, the workspace alignment); a mode other than the two; beta
+ * not finite or < 0; min_sd not finite or <= 0; NULL table; H * W > SZN_HUB_MAX_PIXELS (2^22: S2 <= 2^42 per pixel stays inside int64).
+ *
+ * szn_hub_head is szn_calib_head with one change: the value that enters the two running bests is
+ *   adj[k] = fmaf(sim[k], table[b][k][0], -table[b][k][1])
+ * (k is uniform per wave and b per block or wave: two scalar loads per class).  Everything else is szn_calib_head's: the first index wins, a
+ * strictly larger value replaces, m = va - vb, pred = 0 if m is NaN, else a if m > gamma or (m == gamma and a < b), else b; the keys into the
+ * crossing tables, calib_hist_kernel, pred_index, the workspace layout (szn_hub_head_workspace_bytes == szn_calib_head_workspace_bytes) and
+ * the refusals, plus a NULL table.  With the identity table fmaf(sim, 1, -0.0f) == sim bit for bit, so pred and hist equal szn_calib_head's
+ * exactly.  The table is a plain device input [B][K][2] f32: a caller may pass one of its own (dataset-level statistics, class priors as
+ * shifts) instead of szn_hub_stats'.  A NaN or infinite entry makes that class's adj NaN or infinite for every pixel of the image.
+ * szn_last_kernel(): calib_hist_kernel when hist is given (szn_prev_kernel(): the pixel kernel), else the pixel kernel --
+ * hub_cell_kernel (stride 32) or hub_cell_tab_kernel (stride 8).                                                                          */
+#define SZN_HUB_MEAN 0
+#define SZN_HUB_ZSCORE 1
+#define SZN_HUB_MAX_PIXELS (1 << 22)
+size_t szn_hub_stats_workspace_bytes(int stride, int B, int h, int w, int E, int K);
+int szn_hub_stats(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                  const float* coarse, const float* embed, const int64_t* target, int mode, float beta, float min_sd,
+                  float* table, int64_t* sums, int64_t* counts, void* workspace, szn_stream_t stream);
+size_t szn_hub_head_workspace_bytes(int stride, int B, int h, int w, int E, int K, int n_gammas);
+int szn_hub_head(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                 const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
+                 const float* table, int n_gammas, const float* gammas, int64_t* hist, int pred_index, int64_t* pred,
+                 void* workspace, szn_stream_t stream);
+
 /* ---- ConSE zero-shot inference for the softmax FCN ---------------------------------------------------------------------------------
  * szn_conse_head: convex combination of semantic embeddings (Norouzi et al., ICLR 2014) per pixel, from the logit map of a network that
  * was trained on the seen classes with szn_fused_ce_head, with the seen-class penalty gamma of szn_calib_head swept over n_gammas values

@@ -77,6 +77,7 @@ def class_set(classes):
 
 MS_MAX_VIEWS = 16           # SZN_MS_MAX_VIEWS
 CALIB_MAX_GAMMAS = 64       # SZN_CALIB_MAX_GAMMAS
+HUB_MODES = {"mean": 0, "zscore": 1}    # SZN_HUB_MEAN, SZN_HUB_ZSCORE
 SEEN_SWEEP_MAX_TAUS = 64    # SZN_SEEN_SWEEP_MAX_TAUS
 CONSE_MAX_TOP = 16          # SZN_CONSE_MAX_TOP
 PSEUDO_BINS = 1024          # SZN_PSEUDO_BINS
@@ -214,6 +215,10 @@ SIGNATURES = {
     "szn_soft_gate_head_workspace_bytes": (_SZ, [_I] * 7),
     "szn_soft_gate_head": (_I, [_I] * 11 + [_P, _P, _P, _CS, _P, _F, _F, _I, _FP, _P, _I, _P, _P, _P, _P]),
     "szn_soft_gate_head_tabled": (_I, [_I] * 11 + [_P, _P, _P, _CS, _P, _F, _F, _I, _FP, _P, _I, _P, _P, _P, _P]),
+    "szn_hub_stats_workspace_bytes": (_SZ, [_I] * 6),
+    "szn_hub_stats": (_I, [_I] * 11 + [_P, _P, _P, _I, _F, _F, _P, _P, _P, _P, _P]),
+    "szn_hub_head_workspace_bytes": (_SZ, [_I] * 7),
+    "szn_hub_head": (_I, [_I] * 11 + [_P, _P, _P, _CS, _P, _I, _FP, _P, _I, _P, _P, _P]),
     "szn_conse_head_workspace_bytes": (_SZ, [_I] * 7),
     "szn_conse_head": (_I, [_I] * 11 + [_P, _P, _P, _CS, _I, _I, _I, _FP, _P, _I, _P, _P, _P]),
     "szn_pseudo_head_workspace_bytes": (_SZ, [_I] * 8),

@@ -27,6 +27,9 @@
 //                        head's two answers per pixel (fh_group_bests) and the seen-mask margin as the switch; then calib_hist_kernel
 //   gate_cell_kernel / gate_cell_tab_kernel   szn_soft_gate_head (soft seen/unseen gating): the sweep kernels with the true in-group bests and
 //                        an online log-sum-exp per group (fh_gate_bests); the switch is margin - weight * (l_S - l_U); then calib_hist_kernel
+//   hub_stats_cell_kernel / hub_stats_cell_tab_kernel / hub_table_kernel   szn_hub_stats (hubness correction): the cells' G and Q, exact int64
+//                        moments of every class's similarity per image, then the (scale, shift) table
+//   hub_cell_kernel / hub_cell_tab_kernel   szn_hub_head: the calibrated kernels on fmaf(sim, scale, -shift); then calib_hist_kernel
 //   pseudo_cell_kernel / pseudo_cell_tab_kernel / pseudo_thr_kernel / pseudo_relabel_kernel   szn_pseudo_head (self-training): the same G, Q
 //                        and fh_two_best on the pixels labelled cand_label, a per-class confidence histogram, thresholds, the relabelled target
 //   ohem_cell_kernel / ohem_cell_tab_kernel / ohem_cut_kernel / ohem_relabel_kernel   szn_ohem_head (hard-pixel mining), in launch order: the
@@ -142,14 +145,26 @@ __device__ __forceinline__ int fh_argmax(const FhArgs& a, const float (&wt)[4], 
 // The same trip through the classes with two running bests (szn_calib_head): ia / va over the classes outside `unseen`, ib / vb over
 // its members, each the first index holding its group's maximum.  The group bit is wave-uniform like in_group above: a scalar select,
 // no divergence, no second pass.  Both groups are non-empty (checked on the host).
+// HUB (szn_hub_head): the value that enters the running bests is fmaf(sim, scale_k, -shift_k).  T [K] in LDS holds (en[k], scale_k, shift_k, 0)
+// of the pixel's image (hub_stage): one 16-byte LDS read per class next to G's, in place of the scalar load of en[k] -- as two more scalar
+// loads per class the table cost the stride-8 head 49 % (each is a wait of its own in a loop the compiler does not pipeline).
 struct FhTwoBest { int ia, ib; float va, vb; };
-template <int KP>
+template <int KP, bool HUB = false>
 __device__ __forceinline__ FhTwoBest fh_two_best(const FhArgs& a, const float (&wt)[4], const float* G, float sn,
-                                                 const float* __restrict__ en) {
+                                                 const float* __restrict__ en, const float4* T = nullptr) {
     FhTwoBest r = {-1, -1, 0.f, 0.f};
     for (int k = 0; k < a.K; ++k) {
         const bool u = (bool)((class_word(a.unseen, k >> 6) >> (k & 63)) & 1ull);
-        const float sim = fh_sim<KP>(wt, G, sn, en, k);
+        float sim;
+        if constexpr (HUB) {
+            const float4 t = T[k];
+            float d = 0.f;
+#pragma unroll
+            for (int tp = 0; tp < 4; ++tp) d = fmaf(wt[tp], G[tp * KP + k], d);
+            sim = fmaf(d / (sn * t.x), t.y, -t.z);                  // fh_sim's operations on the staged en[k], then the correction
+        } else {
+            sim = fh_sim<KP>(wt, G, sn, en, k);
+        }
         const bool first = u ? r.ib < 0 : r.ia < 0;
         const bool take = first || sim > (u ? r.vb : r.va);
         if (take && u) { r.vb = sim; r.ib = k; }
@@ -1078,15 +1093,16 @@ __global__ __launch_bounds__(256) void fh_gather_kernel(const float* __restrict_
 
 // Pixel (ty, tx) of cell (I, J) of image b: the prediction at gammas[pred_index] (where wanted) and the pixel's key
 // t | a << 8 | b << 16 | bin << 24, or -1 where it is not counted (no histogram, outside the image, label outside [0, K))
-template <int KP, int S>
+// HUB: szn_hub_head's hubness-corrected similarities (fh_two_best), T = the image's staged rows in LDS; nothing else differs
+template <int KP, int S, bool HUB = false>
 __device__ __forceinline__ int calib_pixel(const FhArgs& a, const CalArgs& c, int b, int I, int J, int ty, int tx, bool live,
-                                           const float* G, const float* Q, const float* __restrict__ en) {
+                                           const float* G, const float* Q, const float* __restrict__ en, const float4* T = nullptr) {
     const int y = S * I + ty - a.crop, x = S * J + tx - a.crop;
     if (!(live && y >= 0 && y < a.H && x >= 0 && x < a.W)) return -1;
     float wt[4];
     cell_weights<S>(ty, tx, wt);
     const float sn = sqrtf(fh_ss(wt, Q));
-    FhTwoBest r = fh_two_best<KP>(a, wt, G, sn, en);
+    FhTwoBest r = fh_two_best<KP, HUB>(a, wt, G, sn, en, T);
     const float m = r.va - r.vb;
     int bin = 0;
     if (m != m) { r.ia = 0; r.ib = 0; bin = c.n; }        // NaN: class 0 at every gamma
@@ -1285,22 +1301,313 @@ __global__ __launch_bounds__(256) void gate_cell_tab_kernel(FhArgs a, CalArgs c,
     });
 }
 
-// gate: szn_soft_gate_head's pixel kernels; else margin == nullptr: szn_calib_head's; else szn_seen_sweep_head's -- same grids and LDS.
+// ---- hubness correction (szn_hub_stats, szn_hub_head; include/szn.h) --------------------------------------------------------------
+// szn_hub_head's pixel kernels: the calibrated head's with calib_pixel<HUB>.  hub_stage: (en[k], scale, shift, 0) of image b's classes
+// i0, i0 + step, ... into T [K] (LDS); the walks synchronise before the first pixel reads it
+template <int KP>
+__device__ __forceinline__ void hub_stage(const FhArgs& a, const float* __restrict__ table, int b, int i0, int step, float4* T) {
+    const float* en = a.ws_f + (size_t)a.E * KP;
+    const float* tb = table + (size_t)b * a.K * 2;
+    for (int k = i0; k < a.K; k += step) T[k] = make_float4(en[k], tb[2 * k], tb[2 * k + 1], 0.f);
+}
+
+template <int KP>
+__global__ __launch_bounds__(256) void hub_cell_kernel(FhArgs a, CalArgs c, const float* __restrict__ table) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float4* T = (float4*)(sm + fh_lds(a.E, KP, false).Q + 16);            // behind Ct | G | Q: 16 (E + KP + 4) bytes in, 16-byte aligned
+    hub_stage<KP>(a, table, blockIdx.x / ((a.h + 1) * (a.w + 1)), threadIdx.x, 256, T);
+    calib_cell_walk<KP>(a, c, sm, [&](int b, int I, int J, int ty, int tx, bool live, const float* G, const float* Q, const float* en) {
+        return calib_pixel<KP, 32, true>(a, c, b, I, J, ty, tx, live, G, Q, en, T);
+    });
+}
+
+template <int KP>
+__global__ __launch_bounds__(256) void hub_cell_tab_kernel(FhArgs a, CalArgs c, const float* __restrict__ table,
+                                                           const float* __restrict__ D, const float* __restrict__ N) {
+    __shared__ float Gs[4 * 4 * KP];
+    __shared__ float Qs[4 * 16];
+    __shared__ float4 Ts[4 * KP];                                         // one image's rows per wave (calib_cell_tab_walk's cell of the wave)
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long cells = (long)(a.h + 1) * (a.w + 1), cid = (long)blockIdx.x * 4 + wave;
+    float4* T = Ts + wave * KP;
+    hub_stage<KP>(a, table, cid < a.B * cells ? (int)(cid / cells) : 0, threadIdx.x & 63, 64, T);
+    calib_cell_tab_walk<KP>(a, c, D, N, Gs, Qs, [&](int b, int I, int J, int ty, int tx, bool live, const float* G, const float* Q, const float* en) {
+        return calib_pixel<KP, 8, true>(a, c, b, I, J, ty, tx, live, G, Q, en, T);
+    });
+}
+
+// szn_hub_stats, pass 1: S[b][k] = (sum q, sum q^2) over the counted pixels of image b, q = the similarity in units of 2^-20, and n[b] = their
+// number, all int64 and zeroed by the call.  Integers: any order of accumulation gives the same bits.  Classes outermost, eight at a time, so
+// a thread holds 24 partial sums, not 2 K: each thread adds its own pixels of the cell for the eight classes, the wave reduces them
+// (wave_sum8), one LDS slot per wave, class and moment, and after the loop one 64-bit integer atomic add per block (stride 8: per image
+// present in the block), class and moment.  Inside a wave everything fits 32 bits: |q| <= 2^21 and at most 256 pixels per wave give
+// |sum q| <= 2^29, and q^2 <= 2^42 travels as its low 20 bits (sum < 2^28) and the rest (sum <= 2^30), put together in 64 bits at the slot.
+// SZN_HUB_NO_ACCUM (tools/bench_hub.py builds a second library with it): the walk and the similarities alone, for timing what the
+// quantisation, the reductions and the atomics cost; the sums stay zero.
+__device__ __forceinline__ long long wave_sum_ll(long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// The wave's totals of v[0..7] in 10 exchanges instead of 48: three halving steps hand each lane the values its partner keeps (lanes 32, 16,
+// 8 apart), three plain steps finish the one value left.  Afterwards every lane holds the total of v[hub_slot(lane)].
+__device__ __forceinline__ int wave_sum8(const int (&v)[8], int lane) {
+    const bool h5 = lane & 32, h4 = lane & 16, h3 = lane & 8;
+    int x[4], y[2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) x[i] = (h5 ? v[4 + i] : v[i]) + __shfl_xor(h5 ? v[i] : v[4 + i], 32, 64);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) y[i] = (h4 ? x[2 + i] : x[i]) + __shfl_xor(h4 ? x[i] : x[2 + i], 16, 64);
+    int z = (h3 ? y[1] : y[0]) + __shfl_xor(h3 ? y[0] : y[1], 8, 64);
+#pragma unroll
+    for (int o = 4; o > 0; o >>= 1) z += __shfl_xor(z, o, 64);
+    return z;
+}
+__device__ __forceinline__ int hub_slot(int lane) { return ((lane >> 5) & 1) * 4 + ((lane >> 4) & 1) * 2 + ((lane >> 3) & 1); }
+// eight classes' partial sums of a lane (s1 = sum q, lo / hi = sum of the low 20 bits / the rest of q^2) -> the wave's totals into the LDS
+// slots red [KP][2] of the wave, classes k0 .. k0 + 7 below K
+__device__ __forceinline__ void hub_reduce8(const int (&s1)[8], const int (&lo)[8], const int (&hi)[8], int k0, int K, int lane,
+                                            long long* red) {
+    const int t1 = wave_sum8(s1, lane), tl = wave_sum8(lo, lane), th = wave_sum8(hi, lane);
+    const int k = k0 + hub_slot(lane);
+    if ((lane & 7) == 0 && k < K) {
+        red[k * 2] = t1;
+        red[k * 2 + 1] = ((long long)th << 20) + tl;
+    }
+}
+__device__ __forceinline__ void hub_add(long long q, int& s1, int& lo, int& hi) {
+    const unsigned long long q2 = (unsigned long long)(q * q);
+    s1 += (int)q;
+    lo += (int)(q2 & 0xfffffull);
+    hi += (int)(q2 >> 20);
+}
+__device__ __forceinline__ long long hub_q(float sim) {
+    const float f = fminf(fmaxf(rintf(sim * 1048576.f), -2097152.f), 2097152.f);      // whole numbers: the clamp commutes with the conversion
+    return (long long)f;
+}
+// Pixel (ty, tx) of cell (I, J) of image b: does it count (inside H x W, not padding, a finite norm > 0)?  Its weights and norm.
+template <int S>
+__device__ __forceinline__ bool hub_counted(const FhArgs& a, int b, int I, int J, int ty, int tx, bool live, const float* Q,
+                                            float (&wt)[4], float& sn) {
+    const int y = S * I + ty - a.crop, x = S * J + tx - a.crop;
+    cell_weights<S>(ty, tx, wt);
+    sn = sqrtf(fh_ss(wt, Q));
+    if (!(live && y >= 0 && y < a.H && x >= 0 && x < a.W)) return false;
+    if (a.target && a.target[((size_t)b * a.H + y) * a.W + x] == SZN_PAD_LABEL) return false;
+    return sn > 0.f && sn < INFINITY;
+}
+
+template <int KP>
+__global__ __launch_bounds__(256) void hub_stats_cell_kernel(FhArgs a, unsigned long long* __restrict__ Ssum,
+                                                             unsigned long long* __restrict__ Ncnt) {    // stride 32: one block per (image, cell)
+    constexpr int S = 32;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const FhLds L = fh_lds(a.E, KP, false);
+    float* Ct = sm + L.Ct;
+    float* G = sm + L.G;
+    float* Q = sm + L.Q;
+    long long* red = (long long*)(sm + L.Q + 16);            // [4 waves][KP][2], then [4] counts (L.Q + 16 is even: 8-byte aligned)
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int cells_w = a.w + 1, cells = (a.h + 1) * cells_w;
+    const int b = blockIdx.x / cells, cell = blockIdx.x % cells;
+    const int I = cell / cells_w, J = cell % cells_w;
+    const float* embT = a.ws_f;
+    const float* en = a.ws_f + (size_t)a.E * KP;
+    fh_load_taps(a, b, I, J, tid, Ct);
+    __syncthreads();
+    fh_build_GQ<KP>(a, embT, Ct, lane, wave, G, Q);
+    __syncthreads();
+    float wt[4][4], sn[4];
+    bool cnt[4];
+    int mine = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int q = tid + 256 * j;
+        cnt[j] = hub_counted<S>(a, b, I, J, q / S, q % S, true, Q, wt[j], sn[j]);
+        mine += cnt[j] ? 1 : 0;
+    }
+#ifdef SZN_HUB_NO_ACCUM
+    float sink = 0.f;
+    for (int k = 0; k < a.K; ++k)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) sink = fmaxf(sink, cnt[j] ? fh_sim<KP>(wt[j], G, sn[j], en, k) : 0.f);
+    if (sink == 123456.f) Ncnt[b] = (unsigned long long)mine;      // never true (|sim| <= 1): keeps the similarities alive
+#else
+    for (int k0 = 0; k0 < a.K; k0 += 8) {
+        int s1[8], lo[8], hi[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            s1[c] = lo[c] = hi[c] = 0;
+            if (k0 + c < a.K)                                      // uniform
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (cnt[j]) hub_add(hub_q(fh_sim<KP>(wt[j], G, sn[j], en, k0 + c)), s1[c], lo[c], hi[c]);
+        }
+        hub_reduce8(s1, lo, hi, k0, a.K, lane, red + (size_t)wave * KP * 2);
+    }
+    const long long nw = wave_sum_ll((long long)mine);
+    if (lane == 0) red[4 * KP * 2 + wave] = nw;
+    __syncthreads();
+    for (int i = tid; i < 2 * a.K; i += 256) {
+        long long s = 0;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) s += red[v * KP * 2 + i];
+        if (s) atomicAdd(Ssum + (size_t)b * a.K * 2 + i, (unsigned long long)s);
+    }
+    if (tid == 0) {
+        const long long n = red[4 * KP * 2] + red[4 * KP * 2 + 1] + red[4 * KP * 2 + 2] + red[4 * KP * 2 + 3];
+        if (n) atomicAdd(Ncnt + b, (unsigned long long)n);
+    }
+#endif
+}
+
+// Stride 8: one wave per cell, one pixel per lane; the four cells of a block lie in at most two images (an image has >= 4 cells)
+template <int KP>
+__global__ __launch_bounds__(256) void hub_stats_cell_tab_kernel(FhArgs a, unsigned long long* __restrict__ Ssum,
+                                                                 unsigned long long* __restrict__ Ncnt, const float* __restrict__ D,
+                                                                 const float* __restrict__ N) {
+    constexpr int S = 8;
+    __shared__ float Gs[4 * 4 * KP];
+    __shared__ float Qs[4 * 16];
+    __shared__ long long red[4 * KP * 2];
+    __shared__ long long redn[4];
+    __shared__ int bw[4];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int cells_w = a.w + 1, cells = (a.h + 1) * cells_w;
+    const long ncell = (long)a.B * cells;
+    const long cid = (long)blockIdx.x * 4 + wave;
+    const bool ok = cid < ncell;
+    const long cc = ok ? cid : 0;
+    const int b = (int)(cc / cells), cell = (int)(cc % cells);
+    const int I = cell / cells_w, J = cell % cells_w;
+    const float* en = a.ws_f + (size_t)a.E * KP;
+    float* G = Gs + wave * 4 * KP;
+    float* Q = Qs + wave * 16;
+    long tp[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) tp[t] = tap_pos(b, a.h, a.w, I, J, t);
+    fh_lookup_GQ<KP>(tp, D, N, lane, G, Q);
+    __syncthreads();
+    float wt[4], sn;
+    const bool cnt = hub_counted<S>(a, b, I, J, lane / S, lane % S, ok, Q, wt, sn);
+#ifdef SZN_HUB_NO_ACCUM
+    float sink = 0.f;
+    for (int k = 0; k < a.K; ++k) sink = fmaxf(sink, cnt ? fh_sim<KP>(wt, G, sn, en, k) : 0.f);
+    if (sink == 123456.f) Ncnt[b] = 1ull;                           // never true (|sim| <= 1): keeps the similarities alive
+#else
+    for (int k0 = 0; k0 < a.K; k0 += 8) {
+        int s1[8], lo[8], hi[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            s1[c] = lo[c] = hi[c] = 0;
+            if (k0 + c < a.K && cnt) hub_add(hub_q(fh_sim<KP>(wt, G, sn, en, k0 + c)), s1[c], lo[c], hi[c]);
+        }
+        hub_reduce8(s1, lo, hi, k0, a.K, lane, red + (size_t)wave * KP * 2);
+    }
+    const long long nw = wave_sum_ll(cnt ? 1ll : 0ll);
+    if (lane == 0) { redn[wave] = nw; bw[wave] = ok ? b : -1; }
+    __syncthreads();
+    const int b0 = bw[0];                                           // wave 0's cell always exists
+    for (int i = tid; i < 2 * a.K; i += 256) {
+        long long s0 = 0, s1 = 0;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const long long r = red[v * KP * 2 + i];
+            if (bw[v] == b0) s0 += r;
+            else if (bw[v] >= 0) s1 += r;
+        }
+        if (s0) atomicAdd(Ssum + (size_t)b0 * a.K * 2 + i, (unsigned long long)s0);
+        if (s1) atomicAdd(Ssum + (size_t)(b0 + 1) * a.K * 2 + i, (unsigned long long)s1);
+    }
+    if (tid == 0) {
+        long long n0 = 0, n1 = 0;
+        for (int v = 0; v < 4; ++v) {
+            if (bw[v] == b0) n0 += redn[v];
+            else if (bw[v] >= 0) n1 += redn[v];
+        }
+        if (n0) atomicAdd(Ncnt + b0, (unsigned long long)n0);
+        if (n1) atomicAdd(Ncnt + b0 + 1, (unsigned long long)n1);
+    }
+#endif
+}
+
+// szn_hub_stats, pass 2: one thread per (image, class), double arithmetic: the moments and the (scale, shift) row of the mode
+__global__ __launch_bounds__(256) void hub_table_kernel(const long long* __restrict__ Ssum, const long long* __restrict__ Ncnt, int B, int K,
+                                                        int mode, double beta, double min_sd, float* __restrict__ table,
+                                                        int64_t* __restrict__ sums, int64_t* __restrict__ counts) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= B * K) return;
+    const int b = i / K;
+    const long long n = Ncnt[b], s1 = Ssum[2 * (size_t)i], s2 = Ssum[2 * (size_t)i + 1];
+    float scale = 1.f, shift = 0.f;
+    if (n > 0) {
+        const double mean = (double)s1 / ((double)n * 1048576.0);
+        const double ex2 = (double)s2 / ((double)n * 1099511627776.0);
+        const double sd = sqrt(fmax(ex2 - mean * mean, 0.0));
+        if (mode == 0) shift = (float)(beta * mean);
+        else {
+            const double f = fmax(sd, min_sd);
+            scale = (float)(1.0 / f);
+            shift = (float)(beta * mean / f);
+        }
+    }
+    table[2 * (size_t)i] = scale;
+    table[2 * (size_t)i + 1] = shift;
+    if (sums) { sums[2 * (size_t)i] = s1; sums[2 * (size_t)i + 1] = s2; }
+    if (counts && i % K == 0) counts[b] = n;
+}
+
+// workspace of szn_hub_stats: the fused head's | S [B][K][2] int64 | n [B] int64
+struct HubWorkspace { size_t S, n, bytes; };       // byte offsets
+inline HubWorkspace hub_workspace(int B, int h, int w, int E, int K) {
+    HubWorkspace L;
+    L.S = align256(fh_workspace(B, h, w, E, kp_of(K)).bytes);
+    L.n = L.S + (size_t)B * K * 2 * sizeof(long long);
+    L.bytes = L.n + (size_t)B * sizeof(long long);
+    return L;
+}
+
+template <int KP>
+void hub_stats_launch(int stride, const FhArgs& a, unsigned long long* S, unsigned long long* n, float* tabD, float* tabN, hipStream_t st) {
+    const int cells = (a.h + 1) * (a.w + 1);
+    if (stride == 8) {
+        hipLaunchKernelGGL(fh_tables_kernel<KP>, dim3((unsigned)(((long)a.B * a.h * a.w + 3) / 4)), dim3(256),
+                           (size_t)4 * a.E * sizeof(float), st, a, tabD, tabN);
+        hipLaunchKernelGGL(hub_stats_cell_tab_kernel<KP>, dim3((unsigned)(((long)a.B * cells + 3) / 4)), dim3(256), 0, st, a, S, n,
+                           (const float*)tabD, (const float*)tabN);
+    } else {
+        const size_t lds = (size_t)(fh_lds(a.E, KP, false).Q + 16) * sizeof(float) + ((size_t)4 * KP * 2 + 4) * sizeof(long long);
+        auto kern = hub_stats_cell_kernel<KP>;
+        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(kern, dim3(a.B * cells), dim3(256), lds, st, a, S, n);
+    }
+}
+
+// hub: szn_hub_head's pixel kernels; else gate: szn_soft_gate_head's; else margin == nullptr: szn_calib_head's; else szn_seen_sweep_head's -- same
+// grids and LDS.
 // tabled: the stride-8 position tables are in the workspace already (szn_seen_sweep_head_tabled, szn_soft_gate_head_tabled)
 template <int KP>
 void calib_launch(int stride, const FhArgs& a, const CalArgs& c, const float* margin, const GateArgs* gate, bool tabled, float* tabD,
-                  float* tabN, hipStream_t st) {
+                  float* tabN, hipStream_t st, const float* hub = nullptr) {
     const int cells = (a.h + 1) * (a.w + 1);
     if (stride == 8) {
         const dim3 grid((unsigned)(((long)a.B * cells + 3) / 4));
         if (!tabled) hipLaunchKernelGGL(fh_tables_kernel<KP>, dim3((unsigned)(((long)a.B * a.h * a.w + 3) / 4)), dim3(256),
                                         (size_t)4 * a.E * sizeof(float), st, a, tabD, tabN);
-        if (gate) hipLaunchKernelGGL(gate_cell_tab_kernel<KP>, grid, dim3(256), 0, st, a, c, *gate, (const float*)tabD, (const float*)tabN);
+        if (hub) hipLaunchKernelGGL(hub_cell_tab_kernel<KP>, grid, dim3(256), 0, st, a, c, hub, (const float*)tabD, (const float*)tabN);
+        else if (gate) hipLaunchKernelGGL(gate_cell_tab_kernel<KP>, grid, dim3(256), 0, st, a, c, *gate, (const float*)tabD, (const float*)tabN);
         else if (margin) hipLaunchKernelGGL(sweep_cell_tab_kernel<KP>, grid, dim3(256), 0, st, a, c, margin, (const float*)tabD, (const float*)tabN);
         else hipLaunchKernelGGL(calib_cell_tab_kernel<KP>, grid, dim3(256), 0, st, a, c, (const float*)tabD, (const float*)tabN);
     } else {
         const size_t lds = (size_t)(fh_lds(a.E, KP, false).Q + 16) * sizeof(float);       // Ct | G | Q
-        if (gate) {
+        if (hub) {
+            auto kern = hub_cell_kernel<KP>;
+            const size_t hlds = lds + (size_t)KP * sizeof(float4);                      // + the staged table rows
+            if (hlds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hlds);
+            hipLaunchKernelGGL(kern, dim3(a.B * cells), dim3(256), hlds, st, a, c, hub);
+        } else if (gate) {
             auto kern = gate_cell_kernel<KP>;
             if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             hipLaunchKernelGGL(kern, dim3(a.B * cells), dim3(256), lds, st, a, c, *gate);
@@ -2112,11 +2419,11 @@ namespace {
 // szn_calib_head (sweep == false, margin unused) and szn_seen_sweep_head (sweep == true: `gammas` are its taus, the switch is `margin`):
 // the same refusals, workspace and launch sequence, another pixel kernel.  tabled: the workspace already holds the prepared embedding image
 // and the stride-8 position tables of this map (szn_seen_sweep_head_tabled): neither is rebuilt.  gate: szn_soft_gate_head (sweep == true
-// with the gate's pixel kernels; its eff output counts as a result)
+// with the gate's pixel kernels; its eff output counts as a result).  hub: szn_hub_head (sweep == false with the table's pixel kernels)
 int calib_head_impl(const char* who, const char* vals, bool sweep, bool tabled, int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W,
                     int crop, int K, const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
                     const float* margin, int n_gammas, const float* gammas, int64_t* hist, int pred_index, int64_t* pred, void* workspace,
-                    szn_stream_t stream, GateArgs* gate = nullptr) {
+                    szn_stream_t stream, GateArgs* gate = nullptr, const float* hub = nullptr) {
     if (const char* why = calib_bad_geometry(stride, B, h, w, E, K, n_gammas)) SZN_FAIL(SZN_ERR_ARG, "%s: %s", who, why);
     if (!coarse || !embed || !workspace || !gammas) SZN_FAIL(SZN_ERR_ARG, "%s: coarse, embed, workspace and %s are required", who, vals);
     if (sweep && !margin) SZN_FAIL(SZN_ERR_ARG, "%s: margin is required", who);
@@ -2157,14 +2464,15 @@ int calib_head_impl(const char* who, const char* vals, bool sweep, bool tabled, 
     float* tabD = (float*)(ws + wl.tabD);
     float* tabN = (float*)(ws + wl.tabN);
     switch (KP) {
-        case 24: calib_launch<24>(stride, a, c, margin, gate, tabled, tabD, tabN, st); break;
-        case 40: calib_launch<40>(stride, a, c, margin, gate, tabled, tabD, tabN, st); break;
-        case 64: calib_launch<64>(stride, a, c, margin, gate, tabled, tabD, tabN, st); break;
-        case 128: calib_launch<128>(stride, a, c, margin, gate, tabled, tabD, tabN, st); break;
-        case 192: calib_launch<192>(stride, a, c, margin, gate, tabled, tabD, tabN, st); break;
-        default: calib_launch<256>(stride, a, c, margin, gate, tabled, tabD, tabN, st); break;
+        case 24: calib_launch<24>(stride, a, c, margin, gate, tabled, tabD, tabN, st, hub); break;
+        case 40: calib_launch<40>(stride, a, c, margin, gate, tabled, tabD, tabN, st, hub); break;
+        case 64: calib_launch<64>(stride, a, c, margin, gate, tabled, tabD, tabN, st, hub); break;
+        case 128: calib_launch<128>(stride, a, c, margin, gate, tabled, tabD, tabN, st, hub); break;
+        case 192: calib_launch<192>(stride, a, c, margin, gate, tabled, tabD, tabN, st, hub); break;
+        default: calib_launch<256>(stride, a, c, margin, gate, tabled, tabD, tabN, st, hub); break;
     }
-    if (gate) SZN_CHECK_LAUNCH(stride == 8 ? "gate_cell_tab_kernel" : "gate_cell_kernel");
+    if (hub) SZN_CHECK_LAUNCH(stride == 8 ? "hub_cell_tab_kernel" : "hub_cell_kernel");
+    else if (gate) SZN_CHECK_LAUNCH(stride == 8 ? "gate_cell_tab_kernel" : "gate_cell_kernel");
     else if (sweep) SZN_CHECK_LAUNCH(stride == 8 ? "sweep_cell_tab_kernel" : "sweep_cell_kernel");
     else SZN_CHECK_LAUNCH(stride == 8 ? "calib_cell_tab_kernel" : "calib_cell_kernel");
     if (hist) {
@@ -2243,6 +2551,68 @@ extern "C" int szn_soft_gate_head_tabled(int stride, int B, int h, int w, int E,
                                          int pred_index, int64_t* pred, float* eff, void* workspace, szn_stream_t stream) {
     return soft_gate_impl("soft_gate_head_tabled", true, stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, unseen, margin,
                           temperature, weight, n_taus, taus, hist, pred_index, pred, eff, workspace, stream);
+}
+
+// Hubness correction (include/szn.h): szn_hub_stats leaves per image and class a (scale, shift) pair from the first two moments of the
+// class's similarity over the image's pixels; szn_hub_head is szn_calib_head on fmaf(sim, scale, -shift).
+extern "C" size_t szn_hub_stats_workspace_bytes(int stride, int B, int h, int w, int E, int K) {
+    if (calib_bad_geometry(stride, B, h, w, E, K, 1)) return 0;
+    return hub_workspace(B, h, w, E, K).bytes;
+}
+
+extern "C" int szn_hub_stats(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                             const float* coarse, const float* embed, const int64_t* target, int mode, float beta, float min_sd,
+                             float* table, int64_t* sums, int64_t* counts, void* workspace, szn_stream_t stream) {
+    if (const char* why = calib_bad_geometry(stride, B, h, w, E, K, 1)) SZN_FAIL(SZN_ERR_ARG, "hub_stats: %s", why);
+    if (!coarse || !embed || !workspace || !table) SZN_FAIL(SZN_ERR_ARG, "hub_stats: coarse, embed, workspace and table are required");
+    if (int rc = calib_check_window("hub_stats", stride, h, w, E, ldc, c0, H, W, crop, workspace)) return rc;
+    if (mode != SZN_HUB_MEAN && mode != SZN_HUB_ZSCORE) SZN_FAIL(SZN_ERR_ARG, "hub_stats: mode %d is neither SZN_HUB_MEAN nor SZN_HUB_ZSCORE", mode);
+    if (!isfinite(beta) || !(beta >= 0.f)) SZN_FAIL(SZN_ERR_ARG, "hub_stats: beta must be finite and >= 0");
+    if (!isfinite(min_sd) || !(min_sd > 0.f)) SZN_FAIL(SZN_ERR_ARG, "hub_stats: min_sd must be finite and > 0");
+    if ((long long)H * W > SZN_HUB_MAX_PIXELS) SZN_FAIL(SZN_ERR_ARG, "hub_stats: H * W above SZN_HUB_MAX_PIXELS (the second moment must fit int64)");
+    const int KP = kp_of(K);
+    if (fh_lds(E, KP, false).bytes() > 150 * 1024) SZN_FAIL(SZN_ERR_UNSUPPORTED, "hub_stats: E=%d too large for LDS", E);
+
+    hipStream_t st = (hipStream_t)stream;
+    const FhWorkspace wl = fh_workspace(B, h, w, E, KP);
+    const HubWorkspace hl = hub_workspace(B, h, w, E, K);
+    char* ws = (char*)workspace;
+    hipLaunchKernelGGL(fh_prep_kernel, dim3(szn_div_up((long)E * KP, 256)), dim3(256), 0, st, embed, (float*)ws, E, K, KP);
+    SZN_CHECK_LAUNCH("fh_prep_kernel");
+    if (hipMemsetAsync(ws + hl.S, 0, hl.bytes - hl.S, st) != hipSuccess) SZN_FAIL(SZN_ERR_LAUNCH, "hub_stats: clearing the sums failed");
+    FhArgs a{};
+    a.coarse = coarse; a.embed = embed; a.target = target; a.ws_f = (float*)ws;
+    a.B = B; a.h = h; a.w = w; a.E = E; a.ldc = ldc; a.c0 = c0; a.H = H; a.W = W; a.crop = crop; a.K = K; a.KP = KP;
+    unsigned long long* S = (unsigned long long*)(ws + hl.S);
+    unsigned long long* n = (unsigned long long*)(ws + hl.n);
+    float* tabD = (float*)(ws + wl.tabD);
+    float* tabN = (float*)(ws + wl.tabN);
+    switch (KP) {
+        case 24: hub_stats_launch<24>(stride, a, S, n, tabD, tabN, st); break;
+        case 40: hub_stats_launch<40>(stride, a, S, n, tabD, tabN, st); break;
+        case 64: hub_stats_launch<64>(stride, a, S, n, tabD, tabN, st); break;
+        case 128: hub_stats_launch<128>(stride, a, S, n, tabD, tabN, st); break;
+        case 192: hub_stats_launch<192>(stride, a, S, n, tabD, tabN, st); break;
+        default: hub_stats_launch<256>(stride, a, S, n, tabD, tabN, st); break;
+    }
+    SZN_CHECK_LAUNCH(stride == 8 ? "hub_stats_cell_tab_kernel" : "hub_stats_cell_kernel");
+    hipLaunchKernelGGL(hub_table_kernel, dim3(szn_div_up((long)B * K, 256)), dim3(256), 0, st, (const long long*)S, (const long long*)n, B, K,
+                       mode, (double)beta, (double)min_sd, table, sums, counts);
+    SZN_CHECK_LAUNCH("hub_table_kernel");
+    return SZN_OK;
+}
+
+extern "C" size_t szn_hub_head_workspace_bytes(int stride, int B, int h, int w, int E, int K, int n_gammas) {
+    return szn_calib_head_workspace_bytes(stride, B, h, w, E, K, n_gammas);
+}
+
+extern "C" int szn_hub_head(int stride, int B, int h, int w, int E, int ldc, int c0, int H, int W, int crop, int K,
+                            const float* coarse, const float* embed, const int64_t* target, const szn_class_set* unseen,
+                            const float* table, int n_gammas, const float* gammas, int64_t* hist, int pred_index, int64_t* pred,
+                            void* workspace, szn_stream_t stream) {
+    if (!table) SZN_FAIL(SZN_ERR_ARG, "hub_head: table is required");
+    return calib_head_impl("hub_head", "gammas", false, false, stride, B, h, w, E, ldc, c0, H, W, crop, K, coarse, embed, target, unseen, nullptr,
+                           n_gammas, gammas, hist, pred_index, pred, workspace, stream, nullptr, table);
 }
 
 // Self-training pseudo labels (include/szn.h): the calibrated rule at one gamma picks the candidates among the pixels labelled cand_label,

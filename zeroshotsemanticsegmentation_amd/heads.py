@@ -20,6 +20,8 @@ szn_fused_ce_head and szn_seenmask_head_k goes through here (models.FCN32s / FCN
             which reads the maps of all views and writes one prediction.
   calib     calibrated stacking (szn_calib_head): a penalty gamma on every seen class, swept over up to 64 values in one pass --
             per gamma a confusion histogram, for one of them the prediction.
+  hub       hubness correction (szn_hub_stats, szn_hub_head): per image and class the mean (and spread) of the class's similarity over the
+            image's pixels is taken off before calib's rule; same gammas, histograms and prediction.
   conse     ConSE zero-shot inference for the softmax network (szn_conse_head): the top-T seen-class softmax mixes class embeddings,
             the nearest class by cosine wins, calib's gamma between the groups, swept in one pass; or forced by the target.
   seen_sweep  full SZN inference with a threshold on the seen-mask logit margin (szn_seenmask_margin, szn_seen_sweep_head): the grouped
@@ -367,6 +369,96 @@ def calib(stride, fmap, emb, H, W, unseen, gammas, target=None, hist=None, pred_
     buf = _scratch(nbytes, dev)
     L.call("szn_calib_head", stride, B, h, w, E, ld, 0, H, W, _CROP[stride], K, L.ptr(fmap), L.ptr(emb), L.ptr(tgt),
            L.class_set(unseen), G, g.ctypes.data_as(C.POINTER(C.c_float)), L.ptr(hist), -1 if pred_index is None else int(pred_index),
+           L.ptr(pred), L.ptr(buf), L.stream_ptr())
+    return hist, pred
+
+
+# ---- hubness correction: per-image, per-class centering / standardising of the similarities ----------------------------------------
+HUB_BETA = 1.0           # the textbook form (the whole mean is subtracted); a default nobody has tuned
+HUB_MIN_SD = 0.05        # floor of the standard deviation in zscore mode; a default nobody has tuned
+
+
+def hub_params(cfg):
+    """a hubness-correction description dict(mode=, beta=, min_sd=) checked -> dict(mode=, beta=, min_sd=) with the float32 values
+    szn_hub_stats reads: mode 'mean' | 'zscore' (required), beta finite and >= 0 (None or absent: HUB_BETA), min_sd finite and > 0
+    (None or absent: HUB_MIN_SD)"""
+    import numpy as np
+    if not isinstance(cfg, dict) or set(cfg) - {"mode", "beta", "min_sd"} or cfg.get("mode") not in L.HUB_MODES:
+        raise L.SznError("hub: the correction must be dict(mode='mean' | 'zscore', beta=, min_sd=), got %r" % (cfg,))
+    beta, min_sd = cfg.get("beta"), cfg.get("min_sd")
+    try:
+        b = float(np.float32(HUB_BETA if beta is None else beta))
+        s = float(np.float32(HUB_MIN_SD if min_sd is None else min_sd))
+    except (TypeError, ValueError):
+        raise L.SznError("hub: beta and min_sd must be numbers, got %r" % (cfg,))
+    if not np.isfinite(b) or b < 0:
+        raise L.SznError("hub: beta must be finite and >= 0 (got %r)" % (beta,))
+    if not np.isfinite(s) or s <= 0:
+        raise L.SznError("hub: min_sd must be finite and > 0 (got %r)" % (min_sd,))
+    return dict(mode=cfg["mode"], beta=b, min_sd=s)
+
+
+def hub_stats(stride, fmap, emb, H, W, mode, beta, min_sd, target=None, want=()):
+    """szn_hub_stats on the contiguous fp32 NHWC map `fmap` (the E embedding channels first): per image and class the (scale, shift) pair
+    of the hubness correction, from the exact int64 moments of the class's similarity over the image's pixels (those `target` labels
+    PAD_LABEL and zero-norm pixels left out).  want: any of 'sums' ((B,K,2) int64: S1, S2 in units of 2^-20 / 2^-40) and 'counts' ((B,)
+    int64).  -> table (B,K,2) fp32, or (table, *requested) in the order of `want`.  No host synchronisation."""
+    B, h, w, ld = fmap.shape
+    K, E = emb.shape
+    if fmap.dtype != torch.float32 or not fmap.is_contiguous():
+        raise L.SznError("hub_stats: the map must be a contiguous fp32 (B,h,w,C) tensor")
+    p = hub_params(dict(mode=mode, beta=beta, min_sd=min_sd))
+    want = tuple(want)
+    if set(want) - {"sums", "counts"}:
+        raise L.SznError("hub_stats: want holds 'sums' and / or 'counts', got %r" % (want,))
+    dev = fmap.device
+    tgt = None if target is None else target.to(device=dev, dtype=torch.int64).contiguous()
+    table = torch.empty(B, K, 2, dtype=torch.float32, device=dev)
+    extra = {"sums": torch.empty(B, K, 2, dtype=torch.int64, device=dev) if "sums" in want else None,
+             "counts": torch.empty(B, dtype=torch.int64, device=dev) if "counts" in want else None}
+    nbytes = L.load().szn_hub_stats_workspace_bytes(stride, B, h, w, E, K)
+    if nbytes == 0:
+        raise L.SznError("hub_stats: bad geometry (stride %d, B %d, map %d x %d, E %d, K %d)" % (stride, B, h, w, E, K))
+    buf = _scratch(nbytes, dev)
+    L.call("szn_hub_stats", stride, B, h, w, E, ld, 0, H, W, _CROP[stride], K, L.ptr(fmap), L.ptr(emb), L.ptr(tgt), L.HUB_MODES[p["mode"]],
+           p["beta"], p["min_sd"], L.ptr(table), L.ptr(extra["sums"]), L.ptr(extra["counts"]), L.ptr(buf), L.stream_ptr())
+    return (table,) + tuple(extra[k] for k in want) if want else table
+
+
+def hub(stride, fmap, emb, H, W, unseen, table, gammas, target=None, hist=None, pred_index=None):
+    """szn_hub_head: calib() on the corrected similarities fmaf(sim, table[b][k][0], -table[b][k][1]) -- table (B,K,2) fp32 from hub_stats, or
+    the caller's own.  Everything else is calib()'s: the gammas, hist, pred_index, what comes back.  -> (hist or None, pred or None)"""
+    import ctypes as C
+    B, h, w, ld = fmap.shape
+    K, E = emb.shape
+    if fmap.dtype != torch.float32 or not fmap.is_contiguous():
+        raise L.SznError("hub: the map must be a contiguous fp32 (B,h,w,C) tensor")
+    dev = fmap.device
+    if (not isinstance(table, torch.Tensor) or table.dtype != torch.float32 or tuple(table.shape) != (B, K, 2) or not table.is_contiguous()
+            or table.device != dev):
+        raise L.SznError("hub: table must be a contiguous fp32 (%d,%d,2) tensor on %s" % (B, K, dev))
+    g = calib_gammas(gammas)
+    G = int(g.size)
+    if target is None and hist is not None:
+        raise L.SznError("hub: a histogram needs the target")
+    if target is None and pred_index is None:
+        raise L.SznError("hub: nothing to compute (no target for a histogram, no pred_index for a prediction)")
+    if pred_index is not None and not 0 <= int(pred_index) < G:
+        raise L.SznError("hub: pred_index %r outside [0, %d)" % (pred_index, G))
+    tgt = None
+    if target is not None:
+        tgt = target.to(device=dev, dtype=torch.int64).contiguous()
+        if hist is None:
+            hist = torch.zeros(G, K, K, dtype=torch.int64, device=dev)
+        elif hist.dtype != torch.int64 or tuple(hist.shape) != (G, K, K) or not hist.is_contiguous() or hist.device != dev:
+            raise L.SznError("hub: hist must be a contiguous int64 (%d,%d,%d) tensor on %s" % (G, K, K, dev))
+    pred = torch.empty(B, H, W, dtype=torch.int64, device=dev) if pred_index is not None else None
+    nbytes = L.load().szn_hub_head_workspace_bytes(stride, B, h, w, E, K, G)
+    if nbytes == 0:
+        raise L.SznError("hub: bad geometry (stride %d, B %d, map %d x %d, E %d, K %d, %d gammas)" % (stride, B, h, w, E, K, G))
+    buf = _scratch(nbytes, dev)
+    L.call("szn_hub_head", stride, B, h, w, E, ld, 0, H, W, _CROP[stride], K, L.ptr(fmap), L.ptr(emb), L.ptr(tgt), L.class_set(unseen),
+           L.ptr(table), G, g.ctypes.data_as(C.POINTER(C.c_float)), L.ptr(hist), -1 if pred_index is None else int(pred_index),
            L.ptr(pred), L.ptr(buf), L.stream_ptr())
     return hist, pred
 

@@ -1548,6 +1548,27 @@ class FCN32s(nn.Module):
             self._last_pred = pred
         return loss_t, pred, hist
 
+    def hub_predict(self, x, embeddings, unseen, hub, gammas, target=None, hist=None, pred_index=None, loss="cos"):
+        """calib_predict with the hubness correction hub = dict(mode=, beta=, min_sd=) (heads.hub_params): the same forward pass and loss
+        head, then szn_hub_stats on the same map -- per image and class the mean (mode 'zscore': and the spread) of the class's similarity
+        over the image's pixels, padding (target == PAD_LABEL) left out -- and szn_hub_head, which is szn_calib_head on the corrected
+        similarities.  Per-image statistics: the batch's composition changes nothing.  -> calib_predict's (loss, pred, hist); the loss is
+        the stored image's, unchanged.  The table is left in self._last_hub_table."""
+        kind = heads.embed_kind(loss)
+        p = heads.hub_params(hub)
+        with torch.no_grad():
+            ctx, stride, fmap = self._head_map(x)
+            emb = heads.embeddings(embeddings, self.n_class, fmap.device)
+            loss_t, pred = heads.embed_predict(kind, stride, fmap, emb, ctx.H, ctx.W, target, **self._head_kw(kind))
+            if target is not None or pred_index is not None:
+                fmap32 = fmap if fmap.dtype == torch.float32 else fmap.to(torch.float32)
+                self._last_hub_table = heads.hub_stats(stride, fmap32, emb, ctx.H, ctx.W, p["mode"], p["beta"], p["min_sd"], target)
+                hist, cpred = heads.hub(stride, fmap32, emb, ctx.H, ctx.W, unseen, self._last_hub_table, gammas, target, hist, pred_index)
+                if pred_index is not None:
+                    pred = cpred
+            self._last_pred = pred
+        return loss_t, pred, hist
+
     def conse_predict(self, x, embeddings, unseen, top_t, gammas=None, target=None, hist=None, pred_index=None, forced=False):
         """ConSE zero-shot inference for the softmax network (Norouzi et al., ICLR 2014): one forward pass, then on the same logit map
         szn_fused_ce_head for the loss and szn_conse_head, which mixes the (K,E) class `embeddings` of the top `top_t` SEEN classes

@@ -30,6 +30,11 @@ Added for this implementation (none change the reference flags):
                        the margin minus WEIGHT * (log P_U(best unseen) - log P_S(best seen)), the experts' softmaxes over the cosines at
                        --gate-temperature T (default 0.1, a hyper-parameter default, not a tuned value).  0 = the hard cut, 1 = the
                        probabilistic rule.  Composes with --seen-threshold / --seen-sweep; the sweep's rows go to seen_gate_log.csv
+  --hub-correct MODE   hubness correction in validation and -m test_fcn (szn_hub_stats, szn_hub_head): per image, every class's mean cosine
+                       similarity over the image's pixels is taken off its similarity (mean), and the result divided by the class's
+                       spread (zscore), before --calibration's rule (gamma 0 without it); --hub-beta B scales the mean taken off (default
+                       1, the textbook form) and --hub-min-sd S floors the spread (default 0.05): defaults nobody has tuned.  Composes
+                       with --calibration / --calib-sweep; the rows, with the hubness of each prediction, go to <log_dir>/hub_log.csv
   -loss sim_ce         similarity cross-entropy: softmax over the seen classes' cosine similarities to the pixel embedding, cross
                        entropy against the label (szn_fused_simce_head; the unseen classes do not compete); --sim-temperature T
                        (default 0.1, a hyper-parameter default, not a tuned value) divides the similarities
@@ -72,7 +77,7 @@ from . import engine as _engine
 from . import models, trainer_fcn, trainer_seenmask
 from .configs import configurations
 from ._lib import CONSE_MAX_TOP
-from .heads import GATE_TEMPERATURE, RANK_MARGIN, SIM_TEMPERATURE
+from .heads import GATE_TEMPERATURE, HUB_BETA, HUB_MIN_SD, RANK_MARGIN, SIM_TEMPERATURE
 from .optim import FusedAdam, FusedSGD
 from .synthetic_dataset import SyntheticSegmentation
 
@@ -153,6 +158,17 @@ def build_parser():
     p.add_argument('--seen-sweep', type=float, nargs=3, metavar=('LO', 'HI', 'N'), default=None,
                    help="with -m test_all: also evaluates N thresholds (2 to 64) evenly spaced from LO to HI in the same pass of the "
                         "head and appends their metrics and the harmonic mean of seen and unseen mIoU to <log_dir>/seen_sweep_log.csv")
+    p.add_argument('--hub-correct', choices=('mean', 'zscore'), default=None,
+                   help="hubness correction in validation (and -m test_fcn): per image, every class's mean cosine similarity over the "
+                        "image's pixels is taken off its similarity before the class is chosen (mean), and the result divided by the "
+                        "class's spread over those pixels (zscore).  Composes with --calibration / --calib-sweep (gamma 0 without them); "
+                        "the rows, with the hubness (skewness of the per-class prediction counts) of each, go to <log_dir>/hub_log.csv")
+    p.add_argument('--hub-beta', type=float, default=None, metavar='B',
+                   help="with --hub-correct: the share of the class mean that is taken off.  Default %g, the textbook form: a default "
+                        "nobody has tuned.  An error without --hub-correct" % HUB_BETA)
+    p.add_argument('--hub-min-sd', type=float, default=None, metavar='S',
+                   help="with --hub-correct zscore: the smallest spread a class's similarities are divided by.  Default %g: a default "
+                        "nobody has tuned.  An error without --hub-correct" % HUB_MIN_SD)
     p.add_argument('--seen-gate', type=float, default=None, metavar='WEIGHT',
                    help="with -m test_all: soft seen/unseen gating -- p(class) = p(group) * p(class | group) with p(seen) = "
                         "sigmoid(margin - TAU) and a softmax over the cosines inside each class group, which cuts the margin minus WEIGHT * "
@@ -417,6 +433,27 @@ def check_seen_gate(weight, temperature, cfg, calibration=None, calib_sweep=None
     return dict(weight=weight, temperature=GATE_TEMPERATURE if temperature is None else temperature)
 
 
+def check_hub(mode, beta, min_sd, cfg, eval_scales=None, eval_flip=False):
+    """--hub-correct / --hub-beta / --hub-min-sd -> the Trainer's hub dict, or None without the flags: beta and min_sd belong to the
+    correction; otherwise check_calibration's rules (trainer_fcn.hub_refused)"""
+    if mode is None:
+        if beta is not None or min_sd is not None:
+            raise Exception("--hub-beta / --hub-min-sd: belong to --hub-correct, which is off")
+        return None
+    if beta is not None and not (beta == beta and 0 <= beta < float('inf')):
+        raise Exception("--hub-beta: B must be finite and >= 0 (got %r)" % (beta,))
+    if min_sd is not None and not (min_sd == min_sd and 0 < min_sd < float('inf')):
+        raise Exception("--hub-min-sd: S must be finite and > 0 (got %r)" % (min_sd,))
+    n_class = 21 if cfg['dataset'] == 'pascal' else 33
+    why = trainer_fcn.hub_refused(bool(cfg['train_unseen'] or cfg['val_unseen']),
+                                  bool(cfg['embed_dim']) and cfg['fcn_loss'] in _EMBED_LOSSES, bool(cfg['forced_unseen']),
+                                  cfg['mode'] == 'test_all', bool(eval_scales or eval_flip), n_class,
+                                  os.environ.get("SZN_VERBOSE_VAL", "0") == "1")
+    if why:
+        raise Exception("--hub-correct: " + why)
+    return dict(mode=mode, beta=HUB_BETA if beta is None else beta, min_sd=HUB_MIN_SD if min_sd is None else min_sd)
+
+
 def check_calibration(calibration, sweep, cfg, eval_scales=None, eval_flip=False):
     """--calibration / --calib-sweep: unseen classes, an embedding configuration, and none of the other class-assignment rules
     (forced unseen, -m test_all, multi-scale views); more than 256 classes and SZN_VERBOSE_VAL keep the materialised score"""
@@ -573,6 +610,7 @@ def main(argv=None):
     check_calibration(args.calibration, args.calib_sweep, cfg, args.eval_scales, args.eval_flip)
     check_seen_threshold(args.seen_threshold, args.seen_sweep, cfg, args.calibration, args.calib_sweep, args.eval_scales, args.eval_flip)
     seen_gate = check_seen_gate(args.seen_gate, args.gate_temperature, cfg, args.calibration, args.calib_sweep, args.eval_scales, args.eval_flip)
+    hub = check_hub(args.hub_correct, args.hub_beta, args.hub_min_sd, cfg, args.eval_scales, args.eval_flip)
     conse = check_conse(args.conse, args.conse_dim, args.conse_gamma, args.conse_sweep, cfg, args.eval_scales, args.eval_flip)
     check_pseudo(args.pseudo_label, args.pseudo_gamma, args.pseudo_floor, args.pseudo_start_epoch, args.hide_unseen, cfg)
     check_ohem(args.ohem, args.ohem_thresh, args.ohem_start_epoch, cfg)
@@ -721,7 +759,7 @@ def main(argv=None):
         ohem=None if args.ohem is None else dict(keep=args.ohem, thresh=args.ohem_thresh), ohem_start_epoch=args.ohem_start_epoch or 0,
         calibration=args.calibration, calib_sweep=calib_sweep_values(args.calib_sweep), eval_scales=args.eval_scales,
         eval_flip=args.eval_flip, bias_loss=args.bias_loss, bias_start_epoch=args.bias_start_epoch or 0,
-        conse=conse, conse_sweep=calib_sweep_values(args.conse_sweep, "--conse-sweep"))
+        conse=conse, conse_sweep=calib_sweep_values(args.conse_sweep, "--conse-sweep"), hub=hub)
     fcn_trainer.epoch, fcn_trainer.iteration = start_epoch, start_iteration
 
     if cfg['mode'] == 'train':

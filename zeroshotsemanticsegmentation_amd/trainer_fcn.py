@@ -92,6 +92,19 @@ def seen_gate_refused(has_unseen, embed_cfg, forced_unseen, test_all, eval_views
     return None if why is None else why.replace("a seen-mask threshold", "the soft seen/unseen gate")
 
 
+def hub_refused(has_unseen, embed_cfg, forced_unseen, test_all, eval_views, n_class, verbose_val=False):
+    """why a configuration cannot run the hubness correction (hub=, train.py --hub-correct), or None: the correction acts on the
+    similarities that enter calibrated stacking's rule inside the same head, so calibration_refused's reasons are its reasons"""
+    why = calibration_refused(has_unseen, embed_cfg, forced_unseen, test_all, eval_views, n_class, verbose_val)
+    if why is None:
+        return None
+    why = why.replace("calibration and forced_unseen", "the hubness correction and forced_unseen")
+    why = why.replace("there is no seen group to penalise", "there are no two class groups to decide between")
+    why = why.replace("the view-ensemble head has no penalty", "the view-ensemble head has no correction")
+    why = why.replace("which the calibrated head never forms", "which the corrected head never forms")
+    return why.replace("calibration", "the hubness correction", 1)
+
+
 def conse_refused(has_unseen, softmax_cfg, forced_unseen, test_all, eval_views, tuned):
     """why a configuration cannot run ConSE zero-shot inference (conse= / conse_sweep=, train.py --conse / --conse-sweep), or None: ConSE
     mixes class embeddings with the softmax network's seen-class probabilities, so it needs unseen classes and the softmax
@@ -197,7 +210,7 @@ class Trainer(object):
     def __init__(self, cuda, model, optimizer, train_loader, val_loader, log_dir, dataset, max_epoch, tb_writer,
                  pixel_embeddings=None, loss_func=None, unseen=None, val_unseen=None, label_names=None,
                  forced_unseen=False, embed_arr=None, precision=torch.float32, fused_step=True, rank=0, visualize=0, augment=None,
-                 seen_threshold=None, seen_sweep=None, proto=None, support_loader=None, conse=None, conse_sweep=None, seen_gate=None,
+                 seen_threshold=None, seen_sweep=None, proto=None, support_loader=None, conse=None, conse_sweep=None, seen_gate=None, hub=None,
                  sim_temperature=None, rank_margin=None, rank_hardest=False, bias_loss=None, bias_start_epoch=0, pseudo=None, pseudo_start_epoch=0, ohem=None, ohem_start_epoch=0, calibration=None,
                  calib_sweep=None, eval_scales=None, eval_flip=False):
         if not cuda:
@@ -262,6 +275,15 @@ class Trainer(object):
             self.calib_sweep = calib_gammas(calib_sweep)
         self.best_gamma = None
         self.best_harmonic_mean_iu = None
+        # hubness correction (models.hub_predict): hub = dict(mode='mean' | 'zscore', beta=, min_sd=) -- validation takes every class's mean
+        # similarity over the image's pixels (zscore: and divides by its spread) off the similarities before calibrated stacking's rule, at
+        # the gamma of `calibration` (0 without it) and over calib_sweep's gammas; the rows go to hub_log.csv with the hubness (skewness of
+        # the per-class prediction counts) of each.  Training steps never see it.
+        self.hub = None
+        if hub is not None:
+            from .heads import hub_params
+            self.hub = hub_params(hub)
+        self.last_hub_skew = None
         # the seen-mask threshold of the full SZN network (models.seen_sweep_predict), validate(True) only: a pixel takes the seen group
         # iff its seen-mask logit margin s1 - s0 exceeds `seen_threshold` (None: the plain route, which is tau = 0); `seen_sweep` =
         # ascending candidate taus whose metrics validate(True) writes to seen_sweep_log.csv from the same head launch
@@ -300,6 +322,12 @@ class Trainer(object):
             if self.calibration is not None and not np.isfinite(self.calibration):
                 from ._lib import SznError
                 raise SznError("calibration: gamma must be finite (got %r)" % (calibration,))
+        if self.hub is not None:
+            from ._lib import SznError
+            why = hub_refused(bool(self.unseen), bool(pixel_embeddings) and loss_func in _EMBED_LOSSES, forced_unseen,
+                              False, bool(self.eval_scales), self.n_class, self.verbose_val)
+            if why:
+                raise SznError(why)
         if self.seen_threshold is not None or self.seen_sweep is not None:
             from ._lib import SznError
             why = seen_threshold_refused(bool(self.unseen), bool(pixel_embeddings) and loss_func in _EMBED_LOSSES, forced_unseen,
@@ -707,6 +735,11 @@ class Trainer(object):
             if self.eval_scales:
                 loss, pred = self.model.ms_predict(data, self.embeddings, self.eval_scales, self.eval_flip, target, loss=self.loss_func)
                 return None, loss, pred, target
+            if self.hub is not None:
+                # hubness correction: calibrated stacking's route with szn_hub_stats + szn_hub_head; without a calibration gamma = 0
+                loss, pred, _ = self.model.hub_predict(data, self.embeddings, self.unseen, self.hub, self._hub_gammas(), target,
+                                                       hist=self._calib_hist, pred_index=self._hub_index(), loss=self.loss_func)
+                return None, loss, pred, target
             if self.calibration is not None or self._calib_hist is not None:
                 # calibrated stacking: the penalised classes are those not in self.unseen.  One forward pass; the sweep's histogram
                 # and the calibrated prediction come from szn_calib_head launches on the map the loss used
@@ -800,6 +833,45 @@ class Trainer(object):
         if self.calibration is None:
             return None
         return 0 if self._calib_hist is None else int(np.searchsorted(self._calib_all, np.float32(self.calibration)))
+
+    # hubness correction: the same, with gamma = 0 in use when there is no calibration
+    def _hub_gamma(self):
+        return 0.0 if self.calibration is None else self.calibration
+
+    def _hub_gammas(self):
+        return [self._hub_gamma()] if self._calib_hist is None else self._calib_all
+
+    def _hub_index(self):
+        return 0 if self._calib_hist is None else int(np.searchsorted(self._calib_all, np.float32(self._hub_gamma())))
+
+    def _hub_report(self, h, hist_all):
+        """rank 0, once per validation: hub_log.csv -- one 'used' row for the prediction validation reports (h: the {all, seen, unseen}
+        histograms) and one 'sweep' row per gamma of calib_sweep (hist_all, or None), each with the hubness of its prediction"""
+        path = osp.join(self.log_dir, 'hub_log.csv')
+        if not osp.exists(path):
+            with open(path, 'w') as f:
+                f.write('epoch,iteration,row,mode,beta,min_sd,gamma,val/mean_iu,val/seen/mean_iu,val/unseen/mean_iu,val/harmonic_mean_iu,'
+                        'val/hubness_skew\n')
+        head = [self.epoch, self.iteration]
+        cfg = [self.hub["mode"], self.hub["beta"], self.hub["min_sd"]]
+        best = None
+        with open(path, 'a') as f:
+            m, ms, mu = (utils._hist_to_metrics(x) for x in h)
+            self.last_hub_skew = utils.hubness_skew(h[0])
+            f.write(','.join(map(str, head + ['used'] + cfg + [self._hub_gamma(), m[2], ms[2], mu[2], utils.harmonic_mean_iu(ms, mu),
+                                                                self.last_hub_skew])) + '\n')
+            if hist_all is not None:
+                for val, g in zip(self.calib_sweep, np.searchsorted(self._calib_all, self.calib_sweep)):
+                    m, ms, mu = utils.calib_rows(hist_all[g], self.n_class, self.val_unseen)
+                    hm = utils.harmonic_mean_iu(ms, mu)
+                    f.write(','.join(map(str, head + ['sweep'] + cfg + [float(val), m[2], ms[2], mu[2], hm,
+                                                                         utils.hubness_skew(hist_all[g])])) + '\n')
+                    if not np.isnan(hm) and (best is None or hm > best[1] or (hm == best[1] and abs(float(val)) < abs(best[0]))):
+                        best = (float(val), hm)
+        self.tb_writer.add_scalar('fcn/val/hub/skew', self.last_hub_skew, self.epoch)
+        if best is not None:
+            self.best_gamma, self.best_harmonic_mean_iu = best
+            print('hubness correction (%s): best gamma %g, harmonic mean IU %.3f' % ((self.hub["mode"],) + best))
 
     def _sweep_report(self, hist_all, all_vals, sweep, fname, column, extra=()):
         """one <fname> row per value of the sweep (hist_all follows all_vals) -> (value, harmonic mean) of the largest harmonic mean, or
@@ -964,8 +1036,13 @@ class Trainer(object):
         if both_fcn_and_seenmask and (self.calibration is not None or self.calib_sweep is not None):
             from ._lib import SznError
             raise SznError(calibration_refused(True, True, False, True, False, self.n_class))
+        if both_fcn_and_seenmask and self.hub is not None:
+            from ._lib import SznError
+            raise SznError(hub_refused(True, True, False, True, False, self.n_class))
         if self.calib_sweep is not None:
             extra = [] if self.calibration is None else [np.float32(self.calibration)]
+            if self.hub is not None:
+                extra = [np.float32(self._hub_gamma())]
             self._calib_all = np.unique(np.concatenate([self.calib_sweep, np.asarray(extra, dtype=np.float32)]))
             if self._calib_all.size > 64:
                 from ._lib import SznError
@@ -1027,8 +1104,10 @@ class Trainer(object):
         h = hist.cpu().numpy()
         if calib_hist is not None:
             calib_hist = calib_hist.cpu().numpy()
-            if self.rank == 0:
+            if self.rank == 0 and self.hub is None:
                 self._calib_report(calib_hist)
+        if self.hub is not None and self.rank == 0:
+            self._hub_report(h, calib_hist)
         if seen_hist is not None:
             seen_hist = seen_hist.cpu().numpy()
             if self.rank == 0:

@@ -565,6 +565,68 @@ def soft_gate_infer(score, seen_mask_score, embeddings, unseen, tau, temperature
     return torch.where(torch.isnan(d), torch.zeros_like(pred), pred)
 
 
+def hub_infer(score, embeddings, unseen, mode, beta, gamma=0.0, min_sd=0.05, valid=None):
+    """hubness-corrected class assignment on a materialised (B,E,H,W) embedding score with torch operations: the referee of szn_hub_stats
+    + szn_hub_head (heads.hub_stats, heads.hub, FCN32s.hub_predict).  Runs on the score's device, CPU included.  Per pixel the cosine of
+    the score with every row of `embeddings` (K,E) (a zero-norm pixel: NaN); per image and class the mean and the standard deviation
+    (population form) of that cosine over the image's pixels with a finite norm > 0 -- and valid (B,H,W) bool where given (False: a padding
+    pixel) -- as plain floating means, no quantisation.  mode 'mean': adj = cos - beta * mean; 'zscore': adj = (cos - beta * mean) /
+    max(sd, min_sd).  An image without such a pixel keeps its cosines.  a / b = the first best seen / unseen class by adj, m = their
+    difference: a where m > gamma, or m == gamma and a < b; else b; class 0 where m is NaN.  -> int64 (B,H,W) tensor on the score's device."""
+    score = _data(score).detach().float()
+    dev = score.device
+    emb = _data(embeddings).to(device=dev, dtype=torch.float32)
+    K = emb.shape[0]
+    if emb.dim() != 2 or emb.shape[1] != score.shape[1]:
+        raise L.SznError("hub_infer: embeddings must be (K,%d), got %s" % (score.shape[1], tuple(emb.shape)))
+    uns = sorted(set(int(k) for k in unseen))
+    if not uns or len(uns) >= K or uns[0] < 0 or uns[-1] >= K:
+        raise L.SznError("hub_infer: the unseen classes must be a non-empty proper subset of range(%d)" % K)
+    if mode not in L.HUB_MODES:
+        raise L.SznError("hub_infer: mode must be one of %s, got %r" % (sorted(L.HUB_MODES), mode))
+    bt, ms = float(np.float32(beta)), float(np.float32(min_sd))
+    if not (np.isfinite(bt) and bt >= 0 and np.isfinite(ms) and ms > 0):
+        raise L.SznError("hub_infer: beta must be finite and >= 0, min_sd finite and > 0")
+    is_unseen = torch.zeros(K, dtype=torch.bool, device=dev)
+    is_unseen[uns] = True
+    seen_idx, unseen_idx = torch.nonzero(~is_unseen)[:, 0], torch.nonzero(is_unseen)[:, 0]
+    sn = score.norm(dim=1, keepdim=True)
+    en = emb.norm(dim=1)
+    sim = torch.einsum('behw,ke->bkhw', score, emb) / (sn * torch.where(en == 0, torch.ones_like(en), en).view(1, K, 1, 1))
+    counted = torch.isfinite(sn) & (sn > 0)
+    if valid is not None:
+        counted = counted & _data(valid).to(device=dev, dtype=torch.bool).unsqueeze(1)
+    n = counted.sum(dim=(2, 3), keepdim=True).to(torch.float32)
+    s0 = torch.where(counted, sim, torch.zeros_like(sim))
+    n1 = n.clamp(min=1)
+    mean = s0.sum(dim=(2, 3), keepdim=True) / n1
+    var = ((s0 * s0).sum(dim=(2, 3), keepdim=True) / n1 - mean * mean).clamp(min=0)
+    scale = torch.ones_like(mean) if mode == "mean" else 1.0 / var.sqrt().clamp(min=ms)
+    some = n > 0
+    scale = torch.where(some, scale, torch.ones_like(scale))
+    shift = torch.where(some, bt * mean * scale, torch.zeros_like(mean))
+    adj = sim * scale - shift
+    a, va = _first_max(adj, seen_idx)
+    b, vb = _first_max(adj, unseen_idx)
+    m = va - vb
+    g = float(np.float32(gamma))
+    pred = torch.where((m > g) | ((m == g) & (a < b)), a, b)
+    return torch.where(torch.isnan(m), torch.zeros_like(pred), pred)
+
+
+def hubness_skew(hist):
+    """the hubness of a prediction: the skewness of N_k, the number of pixels each class was predicted for (the column sums of a (K,K)
+    confusion histogram, or the (K,) counts themselves) -- E[(N_k - mu)^3] / sigma^3 over the classes, population moments (Radovanovic et
+    al. 2010).  Large and positive: a few classes take most pixels.  0.0 when every class has the same count."""
+    h = np.asarray(hist, dtype=np.float64)
+    nk = h.sum(axis=0) if h.ndim == 2 else h.reshape(-1)
+    d = nk - nk.mean()
+    var = (d * d).mean()
+    if not var > 0:
+        return 0.0
+    return float((d ** 3).mean() / var ** 1.5)
+
+
 def _fast_hist(label_true, label_pred, n_class, target='all', unseen=None):
     """host restatement of utils.py:104-119 for numpy label maps (validation logs on the host)"""
     label_true = np.asarray(label_true)
