@@ -70,13 +70,22 @@ class Workspace(object):
     def map_key(stride, fmap):
         return (stride, fmap.data_ptr(), fmap._version, tuple(fmap.shape))
 
+    def _prep_key(self, emb):
+        K, E = emb.shape
+        return (self.buf.data_ptr(), emb.data_ptr(), emb._version, K, E)
+
     def prepared(self, nbytes, emb, K, E, stream):
         ws = self.get(nbytes)
-        key = (ws.data_ptr(), emb.data_ptr(), emb._version, K, E)
+        key = self._prep_key(emb)
         if self.prep != key:
             L.call("szn_fused_head_prepare", E, K, L.ptr(emb), L.ptr(ws), stream)
             self.prep = key
         return ws
+
+    def holds(self, nbytes, stride, fmap, emb):
+        """is this the Workspace, `nbytes` or more, in which the embedding head last ran on this very map and embedding matrix"""
+        return (self.buf is not None and self.buf.numel() >= nbytes and self.tables == Workspace.map_key(stride, fmap)
+                and self.prep == self._prep_key(emb))
 
 
 def _scratch(nbytes, device):
@@ -325,15 +334,71 @@ def ms_predict(stride, views, emb, H, W, target=None, mode=0, unseen=None, gmap=
 
 
 # ---- calibrated stacking: seen-class penalty, one-pass sweep -----------------------------------------------------------------
+def _sweep_values(who, noun, values, most):
+    """the candidate values of a sweep as the float32 HOST array the sweep heads read: 1 to `most` finite, strictly ascending values"""
+    import numpy as np
+    v = np.ascontiguousarray(np.asarray(values, dtype=np.float32).reshape(-1))
+    if not 1 <= v.size <= most:
+        raise L.SznError("%s: %d %s, between 1 and %d are taken" % (who, v.size, noun, most))
+    if not np.isfinite(v).all() or not (np.diff(v) > 0).all():
+        raise L.SznError("%s: the %s must be finite and strictly ascending as float32 (got %r)" % (who, noun, v.tolist()))
+    return v
+
+
 def calib_gammas(gammas):
     """the candidate penalties as the float32 HOST array szn_calib_head reads: 1 to CALIB_MAX_GAMMAS finite, strictly ascending values"""
-    import numpy as np
-    g = np.ascontiguousarray(np.asarray(gammas, dtype=np.float32).reshape(-1))
-    if not 1 <= g.size <= L.CALIB_MAX_GAMMAS:
-        raise L.SznError("calibration: %d gammas, between 1 and %d are taken" % (g.size, L.CALIB_MAX_GAMMAS))
-    if not np.isfinite(g).all() or not (np.diff(g) > 0).all():
-        raise L.SznError("calibration: the gammas must be finite and strictly ascending as float32 (got %r)" % (g.tolist(),))
-    return g
+    return _sweep_values("calibration", "gammas", gammas, L.CALIB_MAX_GAMMAS)
+
+
+def _check_map(who, fmap):
+    if fmap.dtype != torch.float32 or not fmap.is_contiguous():
+        raise L.SznError("%s: the map must be a contiguous fp32 (B,h,w,C) tensor" % who)
+
+
+class _SweepCall(object):
+    """the host front end calib, hub, conse, seen_sweep and soft_gate share, after the map check and their own checks: the values
+    (`noun` "gammas": calib_gammas, "taus": seen_sweep_taus), then what target / hist / pred_index ask for.  extra: None, or (name,
+    wanted) of a further output that counts as something to compute.  Holds what the C side takes: tgt (the target as int64 on the
+    map's device, or None), hist, pred (an empty (B,H,W) int64 tensor, or None without a pred_index), G, values (the host float
+    pointer) and pred_index (-1: none)."""
+
+    def __init__(self, who, noun, fmap, emb, H, W, values, target, hist, pred_index, extra=None):
+        import ctypes as C
+        v = (calib_gammas if noun == "gammas" else seen_sweep_taus)(values)
+        G, K, dev = int(v.size), emb.shape[0], fmap.device
+        if target is None and hist is not None:
+            raise L.SznError("%s: a histogram needs the target" % who)
+        if target is None and pred_index is None and not (extra and extra[1]):
+            raise L.SznError("%s: nothing to compute (no target for a histogram, no pred_index for a prediction%s)"
+                             % (who, ", no " + extra[0] if extra else ""))
+        if pred_index is not None and not 0 <= int(pred_index) < G:
+            raise L.SznError("%s: pred_index %r outside [0, %d)" % (who, pred_index, G))
+        self.tgt = None
+        if target is not None:
+            self.tgt = target.to(device=dev, dtype=torch.int64).contiguous()
+            if hist is None:
+                hist = torch.zeros(G, K, K, dtype=torch.int64, device=dev)
+            elif hist.dtype != torch.int64 or tuple(hist.shape) != (G, K, K) or not hist.is_contiguous() or hist.device != dev:
+                raise L.SznError("%s: hist must be a contiguous int64 (%d,%d,%d) tensor on %s" % (who, G, K, K, dev))
+        self.who, self.noun, self.fmap, self.emb, self.hist, self.G = who, noun, fmap, emb, hist, G
+        self.pred = torch.empty(fmap.shape[0], H, W, dtype=torch.int64, device=dev) if pred_index is not None else None
+        self.values = v.ctypes.data_as(C.POINTER(C.c_float))       # (the pointer object keeps the array alive)
+        self.pred_index = -1 if pred_index is None else int(pred_index)
+
+    def scratch(self, stride, nbytes, ws=None):
+        """the head's workspace from what its szn_*_workspace_bytes said (0: a geometry it refuses): fresh scratch, or the buffer of
+        the Workspace `ws` when that holds this map's tables (Workspace.holds)"""
+        B, h, w, _ = self.fmap.shape
+        K, E = self.emb.shape
+        if nbytes == 0:
+            raise L.SznError("%s: bad geometry (stride %d, B %d, map %d x %d, E %d, K %d, %d %s)"
+                             % (self.who, stride, B, h, w, E, K, self.G, self.noun))
+        if ws is None:
+            return _scratch(nbytes, self.fmap.device)
+        if not ws.holds(nbytes, stride, self.fmap, self.emb):
+            raise L.SznError("%s: ws must be the Workspace in which the embedding head last ran on this very map and embedding "
+                             "matrix, %d bytes or more" % (self.who, nbytes))
+        return ws.buf
 
 
 def calib(stride, fmap, emb, H, W, unseen, gammas, target=None, hist=None, pred_index=None):
@@ -341,36 +406,14 @@ def calib(stride, fmap, emb, H, W, unseen, gammas, target=None, hist=None, pred_
     similarity of every class NOT in `unseen` before the argmax, for every gamma of `gammas` (ascending) in one pass.
     target given: hist (G,K,K) int64 += the confusion counts of every gamma (allocated as zeros when None).  pred_index given: pred
     (B,H,W) int64 at gammas[pred_index].  -> (hist or None, pred or None)"""
-    import ctypes as C
     B, h, w, ld = fmap.shape
     K, E = emb.shape
-    if fmap.dtype != torch.float32 or not fmap.is_contiguous():
-        raise L.SznError("calib: the map must be a contiguous fp32 (B,h,w,C) tensor")
-    g = calib_gammas(gammas)
-    G = int(g.size)
-    if target is None and hist is not None:
-        raise L.SznError("calib: a histogram needs the target")
-    if target is None and pred_index is None:
-        raise L.SznError("calib: nothing to compute (no target for a histogram, no pred_index for a prediction)")
-    if pred_index is not None and not 0 <= int(pred_index) < G:
-        raise L.SznError("calib: pred_index %r outside [0, %d)" % (pred_index, G))
-    dev = fmap.device
-    tgt = None
-    if target is not None:
-        tgt = target.to(device=dev, dtype=torch.int64).contiguous()
-        if hist is None:
-            hist = torch.zeros(G, K, K, dtype=torch.int64, device=dev)
-        elif hist.dtype != torch.int64 or tuple(hist.shape) != (G, K, K) or not hist.is_contiguous() or hist.device != dev:
-            raise L.SznError("calib: hist must be a contiguous int64 (%d,%d,%d) tensor on %s" % (G, K, K, dev))
-    pred = torch.empty(B, H, W, dtype=torch.int64, device=dev) if pred_index is not None else None
-    nbytes = L.load().szn_calib_head_workspace_bytes(stride, B, h, w, E, K, G)
-    if nbytes == 0:
-        raise L.SznError("calib: bad geometry (stride %d, B %d, map %d x %d, E %d, K %d, %d gammas)" % (stride, B, h, w, E, K, G))
-    buf = _scratch(nbytes, dev)
-    L.call("szn_calib_head", stride, B, h, w, E, ld, 0, H, W, _CROP[stride], K, L.ptr(fmap), L.ptr(emb), L.ptr(tgt),
-           L.class_set(unseen), G, g.ctypes.data_as(C.POINTER(C.c_float)), L.ptr(hist), -1 if pred_index is None else int(pred_index),
-           L.ptr(pred), L.ptr(buf), L.stream_ptr())
-    return hist, pred
+    _check_map("calib", fmap)
+    s = _SweepCall("calib", "gammas", fmap, emb, H, W, gammas, target, hist, pred_index)
+    buf = s.scratch(stride, L.load().szn_calib_head_workspace_bytes(stride, B, h, w, E, K, s.G))
+    L.call("szn_calib_head", stride, B, h, w, E, ld, 0, H, W, _CROP[stride], K, L.ptr(fmap), L.ptr(emb), L.ptr(s.tgt),
+           L.class_set(unseen), s.G, s.values, L.ptr(s.hist), s.pred_index, L.ptr(s.pred), L.ptr(buf), L.stream_ptr())
+    return s.hist, s.pred
 
 
 # ---- hubness correction: per-image, per-class centering / standardising of the similarities ----------------------------------------
@@ -428,39 +471,18 @@ def hub_stats(stride, fmap, emb, H, W, mode, beta, min_sd, target=None, want=())
 def hub(stride, fmap, emb, H, W, unseen, table, gammas, target=None, hist=None, pred_index=None):
     """szn_hub_head: calib() on the corrected similarities fmaf(sim, table[b][k][0], -table[b][k][1]) -- table (B,K,2) fp32 from hub_stats, or
     the caller's own.  Everything else is calib()'s: the gammas, hist, pred_index, what comes back.  -> (hist or None, pred or None)"""
-    import ctypes as C
     B, h, w, ld = fmap.shape
     K, E = emb.shape
-    if fmap.dtype != torch.float32 or not fmap.is_contiguous():
-        raise L.SznError("hub: the map must be a contiguous fp32 (B,h,w,C) tensor")
+    _check_map("hub", fmap)
     dev = fmap.device
     if (not isinstance(table, torch.Tensor) or table.dtype != torch.float32 or tuple(table.shape) != (B, K, 2) or not table.is_contiguous()
             or table.device != dev):
         raise L.SznError("hub: table must be a contiguous fp32 (%d,%d,2) tensor on %s" % (B, K, dev))
-    g = calib_gammas(gammas)
-    G = int(g.size)
-    if target is None and hist is not None:
-        raise L.SznError("hub: a histogram needs the target")
-    if target is None and pred_index is None:
-        raise L.SznError("hub: nothing to compute (no target for a histogram, no pred_index for a prediction)")
-    if pred_index is not None and not 0 <= int(pred_index) < G:
-        raise L.SznError("hub: pred_index %r outside [0, %d)" % (pred_index, G))
-    tgt = None
-    if target is not None:
-        tgt = target.to(device=dev, dtype=torch.int64).contiguous()
-        if hist is None:
-            hist = torch.zeros(G, K, K, dtype=torch.int64, device=dev)
-        elif hist.dtype != torch.int64 or tuple(hist.shape) != (G, K, K) or not hist.is_contiguous() or hist.device != dev:
-            raise L.SznError("hub: hist must be a contiguous int64 (%d,%d,%d) tensor on %s" % (G, K, K, dev))
-    pred = torch.empty(B, H, W, dtype=torch.int64, device=dev) if pred_index is not None else None
-    nbytes = L.load().szn_hub_head_workspace_bytes(stride, B, h, w, E, K, G)
-    if nbytes == 0:
-        raise L.SznError("hub: bad geometry (stride %d, B %d, map %d x %d, E %d, K %d, %d gammas)" % (stride, B, h, w, E, K, G))
-    buf = _scratch(nbytes, dev)
-    L.call("szn_hub_head", stride, B, h, w, E, ld, 0, H, W, _CROP[stride], K, L.ptr(fmap), L.ptr(emb), L.ptr(tgt), L.class_set(unseen),
-           L.ptr(table), G, g.ctypes.data_as(C.POINTER(C.c_float)), L.ptr(hist), -1 if pred_index is None else int(pred_index),
-           L.ptr(pred), L.ptr(buf), L.stream_ptr())
-    return hist, pred
+    s = _SweepCall("hub", "gammas", fmap, emb, H, W, gammas, target, hist, pred_index)
+    buf = s.scratch(stride, L.load().szn_hub_head_workspace_bytes(stride, B, h, w, E, K, s.G))
+    L.call("szn_hub_head", stride, B, h, w, E, ld, 0, H, W, _CROP[stride], K, L.ptr(fmap), L.ptr(emb), L.ptr(s.tgt), L.class_set(unseen),
+           L.ptr(table), s.G, s.values, L.ptr(s.hist), s.pred_index, L.ptr(s.pred), L.ptr(buf), L.stream_ptr())
+    return s.hist, s.pred
 
 
 # ---- ConSE: zero-shot inference for the softmax FCN ---------------------------------------------------------------------------
@@ -479,11 +501,9 @@ def conse(stride, fmap, emb, H, W, unseen, top_t, gammas=None, target=None, hist
     (allocated as zeros when None).  pred_index given: pred (B,H,W) int64 at gammas[pred_index].  forced=True (the reference's -fu):
     pred = the best unseen class where `target` names an unseen class, the best seen class elsewhere; no gammas, no hist.
     -> (hist or None, pred or None)"""
-    import ctypes as C
     B, h, w, ld = fmap.shape
     K, E = emb.shape
-    if fmap.dtype != torch.float32 or not fmap.is_contiguous():
-        raise L.SznError("conse: the map must be a contiguous fp32 (B,h,w,C) tensor")
+    _check_map("conse", fmap)
     if emb.dtype != torch.float32 or not emb.is_contiguous() or emb.device != fmap.device:
         raise L.SznError("conse: the embeddings must be a contiguous fp32 (K,E) tensor on the map's device")
     top_t = conse_top(top_t)
@@ -499,24 +519,10 @@ def conse(stride, fmap, emb, H, W, unseen, top_t, gammas=None, target=None, hist
     else:
         if gammas is None:
             raise L.SznError("conse: gammas are required (forced=False)")
-        g = calib_gammas(gammas)
-        G = int(g.size)
-        gp = g.ctypes.data_as(C.POINTER(C.c_float))
-        if tgt is None and hist is not None:
-            raise L.SznError("conse: a histogram needs the target")
-        if tgt is None and pred_index is None:
-            raise L.SznError("conse: nothing to compute (no target for a histogram, no pred_index for a prediction)")
-        if pred_index is not None and not 0 <= int(pred_index) < G:
-            raise L.SznError("conse: pred_index %r outside [0, %d)" % (pred_index, G))
-        if tgt is not None:
-            if hist is None:
-                hist = torch.zeros(G, K, K, dtype=torch.int64, device=dev)
-            elif hist.dtype != torch.int64 or tuple(hist.shape) != (G, K, K) or not hist.is_contiguous() or hist.device != dev:
-                raise L.SznError("conse: hist must be a contiguous int64 (%d,%d,%d) tensor on %s" % (G, K, K, dev))
-        pidx = -1 if pred_index is None else int(pred_index)
-        pred = torch.empty(B, H, W, dtype=torch.int64, device=dev) if pred_index is not None else None
+        s = _SweepCall("conse", "gammas", fmap, emb, H, W, gammas, tgt, hist, pred_index)
+        G, gp, hist, pidx, pred = s.G, s.values, s.hist, s.pred_index, s.pred
     nbytes = L.load().szn_conse_head_workspace_bytes(stride, B, h, w, E, K, G)
-    if nbytes == 0:
+    if nbytes == 0:         # (both branches: a forced call has no sweep to ask)
         raise L.SznError("conse: bad geometry (stride %d, B %d, map %d x %d, E %d, K %d, %d gammas)" % (stride, B, h, w, E, K, G))
     buf = _scratch(nbytes, dev)
     L.call("szn_conse_head", stride, B, h, w, K, ld, 0, H, W, _CROP[stride], E, L.ptr(fmap), L.ptr(emb), L.ptr(tgt),
@@ -528,13 +534,7 @@ def conse(stride, fmap, emb, H, W, unseen, top_t, gammas=None, target=None, hist
 def seen_sweep_taus(taus):
     """the candidate thresholds (logit units) as the float32 HOST array szn_seen_sweep_head reads: 1 to SEEN_SWEEP_MAX_TAUS finite,
     strictly ascending values"""
-    import numpy as np
-    t = np.ascontiguousarray(np.asarray(taus, dtype=np.float32).reshape(-1))
-    if not 1 <= t.size <= L.SEEN_SWEEP_MAX_TAUS:
-        raise L.SznError("seen sweep: %d taus, between 1 and %d are taken" % (t.size, L.SEEN_SWEEP_MAX_TAUS))
-    if not np.isfinite(t).all() or not (np.diff(t) > 0).all():
-        raise L.SznError("seen sweep: the taus must be finite and strictly ascending as float32 (got %r)" % (t.tolist(),))
-    return t
+    return _sweep_values("seen sweep", "taus", taus, L.SEEN_SWEEP_MAX_TAUS)
 
 
 def seen_sweep_workspace_bytes(stride, fmap, emb, n_taus):
@@ -544,6 +544,11 @@ def seen_sweep_workspace_bytes(stride, fmap, emb, n_taus):
     return L.load().szn_seen_sweep_head_workspace_bytes(stride, B, h, w, E, K, int(n_taus))
 
 
+def _check_margin(who, margin, B, H, W, dev):
+    if margin is None or margin.dtype != torch.float32 or tuple(margin.shape) != (B, H, W) or not margin.is_contiguous() or margin.device != dev:
+        raise L.SznError("%s: margin must be a contiguous fp32 (%d,%d,%d) tensor on %s" % (who, B, H, W, dev))
+
+
 def seen_sweep(stride, fmap, emb, H, W, unseen, margin, taus, target=None, hist=None, pred_index=None, ws=None):
     """szn_seen_sweep_head on the contiguous fp32 NHWC map `fmap` (the E embedding channels first): the grouped head's class assignment
     with a pixel in the seen group iff margin > tau (margin: seenmask_margin's (B,H,W) f32 map), for every tau of `taus` (ascending) in
@@ -551,42 +556,16 @@ def seen_sweep(stride, fmap, emb, H, W, unseen, margin, taus, target=None, hist=
     pred (B,H,W) int64 at taus[pred_index].  -> (hist or None, pred or None).  ws: None, or the Workspace in which embed() / embed_loss()
     has just run on this very map and embedding matrix, already as large as seen_sweep_workspace_bytes says: the embedding tables and the
     stride-8 position tables that call left there are reused (szn_seen_sweep_head_tabled)"""
-    import ctypes as C
     B, h, w, ld = fmap.shape
     K, E = emb.shape
-    if fmap.dtype != torch.float32 or not fmap.is_contiguous():
-        raise L.SznError("seen_sweep: the map must be a contiguous fp32 (B,h,w,C) tensor")
-    dev = fmap.device
-    if margin is None or margin.dtype != torch.float32 or tuple(margin.shape) != (B, H, W) or not margin.is_contiguous() or margin.device != dev:
-        raise L.SznError("seen_sweep: margin must be a contiguous fp32 (%d,%d,%d) tensor on %s" % (B, H, W, dev))
-    t = seen_sweep_taus(taus)
-    G = int(t.size)
-    if target is None and hist is not None:
-        raise L.SznError("seen_sweep: a histogram needs the target")
-    if target is None and pred_index is None:
-        raise L.SznError("seen_sweep: nothing to compute (no target for a histogram, no pred_index for a prediction)")
-    if pred_index is not None and not 0 <= int(pred_index) < G:
-        raise L.SznError("seen_sweep: pred_index %r outside [0, %d)" % (pred_index, G))
-    tgt = None
-    if target is not None:
-        tgt = target.to(device=dev, dtype=torch.int64).contiguous()
-        if hist is None:
-            hist = torch.zeros(G, K, K, dtype=torch.int64, device=dev)
-        elif hist.dtype != torch.int64 or tuple(hist.shape) != (G, K, K) or not hist.is_contiguous() or hist.device != dev:
-            raise L.SznError("seen_sweep: hist must be a contiguous int64 (%d,%d,%d) tensor on %s" % (G, K, K, dev))
-    pred = torch.empty(B, H, W, dtype=torch.int64, device=dev) if pred_index is not None else None
-    nbytes = seen_sweep_workspace_bytes(stride, fmap, emb, G)
-    if nbytes == 0:
-        raise L.SznError("seen_sweep: bad geometry (stride %d, B %d, map %d x %d, E %d, K %d, %d taus)" % (stride, B, h, w, E, K, G))
-    if ws is not None and (ws.buf is None or ws.buf.numel() < nbytes or ws.tables != Workspace.map_key(stride, fmap)
-                           or ws.prep != (ws.buf.data_ptr(), emb.data_ptr(), emb._version, K, E)):
-        raise L.SznError("seen_sweep: ws must be the Workspace in which the embedding head last ran on this very map and embedding "
-                         "matrix, %d bytes or more" % nbytes)
-    buf = _scratch(nbytes, dev) if ws is None else ws.buf
-    L.call("szn_seen_sweep_head" if ws is None else "szn_seen_sweep_head_tabled", stride, B, h, w, E, ld, 0, H, W, _CROP[stride], K, L.ptr(fmap), L.ptr(emb), L.ptr(tgt),
-           L.class_set(unseen), L.ptr(margin), G, t.ctypes.data_as(C.POINTER(C.c_float)), L.ptr(hist),
-           -1 if pred_index is None else int(pred_index), L.ptr(pred), L.ptr(buf), L.stream_ptr())
-    return hist, pred
+    _check_map("seen_sweep", fmap)
+    _check_margin("seen_sweep", margin, B, H, W, fmap.device)
+    s = _SweepCall("seen_sweep", "taus", fmap, emb, H, W, taus, target, hist, pred_index)
+    buf = s.scratch(stride, seen_sweep_workspace_bytes(stride, fmap, emb, s.G), ws)
+    L.call("szn_seen_sweep_head" if ws is None else "szn_seen_sweep_head_tabled", stride, B, h, w, E, ld, 0, H, W, _CROP[stride], K,
+           L.ptr(fmap), L.ptr(emb), L.ptr(s.tgt), L.class_set(unseen), L.ptr(margin), s.G, s.values, L.ptr(s.hist), s.pred_index,
+           L.ptr(s.pred), L.ptr(buf), L.stream_ptr())
+    return s.hist, s.pred
 
 
 # ---- full SZN inference with a soft seen/unseen gate ----------------------------------------------------------------------------
@@ -627,59 +606,38 @@ def soft_gate(stride, fmap, emb, H, W, unseen, margin, taus, temperature, weight
     the true in-group argmaxes.  Every tau of `taus` (ascending) in one pass.  target given: hist (G,K,K) int64 += the confusion counts of
     every tau (allocated as zeros when None).  pred_index given: pred (B,H,W) int64 at taus[pred_index].  want_eff: eff (B,H,W) f32 = e.
     -> (hist or None, pred or None, eff or None).  ws: as in seen_sweep() (szn_soft_gate_head_tabled)"""
-    import ctypes as C
     B, h, w, ld = fmap.shape
     K, E = emb.shape
-    if fmap.dtype != torch.float32 or not fmap.is_contiguous():
-        raise L.SznError("soft_gate: the map must be a contiguous fp32 (B,h,w,C) tensor")
-    dev = fmap.device
-    if margin is None or margin.dtype != torch.float32 or tuple(margin.shape) != (B, H, W) or not margin.is_contiguous() or margin.device != dev:
-        raise L.SznError("soft_gate: margin must be a contiguous fp32 (%d,%d,%d) tensor on %s" % (B, H, W, dev))
+    _check_map("soft_gate", fmap)
+    _check_margin("soft_gate", margin, B, H, W, fmap.device)
     wgt, temp = gate_params(dict(weight=weight, temperature=temperature))
-    t = seen_sweep_taus(taus)
-    G = int(t.size)
-    if target is None and hist is not None:
-        raise L.SznError("soft_gate: a histogram needs the target")
-    if target is None and pred_index is None and not want_eff:
-        raise L.SznError("soft_gate: nothing to compute (no target for a histogram, no pred_index for a prediction, no eff)")
-    if pred_index is not None and not 0 <= int(pred_index) < G:
-        raise L.SznError("soft_gate: pred_index %r outside [0, %d)" % (pred_index, G))
-    tgt = None
-    if target is not None:
-        tgt = target.to(device=dev, dtype=torch.int64).contiguous()
-        if hist is None:
-            hist = torch.zeros(G, K, K, dtype=torch.int64, device=dev)
-        elif hist.dtype != torch.int64 or tuple(hist.shape) != (G, K, K) or not hist.is_contiguous() or hist.device != dev:
-            raise L.SznError("soft_gate: hist must be a contiguous int64 (%d,%d,%d) tensor on %s" % (G, K, K, dev))
-    pred = torch.empty(B, H, W, dtype=torch.int64, device=dev) if pred_index is not None else None
-    eff = torch.empty(B, H, W, dtype=torch.float32, device=dev) if want_eff else None
-    nbytes = soft_gate_workspace_bytes(stride, fmap, emb, G)
-    if nbytes == 0:
-        raise L.SznError("soft_gate: bad geometry (stride %d, B %d, map %d x %d, E %d, K %d, %d taus)" % (stride, B, h, w, E, K, G))
-    if ws is not None and (ws.buf is None or ws.buf.numel() < nbytes or ws.tables != Workspace.map_key(stride, fmap)
-                           or ws.prep != (ws.buf.data_ptr(), emb.data_ptr(), emb._version, K, E)):
-        raise L.SznError("soft_gate: ws must be the Workspace in which the embedding head last ran on this very map and embedding "
-                         "matrix, %d bytes or more" % nbytes)
-    buf = _scratch(nbytes, dev) if ws is None else ws.buf
+    s = _SweepCall("soft_gate", "taus", fmap, emb, H, W, taus, target, hist, pred_index, extra=("eff", want_eff))
+    eff = torch.empty(B, H, W, dtype=torch.float32, device=fmap.device) if want_eff else None
+    buf = s.scratch(stride, soft_gate_workspace_bytes(stride, fmap, emb, s.G), ws)
     L.call("szn_soft_gate_head" if ws is None else "szn_soft_gate_head_tabled", stride, B, h, w, E, ld, 0, H, W, _CROP[stride], K,
-           L.ptr(fmap), L.ptr(emb), L.ptr(tgt), L.class_set(unseen), L.ptr(margin), temp, wgt, G, t.ctypes.data_as(C.POINTER(C.c_float)),
-           L.ptr(hist), -1 if pred_index is None else int(pred_index), L.ptr(pred), L.ptr(eff), L.ptr(buf), L.stream_ptr())
-    return hist, pred, eff
+           L.ptr(fmap), L.ptr(emb), L.ptr(s.tgt), L.class_set(unseen), L.ptr(margin), temp, wgt, s.G, s.values, L.ptr(s.hist),
+           s.pred_index, L.ptr(s.pred), L.ptr(eff), L.ptr(buf), L.stream_ptr())
+    return s.hist, s.pred, eff
 
 
 # ---- self-training: top-p% pseudo labels on the hidden pixels ------------------------------------------------------------------
 _PSEUDO_EXTRAS = ("cand", "conf", "qhist", "thr", "counts")
 
 
-def pseudo_permille(keep):
-    """the share of the candidates to keep, a number in (0, 1], as the integer permille szn_pseudo_head takes (rounded; at least 1)"""
+def _permille(who, keep):
+    """a share in (0, 1] as the integer permille szn_pseudo_head / szn_ohem_head take (rounded; at least 1)"""
     try:
         k = float(keep)
     except (TypeError, ValueError):
-        raise L.SznError("pseudo labels: keep must be a number in (0, 1], got %r" % (keep,))
+        raise L.SznError("%s: keep must be a number in (0, 1], got %r" % (who, keep))
     if not 0.0 < k <= 1.0:
-        raise L.SznError("pseudo labels: keep must lie in (0, 1], got %r" % (keep,))
+        raise L.SznError("%s: keep must lie in (0, 1], got %r" % (who, keep))
     return max(1, int(round(k * 1000.0)))
+
+
+def pseudo_permille(keep):
+    """the share of the candidates to keep, a number in (0, 1], as the integer permille szn_pseudo_head takes (rounded; at least 1)"""
+    return _permille("pseudo labels", keep)
 
 
 def pseudo_call(stride, fmap, emb, H, W, target, unseen_cs, gamma, permille, conf_floor, cand_label, target_out, ws_buf, stream,
@@ -744,13 +702,7 @@ _OHEM_EXTRAS = ("conf", "qhist", "cut", "counts")
 def ohem_permille(keep):
     """the share of an image's labelled pixels to keep, a number in (0, 1], as the integer permille szn_ohem_head takes (rounded; at
     least 1)"""
-    try:
-        k = float(keep)
-    except (TypeError, ValueError):
-        raise L.SznError("ohem: keep must be a number in (0, 1], got %r" % (keep,))
-    if not 0.0 < k <= 1.0:
-        raise L.SznError("ohem: keep must lie in (0, 1], got %r" % (keep,))
-    return max(1, int(round(k * 1000.0)))
+    return _permille("ohem", keep)
 
 
 def ohem_call(stride, fmap, emb, H, W, target, skip_cs, permille, thresh, drop_label, target_out, ws_buf, stream, conf=None, qhist=None,

@@ -36,6 +36,11 @@ def get_upsampling_weight(in_channels, out_channels, kernel_size):
     return torch.from_numpy(synth.bilinear_weight(in_channels, out_channels, kernel_size))
 
 
+def _fp32_map(fmap):
+    """the fp32 view of a head map the fp32-only heads read: the map itself when it is fp32 already"""
+    return fmap if fmap.dtype == torch.float32 else fmap.to(torch.float32)
+
+
 def _round_up(a, b):
     return (a + b - 1) // b * b
 
@@ -1535,18 +1540,9 @@ class FCN32s(nn.Module):
         -> (loss, pred, hist): the loss is embed_predict's on that map, bit for bit (None without a target); pred (B,H,W) int64 is
         the calibrated prediction at gammas[pred_index], or embed_predict's own when pred_index is None; hist (G,K,K) int64 holds
         the confusion counts of every gamma: `hist` accumulated in place when given, a fresh one with a target, else None."""
-        kind = heads.embed_kind(loss)
-        with torch.no_grad():
-            ctx, stride, fmap = self._head_map(x)
-            emb = heads.embeddings(embeddings, self.n_class, fmap.device)
-            loss_t, pred = heads.embed_predict(kind, stride, fmap, emb, ctx.H, ctx.W, target, **self._head_kw(kind))
-            if target is not None or pred_index is not None:
-                fmap32 = fmap if fmap.dtype == torch.float32 else fmap.to(torch.float32)
-                hist, cpred = heads.calib(stride, fmap32, emb, ctx.H, ctx.W, unseen, gammas, target, hist, pred_index)
-                if pred_index is not None:
-                    pred = cpred
-            self._last_pred = pred
-        return loss_t, pred, hist
+        def sweep(ctx, stride, fmap32, emb, ws):
+            return heads.calib(stride, fmap32, emb, ctx.H, ctx.W, unseen, gammas, target, hist, pred_index)
+        return self._sweep_route(x, embeddings, heads.embed_kind(loss), target, hist, pred_index, sweep)
 
     def hub_predict(self, x, embeddings, unseen, hub, gammas, target=None, hist=None, pred_index=None, loss="cos"):
         """calib_predict with the hubness correction hub = dict(mode=, beta=, min_sd=) (heads.hub_params): the same forward pass and loss
@@ -1556,18 +1552,11 @@ class FCN32s(nn.Module):
         the stored image's, unchanged.  The table is left in self._last_hub_table."""
         kind = heads.embed_kind(loss)
         p = heads.hub_params(hub)
-        with torch.no_grad():
-            ctx, stride, fmap = self._head_map(x)
-            emb = heads.embeddings(embeddings, self.n_class, fmap.device)
-            loss_t, pred = heads.embed_predict(kind, stride, fmap, emb, ctx.H, ctx.W, target, **self._head_kw(kind))
-            if target is not None or pred_index is not None:
-                fmap32 = fmap if fmap.dtype == torch.float32 else fmap.to(torch.float32)
-                self._last_hub_table = heads.hub_stats(stride, fmap32, emb, ctx.H, ctx.W, p["mode"], p["beta"], p["min_sd"], target)
-                hist, cpred = heads.hub(stride, fmap32, emb, ctx.H, ctx.W, unseen, self._last_hub_table, gammas, target, hist, pred_index)
-                if pred_index is not None:
-                    pred = cpred
-            self._last_pred = pred
-        return loss_t, pred, hist
+
+        def sweep(ctx, stride, fmap32, emb, ws):
+            self._last_hub_table = heads.hub_stats(stride, fmap32, emb, ctx.H, ctx.W, p["mode"], p["beta"], p["min_sd"], target)
+            return heads.hub(stride, fmap32, emb, ctx.H, ctx.W, unseen, self._last_hub_table, gammas, target, hist, pred_index)
+        return self._sweep_route(x, embeddings, kind, target, hist, pred_index, sweep)
 
     def conse_predict(self, x, embeddings, unseen, top_t, gammas=None, target=None, hist=None, pred_index=None, forced=False):
         """ConSE zero-shot inference for the softmax network (Norouzi et al., ICLR 2014): one forward pass, then on the same logit map
@@ -1587,7 +1576,7 @@ class FCN32s(nn.Module):
             loss_t = None
             if target is not None:
                 loss_t, _ = heads.ce_predict(stride, fmap, self.n_class, ctx.H, ctx.W, target)
-            fmap32 = fmap if fmap.dtype == torch.float32 else fmap.to(torch.float32)
+            fmap32 = _fp32_map(fmap)
             hist, pred = heads.conse(stride, fmap32, emb, ctx.H, ctx.W, unseen, top_t, gammas, target, hist, pred_index, forced)
             self._last_pred = pred
         return loss_t, pred, hist
@@ -1600,7 +1589,7 @@ class FCN32s(nn.Module):
         batch is added to it.  utils.blend_prototypes turns them into adapted embeddings."""
         with torch.no_grad():
             ctx, stride, fmap = self._head_map(x)
-            fmap32 = fmap if fmap.dtype == torch.float32 else fmap.to(torch.float32)
+            fmap32 = _fp32_map(fmap)
             return heads.class_proto(stride, fmap32, ctx.H, ctx.W, labels, K, classes, mode, out, E=self.n_class)
 
     def seen_sweep_predict(self, x, embeddings, unseen, taus, target=None, hist=None, pred_index=None, loss="cos"):
@@ -1627,29 +1616,40 @@ class FCN32s(nn.Module):
     def _seen_route_predict(self, x, embeddings, unseen, taus, gate, target, hist, pred_index, loss):
         """seen_sweep_predict (gate None) and seen_gate_predict (gate = (weight, temperature)): one launch sequence, another sweep head"""
         kind = heads.embed_kind(loss)
+        self._last_margin = None
+
+        def sweep(ctx, stride, fmap32, emb, ws):
+            self._last_margin = heads.seenmask_margin(ctx.coarse, self.n_class, self._engine._images["up.w"], ctx.H, ctx.W)
+            counted = target if (hist is not None or pred_index is None) else None
+            if gate is None:
+                return heads.seen_sweep(stride, fmap32, emb, ctx.H, ctx.W, unseen, self._last_margin, taus, counted, hist, pred_index, ws=ws)
+            return heads.soft_gate(stride, fmap32, emb, ctx.H, ctx.W, unseen, self._last_margin, taus, gate[1], gate[0], counted, hist,
+                                   pred_index, ws=ws)[:2]
+
+        def ws_bytes(stride, fmap, emb):
+            return heads.seen_sweep_workspace_bytes(stride, fmap, emb, len(heads.seen_sweep_taus(taus)))
+        return self._sweep_route(x, embeddings, kind, target, hist, pred_index, sweep, ws_bytes)
+
+    def _sweep_route(self, x, embeddings, kind, target, hist, pred_index, sweep, ws_bytes=None):
+        """the route calib_predict, hub_predict, seen_sweep_predict and seen_gate_predict share: one forward pass, the plain embedding
+        head `kind` for the loss, then -- with a target or a pred_index -- sweep(ctx, stride, the map's fp32 view, emb, ws) -> (hist,
+        swept pred) on the same map.  -> (loss, pred, hist): pred is the swept one with a pred_index, else the plain head's; it is also
+        left in self._last_pred.  ws_bytes(stride, fmap, emb), given by the sweeps that reuse the plain head's tables: with a target, a
+        pred_index and an fp32 map the plain head runs for the loss alone in a Workspace of that size, which the sweep receives as ws."""
         with torch.no_grad():
             ctx, stride, fmap = self._head_map(x)
             emb = heads.embeddings(embeddings, self.n_class, fmap.device)
             ws = None
-            if target is not None and pred_index is not None and fmap.dtype == torch.float32:
+            if ws_bytes is not None and target is not None and pred_index is not None and fmap.dtype == torch.float32:
                 # the sweep head writes the prediction: the plain head runs for the loss alone (no class loop per pixel), in the sweep
                 # head's workspace, which then finds the embedding tables and the stride-8 position tables of this map in place
                 ws = heads.Workspace(fmap.device)
-                ws.get(heads.seen_sweep_workspace_bytes(stride, fmap, emb, len(heads.seen_sweep_taus(taus))))
+                ws.get(ws_bytes(stride, fmap, emb))
                 loss_t, pred = heads.embed_loss(kind, stride, fmap, emb, ctx.H, ctx.W, target, ws=ws, **self._head_kw(kind)), None
             else:
                 loss_t, pred = heads.embed_predict(kind, stride, fmap, emb, ctx.H, ctx.W, target, **self._head_kw(kind))
-            self._last_margin = None
             if target is not None or pred_index is not None:
-                self._last_margin = heads.seenmask_margin(ctx.coarse, self.n_class, self._engine._images["up.w"], ctx.H, ctx.W)
-                fmap32 = fmap if fmap.dtype == torch.float32 else fmap.to(torch.float32)
-                counted = target if (hist is not None or pred_index is None) else None
-                if gate is None:
-                    hist, spred = heads.seen_sweep(stride, fmap32, emb, ctx.H, ctx.W, unseen, self._last_margin, taus, counted, hist,
-                                                   pred_index, ws=ws)
-                else:
-                    hist, spred, _ = heads.soft_gate(stride, fmap32, emb, ctx.H, ctx.W, unseen, self._last_margin, taus, gate[1], gate[0],
-                                                     counted, hist, pred_index, ws=ws)
+                hist, spred = sweep(ctx, stride, _fp32_map(fmap), emb, ws)
                 if pred_index is not None:
                     pred = spred
             self._last_pred = pred

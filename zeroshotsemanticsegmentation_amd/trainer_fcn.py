@@ -20,6 +20,7 @@ import torch
 from . import engine as _engine
 from . import utils
 from . import vis_utils
+from ._lib import SznError
 
 _DATA = osp.join(osp.dirname(osp.abspath(__file__)), "data")      # package data: .npy re-saves of the reference's pickles
 
@@ -43,83 +44,95 @@ def _now():
     return datetime.datetime.now(datetime.timezone(datetime.timedelta(hours=-5)))      # 'US/Eastern' (no DST handling)
 
 
+# why a configuration cannot run one of the five inference rules that sweep a scalar: per rule the reasons in the order they are
+# tried, each with its whole sentence (the one with %d names the class count).  A rule's sentences are its own: rewording one
+# changes that rule alone
+_REFUSALS = {
+    "calibration": (
+        ("unseen", "calibration needs unseen classes (train_unseen / val_unseen): without them there is no seen group to penalise"),
+        ("config", "calibration needs an embedding configuration (loss 'cos' | 'mse' | 'sim_ce' | 'rank'): a softmax network has no unseen-class scores"),
+        ("forced", "calibration and forced_unseen are two different class-assignment rules: pick one"),
+        ("mode", "calibration replaces the seen-mask classifier of -m test_all: use -m test_fcn"),
+        ("views", "calibration with eval_scales / eval_flip is not built (the view-ensemble head has no penalty)"),
+        ("classes", "calibration: the fused head holds at most 256 classes, got %d"),
+        ("verbose", "calibration: SZN_VERBOSE_VAL needs the materialised score, which the calibrated head never forms")),
+    "hub": (
+        ("unseen", "the hubness correction needs unseen classes (train_unseen / val_unseen): without them there are no two class groups to decide between"),
+        ("config", "the hubness correction needs an embedding configuration (loss 'cos' | 'mse' | 'sim_ce' | 'rank'): a softmax network has no unseen-class scores"),
+        ("forced", "the hubness correction and forced_unseen are two different class-assignment rules: pick one"),
+        ("mode", "the hubness correction replaces the seen-mask classifier of -m test_all: use -m test_fcn"),
+        ("views", "the hubness correction with eval_scales / eval_flip is not built (the view-ensemble head has no correction)"),
+        ("classes", "the hubness correction: the fused head holds at most 256 classes, got %d"),
+        ("verbose", "the hubness correction: SZN_VERBOSE_VAL needs the materialised score, which the corrected head never forms")),
+    "seen_threshold": (
+        ("unseen", "a seen-mask threshold needs unseen classes (train_unseen / val_unseen): without them there is one class group"),
+        ("config", "a seen-mask threshold needs an embedding configuration (loss 'cos' | 'mse' | 'sim_ce' | 'rank'): a softmax network has no class groups"),
+        ("forced", "a seen-mask threshold and forced_unseen are two different class-assignment rules: pick one"),
+        ("mode", "a seen-mask threshold acts on the full SZN network only: validate(both_fcn_and_seenmask=True), -m test_all"),
+        ("views", "a seen-mask threshold with eval_scales / eval_flip is not built (the view-ensemble head takes its own group map)"),
+        ("classes", "a seen-mask threshold: the fused head holds at most 256 classes, got %d"),
+        ("verbose", "a seen-mask threshold: SZN_VERBOSE_VAL needs the materialised score, which the sweep head never forms")),
+    "seen_gate": (
+        ("unseen", "the soft seen/unseen gate needs unseen classes (train_unseen / val_unseen): without them there is one class group"),
+        ("config", "the soft seen/unseen gate needs an embedding configuration (loss 'cos' | 'mse' | 'sim_ce' | 'rank'): a softmax network has no class groups"),
+        ("forced", "the soft seen/unseen gate and forced_unseen are two different class-assignment rules: pick one"),
+        ("mode", "the soft seen/unseen gate acts on the full SZN network only: validate(both_fcn_and_seenmask=True), -m test_all"),
+        ("views", "the soft seen/unseen gate with eval_scales / eval_flip is not built (the view-ensemble head takes its own group map)"),
+        ("classes", "the soft seen/unseen gate: the fused head holds at most 256 classes, got %d"),
+        ("verbose", "the soft seen/unseen gate: SZN_VERBOSE_VAL needs the materialised score, which the sweep head never forms")),
+    "conse": (
+        ("unseen", "conse needs unseen classes (train_unseen / val_unseen): without them the channel argmax already names every class"),
+        ("config", "conse needs the softmax configuration (fcn_loss 'cross_entropy', embed_dim 0): an embedding network has heads of its own"),
+        ("mode", "conse on the full SZN network (-m test_all, seen-mask grouping) is not built: use -m test_fcn"),
+        ("views", "conse with eval_scales / eval_flip is not built (averaging softmax probabilities over views is not)"),
+        ("forced", "conse: forced_unseen picks the class group from the target, a gamma or a sweep picks it from the margin: pick one")),
+}
+
+
+def _refused(rule, n_class=0, **holds):
+    """the sentence of the first reason of `rule` (_REFUSALS) that holds, or None"""
+    for reason, sentence in _REFUSALS[rule]:
+        if holds[reason]:
+            return sentence % n_class if reason == "classes" else sentence
+    return None
+
+
 def calibration_refused(has_unseen, embed_cfg, forced_unseen, test_all, eval_views, n_class, verbose_val=False):
     """why a configuration cannot run calibrated stacking (calibration= / calib_sweep=, train.py --calibration / --calib-sweep), or
     None: it penalises the seen classes of the plain embedding head, so it needs unseen classes and an embedding configuration, and it
     replaces the other class-assignment rules rather than combining with them"""
-    if not has_unseen:
-        return "calibration needs unseen classes (train_unseen / val_unseen): without them there is no seen group to penalise"
-    if not embed_cfg:
-        return "calibration needs an embedding configuration (loss 'cos' | 'mse' | 'sim_ce' | 'rank'): a softmax network has no unseen-class scores"
-    if forced_unseen:
-        return "calibration and forced_unseen are two different class-assignment rules: pick one"
-    if test_all:
-        return "calibration replaces the seen-mask classifier of -m test_all: use -m test_fcn"
-    if eval_views:
-        return "calibration with eval_scales / eval_flip is not built (the view-ensemble head has no penalty)"
-    if n_class > 256:
-        return "calibration: the fused head holds at most 256 classes, got %d" % n_class
-    if verbose_val:
-        return "calibration: SZN_VERBOSE_VAL needs the materialised score, which the calibrated head never forms"
-    return None
+    return _refused("calibration", n_class, unseen=not has_unseen, config=not embed_cfg, forced=forced_unseen, mode=test_all,
+                    views=eval_views, classes=n_class > 256, verbose=verbose_val)
 
 
 def seen_threshold_refused(has_unseen, embed_cfg, forced_unseen, test_all, eval_views, n_class, verbose_val=False):
     """why a configuration cannot threshold the seen-mask decision (seen_threshold= / seen_sweep=, train.py --seen-threshold /
     --seen-sweep), or None: the threshold moves the operating point of the full SZN network (validate(True), -m test_all), whose
     seen-mask classifier picks the class group per pixel inside the fused embedding head"""
-    if not has_unseen:
-        return "a seen-mask threshold needs unseen classes (train_unseen / val_unseen): without them there is one class group"
-    if not embed_cfg:
-        return "a seen-mask threshold needs an embedding configuration (loss 'cos' | 'mse' | 'sim_ce' | 'rank'): a softmax network has no class groups"
-    if forced_unseen:
-        return "a seen-mask threshold and forced_unseen are two different class-assignment rules: pick one"
-    if not test_all:
-        return "a seen-mask threshold acts on the full SZN network only: validate(both_fcn_and_seenmask=True), -m test_all"
-    if eval_views:
-        return "a seen-mask threshold with eval_scales / eval_flip is not built (the view-ensemble head takes its own group map)"
-    if n_class > 256:
-        return "a seen-mask threshold: the fused head holds at most 256 classes, got %d" % n_class
-    if verbose_val:
-        return "a seen-mask threshold: SZN_VERBOSE_VAL needs the materialised score, which the sweep head never forms"
-    return None
+    return _refused("seen_threshold", n_class, unseen=not has_unseen, config=not embed_cfg, forced=forced_unseen, mode=not test_all,
+                    views=eval_views, classes=n_class > 256, verbose=verbose_val)
 
 
 def seen_gate_refused(has_unseen, embed_cfg, forced_unseen, test_all, eval_views, n_class, verbose_val=False):
     """why a configuration cannot run the soft seen/unseen gate (seen_gate=, train.py --seen-gate), or None: the gate replaces the cut on
     the seen-mask margin by a per-pixel one inside the same sweep head, so seen_threshold_refused's reasons are its reasons"""
-    why = seen_threshold_refused(has_unseen, embed_cfg, forced_unseen, test_all, eval_views, n_class, verbose_val)
-    return None if why is None else why.replace("a seen-mask threshold", "the soft seen/unseen gate")
+    return _refused("seen_gate", n_class, unseen=not has_unseen, config=not embed_cfg, forced=forced_unseen, mode=not test_all,
+                    views=eval_views, classes=n_class > 256, verbose=verbose_val)
 
 
 def hub_refused(has_unseen, embed_cfg, forced_unseen, test_all, eval_views, n_class, verbose_val=False):
     """why a configuration cannot run the hubness correction (hub=, train.py --hub-correct), or None: the correction acts on the
     similarities that enter calibrated stacking's rule inside the same head, so calibration_refused's reasons are its reasons"""
-    why = calibration_refused(has_unseen, embed_cfg, forced_unseen, test_all, eval_views, n_class, verbose_val)
-    if why is None:
-        return None
-    why = why.replace("calibration and forced_unseen", "the hubness correction and forced_unseen")
-    why = why.replace("there is no seen group to penalise", "there are no two class groups to decide between")
-    why = why.replace("the view-ensemble head has no penalty", "the view-ensemble head has no correction")
-    why = why.replace("which the calibrated head never forms", "which the corrected head never forms")
-    return why.replace("calibration", "the hubness correction", 1)
+    return _refused("hub", n_class, unseen=not has_unseen, config=not embed_cfg, forced=forced_unseen, mode=test_all,
+                    views=eval_views, classes=n_class > 256, verbose=verbose_val)
 
 
 def conse_refused(has_unseen, softmax_cfg, forced_unseen, test_all, eval_views, tuned):
     """why a configuration cannot run ConSE zero-shot inference (conse= / conse_sweep=, train.py --conse / --conse-sweep), or None: ConSE
     mixes class embeddings with the softmax network's seen-class probabilities, so it needs unseen classes and the softmax
     configuration (cross entropy, no embedding); `tuned` = a gamma other than 0 or a sweep was asked for"""
-    if not has_unseen:
-        return "conse needs unseen classes (train_unseen / val_unseen): without them the channel argmax already names every class"
-    if not softmax_cfg:
-        return "conse needs the softmax configuration (fcn_loss 'cross_entropy', embed_dim 0): an embedding network has heads of its own"
-    if test_all:
-        return "conse on the full SZN network (-m test_all, seen-mask grouping) is not built: use -m test_fcn"
-    if eval_views:
-        return "conse with eval_scales / eval_flip is not built (averaging softmax probabilities over views is not)"
-    if forced_unseen and tuned:
-        return "conse: forced_unseen picks the class group from the target, a gamma or a sweep picks it from the margin: pick one"
-    return None
+    return _refused("conse", unseen=not has_unseen, config=not softmax_cfg, mode=test_all, views=eval_views,
+                    forced=forced_unseen and tuned)
 
 
 def pseudo_refused(has_unseen, embed_cfg, n_class):
@@ -179,7 +192,6 @@ def proto_refused(has_unseen, embed_cfg, n_class, shots=1):
 
 def check_proto(proto):
     """proto = dict(shots=, alpha=PROTO_ALPHA, mode="unit", min_pixels=1) checked -> the dict with every key filled in"""
-    from ._lib import SznError
     from .heads import proto_mode
     if not isinstance(proto, dict) or "shots" not in proto or set(proto) - {"shots", "alpha", "mode", "min_pixels"}:
         raise SznError("proto = dict(shots=N[, alpha=, mode=, min_pixels=]), got %r" % (proto,))
@@ -197,6 +209,92 @@ def check_proto(proto):
         raise SznError("proto: min_pixels must be at least 1 (got %r)" % (cfg["min_pixels"],))
     proto_mode(cfg["mode"])
     return cfg
+
+
+class _Sweep(object):
+    """one sweep of validation -- the calibration gammas, ConSE's gammas, the seen-mask taus: the trainer's candidate values (its
+    attribute `attr`, None: no sweep) and the value in use (used() -> a float, or None: none), and while a validation runs (begin ..
+    finish) the merged ascending values `all` with their (G,K,K) device histogram `hist`.  With a sweep and a value in use the value
+    joins the candidates for the head call (one launch gives both); the rows of the candidates are picked out afterwards."""
+    all = hist = None
+
+    def __init__(self, trainer, attr, used, label, noun, fname, tag, best, no_room):
+        self.t, self.attr, self.used = trainer, attr, used
+        self.label, self.noun, self.fname, self.tag = label, noun, fname, tag        # prints; '<fname>' and its column; tensorboard
+        self.best, self.no_room = best, no_room          # the trainer's two best-value attributes; the 64-cap sentence
+
+    def candidates(self):
+        return getattr(self.t, self.attr)
+
+    def begin(self):
+        used = self.used()
+        extra = [] if used is None else [np.float32(used)]
+        self.all = np.unique(np.concatenate([self.candidates(), np.asarray(extra, dtype=np.float32)]))
+        if self.all.size > 64:
+            raise SznError(self.no_room)
+        self.hist = torch.zeros(self.all.size, self.t.n_class, self.t.n_class, dtype=torch.int64, device=self.t.device)
+
+    def values(self):
+        """what the head call sweeps: the value in use alone outside a sweep"""
+        return [self.used()] if self.hist is None else self.all
+
+    def index(self):
+        """where the value in use stands among values(), None without one"""
+        used = self.used()
+        if used is None:
+            return None
+        return 0 if self.hist is None else int(np.searchsorted(self.all, np.float32(used)))
+
+    def finish(self, world):
+        """the validation is over: -> its histogram summed over the ranks as a numpy array, or None outside a sweep.  A collective:
+        every rank calls it, for every sweep in the same order"""
+        hist, self.hist = self.hist, None
+        if hist is None:
+            return None
+        if world > 1:
+            import torch.distributed as dist
+            dist.all_reduce(hist)
+        return hist.cpu().numpy()
+
+    def scan(self, hist_all):
+        """-> ([(value, its (K,K) histogram, metrics, seen metrics, unseen metrics, harmonic mean) per candidate], best): hist_all
+        follows `all`; best = the (value, harmonic mean) of the largest harmonic mean, or None; ties go to the value nearest 0 (a NaN
+        never wins)"""
+        rows, best = [], None
+        for val, g in zip(self.candidates(), np.searchsorted(self.all, self.candidates())):
+            m, ms, mu = utils.calib_rows(hist_all[g], self.t.n_class, self.t.val_unseen)
+            hm = utils.harmonic_mean_iu(ms, mu)
+            rows.append((float(val), hist_all[g], m, ms, mu, hm))
+            if not np.isnan(hm) and (best is None or hm > best[1] or (hm == best[1] and abs(float(val)) < abs(best[0]))):
+                best = (float(val), hm)
+        return rows, best
+
+    def keep_best(self, best):
+        if best is not None:
+            setattr(self.t, self.best[0], best[0])
+            setattr(self.t, self.best[1], best[1])
+
+    def report(self, hist_all, fname=None, label=None, detail='', tag=None, extra=()):
+        """rank 0, once per validation: one <fname> row per candidate and the candidate with the largest harmonic mean.  fname /
+        label / tag: another file, print label or tensorboard tag than the sweep's own; detail follows the label in the best-value
+        print; extra: (column, value) pairs appended to every row"""
+        t, label, tag = self.t, label or self.label, tag or self.tag
+        rows, best = self.scan(hist_all)
+        path = osp.join(t.log_dir, fname or self.fname)
+        if not osp.exists(path):
+            with open(path, 'w') as f:
+                f.write(','.join(['epoch,iteration,%s,val/pxl_acc,val/mean_iu,val/seen/mean_iu,val/unseen/mean_iu,val/harmonic_mean_iu' % self.noun]
+                                 + [k for k, _ in extra]) + '\n')
+        with open(path, 'a') as f:
+            for val, _, m, ms, mu, hm in rows:
+                f.write(','.join(map(str, [t.epoch, t.iteration, val, m[0], m[2], ms[2], mu[2], hm] + [v for _, v in extra])) + '\n')
+        self.keep_best(best)
+        if best is not None:
+            print('%s%s: best %s %g, harmonic mean IU %.3f' % ((label, detail, self.noun) + best))
+            t.tb_writer.add_scalar('%s/best_%s' % (tag, self.noun), best[0], t.epoch)
+            t.tb_writer.add_scalar('%s/best_harmonic_mean_iu' % tag, best[1], t.epoch)
+        else:
+            print('%s: no %s has a harmonic mean IU (the validation set holds no seen or no unseen pixels)' % (label, self.noun))
 
 
 class _NullWriter(object):
@@ -239,7 +337,6 @@ class Trainer(object):
         # loss_func "sim_ce" (utils.sim_ce_loss, szn_fused_simce_head): the softmax runs over the seen classes -- its `exclude` is
         # self.unseen -- at this temperature (None: heads.SIM_TEMPERATURE); every fused call reads both from the model
         if sim_temperature is not None and loss_func != "sim_ce":
-            from ._lib import SznError
             raise SznError("sim_temperature belongs to loss 'sim_ce' (got loss %r)" % (loss_func,))
         from .heads import SIM_TEMPERATURE
         self.sim_temperature = float(SIM_TEMPERATURE if sim_temperature is None else sim_temperature)
@@ -248,7 +345,6 @@ class Trainer(object):
         # loss_func "rank" (utils.rank_loss, szn_fused_rank_head): the hinges run over the seen classes -- `exclude` is self.unseen --
         # at this margin (None: heads.RANK_MARGIN), summed or (rank_hardest) the hardest negative alone; the model carries all three
         if (rank_margin is not None or rank_hardest) and loss_func != "rank":
-            from ._lib import SznError
             raise SznError("rank_margin / rank_hardest belong to loss 'rank' (got loss %r)" % (loss_func,))
         from .heads import RANK_MARGIN
         self.rank_margin, self.rank_hardest = float(RANK_MARGIN if rank_margin is None else rank_margin), bool(rank_hardest)
@@ -260,7 +356,6 @@ class Trainer(object):
         self.eval_flip = bool(eval_flip)
         self._ms_warned = False
         if (self.eval_scales or self.eval_flip) and not (pixel_embeddings and loss_func in _EMBED_LOSSES):
-            from ._lib import SznError
             raise SznError("eval_scales / eval_flip need an embedding configuration (loss 'cos' | 'mse' | 'sim_ce' | 'rank'): averaging softmax "
                            "probabilities over views is not built")
         if self.eval_flip and not self.eval_scales:
@@ -301,6 +396,7 @@ class Trainer(object):
         if seen_gate is not None:
             from .heads import gate_params
             self.seen_gate = dict(zip(("weight", "temperature"), gate_params(seen_gate)))
+        self._init_sweeps()
 
         self.epoch = 0
         self.iteration = 0
@@ -317,19 +413,15 @@ class Trainer(object):
             why = calibration_refused(bool(self.unseen), bool(pixel_embeddings) and loss_func in _EMBED_LOSSES, forced_unseen,
                                       False, bool(self.eval_scales), self.n_class, self.verbose_val)
             if why:
-                from ._lib import SznError
                 raise SznError(why)
             if self.calibration is not None and not np.isfinite(self.calibration):
-                from ._lib import SznError
                 raise SznError("calibration: gamma must be finite (got %r)" % (calibration,))
         if self.hub is not None:
-            from ._lib import SznError
             why = hub_refused(bool(self.unseen), bool(pixel_embeddings) and loss_func in _EMBED_LOSSES, forced_unseen,
                               False, bool(self.eval_scales), self.n_class, self.verbose_val)
             if why:
                 raise SznError(why)
         if self.seen_threshold is not None or self.seen_sweep is not None:
-            from ._lib import SznError
             why = seen_threshold_refused(bool(self.unseen), bool(pixel_embeddings) and loss_func in _EMBED_LOSSES, forced_unseen,
                                          True, bool(self.eval_scales), self.n_class, self.verbose_val)
             if why:
@@ -337,7 +429,6 @@ class Trainer(object):
             if self.seen_threshold is not None and not np.isfinite(self.seen_threshold):
                 raise SznError("seen_threshold: tau must be finite (got %r)" % (seen_threshold,))
         if self.seen_gate is not None:
-            from ._lib import SznError
             why = seen_gate_refused(bool(self.unseen), bool(pixel_embeddings) and loss_func in _EMBED_LOSSES, forced_unseen,
                                     True, bool(self.eval_scales), self.n_class, self.verbose_val)
             if why:
@@ -353,10 +444,8 @@ class Trainer(object):
         self.best_conse_gamma = None
         self.best_conse_harmonic_mean_iu = None
         if conse_sweep is not None and conse is None:
-            from ._lib import SznError
             raise SznError("conse_sweep belongs to conse= (ConSE inference), which is off")
         if conse is not None:
-            from ._lib import SznError
             from .heads import calib_gammas, conse_top
             cfg = dict(conse)
             if set(cfg) - {"top", "dim", "gamma"} or "top" not in cfg:
@@ -387,7 +476,6 @@ class Trainer(object):
         self.pseudo = None
         self.pseudo_start_epoch = int(pseudo_start_epoch)
         if pseudo is not None:
-            from ._lib import SznError
             why = pseudo_refused(bool(self.unseen), bool(pixel_embeddings) and loss_func in _EMBED_LOSSES, self.n_class)
             if why:
                 raise SznError(why)
@@ -411,7 +499,6 @@ class Trainer(object):
         self.ohem = None
         self.ohem_start_epoch = int(ohem_start_epoch)
         if ohem is not None:
-            from ._lib import SznError
             why = ohem_refused(bool(pixel_embeddings) and loss_func in _EMBED_LOSSES, self.n_class)
             if why:
                 raise SznError(why)
@@ -431,7 +518,6 @@ class Trainer(object):
         self.bias_loss = None
         self.bias_start_epoch = int(bias_start_epoch)
         if bias_loss is not None:
-            from ._lib import SznError
             from .heads import bias_args
             why = bias_refused(bool(self.unseen), bool(pixel_embeddings), loss_func, self.n_class)
             if why:
@@ -462,7 +548,6 @@ class Trainer(object):
         self.support_loader = support_loader
         self.last_proto = None                       # the last validation's (sums, counts) as numpy arrays
         if proto is not None:
-            from ._lib import SznError
             why = proto_refused(bool(self.unseen), self._embed_cfg(), self.n_class, proto.get("shots", 1) if isinstance(proto, dict) else 1)
             if why:
                 raise SznError(why)
@@ -475,7 +560,6 @@ class Trainer(object):
                     with open(osp.join(self.log_dir, 'proto_log.csv'), 'w') as f:
                         f.write('epoch,class,name,shots,participating,contributing,cos_word_proto\n')
         elif support_loader is not None:
-            from ._lib import SznError
             raise SznError("support_loader belongs to proto= (prototype adaptation), which is off")
 
         base = ['loss', 'pxl_acc', 'class_acc', 'mean_iu', 'fwavacc']
@@ -615,19 +699,16 @@ class Trainer(object):
         step = self._fast_step()
         if self.pseudo is not None:
             if step is None:
-                from ._lib import SznError
                 raise SznError("pseudo labels run inside the fused training step, which this optimizer wiring does not allow")
             step.set_pseudo_active(self.epoch >= self.pseudo_start_epoch)
             step.pseudo_counts.zero_()
         if self.ohem is not None:
             if step is None:
-                from ._lib import SznError
                 raise SznError("ohem runs inside the fused training step, which this optimizer wiring does not allow")
             step.set_ohem_active(self.epoch >= self.ohem_start_epoch)
             step.ohem_counts.zero_()
         if self.bias_loss is not None:
             if step is None:
-                from ._lib import SznError
                 raise SznError("the bias loss runs inside the fused training step, which this optimizer wiring does not allow")
             step.set_bias_active(self.epoch >= self.bias_start_epoch)
         if step is None and self.model._engine.dtype == torch.float16:
@@ -737,14 +818,14 @@ class Trainer(object):
                 return None, loss, pred, target
             if self.hub is not None:
                 # hubness correction: calibrated stacking's route with szn_hub_stats + szn_hub_head; without a calibration gamma = 0
-                loss, pred, _ = self.model.hub_predict(data, self.embeddings, self.unseen, self.hub, self._hub_gammas(), target,
-                                                       hist=self._calib_hist, pred_index=self._hub_index(), loss=self.loss_func)
+                loss, pred, _ = self.model.hub_predict(data, self.embeddings, self.unseen, self.hub, self._calib.values(), target,
+                                                       hist=self._calib.hist, pred_index=self._calib.index(), loss=self.loss_func)
                 return None, loss, pred, target
-            if self.calibration is not None or self._calib_hist is not None:
+            if self.calibration is not None or self._calib.hist is not None:
                 # calibrated stacking: the penalised classes are those not in self.unseen.  One forward pass; the sweep's histogram
                 # and the calibrated prediction come from szn_calib_head launches on the map the loss used
-                loss, pred, _ = self.model.calib_predict(data, self.embeddings, self.unseen, self._calib_gammas(), target,
-                                                         hist=self._calib_hist, pred_index=self._calib_index(), loss=self.loss_func)
+                loss, pred, _ = self.model.calib_predict(data, self.embeddings, self.unseen, self._calib.values(), target,
+                                                         hist=self._calib.hist, pred_index=self._calib.index(), loss=self.loss_func)
                 return None, loss, pred, target
             loss, pred = self.model.embed_predict(data, self.embeddings, target, loss=self.loss_func)
             return None, loss, pred, target
@@ -758,28 +839,26 @@ class Trainer(object):
                 return None, loss, pred, target
             if szn and self.seen_gate is not None:
                 # the soft gate: the same route with szn_soft_gate_head; without a threshold the reported prediction is tau = 0's
-                loss, pred, _ = self.model.seen_gate_predict(data, self.embeddings, self.unseen, self._seen_taus(), self.seen_gate, target,
-                                                             hist=self._seen_hist, pred_index=self._seen_index(), loss=self.loss_func)
+                loss, pred, _ = self.model.seen_gate_predict(data, self.embeddings, self.unseen, self._seen.values(), self.seen_gate, target,
+                                                             hist=self._seen.hist, pred_index=self._seen.index(), loss=self.loss_func)
                 return None, loss, pred, target
-            if szn and (self.seen_threshold is not None or self._seen_hist is not None):
+            if szn and (self.seen_threshold is not None or self._seen.hist is not None):
                 # the seen-mask decision at a threshold: one forward pass; the sweep's histogram and the reported prediction come from
                 # one szn_seen_sweep_head launch on the map the loss used
-                loss, pred, _ = self.model.seen_sweep_predict(data, self.embeddings, self.unseen, self._seen_taus(), target,
-                                                              hist=self._seen_hist, pred_index=self._seen_index(), loss=self.loss_func)
+                loss, pred, _ = self.model.seen_sweep_predict(data, self.embeddings, self.unseen, self._seen.values(), target,
+                                                              hist=self._seen.hist, pred_index=self._seen.index(), loss=self.loss_func)
                 return None, loss, pred, target
             predict = {"cos": self.model.szn_predict, "mse": self.model.szn_predict_mse,
                        "sim_ce": self.model.szn_predict_sim_ce, "rank": self.model.szn_predict_rank}[self.loss_func]
             loss, pred = predict(data, self.embeddings, self.unseen, target, group='seenmask' if szn else 'target')
             return None, loss, pred, target
-        if szn and (self.seen_threshold is not None or self._seen_hist is not None or self.seen_gate is not None):
-            from ._lib import SznError
+        if szn and (self.seen_threshold is not None or self._seen.hist is not None or self.seen_gate is not None):
             raise SznError("a seen-mask threshold runs on the fused head: dense target embeddings keep the materialised score")
         if self.eval_scales and not self._ms_warned:
             # dense target embeddings, SZN_VERBOSE_VAL and more than 256 classes keep the materialised-score route: one view
             self._ms_warned = True
             print("warning: eval_scales / eval_flip ignored: this validation route materialises the score and evaluates one view")
         if self.conse is not None and szn:
-            from ._lib import SznError
             raise SznError(conse_refused(True, True, False, True, False, False))
         if self._ce_cfg() and self._fused_step and not szn and not self.verbose_val:
             if self.conse is not None:
@@ -790,14 +869,13 @@ class Trainer(object):
                                                              forced=True)
                 else:
                     loss, pred, _ = self.model.conse_predict(data, self.conse_embeddings, self.unseen, self.conse["top"],
-                                                             self._conse_gammas(), target, hist=self._conse_hist,
-                                                             pred_index=self._conse_index())
+                                                             self._conse.values(), target, hist=self._conse.hist,
+                                                             pred_index=self._conse.index())
                 return None, loss, pred, target
             # softmax inference: summed cross entropy + channel argmax straight from the coarse map (no (n,C,h,w) score in HBM)
             loss, pred = self.model.softmax_predict(data, target)
             return None, loss, pred, target
-        if self.conse is not None and self._conse_hist is not None:
-            from ._lib import SznError
+        if self.conse is not None and self._conse.hist is not None:
             raise SznError("conse: a sweep runs on the fused head; this validation route materialises the score")
         if szn:
             score, seen_mask_score = self.model(data, mode='both')
@@ -820,29 +898,23 @@ class Trainer(object):
             pred = utils.infer_lbl_device(score, self.embeddings)
         return score, loss, pred, target
 
-    # calibrated stacking: with a sweep and a calibration the penalty in use joins the sweep's gammas for the call (one launch gives
-    # both); the histogram rows of the sweep's own gammas are picked out afterwards
-    _calib_hist = None                          # the (G,K,K) device histogram of the running validate(), None outside a sweep
+    def _init_sweeps(self):
+        """the three sweeps of validation, in the fixed order every rank begins, finishes (a collective each) and reports them.  The
+        hubness correction runs on calib's sweep (gamma 0 in use without a calibration), the soft gate on seen's"""
+        self._calib = _Sweep(self, 'calib_sweep', self._calib_used, 'calibration', 'gamma', 'calib_log.csv', 'fcn/val/calib',
+                             ('best_gamma', 'best_harmonic_mean_iu'),
+                             "calibration: a 64-gamma sweep has no room for a calibration value that is not one of its gammas")
+        self._seen = _Sweep(self, 'seen_sweep', lambda: 0.0 if self.seen_threshold is None else self.seen_threshold,
+                            'seen-mask threshold', 'tau', 'seen_sweep_log.csv', 'fcn/val/seen_sweep',
+                            ('best_seen_tau', 'best_seen_harmonic_mean_iu'),
+                            "seen sweep: a 64-tau sweep has no room for a reported threshold (seen_threshold, else 0) that is not one of its taus")
+        self._conse = _Sweep(self, 'conse_sweep', lambda: self.conse["gamma"], 'conse', 'gamma', 'conse_log.csv', 'fcn/val/conse',
+                             ('best_conse_gamma', 'best_conse_harmonic_mean_iu'),
+                             "conse: a 64-gamma sweep has no room for a gamma in use that is not one of its gammas")
+        self._sweeps = (self._calib, self._seen, self._conse)
 
-    def _calib_gammas(self):
-        if self._calib_hist is None:
-            return [self.calibration]
-        return self._calib_all
-
-    def _calib_index(self):
-        if self.calibration is None:
-            return None
-        return 0 if self._calib_hist is None else int(np.searchsorted(self._calib_all, np.float32(self.calibration)))
-
-    # hubness correction: the same, with gamma = 0 in use when there is no calibration
-    def _hub_gamma(self):
-        return 0.0 if self.calibration is None else self.calibration
-
-    def _hub_gammas(self):
-        return [self._hub_gamma()] if self._calib_hist is None else self._calib_all
-
-    def _hub_index(self):
-        return 0 if self._calib_hist is None else int(np.searchsorted(self._calib_all, np.float32(self._hub_gamma())))
+    def _calib_used(self):
+        return 0.0 if self.hub is not None and self.calibration is None else self.calibration
 
     def _hub_report(self, h, hist_all):
         """rank 0, once per validation: hub_log.csv -- one 'used' row for the prediction validation reports (h: the {all, seen, unseen}
@@ -854,114 +926,24 @@ class Trainer(object):
                         'val/hubness_skew\n')
         head = [self.epoch, self.iteration]
         cfg = [self.hub["mode"], self.hub["beta"], self.hub["min_sd"]]
-        best = None
+        rows, best = self._calib.scan(hist_all) if hist_all is not None else ([], None)
         with open(path, 'a') as f:
             m, ms, mu = (utils._hist_to_metrics(x) for x in h)
             self.last_hub_skew = utils.hubness_skew(h[0])
-            f.write(','.join(map(str, head + ['used'] + cfg + [self._hub_gamma(), m[2], ms[2], mu[2], utils.harmonic_mean_iu(ms, mu),
+            f.write(','.join(map(str, head + ['used'] + cfg + [self._calib_used(), m[2], ms[2], mu[2], utils.harmonic_mean_iu(ms, mu),
                                                                 self.last_hub_skew])) + '\n')
-            if hist_all is not None:
-                for val, g in zip(self.calib_sweep, np.searchsorted(self._calib_all, self.calib_sweep)):
-                    m, ms, mu = utils.calib_rows(hist_all[g], self.n_class, self.val_unseen)
-                    hm = utils.harmonic_mean_iu(ms, mu)
-                    f.write(','.join(map(str, head + ['sweep'] + cfg + [float(val), m[2], ms[2], mu[2], hm,
-                                                                         utils.hubness_skew(hist_all[g])])) + '\n')
-                    if not np.isnan(hm) and (best is None or hm > best[1] or (hm == best[1] and abs(float(val)) < abs(best[0]))):
-                        best = (float(val), hm)
+            for val, hist, m, ms, mu, hm in rows:
+                f.write(','.join(map(str, head + ['sweep'] + cfg + [val, m[2], ms[2], mu[2], hm, utils.hubness_skew(hist)])) + '\n')
         self.tb_writer.add_scalar('fcn/val/hub/skew', self.last_hub_skew, self.epoch)
+        self._calib.keep_best(best)
         if best is not None:
-            self.best_gamma, self.best_harmonic_mean_iu = best
             print('hubness correction (%s): best gamma %g, harmonic mean IU %.3f' % ((self.hub["mode"],) + best))
 
-    def _sweep_report(self, hist_all, all_vals, sweep, fname, column, extra=()):
-        """one <fname> row per value of the sweep (hist_all follows all_vals) -> (value, harmonic mean) of the largest harmonic mean, or
-        None; ties go to the value nearest 0 (a NaN never wins).  extra: (column, value) pairs appended to every row"""
-        keep = np.searchsorted(all_vals, sweep)
-        path = osp.join(self.log_dir, fname)
-        if not osp.exists(path):
-            with open(path, 'w') as f:
-                f.write(','.join(['epoch,iteration,%s,val/pxl_acc,val/mean_iu,val/seen/mean_iu,val/unseen/mean_iu,val/harmonic_mean_iu' % column]
-                                 + [k for k, _ in extra]) + '\n')
-        best = None
-        with open(path, 'a') as f:
-            for val, g in zip(sweep, keep):
-                m, ms, mu = utils.calib_rows(hist_all[g], self.n_class, self.val_unseen)
-                hm = utils.harmonic_mean_iu(ms, mu)
-                f.write(','.join(map(str, [self.epoch, self.iteration, float(val), m[0], m[2], ms[2], mu[2], hm] + [v for _, v in extra])) + '\n')
-                if not np.isnan(hm) and (best is None or hm > best[1] or (hm == best[1] and abs(float(val)) < abs(best[0]))):
-                    best = (float(val), hm)
-        return best
-
-    def _calib_report(self, hist_all):
-        """rank 0, once per epoch: one calib_log.csv row per gamma of the sweep, and the gamma with the largest harmonic mean"""
-        best = self._sweep_report(hist_all, self._calib_all, self.calib_sweep, 'calib_log.csv', 'gamma')
-        if best is not None:
-            self.best_gamma, self.best_harmonic_mean_iu = best
-            print('calibration: best gamma %g, harmonic mean IU %.3f' % best)
-            self.tb_writer.add_scalar('fcn/val/calib/best_gamma', best[0], self.epoch)
-            self.tb_writer.add_scalar('fcn/val/calib/best_harmonic_mean_iu', best[1], self.epoch)
-        else:
-            print('calibration: no gamma has a harmonic mean IU (the validation set holds no seen or no unseen pixels)')
-
-    # ConSE: as above, the gamma in use (0 without one) joins the sweep's gammas for the call
-    _conse_hist = None                          # the (G,K,K) device histogram of the running validate(), None outside a sweep
-
-    def _conse_gammas(self):
-        if self._conse_hist is None:
-            return [self.conse["gamma"]]
-        return self._conse_all
-
-    def _conse_index(self):
-        return 0 if self._conse_hist is None else int(np.searchsorted(self._conse_all, np.float32(self.conse["gamma"])))
-
-    def _conse_report(self, hist_all):
-        """rank 0, once per epoch: one conse_log.csv row per gamma of the sweep, and the gamma with the largest harmonic mean"""
-        best = self._sweep_report(hist_all, self._conse_all, self.conse_sweep, 'conse_log.csv', 'gamma')
-        if best is not None:
-            self.best_conse_gamma, self.best_conse_harmonic_mean_iu = best
-            print('conse: best gamma %g, harmonic mean IU %.3f' % best)
-            self.tb_writer.add_scalar('fcn/val/conse/best_gamma', best[0], self.epoch)
-            self.tb_writer.add_scalar('fcn/val/conse/best_harmonic_mean_iu', best[1], self.epoch)
-        else:
-            print('conse: no gamma has a harmonic mean IU (the validation set holds no seen or no unseen pixels)')
-
-    # the seen-mask threshold: as above, the threshold in use (tau = 0 without one: the plain route's decision) joins the sweep's taus
-    _seen_hist = None                           # the (G,K,K) device histogram of the running validate(True), None outside a sweep
-
-    def _seen_taus(self):
-        if self._seen_hist is None:
-            return [0.0 if self.seen_threshold is None else self.seen_threshold]      # (None: the gate alone)
-        return self._seen_all
-
-    def _seen_index(self):
-        tau = 0.0 if self.seen_threshold is None else self.seen_threshold
-        return 0 if self._seen_hist is None else int(np.searchsorted(self._seen_all, np.float32(tau)))
-
-    def _seen_report(self, hist_all):
-        """rank 0, once per validate(True): one seen_sweep_log.csv row per tau of the sweep, and the tau with the largest harmonic mean"""
-        if self.seen_gate is not None:
-            return self._gate_report(hist_all)
-        best = self._sweep_report(hist_all, self._seen_all, self.seen_sweep, 'seen_sweep_log.csv', 'tau')
-        if best is not None:
-            self.best_seen_tau, self.best_seen_harmonic_mean_iu = best
-            print('seen-mask threshold: best tau %g, harmonic mean IU %.3f' % best)
-            self.tb_writer.add_scalar('fcn/val/seen_sweep/best_tau', best[0], self.epoch)
-            self.tb_writer.add_scalar('fcn/val/seen_sweep/best_harmonic_mean_iu', best[1], self.epoch)
-        else:
-            print('seen-mask threshold: no tau has a harmonic mean IU (the validation set holds no seen or no unseen pixels)')
-
     def _gate_report(self, hist_all):
-        """the same with the soft gate on: the rows go to seen_gate_log.csv, which also names the gate's weight and temperature"""
+        """the seen sweep's report with the soft gate on: the rows go to seen_gate_log.csv, which also names the gate's weight and temperature"""
         g = self.seen_gate
-        best = self._sweep_report(hist_all, self._seen_all, self.seen_sweep, 'seen_gate_log.csv', 'tau',
-                                  (('weight', g["weight"]), ('temperature', g["temperature"])))
-        if best is not None:
-            self.best_seen_tau, self.best_seen_harmonic_mean_iu = best
-            print('soft gate (weight %g, temperature %g): best tau %g, harmonic mean IU %.3f' % ((g["weight"], g["temperature"]) + best))
-            self.tb_writer.add_scalar('fcn/val/seen_gate/best_tau', best[0], self.epoch)
-            self.tb_writer.add_scalar('fcn/val/seen_gate/best_harmonic_mean_iu', best[1], self.epoch)
-        else:
-            print('soft gate: no tau has a harmonic mean IU (the validation set holds no seen or no unseen pixels)')
+        self._seen.report(hist_all, 'seen_gate_log.csv', 'soft gate', ' (weight %g, temperature %g)' % (g["weight"], g["temperature"]),
+                          'fcn/val/seen_gate', (('weight', g["weight"]), ('temperature', g["temperature"])))
 
     def pool_prototypes(self):
         """the prototypes of self.unseen pooled over the support loader with the current weights: one inference forward per support
@@ -1034,42 +1016,18 @@ class Trainer(object):
         hist = torch.zeros(3, self.n_class, self.n_class, dtype=torch.int64, device=self.device)
         acc = torch.zeros(2, dtype=torch.float64, device=self.device)          # loss sum, image-batch count
         if both_fcn_and_seenmask and (self.calibration is not None or self.calib_sweep is not None):
-            from ._lib import SznError
             raise SznError(calibration_refused(True, True, False, True, False, self.n_class))
         if both_fcn_and_seenmask and self.hub is not None:
-            from ._lib import SznError
             raise SznError(hub_refused(True, True, False, True, False, self.n_class))
-        if self.calib_sweep is not None:
-            extra = [] if self.calibration is None else [np.float32(self.calibration)]
-            if self.hub is not None:
-                extra = [np.float32(self._hub_gamma())]
-            self._calib_all = np.unique(np.concatenate([self.calib_sweep, np.asarray(extra, dtype=np.float32)]))
-            if self._calib_all.size > 64:
-                from ._lib import SznError
-                raise SznError("calibration: a 64-gamma sweep has no room for a calibration value that is not one of its gammas")
-            self._calib_hist = torch.zeros(self._calib_all.size, self.n_class, self.n_class, dtype=torch.int64, device=self.device)
         if both_fcn_and_seenmask and self.conse is not None:
-            from ._lib import SznError
             raise SznError(conse_refused(True, True, False, True, False, False))
-        if self.conse_sweep is not None:
-            self._conse_all = np.unique(np.concatenate([self.conse_sweep, np.asarray([self.conse["gamma"]], dtype=np.float32)]))
-            if self._conse_all.size > 64:
-                from ._lib import SznError
-                raise SznError("conse: a 64-gamma sweep has no room for a gamma in use that is not one of its gammas")
-            self._conse_hist = torch.zeros(self._conse_all.size, self.n_class, self.n_class, dtype=torch.int64, device=self.device)
         if not both_fcn_and_seenmask and (self.seen_threshold is not None or self.seen_sweep is not None):
-            from ._lib import SznError
             raise SznError(seen_threshold_refused(True, True, False, False, False, self.n_class))
         if not both_fcn_and_seenmask and self.seen_gate is not None:
-            from ._lib import SznError
             raise SznError(seen_gate_refused(True, True, False, False, False, self.n_class))
-        if both_fcn_and_seenmask and self.seen_sweep is not None:
-            extra = [np.float32(0.0 if self.seen_threshold is None else self.seen_threshold)]
-            self._seen_all = np.unique(np.concatenate([self.seen_sweep, np.asarray(extra, dtype=np.float32)]))
-            if self._seen_all.size > 64:
-                from ._lib import SznError
-                raise SznError("seen sweep: a 64-tau sweep has no room for a reported threshold (seen_threshold, else 0) that is not one of its taus")
-            self._seen_hist = torch.zeros(self._seen_all.size, self.n_class, self.n_class, dtype=torch.int64, device=self.device)
+        for sweep in self._sweeps:
+            if sweep.candidates() is not None:
+                sweep.begin()
         n_viz = self.visualize if self.rank == 0 else 0                        # rank 0 renders the first images of its own shard
         tiles = []                                                             # device pictures, kept there until the epoch ends
         mean_bgr = vis_utils.dataset_mean_bgr(getattr(self.val_loader, 'dataset', None)) if n_viz else None
@@ -1089,33 +1047,22 @@ class Trainer(object):
                 if self.verbose_val and self.rank == 0:
                     print("Test Epoch {:<5} | Iteration {:<5} | Loss {:5.5f} | Score Sum {:10.5f}".format(
                         int(self.epoch), int(batch_idx), float(loss.item()), float(score.sum().item())))
-        calib_hist, self._calib_hist = self._calib_hist, None
-        seen_hist, self._seen_hist = self._seen_hist, None
-        conse_hist, self._conse_hist = self._conse_hist, None
         if world > 1:
             dist.all_reduce(hist)
             dist.all_reduce(acc)
-            if conse_hist is not None:
-                dist.all_reduce(conse_hist)
-            if calib_hist is not None:
-                dist.all_reduce(calib_hist)
-            if seen_hist is not None:
-                dist.all_reduce(seen_hist)
+        calib_hist, seen_hist, conse_hist = (sweep.finish(world) for sweep in self._sweeps)     # collectives: every rank, this order
         h = hist.cpu().numpy()
-        if calib_hist is not None:
-            calib_hist = calib_hist.cpu().numpy()
-            if self.rank == 0 and self.hub is None:
-                self._calib_report(calib_hist)
-        if self.hub is not None and self.rank == 0:
-            self._hub_report(h, calib_hist)
-        if seen_hist is not None:
-            seen_hist = seen_hist.cpu().numpy()
-            if self.rank == 0:
-                self._seen_report(seen_hist)
-        if conse_hist is not None:
-            conse_hist = conse_hist.cpu().numpy()
-            if self.rank == 0:
-                self._conse_report(conse_hist)
+        if self.rank == 0:
+            if self.hub is not None:
+                self._hub_report(h, calib_hist)
+            elif calib_hist is not None:
+                self._calib.report(calib_hist)
+            if seen_hist is not None and self.seen_gate is not None:
+                self._gate_report(seen_hist)
+            elif seen_hist is not None:
+                self._seen.report(seen_hist)
+            if conse_hist is not None:
+                self._conse.report(conse_hist)
         accn = acc.cpu().numpy()
         if np.isnan(accn[0]):
             raise ValueError('loss is nan while validating')
