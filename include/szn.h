@@ -674,6 +674,23 @@ int szn_sgd_momentum_step_scaled(long n, float* param, const float* grad, float*
 int szn_loss_scale_update(float* scale_state, float growth, float backoff, int growth_interval, float min_scale,
                           float max_scale, szn_stream_t stream);
 
+/* ---- averaged weights (exponential moving average of the parameters, Polyak averaging; the reference has no counterpart) ----
+ * One step of the average over n fp32 elements:   avg = fmaf(D, avg - param, param)   =   param + D * (avg - param),
+ *     D = pow(min(decay, (1 + s) / (10 + s)), every)     (computed in double, rounded to float once)
+ * with s = the optimizer steps applied BEFORE this one: step - 1 from the host when scale_state == NULL, scale_state[2] otherwise
+ * (as the *_scaled optimizer entries take their step count).  The (1 + s) / (10 + s) ramp is the usual warm-up; step == 0 switches
+ * it off (D = decay^every).  `every` = the optimizer steps this one update stands for (the caller launches it every `every`-th
+ * step).  With scale_state != NULL and its found_inf flag set the kernel does nothing -- the optimizer entries skipped the same
+ * step -- so launch it before szn_loss_scale_update clears the flag.  Exact corners: D == 1 leaves avg untouched, D == 0 makes
+ * avg a bitwise copy of param, avg == param is a fixed point.  Any 4-byte-aligned pointer pair is taken (16-byte accesses where
+ * both pointers allow them).  decay outside [0, 1], every < 1, step < 0, n < 0 or a NULL buffer with n > 0: SZN_ERR_ARG; n == 0 is
+ * a successful no-op.  szn_last_kernel: "ema_kernel".                                                                          */
+int szn_ema_step(long n, float* avg, const float* param, float decay, int every, int step, const float* scale_state,
+                 szn_stream_t stream);
+/* Exchange the contents of two non-overlapping fp32 buffers as 32-bit words (NaN payloads and -0 survive).  Overlapping ranges:
+ * SZN_ERR_ARG, nothing is written.  szn_last_kernel: "swap_kernel".                                                             */
+int szn_swap_f32(long n, float* a, float* b, szn_stream_t stream);
+
 /* ---- row / column remapping of an NHWC map (the constant band of the pad-100 network inside the conv3 block) --------------
  * models.py:43 pads conv1_1 by 100: at 1/4 resolution most rows / columns between the tensor edge and the image's reach hold one
  * value per channel, and conv3_1 .. conv3_3 (models.py:56-62,123-128) need not compute them.  One kernel does the four index maps

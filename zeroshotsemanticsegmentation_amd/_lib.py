@@ -193,6 +193,8 @@ SIGNATURES = {
     "szn_adam_step_scaled": (_I, [_L, _P, _P, _P, _P, _F, _F, _F, _F, _F, _P, _F, _P, _I, _P]),
     "szn_sgd_momentum_step_scaled": (_I, [_L, _P, _P, _P, _F, _F, _F, _P, _F, _P, _I, _P]),
     "szn_loss_scale_update": (_I, [_P, _F, _F, _I, _F, _F, _P]),
+    "szn_ema_step": (_I, [_L, _P, _P, _F, _I, _I, _P, _P]),
+    "szn_swap_f32": (_I, [_L, _P, _P, _P]),
     "szn_cast": (_I, [_I, _I, _L, _P, _P, _P]),
     "szn_band_remap": (_I, [_I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "szn_band_fold": (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P]),

@@ -9,6 +9,7 @@ module's Parameters are channels_last views into them), the head runs fused from
 (szn_fused_head) and the per-layer gradient buckets are all-reduced on RCCL's stream while the rest of the
 backward pass is still running.
 """
+import contextlib
 import os
 
 import torch
@@ -376,7 +377,7 @@ class TrainStep(object):
                  scale_growth=2.0, scale_backoff=0.5, scale_growth_interval=2000, force_comm=None, reserved_cus=None,
                  fused_adam=None, keep_grads=True, exchange=None, direct_wire=None, sharded=None, forced_unseen=None,
                  class_weight=None, size_average=False, sim_exclude=None, sim_temperature=None, pseudo=None, ohem=None,
-                 rank_margin=None, rank_hardest=False, bias=None):
+                 rank_margin=None, rank_hardest=False, bias=None, ema=None):
         """Data-parallel knobs (the reference is single-GPU): grad_comm_dtype (SZN_GRAD_COMM = fp32 | bf16) = the
         wire format of the gradient buckets; exchange=False (SZN_GRAD_COMM=off) = no exchange at all (bench.py's comm-off timing);
         direct_wire (default: on for a 16-bit wire with keep_grads=False; SZN_WIRE_DIRECT=0 turns it off) = the weight-gradient
@@ -425,7 +426,23 @@ class TrainStep(object):
         supervised term and only the still-hidden ones the bias term; mining neither counts nor drops hidden pixels (it evaluates labels
         in [0, K) only and copies every other label through).  `unseen` stays as given when active pseudo labels empty sim_exclude.
         set_bias_active(False) makes the step the plain sim_ce step again, launch for launch.  Under data parallelism nothing is
-        exchanged: the term is per pixel."""
+        exchanged: the term is per pixel.
+        ema=dict(decay=, every=1, warmup=True): averaged weights (Polyak averaging).  ema_w / ema_b are fp32 copies of the flat
+        parameter buffers; after the last optimizer launch of every `every`-th step szn_ema_step moves them towards the parameters,
+        avg = param + D (avg - param) with D = min(decay, (1 + s) / (10 + s)) ^ every, s = the optimizer steps applied before this one
+        (warmup=False: D = decay ^ every).  The launches sit in front of szn_loss_scale_update, so a step the dynamic loss scale skips
+        on the device skips the average too, without a host sync; such a step that falls on an `every` boundary is simply lost to the
+        average (the next update comes `every` steps later).  The average never feeds back into training.  averaged_weights() puts it
+        under the model for a block (validation, export), ema_state_dict() / load_ema_state_dict() move it in and out of checkpoints,
+        reset_ema() restarts it from the current parameters (import_optimizer_state does: a resumed run without a stored average),
+        ema_updates counts the launches (for logs).  Plain data parallelism needs nothing: every rank holds the same parameters after
+        the all-reduce and therefore the same average.  Refused with a ValueError: the sharded optimizer (the fp32 masters of the
+        other ranks' slices are stale there), decay outside [0, 1), every < 1, and every > 1 while a stream capture is in progress
+        (the host decides which steps update).  None (default): nothing changes, launch for launch."""
+        self._ema = None if ema is None else self._check_ema(ema)
+        self.ema_w = self.ema_b = None
+        self.ema_updates = 0
+        self._ema_in = False                                          # inside averaged_weights(): the buffers are exchanged
         if loss not in ("cos", "mse", "sim_ce", "rank", "cross_entropy"):
             raise L.SznError("TrainStep: loss must be 'cos', 'mse', 'sim_ce', 'rank' or 'cross_entropy', got %r" % (loss,))
         if (loss not in ("sim_ce", "rank") and sim_exclude is not None) or (loss != "sim_ce" and sim_temperature is not None):
@@ -580,6 +597,10 @@ class TrainStep(object):
         self.nstep = 0
         self._flatten()
         self._buckets(bucket_mb)
+        if self._ema is not None:
+            if self.buckets.sharded:
+                raise ValueError("TrainStep: ema= does not run with the sharded optimizer, whose fp32 masters of the other ranks' slices are stale")
+            self.reset_ema()
         # CUs the persistent one-block-per-CU backward kernels (conv3x3_regw dgrad, conv_wgrad_taps) leave to RCCL's workgroups
         # while an exchange is in flight (default SZN_RESERVED_CUS, 0 = none; only when buckets are actually exchanged)
         if reserved_cus is None:
@@ -930,6 +951,8 @@ class TrainStep(object):
         """forward -> the head map (the 1/32 map, or FCN8s' 1/8 fused map) -> head (fused, or the materialised referee) -> loss
         scale -> backward -> exchange -> optimizer -> confusion histogram"""
         m, eng = self.model, self.eng
+        if self._ema_in:
+            raise L.SznError("TrainStep: no training step inside averaged_weights(): the model holds the averaged weights")
         B, _, H, W = x.shape
         st = L.stream_ptr()
         eng.keep_prepool = bool(self.keep_ctx)          # tests that read the forward state need the un-pooled tensors too
@@ -1209,6 +1232,8 @@ class TrainStep(object):
         self.eng.fused_opt = None
         self.eng.fused_done = set()
         self._opt_launch("b", 0, self.flat_b.numel(), self.nstep)
+        if self._ema is not None:        # after the step's last optimizer launch, before the found_inf flag is cleared
+            self._ema_launch(st)
         if self.dynamic:
             g, b, iv, lo, hi = self.scale_cfg
             L.call("szn_loss_scale_update", L.ptr(dyn), g, b, iv, lo, hi, st)
@@ -1291,6 +1316,111 @@ class TrainStep(object):
             self.nstep = max(steps)
             if self.dynamic:
                 self.scale_state[2] = float(self.nstep)
+        if self._ema is not None:        # a resumed run: the average restarts from the loaded weights unless load_ema_state_dict follows
+            self.reset_ema()
+
+    # ---- averaged weights (ema=) --------------------------------------------------------------------------------------------
+    @staticmethod
+    def _check_ema(cfg):
+        """ema= checked on the host (before anything touches a device) -> (decay, every, warmup)"""
+        if not isinstance(cfg, dict) or "decay" not in cfg or set(cfg) - {"decay", "every", "warmup"}:
+            raise ValueError("TrainStep: ema must be a dict(decay=, every=1, warmup=True), got %r" % (cfg,))
+        try:
+            decay, every = float(cfg["decay"]), cfg.get("every", 1)
+            every = 1 if every is None else every
+            whole = int(every) == every
+        except (TypeError, ValueError):
+            raise ValueError("TrainStep: ema decay must be a number and every an integer (got %r)" % (cfg,))
+        if not 0.0 <= decay < 1.0:
+            raise ValueError("TrainStep: ema decay must lie in [0, 1), got %r" % (cfg["decay"],))
+        if not whole or int(every) < 1:
+            raise ValueError("TrainStep: ema every must be an integer >= 1, got %r" % (every,))
+        warm = cfg.get("warmup", True)
+        return decay, int(every), bool(True if warm is None else warm)
+
+    def reset_ema(self):
+        """(re)start the average from the current parameters"""
+        if self._ema is None:
+            raise L.SznError("TrainStep: reset_ema() on a step built without ema=")
+        if self._ema_in:
+            raise L.SznError("TrainStep: reset_ema() inside averaged_weights()")
+        self.ema_w, self.ema_b = self.flat_w.clone(), self.flat_b.clone()
+        self.ema_updates = 0
+
+    def _ema_launch(self, st):
+        decay, every, warm = self._ema
+        if every > 1 and torch.cuda.is_current_stream_capturing():
+            raise ValueError("TrainStep: ema every > 1 cannot be captured into a graph, the host decides which steps update the average")
+        if self.nstep % every:
+            return
+        dyn = L.ptr(self.scale_state) if self.dynamic else None
+        for avg, p in ((self.ema_w, self.flat_w), (self.ema_b, self.flat_b)):
+            L.call("szn_ema_step", p.numel(), L.ptr(avg), L.ptr(p), decay, every, self.nstep if warm else 0, dyn, st)
+        self.ema_updates += 1
+
+    def _ema_swap(self, only=2):
+        """exchange parameters and average in place (bit for bit), bring the 16-bit weight image in line with the fp32 buffer now in
+        place; the rows behind score_fr's slot (seenmask_score's, the padding) lie outside flat_w and are not touched"""
+        self._ema_swapped = 0            # how many of the two exchanges this call has queued
+        st = L.stream_ptr()
+        for i, (p, avg) in enumerate(((self.flat_w, self.ema_w), (self.flat_b, self.ema_b))):
+            if i < only:
+                L.call("szn_swap_f32", p.numel(), L.ptr(p), L.ptr(avg), st)
+                self._ema_swapped = i + 1
+        if self.flat_w_lp is not None:
+            # the optimizer kernels round their image with the conversion szn_cast uses: casting the restored masters reproduces it
+            L.call("szn_cast", L.SZN_F32, L.dtype_code(self.flat_w_lp.dtype), self.flat_w.numel(), L.ptr(self.flat_w),
+                   L.ptr(self.flat_w_lp), st)
+        self.eng.mark_dirty()
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """for the duration of the block the model (flat_w, flat_b, the 16-bit weight image, every image the engine derives) holds the
+        averaged weights and ema_w / ema_b the raw iterate: an exact in-place exchange, undone in a `finally`, after which all five
+        buffers hold the bits they held before and training continues bit for bit.  Nested entry is a no-op.  No step() inside."""
+        if self._ema is None:
+            raise L.SznError("TrainStep: averaged_weights() on a step built without ema=")
+        if self._ema_in:
+            yield
+            return
+        self._ema_in = True
+        self._ema_swapped = 0
+        try:
+            self._ema_swap()
+            yield
+        finally:
+            try:
+                # (an entry that failed half way left weights or biases un-exchanged: both kernels are their own inverse, so the
+                # exit exchanges exactly what the entry did)
+                self._ema_swap(self._ema_swapped)
+            finally:
+                self._ema_in = False
+
+    def _ema_names(self):
+        names = {id(p): k for k, p in self.model.named_parameters()}
+        for p, key, view in self._param_slots():
+            yield names[id(p)], key, view
+
+    def ema_state_dict(self):
+        """the average with model.state_dict()'s keys and layout; entries outside the flat buffers (frozen layers) are the model's"""
+        if self._ema is None:
+            raise L.SznError("TrainStep: ema_state_dict() on a step built without ema=")
+        sd = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
+        w, b = (self.flat_w, self.flat_b) if self._ema_in else (self.ema_w, self.ema_b)
+        for name, key, view in self._ema_names():
+            sd[name] = view(w if key == "w" else b).clone()
+        return sd
+
+    def load_ema_state_dict(self, sd):
+        """inverse of ema_state_dict (resume): the flat-buffer entries of `sd` become the average"""
+        if self._ema is None:
+            raise L.SznError("TrainStep: load_ema_state_dict() on a step built without ema=")
+        if self._ema_in:
+            raise L.SznError("TrainStep: load_ema_state_dict() inside averaged_weights()")
+        for name, key, view in self._ema_names():
+            if name not in sd:
+                raise L.SznError("TrainStep: the stored average lacks %r" % name)
+            view(self.ema_w if key == "w" else self.ema_b).copy_(sd[name].to(self.dev, torch.float32))
 
     def metrics(self, reset=True):
         """running train metrics from the device histogram (trainer_fcn.py:164)"""

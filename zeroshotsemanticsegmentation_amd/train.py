@@ -61,6 +61,12 @@ Added for this implementation (none change the reference flags):
                        midpoint: a hyper-parameter nobody has tuned) of the way from the word vector to it; --proto-mode unit|raw
                        (default unit), --proto-min-pixels P (default 1); one row per class in <log_dir>/proto_log.csv.  Training never
                        sees the adapted rows
+  --ema DECAY          averaged weights (Polyak averaging) for the FCN phase: an fp32 copy of the parameters follows them on the GPU
+                       (szn_ema_step, skipped on the device with the steps the fp16 loss scale skips); --ema-every N (default 1),
+                       --ema-no-warmup.  Validation and all its logs run on the average (szn_swap_f32 puts it under the model and takes
+                       it out again, bit for bit); checkpoints carry 'ema_state_dict' / 'ema_updates' next to the raw iterate and -r
+                       restores them; -m test_fcn / test_all --use-ema evaluates the stored average; one row per validation in
+                       <log_dir>/ema_log.csv.  DECAY has no default
   --init synthetic|vgg path handling: without the caffe VGG16 file the backbone starts from synth weights
   torchrun: RANK / LOCAL_RANK / WORLD_SIZE are honoured (one process per GPU, RCCL gradient all-reduce).
 """
@@ -227,6 +233,19 @@ def build_parser():
                         "score vectors (raw)")
     p.add_argument('--proto-min-pixels', type=int, default=None, metavar='P',
                    help="with --proto-shots: a class with fewer than P pooled pixels keeps its word vector (default 1)")
+    p.add_argument('--ema', type=float, default=None, metavar='DECAY',
+                   help="averaged weights: every training step of the FCN phase moves an fp32 copy of the parameters towards them on the "
+                        "GPU (avg = w + D (avg - w), D = min(DECAY, (1 + s) / (10 + s)) after s applied steps); validation, its logs, "
+                        "sweeps and pictures run on the average and the checkpoint carries it as 'ema_state_dict' next to the raw "
+                        "iterate.  DECAY in [0, 1) has no default: nobody has tuned it here.  Needs a configuration that trains on the "
+                        "fused step (-loss cos | mse | sim_ce | rank, or -c 1 cross entropy).  Default: off")
+    p.add_argument('--ema-every', type=int, default=None, metavar='N',
+                   help="with --ema: update the average every N-th step, with D ^ N (default 1)")
+    p.add_argument('--ema-no-warmup', action='store_true', help="with --ema: D = DECAY from the first step on, without the (1 + s) / (10 + s) ramp")
+    p.add_argument('--use-ema', action='store_true',
+                   help="with -m test_fcn / -m test_all: evaluate the averaged weights of the checkpoint ('ema_state_dict') instead of the "
+                        "raw iterate ('model_state_dict'); an error for a checkpoint written without --ema.  The checkpoint this "
+                        "evaluation writes into its own log directory holds the weights it evaluated, the average, as 'model_state_dict'")
     p.add_argument('--hide-unseen', action='store_true',
                    help="the FCN phase trains on every image 'train_seen' would drop for an unseen class as well, with the pixels of "
                         "the unseen classes hidden from every loss and metric (label -3)")
@@ -579,6 +598,40 @@ def check_proto(shots, alpha, mode, min_pixels, cfg):
     return trainer_fcn.check_proto(dict(shots=shots, alpha=alpha, mode=mode, min_pixels=min_pixels))
 
 
+def check_ema(decay, every, no_warmup, use_ema, cfg):
+    """--ema / --ema-every / --ema-no-warmup / --use-ema: DECAY in [0, 1), N >= 1; the satellites only with --ema; --ema only where the
+    FCN phase trains on engine.TrainStep (trainer_fcn.ema_refused), --use-ema only with the test modes -> the Trainer's ema dict, or None"""
+    if use_ema and cfg['mode'] not in ('test_fcn', 'test_all'):
+        raise Exception("--use-ema evaluates a checkpoint's averaged weights: -m test_fcn / -m test_all only")
+    if decay is None:
+        if every is not None or no_warmup:
+            raise Exception("--ema-every / --ema-no-warmup need --ema")
+        return None
+    if cfg['mode'] != 'train':
+        raise Exception("--ema averages the weights while training (-m train); --use-ema evaluates a stored average")
+    if not 0.0 <= decay < 1.0:
+        raise Exception("--ema: DECAY must lie in [0, 1) (got %r)" % (decay,))
+    if every is not None and every < 1:
+        raise Exception("--ema-every: N must be at least 1 (got %r)" % (every,))
+    step_cfg = (cfg['fcn_loss'] in _EMBED_LOSSES and cfg['embed_dim']) or (cfg['fcn_loss'] == 'cross_entropy' and not cfg['embed_dim'])
+    why = trainer_fcn.ema_refused(bool(step_cfg))
+    if why:
+        raise trainer_fcn.SznError("--ema: " + why)
+    return dict(decay=decay, every=1 if every is None else every, warmup=not no_warmup)
+
+
+USE_EMA_MISSING = "--use-ema: the checkpoint %s carries no 'ema_state_dict' (it was written without --ema)"
+
+
+def checkpoint_weights(checkpoint, use_ema, path=''):
+    """the state dict a loaded checkpoint hands the model: the raw iterate, or with --use-ema its averaged weights"""
+    if not use_ema:
+        return checkpoint['model_state_dict']
+    if 'ema_state_dict' not in checkpoint:
+        raise Exception(USE_EMA_MISSING % path)
+    return checkpoint['ema_state_dict']
+
+
 def check_sim_temperature(temperature, cfg):
     """--sim-temperature: only with fcn_loss 'sim_ce', positive and finite"""
     if temperature is None:
@@ -616,6 +669,7 @@ def main(argv=None):
     check_ohem(args.ohem, args.ohem_thresh, args.ohem_start_epoch, cfg)
     check_bias(args.bias_loss, args.bias_start_epoch, cfg)
     proto = check_proto(args.proto_shots, args.proto_alpha, args.proto_mode, args.proto_min_pixels, cfg)
+    ema = check_ema(args.ema, args.ema_every, args.ema_no_warmup, args.use_ema, cfg)
     hide_unseen = args.hide_unseen or args.pseudo_label is not None or args.bias_loss is not None
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -727,7 +781,7 @@ def main(argv=None):
     start_epoch, start_iteration, checkpoint = 0, 0, None
     if cfg['load_fcn_path']:
         checkpoint = torch.load(osp.join(args.data_dir, 'logs', cfg['load_fcn_path'], 'best'), map_location='cpu', weights_only=False)
-        model.load_state_dict(checkpoint['model_state_dict'], strict=False)
+        model.load_state_dict(checkpoint_weights(checkpoint, args.use_ema, cfg['load_fcn_path']), strict=False)
         start_epoch, start_iteration = checkpoint['epoch'], checkpoint['iteration']
     else:
         try:
@@ -759,7 +813,7 @@ def main(argv=None):
         ohem=None if args.ohem is None else dict(keep=args.ohem, thresh=args.ohem_thresh), ohem_start_epoch=args.ohem_start_epoch or 0,
         calibration=args.calibration, calib_sweep=calib_sweep_values(args.calib_sweep), eval_scales=args.eval_scales,
         eval_flip=args.eval_flip, bias_loss=args.bias_loss, bias_start_epoch=args.bias_start_epoch or 0,
-        conse=conse, conse_sweep=calib_sweep_values(args.conse_sweep, "--conse-sweep"), hub=hub)
+        conse=conse, conse_sweep=calib_sweep_values(args.conse_sweep, "--conse-sweep"), hub=hub, ema=ema, ema_checkpoint=checkpoint)
     fcn_trainer.epoch, fcn_trainer.iteration = start_epoch, start_iteration
 
     if cfg['mode'] == 'train':

@@ -86,6 +86,10 @@ _REFUSALS = {
         ("mode", "conse on the full SZN network (-m test_all, seen-mask grouping) is not built: use -m test_fcn"),
         ("views", "conse with eval_scales / eval_flip is not built (averaging softmax probabilities over views is not)"),
         ("forced", "conse: forced_unseen picks the class group from the target, a gamma or a sweep picks it from the margin: pick one")),
+    "ema": (
+        ("config", "averaged weights (ema) live in the fused training step's flat buffers: an embedding configuration (loss 'cos' | 'mse' | 'sim_ce' | 'rank') or the softmax configuration (fcn_loss 'cross_entropy', no embedding) only"),
+        ("fused", "averaged weights (ema) live in the fused training step's flat buffers (fused_step=True)"),
+        ("wiring", "averaged weights (ema) live in the fused training step, which this optimizer wiring does not allow")),
 }
 
 
@@ -133,6 +137,13 @@ def conse_refused(has_unseen, softmax_cfg, forced_unseen, test_all, eval_views, 
     configuration (cross entropy, no embedding); `tuned` = a gamma other than 0 or a sweep was asked for"""
     return _refused("conse", unseen=not has_unseen, config=not softmax_cfg, mode=test_all, views=eval_views,
                     forced=forced_unseen and tuned)
+
+
+def ema_refused(step_cfg, fused_step=True, wired=True):
+    """why a configuration cannot average its weights (ema=, train.py --ema), or None: the average is kept by engine.TrainStep next to
+    its flat parameter buffers, so it exists only where training runs on that step -- step_cfg: loss 'cos' | 'mse' | 'sim_ce' | 'rank'
+    with embeddings, or the softmax cross entropy"""
+    return _refused("ema", config=not step_cfg, fused=not fused_step, wiring=not wired)
 
 
 def pseudo_refused(has_unseen, embed_cfg, n_class):
@@ -309,7 +320,7 @@ class Trainer(object):
                  pixel_embeddings=None, loss_func=None, unseen=None, val_unseen=None, label_names=None,
                  forced_unseen=False, embed_arr=None, precision=torch.float32, fused_step=True, rank=0, visualize=0, augment=None,
                  seen_threshold=None, seen_sweep=None, proto=None, support_loader=None, conse=None, conse_sweep=None, seen_gate=None, hub=None,
-                 sim_temperature=None, rank_margin=None, rank_hardest=False, bias_loss=None, bias_start_epoch=0, pseudo=None, pseudo_start_epoch=0, ohem=None, ohem_start_epoch=0, calibration=None,
+                 ema=None, ema_checkpoint=None, sim_temperature=None, rank_margin=None, rank_hardest=False, bias_loss=None, bias_start_epoch=0, pseudo=None, pseudo_start_epoch=0, ohem=None, ohem_start_epoch=0, calibration=None,
                  calib_sweep=None, eval_scales=None, eval_flip=False):
         if not cuda:
             raise RuntimeError("this implementation runs on the GPU only (cuda=False has no CPU fallback)")
@@ -528,6 +539,26 @@ class Trainer(object):
             bias_args(loss_func, cfg, self.n_class)
             self.bias_loss = cfg
 
+        # averaged weights (engine.TrainStep ema=): ema = dict(decay=, every=1, warmup=True).  Every training step moves an fp32 copy of the
+        # parameters towards them on the device; validate() runs entirely on that copy (averaged_weights: val_log.csv, best_mean_iu, every
+        # sweep log, the prototypes and the pictures describe the averaged model) and the checkpoint carries it as 'ema_state_dict' /
+        # 'ema_updates' next to the raw iterate.  ema_checkpoint: the checkpoint dict a run resumes from -- its average, if it has one,
+        # is restored; without one the average starts from the loaded weights.  Per validation one row in ema_log.csv
+        self.ema = None
+        self._ema_resume = ema_checkpoint if ema is not None else None
+        if ema is not None:
+            why = ema_refused((bool(pixel_embeddings) and loss_func in _EMBED_LOSSES) or (not pixel_embeddings and loss_func == "cross_entropy"),
+                              fused_step)
+            if why:
+                raise SznError(why)
+            decay, every, warm = _engine.TrainStep._check_ema(ema)
+            self.ema = dict(decay=decay, every=every, warmup=warm)
+            if self.rank == 0:
+                os.makedirs(self.log_dir, exist_ok=True)
+                if not osp.exists(osp.join(self.log_dir, 'ema_log.csv')):
+                    with open(osp.join(self.log_dir, 'ema_log.csv'), 'w') as f:
+                        f.write('epoch,iteration,decay,every,updates,rel_l2_distance\n')
+
         if self.pixel_embeddings:
             arr = np.asarray(embed_arr, dtype=np.float32) if embed_arr is not None else \
                 load_embeddings(dataset, pixel_embeddings)
@@ -685,6 +716,8 @@ class Trainer(object):
                 kw.update(ohem=self.ohem)
             if self.bias_loss is not None:
                 kw.update(bias=self.bias_loss)
+        if self.ema is not None:
+            kw.update(ema=self.ema)
         self._step = _engine.TrainStep(self.model, lr=gw['lr'], bias_lr=gb['lr'],
                                        bias_weight_decay=gb.get('weight_decay', 0.0), precision=self.precision,
                                        fused_head=True, keep_grads=os.environ.get("SZN_KEEP_GRADS", "0") == "1", **kw)
@@ -692,11 +725,25 @@ class Trainer(object):
         # calls zero_grad() next (train.py:170-175) and nothing reads the weight gradients in between, so the layers whose Adam
         # step rides in their weight-gradient kernel do not store theirs -- those `.grad`s are None, not stale
         self._step.import_optimizer_state(self.optim)       # resumed runs (train.py:135-136)
+        if self.ema is not None and self._ema_resume is not None and 'ema_state_dict' in self._ema_resume:
+            # the checkpoint carries an average: restore it (without one import_optimizer_state started it from the loaded weights)
+            self._step.load_ema_state_dict(self._ema_resume['ema_state_dict'])
+            self._step.ema_updates = int(self._ema_resume.get('ema_updates', 0))
+        self._ema_resume = None
         return self._step
+
+    def _ema_step(self):
+        """the fused step that keeps the average (ema=), built if need be; an SznError where this optimizer wiring has none"""
+        step = self._fast_step()
+        if step is None:
+            raise SznError(ema_refused(True, True, False))
+        return step
 
     def train_epoch(self):
         self.model.train()
         step = self._fast_step()
+        if self.ema is not None:
+            self._ema_step()
         if self.pseudo is not None:
             if step is None:
                 raise SznError("pseudo labels run inside the fused training step, which this optimizer wiring does not allow")
@@ -975,6 +1022,7 @@ class Trainer(object):
                 name = str(self.label_names[k]) if self.label_names is not None and k < len(self.label_names) else 'class%d' % k
                 f.write('%d,%d,%s,%d,%d,%d,%r\n' % (self.epoch, k, name.replace(',', ' '), shots[k], counts[k, 0], counts[k, 1], cosv))
 
+    ema = None                                  # dict(decay, every, warmup) with ema=
     _proto_saved = None                         # (embeddings, seen_embeddings, unseen_embeddings) while the adapted rows are swapped in
 
     @contextlib.contextmanager
@@ -1005,11 +1053,29 @@ class Trainer(object):
         """reference :182-292.  The {all, seen, unseen} K x K histograms and the loss sum are accumulated on the GPU
         (szn_confusion_hist on the device prediction) and read back ONCE per epoch; under data parallelism the validation
         images are split across the ranks and the histograms / loss sums are all-reduced before the metrics.  With proto= the whole
-        validation runs on the adapted class embeddings (adapted_embeddings)."""
-        with self.adapted_embeddings():
-            return self._validate(both_fcn_and_seenmask)
+        validation runs on the adapted class embeddings (adapted_embeddings).  With ema= it runs, prototype pooling included, on the
+        averaged weights (engine.TrainStep.averaged_weights); the checkpoint is written after the raw iterate is back in place."""
+        step = None
+        if self.ema is not None:
+            step = self._ema_step()
+            self._ema_report(step)
+        with (step.averaged_weights() if step is not None else contextlib.nullcontext()):
+            with self.adapted_embeddings():
+                metrics, is_best = self._validate(both_fcn_and_seenmask)
+        self._save_checkpoint(is_best)
+        return metrics
+
+    def _ema_report(self, step):
+        """once per validation: one ema_log.csv row (rank 0) with the relative L2 distance |avg - w| / |w| of the weight buffer"""
+        if self.rank != 0:
+            return
+        rel = float((torch.linalg.vector_norm(step.ema_w - step.flat_w) / torch.linalg.vector_norm(step.flat_w)).item())
+        with open(osp.join(self.log_dir, 'ema_log.csv'), 'a') as f:
+            f.write(','.join(map(str, [self.epoch, self.iteration, self.ema["decay"], self.ema["every"], step.ema_updates, rel])) + '\n')
+        self.tb_writer.add_scalar('fcn/val/ema_rel_l2_distance', rel, self.epoch)
 
     def _validate(self, both_fcn_and_seenmask):
+        """-> (metrics, whether this validation's mean IU is the best so far)"""
         import torch.distributed as dist
         self.model.eval()
         world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
@@ -1097,22 +1163,29 @@ class Trainer(object):
         is_best = mean_iu > self.best_mean_iu
         if is_best:
             self.best_mean_iu = mean_iu
+        return metrics, is_best
+
+    def _save_checkpoint(self, is_best):
+        """reference :281-292; with ema= the average rides next to the raw iterate ('model_state_dict' stays the raw iterate)"""
         if self._step is not None:
             self._step.gather_masters()          # sharded optimizer: a collective -- every rank, before rank 0 reads the parameters
         if self.rank == 0:
             if self._step is not None:
                 self._step.export_optimizer_state(self.optim)   # flat moments -> per-parameter torch optimizer state
-            torch.save({
+            ckpt = {
                 'epoch': self.epoch,
                 'iteration': self.iteration,
                 'arch': self.model.__class__.__name__,
                 'optim_state_dict': self.optim.state_dict(),
                 'model_state_dict': self.model.state_dict(),
                 'best_mean_iu': self.best_mean_iu,
-            }, osp.join(self.log_dir, 'checkpoint'))
+            }
+            if self.ema is not None:
+                ckpt['ema_state_dict'] = self._step.ema_state_dict()
+                ckpt['ema_updates'] = self._step.ema_updates
+            torch.save(ckpt, osp.join(self.log_dir, 'checkpoint'))
             if is_best:
                 shutil.copy(osp.join(self.log_dir, 'checkpoint'), osp.join(self.log_dir, 'best'))
-        return metrics
 
     def train(self):
         for epoch in range(self.max_epoch):
