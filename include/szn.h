@@ -691,6 +691,52 @@ int szn_ema_step(long n, float* avg, const float* param, float decay, int every,
  * SZN_ERR_ARG, nothing is written.  szn_last_kernel: "swap_kernel".                                                             */
 int szn_swap_f32(long n, float* a, float* b, szn_stream_t stream);
 
+/* ---- gradient statistics and gradient-norm clipping (torch.nn.utils.clip_grad_norm_'s rule; the reference does not clip, it
+ * prints score_fr's gradient sum: trainer_fcn.py:160-162) ----
+ * szn_grad_stats: per segment s = elements [seg_end[s-1], seg_end[s]) of one flat buffer (fp32, or a 16-bit image: the summed wire
+ * buffer of the exchange), stats[s] = {sum g, sum g*g}.  seg_end is a HOST array read during the call (ascending, seg_end[n_seg-1]
+ * == n); the table travels by value in the kernel arguments -- hence at most SZN_GRAD_STATS_MAX_SEGS segments -- so nothing is
+ * copied to the device and the call can be captured.  Segments start at any element offset; an empty one gives {0, 0}; rows of
+ * stats are overwritten; grad is only read.  Arithmetic: every element is widened to double first, so g*g is exact for all three
+ * input types and the additions in double are the only roundings.  Their order is fixed: a segment is cut into chunks of 16384
+ * elements from its own start; one block reduces a chunk (grad_stats_chunk_kernel: per lane its vectors in ascending order, the
+ * wave by halving shuffles, the four waves through LDS in ascending order) and writes its pair to the workspace; a second kernel
+ * (grad_stats_sum_kernel, one wave per segment) adds the segment's chunk pairs: 64 contiguous runs, each in ascending chunk order,
+ * then the 64 run sums in ascending order.  No atomics: two calls give the same bits.  A non-finite element makes its segment's
+ * sum of squares non-finite.  Any pointer aligned to its element size is taken (16-byte loads -- 8-byte for 16-bit input -- on the
+ * aligned body of each chunk, scalar loads for the <= 3 elements in front and behind).  SZN_ERR_ARG before any launch: n < 0,
+ * n_seg outside [1, SZN_GRAD_STATS_MAX_SEGS], seg_end not ascending or not ending at n, NULL seg_end / stats, NULL grad /
+ * workspace with n > 0, a dtype other than SZN_F32 | SZN_BF16 | SZN_F16, grad not aligned to its element size, stats / workspace
+ * not 8-byte aligned.  n == 0 writes zeros.  workspace: szn_grad_stats_workspace_bytes(n, n_seg).
+ * szn_last_kernel(): grad_stats_sum_kernel; szn_prev_kernel(): grad_stats_chunk_kernel.                                        */
+#define SZN_GRAD_STATS_MAX_SEGS 64
+size_t szn_grad_stats_workspace_bytes(long n, int n_seg);
+int szn_grad_stats(long n, const void* grad, int grad_dtype, int n_seg, const int64_t* seg_end, double* stats, void* workspace,
+                   szn_stream_t stream);
+/* The step's decision from the statistics of all its buffers (stats: device [n_seg][2], any n_seg >= 1), one tiny launch:
+ *     total = sum_s stats[s][1] (ascending, double);  S = scale_state ? scale_state[0] : 1;  norm = sqrt(total) * grad_scale / S
+ * total not finite (an element was inf / NaN: finite fp32 squares cannot overflow a double): clip_state = {1, (float)norm, -, -}
+ * with both counters untouched and, if scale_state is given, scale_state[1] = 1 -- the found_inf flag szn_grad_check_finite would
+ * have raised.  Otherwise coef = norm + 1e-6 > max_norm ? (float)(max_norm / (norm + 1e-6)) : 1 and
+ *     clip_state = {coef, (float)norm, steps clipped + (coef < 1), steps seen + 1}       (device float[4])
+ * max_norm = +inf measures only (coef is exactly 1).  SZN_ERR_ARG: max_norm NaN or <= 0, n_seg < 1, NULL stats / clip_state.
+ * szn_last_kernel(): clip_coef_kernel.                                                                                          */
+int szn_clip_coef(int n_seg, const double* stats, float max_norm, float grad_scale, float* scale_state, float* clip_state,
+                  szn_stream_t stream);
+/* The optimizer steps under clipping: supersets of szn_*_step, _g16 and _scaled.  The only new arithmetic is one fp32 multiply in
+ * the kernel preamble: the effective gradient scale is grad_scale * clip_state[0], or (grad_scale / scale_state[0]) *
+ * clip_state[0] with scale_state; the per-element chain is unchanged, so clip_state[0] == 1 reproduces the matching entry above
+ * bit for bit.  With scale_state the step count / first_step flag and the skip come from it as in the _scaled entries (step /
+ * first_step are ignored).  SZN_ERR_ARG: NULL clip_state, a 16-bit grad_dtype together with scale_state, and what the entries
+ * above refuse.                                                                                                                  */
+int szn_adam_step_clipped(long n, float* param, const void* grad, int grad_dtype, float* exp_avg, float* exp_avg_sq, float lr,
+                          float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                          const float* scale_state, const float* clip_state, void* w_lp, int w_lp_dtype, szn_stream_t stream);
+int szn_sgd_momentum_step_clipped(long n, float* param, const void* grad, int grad_dtype, float* momentum_buf, float lr,
+                                  float momentum, float weight_decay, int first_step, float grad_scale,
+                                  const float* scale_state, const float* clip_state, void* w_lp, int w_lp_dtype,
+                                  szn_stream_t stream);
+
 /* ---- row / column remapping of an NHWC map (the constant band of the pad-100 network inside the conv3 block) --------------
  * models.py:43 pads conv1_1 by 100: at 1/4 resolution most rows / columns between the tensor edge and the image's reach hold one
  * value per channel, and conv3_1 .. conv3_3 (models.py:56-62,123-128) need not compute them.  One kernel does the four index maps

@@ -82,6 +82,7 @@ SEEN_SWEEP_MAX_TAUS = 64    # SZN_SEEN_SWEEP_MAX_TAUS
 CONSE_MAX_TOP = 16          # SZN_CONSE_MAX_TOP
 PSEUDO_BINS = 1024          # SZN_PSEUDO_BINS
 OHEM_BINS = 1024            # SZN_OHEM_BINS
+GRAD_STATS_MAX_SEGS = 64    # SZN_GRAD_STATS_MAX_SEGS
 PROTO_RAW, PROTO_UNIT = 0, 1   # SZN_PROTO_RAW, SZN_PROTO_UNIT (szn_class_proto's mode)
 
 
@@ -97,6 +98,7 @@ _IP = C.POINTER(C.c_int)
 _CS = C.POINTER(ClassSet)
 _MV = C.POINTER(MsView)
 _FP = C.POINTER(C.c_float)      # a HOST float array
+_I64P = C.POINTER(C.c_int64)    # a HOST int64 array (szn_grad_stats' segment table)
 
 # name -> (restype, argtypes); must list every symbol of include/szn.h (tests/test_abi.py checks that)
 SIGNATURES = {
@@ -195,6 +197,11 @@ SIGNATURES = {
     "szn_loss_scale_update": (_I, [_P, _F, _F, _I, _F, _F, _P]),
     "szn_ema_step": (_I, [_L, _P, _P, _F, _I, _I, _P, _P]),
     "szn_swap_f32": (_I, [_L, _P, _P, _P]),
+    "szn_grad_stats_workspace_bytes": (_SZ, [_L, _I]),
+    "szn_grad_stats": (_I, [_L, _P, _I, _I, _I64P, _P, _P, _P]),
+    "szn_clip_coef": (_I, [_I, _P, _F, _F, _P, _P, _P]),
+    "szn_adam_step_clipped": (_I, [_L, _P, _P, _I, _P, _P, _F, _F, _F, _F, _F, _I, _F, _P, _P, _P, _I, _P]),
+    "szn_sgd_momentum_step_clipped": (_I, [_L, _P, _P, _I, _P, _F, _F, _F, _I, _F, _P, _P, _P, _I, _P]),
     "szn_cast": (_I, [_I, _I, _L, _P, _P, _P]),
     "szn_band_remap": (_I, [_I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "szn_band_fold": (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P]),

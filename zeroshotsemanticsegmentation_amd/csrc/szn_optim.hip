@@ -41,7 +41,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
                                                    float* __restrict__ m, float* __restrict__ v, long n, float lr,
                                                    float b1, float b2, float eps, float wd, float step_size,
                                                    float inv_bc2_sqrt, float gscale, uint16_t* __restrict__ wlp, int vec,
-                                                   const float* __restrict__ dyn) {
+                                                   const float* __restrict__ dyn, const float* __restrict__ clip) {
     if (dyn) {          // dynamic loss scaling: {scale S, found_inf, steps applied, ...}; see szn_adam_step_scaled
         if (dyn[1] != 0.f) return;                       // a non-finite gradient somewhere: the whole step is skipped
         gscale = gscale / dyn[0];
@@ -49,6 +49,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
         step_size = (float)((double)lr / (1.0 - pow((double)b1, step)));
         inv_bc2_sqrt = (float)(1.0 / sqrt(1.0 - pow((double)b2, step)));
     }
+    if (clip) gscale = gscale * clip[0];                 // szn_*_step_clipped: the step's clipping coefficient (szn_clip_coef), one fp32 multiply
     const long n4 = vec ? (n >> 2) : 0;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
         const f32x4_t gq = grad_src<G>::ld4(g, i);
@@ -88,12 +89,13 @@ template <typename LP, typename G = float>
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const void* __restrict__ g,
                                                   float* __restrict__ buf, long n, float lr, float mom, float wd,
                                                   int first, float gscale, uint16_t* __restrict__ wlp, int vec,
-                                                  const float* __restrict__ dyn) {
+                                                  const float* __restrict__ dyn, const float* __restrict__ clip) {
     if (dyn) {
         if (dyn[1] != 0.f) return;
         gscale = gscale / dyn[0];
         first = dyn[2] == 0.f;
     }
+    if (clip) gscale = gscale * clip[0];
     const long n4 = vec ? (n >> 2) : 0;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
         const f32x4_t gq = grad_src<G>::ld4(g, i);
@@ -125,7 +127,7 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const v
 
 static int adam_impl(long n, float* param, const void* grad, int grad_dtype, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
                      float beta2, float eps, float weight_decay, int step, float grad_scale, void* w_lp, int w_lp_dtype,
-                     const float* dyn, szn_stream_t stream) {
+                     const float* dyn, szn_stream_t stream, const float* clip = nullptr) {
     if (!param || !grad || !exp_avg || !exp_avg_sq || n <= 0 || step < 1) SZN_FAIL(SZN_ERR_ARG, "adam_step: bad argument");
     if (w_lp && !szn_is16(w_lp_dtype)) SZN_FAIL(SZN_ERR_ARG, "adam_step: the weight image must be SZN_BF16 or SZN_F16");
     if (grad_dtype != SZN_F32 && !szn_is16(grad_dtype)) SZN_FAIL(SZN_ERR_ARG, "adam_step: the gradient must be SZN_F32, SZN_BF16 or SZN_F16");
@@ -141,7 +143,7 @@ static int adam_impl(long n, float* param, const void* grad, int grad_dtype, flo
         using G = decltype(gtag);
         const auto kernel = lp_f16 ? adam_kernel<f16_raw, G> : adam_kernel<bf16_raw, G>;
         hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps,
-                           weight_decay, step_size, inv_bc2_sqrt, grad_scale, (uint16_t*)w_lp, vec, dyn);
+                           weight_decay, step_size, inv_bc2_sqrt, grad_scale, (uint16_t*)w_lp, vec, dyn, clip);
     });
     SZN_CHECK_LAUNCH(grad_dtype == SZN_F32 ? "adam_kernel" : "adam_kernel_g16");
     return SZN_OK;
@@ -172,7 +174,7 @@ extern "C" int szn_adam_step_scaled(long n, float* param, const float* grad, flo
 
 static int sgd_impl(long n, float* param, const void* grad, int grad_dtype, float* momentum_buf, float lr, float momentum,
                     float weight_decay, int first_step, float grad_scale, void* w_lp, int w_lp_dtype, const float* dyn,
-                    szn_stream_t stream) {
+                    szn_stream_t stream, const float* clip = nullptr) {
     if (!param || !grad || !momentum_buf || n <= 0) SZN_FAIL(SZN_ERR_ARG, "sgd_momentum_step: bad argument");
     if (w_lp && !szn_is16(w_lp_dtype)) SZN_FAIL(SZN_ERR_ARG, "sgd_momentum_step: the weight image must be SZN_BF16 or SZN_F16");
     if (grad_dtype != SZN_F32 && !szn_is16(grad_dtype)) SZN_FAIL(SZN_ERR_ARG, "sgd_momentum_step: the gradient must be SZN_F32, SZN_BF16 or SZN_F16");
@@ -185,7 +187,7 @@ static int sgd_impl(long n, float* param, const void* grad, int grad_dtype, floa
         using G = decltype(gtag);
         const auto kernel = lp_f16 ? sgd_kernel<f16_raw, G> : sgd_kernel<bf16_raw, G>;
         hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, param, grad, momentum_buf, n, lr, momentum, weight_decay,
-                           first_step, grad_scale, (uint16_t*)w_lp, vec, dyn);
+                           first_step, grad_scale, (uint16_t*)w_lp, vec, dyn, clip);
     });
     SZN_CHECK_LAUNCH(grad_dtype == SZN_F32 ? "sgd_kernel" : "sgd_kernel_g16");
     return SZN_OK;
@@ -210,6 +212,27 @@ extern "C" int szn_sgd_momentum_step_scaled(long n, float* param, const float* g
                                             void* w_lp, int w_lp_dtype, szn_stream_t stream) {
     if (!scale_state) SZN_FAIL(SZN_ERR_ARG, "sgd_momentum_step_scaled: scale_state is NULL");
     return sgd_impl(n, param, grad, SZN_F32, momentum_buf, lr, momentum, weight_decay, 0, grad_scale, w_lp, w_lp_dtype, scale_state, stream);
+}
+
+// ---- the steps under gradient-norm clipping: supersets of the three forms above, the effective scale times clip_state[0] ----
+extern "C" int szn_adam_step_clipped(long n, float* param, const void* grad, int grad_dtype, float* exp_avg, float* exp_avg_sq, float lr,
+                                     float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                                     const float* scale_state, const float* clip_state, void* w_lp, int w_lp_dtype, szn_stream_t stream) {
+    if (!clip_state) SZN_FAIL(SZN_ERR_ARG, "adam_step_clipped: clip_state is NULL");
+    if (scale_state && grad_dtype != SZN_F32) SZN_FAIL(SZN_ERR_ARG, "adam_step_clipped: scale_state goes with an SZN_F32 gradient only");
+    return adam_impl(n, param, grad, grad_dtype, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, scale_state ? 1 : step,
+                     grad_scale, w_lp, w_lp_dtype, scale_state, stream, clip_state);
+}
+
+extern "C" int szn_sgd_momentum_step_clipped(long n, float* param, const void* grad, int grad_dtype, float* momentum_buf, float lr,
+                                             float momentum, float weight_decay, int first_step, float grad_scale,
+                                             const float* scale_state, const float* clip_state, void* w_lp, int w_lp_dtype,
+                                             szn_stream_t stream) {
+    if (!clip_state) SZN_FAIL(SZN_ERR_ARG, "sgd_momentum_step_clipped: clip_state is NULL");
+    if (scale_state && grad_dtype != SZN_F32)
+        SZN_FAIL(SZN_ERR_ARG, "sgd_momentum_step_clipped: scale_state goes with an SZN_F32 gradient only");
+    return sgd_impl(n, param, grad, grad_dtype, momentum_buf, lr, momentum, weight_decay, scale_state ? 0 : first_step, grad_scale, w_lp,
+                    w_lp_dtype, scale_state, stream, clip_state);
 }
 
 // ---- dynamic loss scaling (fp16 path) ------------------------------------------------------------------------------------------

@@ -39,6 +39,16 @@ def init_process_group(backend="nccl", device=None, **kw):
     return dist.init_process_group(backend, **kw)
 
 
+def grad_report(names, stats, clip_state, factor):
+    """host numbers of one step of TrainStep(clip=): stats = grad_stats ([n_seg][2] = {sum g, sum g*g} of the buffers as they stand),
+    clip_state = {coef, norm, steps clipped, steps seen}, factor = what turns a buffer element into the true gradient (1 / (world x
+    loss scale)).  -> dict(norm, coef, clipped, seen, sums={name: sum g}, norms={name: |g|})"""
+    import math
+    return dict(norm=float(clip_state[1]), coef=float(clip_state[0]), clipped=int(clip_state[2]), seen=int(clip_state[3]),
+                sums={n: float(stats[i][0]) * factor for i, n in enumerate(names)},
+                norms={n: math.sqrt(float(stats[i][1])) * factor if stats[i][1] >= 0 else float("nan") for i, n in enumerate(names)})
+
+
 class GradBuckets(object):
     """Data-parallel exchange of the flat weight gradient: contiguous buckets in BACKWARD completion order.
 
@@ -377,7 +387,7 @@ class TrainStep(object):
                  scale_growth=2.0, scale_backoff=0.5, scale_growth_interval=2000, force_comm=None, reserved_cus=None,
                  fused_adam=None, keep_grads=True, exchange=None, direct_wire=None, sharded=None, forced_unseen=None,
                  class_weight=None, size_average=False, sim_exclude=None, sim_temperature=None, pseudo=None, ohem=None,
-                 rank_margin=None, rank_hardest=False, bias=None, ema=None):
+                 rank_margin=None, rank_hardest=False, bias=None, ema=None, clip=None):
         """Data-parallel knobs (the reference is single-GPU): grad_comm_dtype (SZN_GRAD_COMM = fp32 | bf16) = the
         wire format of the gradient buckets; exchange=False (SZN_GRAD_COMM=off) = no exchange at all (bench.py's comm-off timing);
         direct_wire (default: on for a 16-bit wire with keep_grads=False; SZN_WIRE_DIRECT=0 turns it off) = the weight-gradient
@@ -438,7 +448,22 @@ class TrainStep(object):
         ema_updates counts the launches (for logs).  Plain data parallelism needs nothing: every rank holds the same parameters after
         the all-reduce and therefore the same average.  Refused with a ValueError: the sharded optimizer (the fp32 masters of the
         other ranks' slices are stale there), decay outside [0, 1), every < 1, and every > 1 while a stream capture is in progress
-        (the host decides which steps update).  None (default): nothing changes, launch for launch."""
+        (the host decides which steps update).  None (default): nothing changes, launch for launch.
+        clip=dict(max_norm=M), M > 0: clipping by the global gradient norm (torch.nn.utils.clip_grad_norm_'s rule) and a per-layer
+        gradient log; M = float('inf') takes the statistics only.  After the exchange and in front of the first optimizer launch two
+        szn_grad_stats launches (weights -- the 16-bit wire image on the direct wire --, then biases) write {sum g, sum g*g} per layer
+        into grad_stats (device double [n_seg][2]; grad_segments names the rows: every "<layer>.weight" in flat order, then every
+        "<layer>.bias"), szn_clip_coef turns them into clip_state (device float[4] = {coef, norm, steps clipped, steps seen}) and every
+        optimizer launch goes through the *_clipped entries, which multiply their gradient scale by coef.  The norm is that of the
+        unscaled gradient (the loss scale and 1/world are divided out) over exactly the elements the optimizer launches update.  On
+        the dynamic loss-scale path szn_clip_coef raises found_inf itself (a non-finite element makes the sum of squares non-finite)
+        and the two szn_grad_check_finite launches are not issued; a skipped step moves neither counter.  grad_norms() reads the
+        numbers back (a host sync).  The norm needs every gradient before any update, so the fc6 Adam epilogue and the early
+        side-stream optimizer pass are off -- the path a data-parallel step takes anyway.  Data parallelism needs nothing: every rank
+        reads the same all-reduced buffers.  Refused with a ValueError: a bad max_norm, and the sharded optimizer (a rank holds
+        slices of the summed gradient only).  None (default): nothing changes, launch for launch."""
+        self._clip = None if clip is None else self._check_clip(clip)
+        self.grad_segments = self.grad_stats = self.clip_state = self.clip_scale = None
         self._ema = None if ema is None else self._check_ema(ema)
         self.ema_w = self.ema_b = None
         self.ema_updates = 0
@@ -601,6 +626,10 @@ class TrainStep(object):
             if self.buckets.sharded:
                 raise ValueError("TrainStep: ema= does not run with the sharded optimizer, whose fp32 masters of the other ranks' slices are stale")
             self.reset_ema()
+        if self._clip is not None:
+            if self.buckets.sharded:
+                raise ValueError("TrainStep: clip= does not run with the sharded optimizer, where a rank holds slices of the summed gradient only")
+            self._init_clip()
         # CUs the persistent one-block-per-CU backward kernels (conv3x3_regw dgrad, conv_wgrad_taps) leave to RCCL's workgroups
         # while an exchange is in flight (default SZN_RESERVED_CUS, 0 = none; only when buckets are actually exchanged)
         if reserved_cus is None:
@@ -623,8 +652,10 @@ class TrainStep(object):
         if fused_adam is None:
             fused_adam = os.environ.get("SZN_FUSED_ADAM", "1") == "1"
         self._own_stream = None          # see step(): the non-blocking stream of a small step
+        # clip=: the norm needs every gradient before any update, so no update may ride in a weight-gradient kernel
         self.fused_adam = bool(fused_adam and optimizer == "adam" and not self.dynamic and not self.buckets.active
-                               and self.flat_w_lp is not None and os.environ.get("SZN_EARLY_ADAM", "auto") != "1")
+                               and self.flat_w_lp is not None and os.environ.get("SZN_EARLY_ADAM", "auto") != "1"
+                               and self._clip is None)
         if self.fused_adam and not self.keep_grads:
             # the fused layers' gradients are consumed inside their weight-gradient kernel and never stored: `.grad` must not
             # look like a gradient (the reference keeps .grad valid until zero_grad(); keep_grads=True restores that)
@@ -1112,6 +1143,8 @@ class TrainStep(object):
         on = mode == "1" or (mode == "auto" and pixels <= 2 * 512 * 512 and self.eng.dtype == torch.float32)
         if not on or self.buckets.active or self.dynamic or self.is8 or "fc6" not in self.woff:
             return base
+        if self._clip is not None:       # the early pass would update fc6 .. score_fr before the step's norm is known
+            return base
 
         def done(name):
             base(name)
@@ -1165,6 +1198,19 @@ class TrainStep(object):
         lp_code = L.dtype_code(self.flat_w_lp.dtype) if self.flat_w_lp is not None else 0
         lp = L.ptr(self.flat_w_lp[lo:hi]) if lp_on else None
         n = hi - lo
+        if self._clip is not None:       # the *_clipped entries: supersets of the three forms below, gradient scale x clip_state[0]
+            gcode = L.dtype_code(grad.dtype)
+            if self.opt == "adam":
+                m1, m2 = self.state[key]
+                awd = float(self.bias_wd if key == "b" else self.adam_wd)
+                L.call("szn_adam_step_clipped", n, L.ptr(flat[lo:hi]), L.ptr(grad[lo:hi]), gcode, L.ptr(m1[lo:hi]), L.ptr(m2[lo:hi]),
+                       float(lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), awd, nstep, gs, L.ptr(dyn),
+                       L.ptr(self.clip_state), lp, lp_code, st)
+            else:
+                (buf,) = self.state[key]
+                L.call("szn_sgd_momentum_step_clipped", n, L.ptr(flat[lo:hi]), L.ptr(grad[lo:hi]), gcode, L.ptr(buf[lo:hi]), float(lr),
+                       float(self.momentum), float(wd), int(nstep == 1), gs, L.ptr(dyn), L.ptr(self.clip_state), lp, lp_code, st)
+            return
         if self.opt == "adam":           # train.py:130-133 (Adam has no weight decay in the reference wiring)
             m1, m2 = self.state[key]
             awd = float(self.bias_wd if key == "b" else self.adam_wd)
@@ -1194,7 +1240,9 @@ class TrainStep(object):
         self.nstep += 1
         st = L.stream_ptr()
         dyn = self.scale_state
-        if self.dynamic:                 # raise the overflow flag from the (already all-reduced) gradients
+        if self._clip is not None:       # statistics of the (already all-reduced) gradients, the step's coefficient, the overflow flag
+            self._clip_launch(st)
+        elif self.dynamic:               # raise the overflow flag from the (already all-reduced) gradients
             L.call("szn_grad_check_finite", self.flat_gw.numel(), L.ptr(self.flat_gw), L.ptr(dyn), st)
             L.call("szn_grad_check_finite", self.flat_gb.numel(), L.ptr(self.flat_gb), L.ptr(dyn), st)
         whi = self.flat_w.numel()
@@ -1318,6 +1366,58 @@ class TrainStep(object):
                 self.scale_state[2] = float(self.nstep)
         if self._ema is not None:        # a resumed run: the average restarts from the loaded weights unless load_ema_state_dict follows
             self.reset_ema()
+
+    # ---- gradient statistics and gradient-norm clipping (clip=) -------------------------------------------------------------
+    @staticmethod
+    def _check_clip(cfg):
+        """clip= checked on the host (before anything touches a device) -> max_norm"""
+        if not isinstance(cfg, dict) or set(cfg) != {"max_norm"}:
+            raise ValueError("TrainStep: clip must be a dict(max_norm=), got %r" % (cfg,))
+        try:
+            m = float(cfg["max_norm"])
+        except (TypeError, ValueError):
+            raise ValueError("TrainStep: clip max_norm must be a number, got %r" % (cfg["max_norm"],))
+        if isinstance(cfg["max_norm"], bool) or not m > 0.0:
+            raise ValueError("TrainStep: clip max_norm must be > 0 (float('inf'): statistics only), got %r" % (cfg["max_norm"],))
+        return m
+
+    def _init_clip(self):
+        import ctypes
+        if len(self.layers) > L.GRAD_STATS_MAX_SEGS:
+            raise ValueError("TrainStep: clip= holds at most %d layers per buffer" % L.GRAD_STATS_MAX_SEGS)
+        self.grad_segments = [n + ".weight" for n in self.layers] + [n + ".bias" for n in self.layers]
+        nl = len(self.layers)
+        self.grad_stats = torch.zeros(2 * nl, 2, dtype=torch.float64, device=self.dev)
+        self.clip_state = torch.tensor([1.0, 0.0, 0.0, 0.0], device=self.dev)
+        self.clip_scale = torch.ones(1, device=self.dev)      # dynamic path: the loss scale the last step's gradients carried
+        self._seg_tabs = []
+        for off in (self.woff, self.boff):                    # HOST tables szn_grad_stats reads during the call
+            ends = [off[n][0] + off[n][1] for n in self.layers]
+            self._seg_tabs.append((ctypes.c_int64 * nl)(*ends))
+        nb = max(L.load().szn_grad_stats_workspace_bytes(t.numel(), nl) for t in (self.flat_gw, self.flat_gb))
+        self._clip_ws = torch.empty(nb, dtype=torch.uint8, device=self.dev)
+
+    def _clip_launch(self, st):
+        nl = len(self.layers)
+        gw = self.buckets.stage[:self.flat_gw.numel()] if self.buckets.direct else self.flat_gw     # (as _opt_launch reads it)
+        for i, g in enumerate((gw, self.flat_gb)):
+            L.call("szn_grad_stats", g.numel(), L.ptr(g), L.dtype_code(g.dtype), nl, self._seg_tabs[i], L.ptr(self.grad_stats[i * nl:]),
+                   L.ptr(self._clip_ws), st)
+        gs = 1.0 / self.world if self.dynamic else 1.0 / (self.world * self._loss_scale0)           # _opt_launch's grad_scale
+        if self.dynamic:                 # szn_loss_scale_update changes S at the end of the step: keep what these statistics carry
+            self.clip_scale.copy_(self.scale_state[:1])
+        L.call("szn_clip_coef", 2 * nl, L.ptr(self.grad_stats), self._clip, gs, L.ptr(self.scale_state), L.ptr(self.clip_state), st)
+
+    def grad_factor(self):
+        """what the buffers' statistics are multiplied by to describe the true gradient, apart from the dynamic loss scale"""
+        return 1.0 / self.world if self.dynamic else 1.0 / (self.world * self._loss_scale0)
+
+    def grad_norms(self):
+        """the last step's numbers on the host (a sync; tests and logs): grad_report of grad_stats, clip_state and the scale"""
+        if self._clip is None:
+            raise L.SznError("TrainStep: grad_norms() on a step built without clip=")
+        return grad_report(self.grad_segments, self.grad_stats.cpu().numpy(), self.clip_state.cpu().numpy(),
+                           self.grad_factor() / float(self.clip_scale.item()))
 
     # ---- averaged weights (ema=) --------------------------------------------------------------------------------------------
     @staticmethod

@@ -67,6 +67,11 @@ Added for this implementation (none change the reference flags):
                        it out again, bit for bit); checkpoints carry 'ema_state_dict' / 'ema_updates' next to the raw iterate and -r
                        restores them; -m test_fcn / test_all --use-ema evaluates the stored average; one row per validation in
                        <log_dir>/ema_log.csv.  DECAY has no default
+  --clip-grad-norm MAX clip every step's gradient to the global L2 norm MAX (torch.nn.utils.clip_grad_norm_'s rule) inside the fused
+                       step: per-layer sums and sums of squares taken on the GPU after the exchange (szn_grad_stats), the coefficient
+                       by szn_clip_coef, the update by the *_clipped optimizer entries; no host sync.  --grad-stats alone measures
+                       (MAX = inf).  Either flag: one row per iteration in <log_dir>/grad_log.csv (norm, coefficient, clipped steps,
+                       one norm per layer) and score_fr's gradient sum in the progress print.  MAX has no default
   --init synthetic|vgg path handling: without the caffe VGG16 file the backbone starts from synth weights
   torchrun: RANK / LOCAL_RANK / WORLD_SIZE are honoured (one process per GPU, RCCL gradient all-reduce).
 """
@@ -242,6 +247,13 @@ def build_parser():
     p.add_argument('--ema-every', type=int, default=None, metavar='N',
                    help="with --ema: update the average every N-th step, with D ^ N (default 1)")
     p.add_argument('--ema-no-warmup', action='store_true', help="with --ema: D = DECAY from the first step on, without the (1 + s) / (10 + s) ramp")
+    p.add_argument('--clip-grad-norm', type=float, default=None, metavar='MAX',
+                   help="clip the gradient of every training step of the FCN phase to the global L2 norm MAX, coef = min(1, MAX / (norm + "
+                        "1e-6)), on the GPU inside the fused step; rank 0 writes one row per iteration to <log_dir>/grad_log.csv.  MAX > 0 "
+                        "has no default: nobody has tuned it here.  Needs a configuration that trains on the fused step.  Default: off")
+    p.add_argument('--grad-stats', action='store_true',
+                   help="the gradient log of --clip-grad-norm without clipping (MAX = inf): grad_log.csv and score_fr's gradient sum in "
+                        "the progress print")
     p.add_argument('--use-ema', action='store_true',
                    help="with -m test_fcn / -m test_all: evaluate the averaged weights of the checkpoint ('ema_state_dict') instead of the "
                         "raw iterate ('model_state_dict'); an error for a checkpoint written without --ema.  The checkpoint this "
@@ -620,6 +632,22 @@ def check_ema(decay, every, no_warmup, use_ema, cfg):
     return dict(decay=decay, every=1 if every is None else every, warmup=not no_warmup)
 
 
+def check_clip(max_norm, grad_stats, cfg):
+    """--clip-grad-norm / --grad-stats: MAX > 0 (inf allowed: measure only), and only where the FCN phase trains on engine.TrainStep
+    (trainer_fcn.clip_refused) -> the Trainer's (clip_grad_norm, grad_stats)"""
+    if max_norm is None and not grad_stats:
+        return None, False
+    if cfg['mode'] != 'train':
+        raise Exception("--clip-grad-norm / --grad-stats act on training steps (-m train)")
+    if max_norm is not None and not max_norm > 0.0:
+        raise Exception("--clip-grad-norm: MAX must be > 0 (got %r)" % (max_norm,))
+    step_cfg = (cfg['fcn_loss'] in _EMBED_LOSSES and cfg['embed_dim']) or (cfg['fcn_loss'] == 'cross_entropy' and not cfg['embed_dim'])
+    why = trainer_fcn.clip_refused(bool(step_cfg))
+    if why:
+        raise trainer_fcn.SznError("--clip-grad-norm / --grad-stats: " + why)
+    return max_norm, bool(grad_stats)
+
+
 USE_EMA_MISSING = "--use-ema: the checkpoint %s carries no 'ema_state_dict' (it was written without --ema)"
 
 
@@ -670,6 +698,7 @@ def main(argv=None):
     check_bias(args.bias_loss, args.bias_start_epoch, cfg)
     proto = check_proto(args.proto_shots, args.proto_alpha, args.proto_mode, args.proto_min_pixels, cfg)
     ema = check_ema(args.ema, args.ema_every, args.ema_no_warmup, args.use_ema, cfg)
+    clip_grad_norm, grad_stats = check_clip(args.clip_grad_norm, args.grad_stats, cfg)
     hide_unseen = args.hide_unseen or args.pseudo_label is not None or args.bias_loss is not None
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -813,7 +842,8 @@ def main(argv=None):
         ohem=None if args.ohem is None else dict(keep=args.ohem, thresh=args.ohem_thresh), ohem_start_epoch=args.ohem_start_epoch or 0,
         calibration=args.calibration, calib_sweep=calib_sweep_values(args.calib_sweep), eval_scales=args.eval_scales,
         eval_flip=args.eval_flip, bias_loss=args.bias_loss, bias_start_epoch=args.bias_start_epoch or 0,
-        conse=conse, conse_sweep=calib_sweep_values(args.conse_sweep, "--conse-sweep"), hub=hub, ema=ema, ema_checkpoint=checkpoint)
+        conse=conse, conse_sweep=calib_sweep_values(args.conse_sweep, "--conse-sweep"), hub=hub, ema=ema, ema_checkpoint=checkpoint, clip_grad_norm=clip_grad_norm,
+        grad_stats=grad_stats)
     fcn_trainer.epoch, fcn_trainer.iteration = start_epoch, start_iteration
 
     if cfg['mode'] == 'train':

@@ -90,6 +90,10 @@ _REFUSALS = {
         ("config", "averaged weights (ema) live in the fused training step's flat buffers: an embedding configuration (loss 'cos' | 'mse' | 'sim_ce' | 'rank') or the softmax configuration (fcn_loss 'cross_entropy', no embedding) only"),
         ("fused", "averaged weights (ema) live in the fused training step's flat buffers (fused_step=True)"),
         ("wiring", "averaged weights (ema) live in the fused training step, which this optimizer wiring does not allow")),
+    "clip": (
+        ("config", "gradient-norm clipping and the gradient log live in the fused training step: an embedding configuration (loss 'cos' | 'mse' | 'sim_ce' | 'rank') or the softmax configuration (fcn_loss 'cross_entropy', no embedding) only"),
+        ("fused", "gradient-norm clipping and the gradient log live in the fused training step (fused_step=True)"),
+        ("wiring", "gradient-norm clipping and the gradient log live in the fused training step, which this optimizer wiring does not allow")),
 }
 
 
@@ -144,6 +148,13 @@ def ema_refused(step_cfg, fused_step=True, wired=True):
     its flat parameter buffers, so it exists only where training runs on that step -- step_cfg: loss 'cos' | 'mse' | 'sim_ce' | 'rank'
     with embeddings, or the softmax cross entropy"""
     return _refused("ema", config=not step_cfg, fused=not fused_step, wiring=not wired)
+
+
+def clip_refused(step_cfg, fused_step=True, wired=True):
+    """why a configuration cannot clip by the gradient norm or log gradient statistics (clip_grad_norm= / grad_stats=, train.py
+    --clip-grad-norm / --grad-stats), or None: the statistics are taken by engine.TrainStep over its flat gradient buffers, so they
+    exist only where training runs on that step (ema_refused's step_cfg); the autograd routes and the seen-mask phase have none"""
+    return _refused("clip", config=not step_cfg, fused=not fused_step, wiring=not wired)
 
 
 def pseudo_refused(has_unseen, embed_cfg, n_class):
@@ -320,7 +331,7 @@ class Trainer(object):
                  pixel_embeddings=None, loss_func=None, unseen=None, val_unseen=None, label_names=None,
                  forced_unseen=False, embed_arr=None, precision=torch.float32, fused_step=True, rank=0, visualize=0, augment=None,
                  seen_threshold=None, seen_sweep=None, proto=None, support_loader=None, conse=None, conse_sweep=None, seen_gate=None, hub=None,
-                 ema=None, ema_checkpoint=None, sim_temperature=None, rank_margin=None, rank_hardest=False, bias_loss=None, bias_start_epoch=0, pseudo=None, pseudo_start_epoch=0, ohem=None, ohem_start_epoch=0, calibration=None,
+                 ema=None, ema_checkpoint=None, clip_grad_norm=None, grad_stats=False, sim_temperature=None, rank_margin=None, rank_hardest=False, bias_loss=None, bias_start_epoch=0, pseudo=None, pseudo_start_epoch=0, ohem=None, ohem_start_epoch=0, calibration=None,
                  calib_sweep=None, eval_scales=None, eval_flip=False):
         if not cuda:
             raise RuntimeError("this implementation runs on the GPU only (cuda=False has no CPU fallback)")
@@ -559,6 +570,18 @@ class Trainer(object):
                     with open(osp.join(self.log_dir, 'ema_log.csv'), 'w') as f:
                         f.write('epoch,iteration,decay,every,updates,rel_l2_distance\n')
 
+        # gradient-norm clipping and the gradient log (engine.TrainStep clip=): clip_grad_norm = MAX > 0 clips every step's gradient to
+        # that global L2 norm (torch.nn.utils.clip_grad_norm_'s rule); grad_stats alone measures (MAX = inf).  Either way the
+        # per-iteration D2H copy also carries the step's statistics: rank 0 appends one row per iteration to grad_log.csv (its header
+        # is written with the first row, from the step's grad_segments) and the progress print shows score_fr's gradient sum
+        self.clip = None
+        if clip_grad_norm is not None or grad_stats:
+            why = clip_refused((bool(pixel_embeddings) and loss_func in _EMBED_LOSSES) or (not pixel_embeddings and loss_func == "cross_entropy"),
+                               fused_step)
+            if why:
+                raise SznError(why)
+            self.clip = dict(max_norm=_engine.TrainStep._check_clip(dict(max_norm=float('inf') if clip_grad_norm is None else clip_grad_norm)))
+
         if self.pixel_embeddings:
             arr = np.asarray(embed_arr, dtype=np.float32) if embed_arr is not None else \
                 load_embeddings(dataset, pixel_embeddings)
@@ -718,6 +741,8 @@ class Trainer(object):
                 kw.update(bias=self.bias_loss)
         if self.ema is not None:
             kw.update(ema=self.ema)
+        if self.clip is not None:
+            kw.update(clip=self.clip)
         self._step = _engine.TrainStep(self.model, lr=gw['lr'], bias_lr=gb['lr'],
                                        bias_weight_decay=gb.get('weight_decay', 0.0), precision=self.precision,
                                        fused_head=True, keep_grads=os.environ.get("SZN_KEEP_GRADS", "0") == "1", **kw)
@@ -744,6 +769,8 @@ class Trainer(object):
         step = self._fast_step()
         if self.ema is not None:
             self._ema_step()
+        if self.clip is not None and step is None:
+            raise SznError(clip_refused(True, True, False))
         if self.pseudo is not None:
             if step is None:
                 raise SznError("pseudo labels run inside the fused training step, which this optimizer wiring does not allow")
@@ -775,12 +802,17 @@ class Trainer(object):
                 loss, pred = step.step(data, target)
                 # one D2H per iteration: the loss and the K x K histogram the step already accumulated on the device
                 # (the reference logs per-iteration metrics, trainer_fcn.py:164-174)
-                packed = torch.cat([loss.reshape(1).double(), step.hist[0].reshape(-1).double()]).cpu().numpy()
+                parts = [loss.reshape(1).double(), step.hist[0].reshape(-1).double()]
+                if self.clip is not None:            # the step's gradient statistics ride in the same copy
+                    parts += [step.grad_stats.reshape(-1), step.clip_state.double(), step.clip_scale.double()]
+                packed = torch.cat(parts).cpu().numpy()
                 lossv = float(packed[0])
+                gsum = float('nan')                  # not read back on this path (a host sync per iteration for a debug print)
+                if self.clip is not None:            # (before the NaN check: the row of the step that broke is the one to look at)
+                    gsum = self._grad_log(step, packed[1 + self.n_class * self.n_class:])
                 if np.isnan(lossv):
                     raise ValueError('loss is nan while training')
-                metrics = utils._hist_to_metrics(packed[1:].reshape(self.n_class, self.n_class))
-                gsum = float('nan')                  # not read back on this path (a host sync per iteration for a debug print)
+                metrics = utils._hist_to_metrics(packed[1:1 + self.n_class * self.n_class].reshape(self.n_class, self.n_class))
                 ssum = float('nan')                  # the (B,E,H,W) score is never materialised on this path
             elif (hasattr(self.model, 'embed_loss') and self._fused_step and self._embed_cfg()
                   and not self.forced_unseen and self.embeddings.shape[0] <= 256):
@@ -823,6 +855,22 @@ class Trainer(object):
             self._pseudo_report(step)
         if self.ohem is not None:
             self._ohem_report(step)
+
+    def _grad_log(self, step, tail):
+        """one grad_log.csv row (rank 0) from the tail of the iteration's D2H copy: grad_stats, clip_state, the loss scale the
+        gradients carried -> score_fr's gradient sum for the progress print (trainer_fcn.py:160-162 of the reference)"""
+        names = step.grad_segments
+        ns = len(names)
+        r = _engine.grad_report(names, tail[:2 * ns].reshape(ns, 2), tail[2 * ns:2 * ns + 4], step.grad_factor() / float(tail[2 * ns + 4]))
+        if self.rank == 0:
+            path = osp.join(self.log_dir, 'grad_log.csv')
+            new = not osp.exists(path)
+            with open(path, 'a') as f:
+                if new:
+                    f.write(','.join(['epoch', 'iteration', 'grad_norm', 'clip_coef', 'clipped_steps'] + names) + '\n')
+                f.write(','.join(map(str, [self.epoch, self.iteration, r["norm"], r["coef"], r["clipped"]]
+                                     + [r["norms"][n] for n in names])) + '\n')
+        return r["sums"]["score_fr.weight"]
 
     def _ohem_report(self, step):
         """once per epoch: the step's {evaluated, kept} pixel counts, summed over the ranks, as one ohem_log.csv row (rank 0)"""
