@@ -691,6 +691,21 @@ int szn_ema_step(long n, float* avg, const float* param, float decay, int every,
  * SZN_ERR_ARG, nothing is written.  szn_last_kernel: "swap_kernel".                                                             */
 int szn_swap_f32(long n, float* a, float* b, szn_stream_t stream);
 
+/* ---- gradient accumulation (torch's backward() without zero_grad(); the reference steps after every backward) ----
+ * The running sum of a flat fp32 gradient buffer over a window of micro-steps, one IEEE addition per element and nothing else:
+ *     SZN_ACCUM_SET    acc[i] = grad[i]                               the first micro-step of a window    ( 8 B / element)
+ *     SZN_ACCUM_ADD    acc[i] = acc[i] + grad[i]                      the ones in between                 (12 B / element)
+ *     SZN_ACCUM_FINAL  grad[i] = acc[i] + grad[i], acc is only read   the last one                        (12 B / element)
+ * so that after SET, ADD, ..., FINAL grad holds ((g1 + g2) + g3) + ... + gA, left to right, in the buffer every consumer of the
+ * gradient already reads (the exchange, szn_grad_check_finite, szn_grad_stats, the optimizer entries).  inf / NaN survive the sum.
+ * No atomics and no reduction: two calls give the same bits.  Any 4-byte-aligned pointer pair is taken (16-byte accesses where both
+ * pointers allow them).  SZN_ERR_ARG, nothing launched: n < 0, mode outside 0..2, a NULL buffer with n > 0, a pointer not 4-byte
+ * aligned, overlapping ranges.  n == 0 is a successful no-op.  szn_last_kernel: "grad_accum_kernel".                             */
+#define SZN_ACCUM_SET   0
+#define SZN_ACCUM_ADD   1
+#define SZN_ACCUM_FINAL 2
+int szn_grad_accum(long n, float* acc, float* grad, int mode, szn_stream_t stream);
+
 /* ---- gradient statistics and gradient-norm clipping (torch.nn.utils.clip_grad_norm_'s rule; the reference does not clip, it
  * prints score_fr's gradient sum: trainer_fcn.py:160-162) ----
  * szn_grad_stats: per segment s = elements [seg_end[s-1], seg_end[s]) of one flat buffer (fp32, or a 16-bit image: the summed wire

@@ -83,6 +83,7 @@ CONSE_MAX_TOP = 16          # SZN_CONSE_MAX_TOP
 PSEUDO_BINS = 1024          # SZN_PSEUDO_BINS
 OHEM_BINS = 1024            # SZN_OHEM_BINS
 GRAD_STATS_MAX_SEGS = 64    # SZN_GRAD_STATS_MAX_SEGS
+ACCUM_SET, ACCUM_ADD, ACCUM_FINAL = 0, 1, 2    # SZN_ACCUM_SET, SZN_ACCUM_ADD, SZN_ACCUM_FINAL (szn_grad_accum's mode)
 PROTO_RAW, PROTO_UNIT = 0, 1   # SZN_PROTO_RAW, SZN_PROTO_UNIT (szn_class_proto's mode)
 
 
@@ -197,6 +198,7 @@ SIGNATURES = {
     "szn_loss_scale_update": (_I, [_P, _F, _F, _I, _F, _F, _P]),
     "szn_ema_step": (_I, [_L, _P, _P, _F, _I, _I, _P, _P]),
     "szn_swap_f32": (_I, [_L, _P, _P, _P]),
+    "szn_grad_accum": (_I, [_L, _P, _P, _I, _P]),
     "szn_grad_stats_workspace_bytes": (_SZ, [_L, _I]),
     "szn_grad_stats": (_I, [_L, _P, _I, _I, _I64P, _P, _P, _P]),
     "szn_clip_coef": (_I, [_I, _P, _F, _F, _P, _P, _P]),

@@ -206,6 +206,22 @@ static inline int szn_grid_for(long n, int per_block = 256, int cap = 8192) {
     return (int)b;
 }
 
+// ---- streaming passes over a 4-byte-aligned fp32 pointer pair (szn_ema.hip, szn_accum.hip) ------
+// the split of [0, n) into a scalar head, n4 whole 16-B vectors and a scalar tail; a pair whose addresses differ modulo 16 is all head
+static inline void szn_split16(const void* a, const void* b, long n, long* head, long* n4) {
+    if ((((uintptr_t)a ^ (uintptr_t)b) & 15) != 0) { *head = n; *n4 = 0; return; }
+    long h = (long)(((16 - ((uintptr_t)a & 15)) & 15) >> 2);
+    if (h > n) h = n;
+    *head = h;
+    *n4 = (n - h) >> 2;
+}
+// blocks of 256 lanes that take one pair of vectors (or one scalar element) each, at most cap
+static inline int szn_stream_grid(long n, long n4, int cap) {
+    const long per_thread = n4 > 0 ? (n4 + 1) / 2 : n;          // vector pairs, or scalar elements
+    const long rest = n - n4 * 4;
+    return szn_grid_for(per_thread > rest ? per_thread : rest, 256, cap);
+}
+
 // ---- dtype code -> storage tag ----------------------------------------------------------------
 // Calls f with bf16_raw{} / f16_raw{} / float{} for SZN_BF16 / SZN_F16 / SZN_F32 (f: a generic lambda that launches the kernel instantiated
 // on decltype of its argument).  Any other code: f is not called and the result is false -- the caller keeps its own error text.

@@ -89,21 +89,6 @@ __global__ __launch_bounds__(256) void swap_kernel(uint32_t* __restrict__ a, uin
     }
 }
 
-// the split of [0, n) into a scalar head, n4 whole 16-B vectors and a scalar tail for a 4-byte-aligned pointer pair
-void split16(const void* a, const void* b, long n, long* head, long* n4) {
-    if ((((uintptr_t)a ^ (uintptr_t)b) & 15) != 0) { *head = n; *n4 = 0; return; }
-    long h = (long)(((16 - ((uintptr_t)a & 15)) & 15) >> 2);
-    if (h > n) h = n;
-    *head = h;
-    *n4 = (n - h) >> 2;
-}
-
-int stream_grid(long n, long n4) {
-    const long per_thread = n4 > 0 ? (n4 + 1) / 2 : n;          // vector pairs, or scalar elements
-    const long rest = n - n4 * 4;
-    return szn_grid_for(per_thread > rest ? per_thread : rest, 256, EMA_MAX_BLOCKS);
-}
-
 }  // namespace
 
 extern "C" int szn_ema_step(long n, float* avg, const float* param, float decay, int every, int step, const float* scale_state,
@@ -114,8 +99,8 @@ extern "C" int szn_ema_step(long n, float* avg, const float* param, float decay,
     if (!avg || !param) SZN_FAIL(SZN_ERR_ARG, "ema_step: NULL buffer");
     if ((((uintptr_t)avg | (uintptr_t)param) & 3) != 0) SZN_FAIL(SZN_ERR_ARG, "ema_step: buffers must be 4-byte aligned");
     long head, n4;
-    split16(avg, param, n, &head, &n4);
-    hipLaunchKernelGGL(ema_kernel, dim3(stream_grid(n, n4)), dim3(256), 0, (hipStream_t)stream, avg, param, n, head, n4, decay, every,
+    szn_split16(avg, param, n, &head, &n4);
+    hipLaunchKernelGGL(ema_kernel, dim3(szn_stream_grid(n, n4, EMA_MAX_BLOCKS)), dim3(256), 0, (hipStream_t)stream, avg, param, n, head, n4, decay, every,
                        step, scale_state);
     SZN_CHECK_LAUNCH("ema_kernel");
     return SZN_OK;
@@ -129,8 +114,8 @@ extern "C" int szn_swap_f32(long n, float* a, float* b, szn_stream_t stream) {
     const uintptr_t ua = (uintptr_t)a, ub = (uintptr_t)b, bytes = (uintptr_t)n * 4;
     if (ua < ub + bytes && ub < ua + bytes) SZN_FAIL(SZN_ERR_ARG, "swap_f32: the buffers overlap");
     long head, n4;
-    split16(a, b, n, &head, &n4);
-    hipLaunchKernelGGL(swap_kernel, dim3(stream_grid(n, n4)), dim3(256), 0, (hipStream_t)stream, (uint32_t*)a, (uint32_t*)b, n, head,
+    szn_split16(a, b, n, &head, &n4);
+    hipLaunchKernelGGL(swap_kernel, dim3(szn_stream_grid(n, n4, EMA_MAX_BLOCKS)), dim3(256), 0, (hipStream_t)stream, (uint32_t*)a, (uint32_t*)b, n, head,
                        n4);
     SZN_CHECK_LAUNCH("swap_kernel");
     return SZN_OK;

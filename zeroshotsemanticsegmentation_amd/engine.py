@@ -387,7 +387,7 @@ class TrainStep(object):
                  scale_growth=2.0, scale_backoff=0.5, scale_growth_interval=2000, force_comm=None, reserved_cus=None,
                  fused_adam=None, keep_grads=True, exchange=None, direct_wire=None, sharded=None, forced_unseen=None,
                  class_weight=None, size_average=False, sim_exclude=None, sim_temperature=None, pseudo=None, ohem=None,
-                 rank_margin=None, rank_hardest=False, bias=None, ema=None, clip=None):
+                 rank_margin=None, rank_hardest=False, bias=None, ema=None, clip=None, accum=None):
         """Data-parallel knobs (the reference is single-GPU): grad_comm_dtype (SZN_GRAD_COMM = fp32 | bf16) = the
         wire format of the gradient buckets; exchange=False (SZN_GRAD_COMM=off) = no exchange at all (bench.py's comm-off timing);
         direct_wire (default: on for a 16-bit wire with keep_grads=False; SZN_WIRE_DIRECT=0 turns it off) = the weight-gradient
@@ -461,7 +461,37 @@ class TrainStep(object):
         numbers back (a host sync).  The norm needs every gradient before any update, so the fc6 Adam epilogue and the early
         side-stream optimizer pass are off -- the path a data-parallel step takes anyway.  Data parallelism needs nothing: every rank
         reads the same all-reduced buffers.  Refused with a ValueError: a bad max_norm, and the sharded optimizer (a rank holds
-        slices of the summed gradient only).  None (default): nothing changes, launch for launch."""
+        slices of the summed gradient only).  None (default): nothing changes, launch for launch.
+        accum=dict(steps=A, average=True): gradient accumulation, A forward/backward passes per optimizer step.  step() is one
+        micro-step: forward, head, loss, prediction, histogram, pseudo labels, mining and the bias term are per call and it returns the
+        micro-batch's (loss, pred).  Behind everything that writes the flat gradient buffers two szn_grad_accum launches (weights, then
+        biases) keep the window's running sum in acc_w / acc_b (fp32, as large as flat_gw / flat_gb): SET on the first call of a
+        window, ADD on the ones in between -- and nothing else runs on those calls: no exchange (buckets.issued does not move), no
+        overflow check, no statistics, no optimizer, no average, no loss-scale update; nstep stays and the weights are not marked
+        dirty.  The A-th call (the boundary) runs FINAL, which leaves ((g1 + g2) + g3) + ... + gA -- torch's order for A backward()
+        calls without zero_grad() -- in the flat gradient buffers themselves, then the whole exchange (begin_step, every bucket in
+        buckets.buckets order, finish: not overlapped with backward, the other A - 1 micro-steps have none) and the unchanged
+        optimizer step.  average=True multiplies the gradient scale by 1/A (the update, clip= and the gradient log see the mean of the
+        micro-batch gradients), average=False uses the sum.  `.grad` of the parameters holds the micro-batch's gradient after a
+        non-boundary call and the window's unscaled sum after a boundary call.  accum_steps = A, accum_pending = micro-steps summed
+        since the last optimizer step (0 .. A - 1), last_applied = whether the last step() issued the optimizer launches (not whether
+        the dynamic loss scale then skipped them on the device: applied_steps says that).  Every gradient is final only at the
+        boundary, so -- as under clip= -- the fc6 Adam epilogue and the early side-stream optimizer pass are off, and so is the direct
+        16-bit wire (the weight-gradient kernels would write the image of ONE micro-batch; the staged wire is used).  Dynamic loss
+        scale: S changes only in szn_loss_scale_update, hence only at boundaries, so every micro-gradient of a window carries the same
+        S; an inf / NaN in any of them survives the sum, the boundary's check raises found_inf, the optimizer entries and the average
+        skip on the device and S backs off: the WHOLE window is lost.  ema= moves once per optimizer step.  reset_accum() restarts
+        the window (the next call is a SET); import_optimizer_state calls it: pending micro-gradients are not checkpointed.  steps=1
+        is None in every respect.  Refused with a ValueError: a bad dict, the sharded optimizer, and step() while a stream capture is
+        in progress (the host decides which calls update).  None (default): nothing changes, launch for launch."""
+        self._accum = None if accum is None else self._check_accum(accum)
+        if self._accum is not None and self._accum[0] == 1:
+            self._accum = None
+        self.accum_steps = 1 if self._accum is None else self._accum[0]
+        self._accum_scale = 1.0 / self.accum_steps if (self._accum is not None and self._accum[1]) else 1.0
+        self.accum_pending = 0
+        self.last_applied = False
+        self.acc_w = self.acc_b = None
         self._clip = None if clip is None else self._check_clip(clip)
         self.grad_segments = self.grad_stats = self.clip_state = self.clip_scale = None
         self._ema = None if ema is None else self._check_ema(ema)
@@ -630,6 +660,10 @@ class TrainStep(object):
             if self.buckets.sharded:
                 raise ValueError("TrainStep: clip= does not run with the sharded optimizer, where a rank holds slices of the summed gradient only")
             self._init_clip()
+        if self._accum is not None:
+            if self.buckets.sharded:
+                raise ValueError("TrainStep: accum= does not run with the sharded optimizer, which reduce-scatters every step's gradient")
+            self.acc_w, self.acc_b = torch.empty_like(self.flat_gw), torch.empty_like(self.flat_gb)
         # CUs the persistent one-block-per-CU backward kernels (conv3x3_regw dgrad, conv_wgrad_taps) leave to RCCL's workgroups
         # while an exchange is in flight (default SZN_RESERVED_CUS, 0 = none; only when buckets are actually exchanged)
         if reserved_cus is None:
@@ -652,10 +686,10 @@ class TrainStep(object):
         if fused_adam is None:
             fused_adam = os.environ.get("SZN_FUSED_ADAM", "1") == "1"
         self._own_stream = None          # see step(): the non-blocking stream of a small step
-        # clip=: the norm needs every gradient before any update, so no update may ride in a weight-gradient kernel
+        # clip= / accum=: every gradient must be final before any update, so no update may ride in a weight-gradient kernel
         self.fused_adam = bool(fused_adam and optimizer == "adam" and not self.dynamic and not self.buckets.active
                                and self.flat_w_lp is not None and os.environ.get("SZN_EARLY_ADAM", "auto") != "1"
-                               and self._clip is None)
+                               and self._clip is None and self._accum is None)
         if self.fused_adam and not self.keep_grads:
             # the fused layers' gradients are consumed inside their weight-gradient kernel and never stored: `.grad` must not
             # look like a gradient (the reference keeps .grad valid until zero_grad(); keep_grads=True restores that)
@@ -926,8 +960,9 @@ class TrainStep(object):
         m = self.model
         CP, E, F = m.head_width, m.n_class, m.fc7.out_channels
         # direct 16-bit wire: bf16 compute path only (the kernels that write the image are the 16-bit weight-gradient kernels; the
-        # dynamic loss scale's overflow check reads fp32 gradients; the FCN8s skip layers copy theirs in from scratch buffers)
-        direct = self._want_direct and not self.dynamic and not self.is8 and self.eng.dtype != torch.float32
+        # dynamic loss scale's overflow check reads fp32 gradients; the FCN8s skip layers copy theirs in from scratch buffers;
+        # under accum= the image would be that of one micro-batch)
+        direct = self._want_direct and not self.dynamic and not self.is8 and self.eng.dtype != torch.float32 and self._accum is None
         # sharded optimizer: not with the dynamic loss scale either -- after a reduce-scatter a rank holds summed gradients for its own slices
         # only, so the overflow check (szn_grad_check_finite over the whole buffer) would see different data on different ranks and the ranks
         # would disagree on skipping the step / backing the scale off
@@ -950,7 +985,9 @@ class TrainStep(object):
     # ---- one training step -----------------------------------------------------------------------------
     def step(self, x, target):
         """x (B,3,H,W) f32 NCHW, target (B,H,W) int64 (-1 ignore), both on the GPU.
-        Returns (loss 0-dim device tensor, pred (B,H,W) int64 device tensor)."""
+        Returns (loss 0-dim device tensor, pred (B,H,W) int64 device tensor).  Under accum= this is one micro-step."""
+        if self._accum is not None and torch.cuda.is_current_stream_capturing():
+            raise ValueError("TrainStep: accum= cannot be captured into a graph, the host decides which calls update the weights")
         work = self._small_step_stream(x)
         if work is None:
             return self._step(x, target)
@@ -980,7 +1017,8 @@ class TrainStep(object):
 
     def _step(self, x, target):
         """forward -> the head map (the 1/32 map, or FCN8s' 1/8 fused map) -> head (fused, or the materialised referee) -> loss
-        scale -> backward -> exchange -> optimizer -> confusion histogram"""
+        scale -> backward -> exchange -> optimizer -> confusion histogram (accum=: backward -> szn_grad_accum, and on the window's last
+        call -> exchange -> optimizer)"""
         m, eng = self.model, self.eng
         if self._ema_in:
             raise L.SznError("TrainStep: no training step inside averaged_weights(): the model holds the averaged weights")
@@ -1009,10 +1047,13 @@ class TrainStep(object):
             if self._scaled:
                 dcoarse = self._scale(dcoarse, eng.dtype)
         self.stats = stats
-        done = self._layer_done_hook(B * H * W)
+        acc = self._accum is not None
+        boundary = not acc or self.accum_pending == self.accum_steps - 1
+        done = (lambda name: None) if acc else self._layer_done_hook(B * H * W)
         self._fused_begin()
         try:
-            self.buckets.begin_step()
+            if not acc:
+                self.buckets.begin_step()
             # rows [0,E) of the fused head gradient ARE score_fr's slot of the flat gradient (seenmask_score is frozen in phase 1):
             # nothing to copy, the first bucket can go as soon as the head wgrad has been queued
             eng.backward(ctx, dcoarse, self.grads, backbone=True, layer_done=done,
@@ -1021,8 +1062,13 @@ class TrainStep(object):
             for n, s in self.skip.items():
                 bo, bc = self.boff[n]
                 self.flat_gb[bo:bo + bc].copy_(s["gb"][:self.E])
-            self.buckets.finish()
-            self._optimizer_step()
+            if acc:
+                self._accum_launch(boundary, st)
+            else:
+                self.buckets.finish()
+            if boundary:
+                self._optimizer_step()
+            self.last_applied = boundary
         finally:                         # an error in between must not leave the engine armed with this step's Adam arguments
             eng.fused_opt, eng.fused_done = None, set()
         if self.train_metrics:
@@ -1188,7 +1234,7 @@ class TrainStep(object):
             return
         st = L.stream_ptr()
         dyn = self.scale_state
-        gs = 1.0 / self.world if self.dynamic else 1.0 / (self.world * self._loss_scale0)
+        gs = self.grad_factor()
         flat, grad = (self.flat_w, self.flat_gw) if key == "w" else (self.flat_b, self.flat_gb)
         g16 = key == "w" and self.buckets.direct      # the summed 16-bit wire image IS the gradient (szn_*_step_g16)
         if g16:
@@ -1366,6 +1412,40 @@ class TrainStep(object):
                 self.scale_state[2] = float(self.nstep)
         if self._ema is not None:        # a resumed run: the average restarts from the loaded weights unless load_ema_state_dict follows
             self.reset_ema()
+        self.reset_accum()               # ... and its window: pending micro-gradients are not checkpointed
+
+    # ---- gradient accumulation (accum=) -------------------------------------------------------------------------------------
+    @staticmethod
+    def _check_accum(cfg):
+        """accum= checked on the host (before anything touches a device) -> (steps, average)"""
+        if not isinstance(cfg, dict) or "steps" not in cfg or not set(cfg) <= {"steps", "average"}:
+            raise ValueError("TrainStep: accum must be a dict(steps=, average=True), got %r" % (cfg,))
+        steps, average = cfg["steps"], cfg.get("average", True)
+        if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
+            raise ValueError("TrainStep: accum steps must be an integer >= 1, got %r" % (steps,))
+        if not isinstance(average, bool):
+            raise ValueError("TrainStep: accum average must be True or False, got %r" % (average,))
+        return steps, average
+
+    def reset_accum(self):
+        """forget the micro-gradients summed so far: the next step() opens a window (SZN_ACCUM_SET).  A no-op without accum=."""
+        self.accum_pending = 0
+
+    def _accum_launch(self, boundary, st):
+        """behind everything that wrote the flat gradient buffers in this micro-step: the window's running sum (weights, then biases) and,
+        on the window's last call, the whole exchange of the summed buffers"""
+        mode = L.ACCUM_FINAL if boundary else (L.ACCUM_SET if self.accum_pending == 0 else L.ACCUM_ADD)
+        for a, g in ((self.acc_w, self.flat_gw), (self.acc_b, self.flat_gb)):
+            L.call("szn_grad_accum", g.numel(), L.ptr(a), L.ptr(g), mode, st)
+        if not boundary:
+            self.accum_pending += 1
+            return
+        self.accum_pending = 0
+        if self.buckets.active:
+            self.buckets.begin_step()
+            for _, _, name in self.buckets.buckets:
+                self.buckets.layer_done(name)
+            self.buckets.finish()
 
     # ---- gradient statistics and gradient-norm clipping (clip=) -------------------------------------------------------------
     @staticmethod
@@ -1403,14 +1483,15 @@ class TrainStep(object):
         for i, g in enumerate((gw, self.flat_gb)):
             L.call("szn_grad_stats", g.numel(), L.ptr(g), L.dtype_code(g.dtype), nl, self._seg_tabs[i], L.ptr(self.grad_stats[i * nl:]),
                    L.ptr(self._clip_ws), st)
-        gs = 1.0 / self.world if self.dynamic else 1.0 / (self.world * self._loss_scale0)           # _opt_launch's grad_scale
+        gs = self.grad_factor()          # _opt_launch's grad_scale
         if self.dynamic:                 # szn_loss_scale_update changes S at the end of the step: keep what these statistics carry
             self.clip_scale.copy_(self.scale_state[:1])
         L.call("szn_clip_coef", 2 * nl, L.ptr(self.grad_stats), self._clip, gs, L.ptr(self.scale_state), L.ptr(self.clip_state), st)
 
     def grad_factor(self):
-        """what the buffers' statistics are multiplied by to describe the true gradient, apart from the dynamic loss scale"""
-        return 1.0 / self.world if self.dynamic else 1.0 / (self.world * self._loss_scale0)
+        """what the buffers' elements are multiplied by to give the gradient the update uses, apart from the dynamic loss scale and the
+        clip coefficient: 1 / (world x static loss scale), and 1 / A under accum=dict(average=True).  The optimizer launches' grad_scale."""
+        return (1.0 / self.world if self.dynamic else 1.0 / (self.world * self._loss_scale0)) * self._accum_scale
 
     def grad_norms(self):
         """the last step's numbers on the host (a sync; tests and logs): grad_report of grad_stats, clip_state and the scale"""

@@ -72,6 +72,12 @@ Added for this implementation (none change the reference flags):
                        by szn_clip_coef, the update by the *_clipped optimizer entries; no host sync.  --grad-stats alone measures
                        (MAX = inf).  Either flag: one row per iteration in <log_dir>/grad_log.csv (norm, coefficient, clipped steps,
                        one norm per layer) and score_fr's gradient sum in the progress print.  MAX has no default
+  --accum-steps A      gradient accumulation for the FCN phase: A iterations (loader batches) per optimizer step.  The fused step sums its
+                       flat gradient buffers on the GPU (szn_grad_accum, left to right like torch's backward() without zero_grad()) and
+                       runs exchange, clipping, optimizer and --ema on every A-th iteration only; the update uses the mean of the A
+                       gradients (their sum under the pixel-sum cross entropy of -c 1).  Logs stay per iteration, grad_log.csv has one
+                       row per optimizer step, a window is carried across epochs, a resumed run restarts its window.  The seen-mask
+                       phase runs unaccumulated.  Default: 1
   --init synthetic|vgg path handling: without the caffe VGG16 file the backbone starts from synth weights
   torchrun: RANK / LOCAL_RANK / WORLD_SIZE are honoured (one process per GPU, RCCL gradient all-reduce).
 """
@@ -254,6 +260,11 @@ def build_parser():
     p.add_argument('--grad-stats', action='store_true',
                    help="the gradient log of --clip-grad-norm without clipping (MAX = inf): grad_log.csv and score_fr's gradient sum in "
                         "the progress print")
+    p.add_argument('--accum-steps', type=int, default=None, metavar='A',
+                   help="gradient accumulation for the FCN phase: sum the gradients of A iterations (loader batches) on the GPU and run "
+                        "exchange, clipping, optimizer and --ema on every A-th one, with the mean of the A gradients (the sum under the "
+                        "pixel-sum cross entropy of -c 1).  One iteration stays one loader batch in every log; a window is carried across "
+                        "epochs.  Needs a configuration that trains on the fused step; the seen-mask phase runs unaccumulated.  Default: 1")
     p.add_argument('--use-ema', action='store_true',
                    help="with -m test_fcn / -m test_all: evaluate the averaged weights of the checkpoint ('ema_state_dict') instead of the "
                         "raw iterate ('model_state_dict'); an error for a checkpoint written without --ema.  The checkpoint this "
@@ -648,6 +659,22 @@ def check_clip(max_norm, grad_stats, cfg):
     return max_norm, bool(grad_stats)
 
 
+def check_accum(steps, cfg):
+    """--accum-steps: A >= 1, training only, and only where the FCN phase trains on engine.TrainStep (trainer_fcn.accum_refused) -> the
+    Trainer's accum_steps, or None"""
+    if steps is None:
+        return None
+    if cfg['mode'] != 'train':
+        raise Exception("--accum-steps acts on training steps (-m train)")
+    if steps < 1:
+        raise Exception("--accum-steps: A must be at least 1 (got %r)" % (steps,))
+    step_cfg = (cfg['fcn_loss'] in _EMBED_LOSSES and cfg['embed_dim']) or (cfg['fcn_loss'] == 'cross_entropy' and not cfg['embed_dim'])
+    why = trainer_fcn.accum_refused(bool(step_cfg))
+    if why:
+        raise trainer_fcn.SznError("--accum-steps: " + why)
+    return int(steps)
+
+
 USE_EMA_MISSING = "--use-ema: the checkpoint %s carries no 'ema_state_dict' (it was written without --ema)"
 
 
@@ -699,6 +726,7 @@ def main(argv=None):
     proto = check_proto(args.proto_shots, args.proto_alpha, args.proto_mode, args.proto_min_pixels, cfg)
     ema = check_ema(args.ema, args.ema_every, args.ema_no_warmup, args.use_ema, cfg)
     clip_grad_norm, grad_stats = check_clip(args.clip_grad_norm, args.grad_stats, cfg)
+    accum_steps = check_accum(args.accum_steps, cfg)
     hide_unseen = args.hide_unseen or args.pseudo_label is not None or args.bias_loss is not None
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -843,7 +871,7 @@ def main(argv=None):
         calibration=args.calibration, calib_sweep=calib_sweep_values(args.calib_sweep), eval_scales=args.eval_scales,
         eval_flip=args.eval_flip, bias_loss=args.bias_loss, bias_start_epoch=args.bias_start_epoch or 0,
         conse=conse, conse_sweep=calib_sweep_values(args.conse_sweep, "--conse-sweep"), hub=hub, ema=ema, ema_checkpoint=checkpoint, clip_grad_norm=clip_grad_norm,
-        grad_stats=grad_stats)
+        grad_stats=grad_stats, accum_steps=accum_steps)
     fcn_trainer.epoch, fcn_trainer.iteration = start_epoch, start_iteration
 
     if cfg['mode'] == 'train':

@@ -94,6 +94,10 @@ _REFUSALS = {
         ("config", "gradient-norm clipping and the gradient log live in the fused training step: an embedding configuration (loss 'cos' | 'mse' | 'sim_ce' | 'rank') or the softmax configuration (fcn_loss 'cross_entropy', no embedding) only"),
         ("fused", "gradient-norm clipping and the gradient log live in the fused training step (fused_step=True)"),
         ("wiring", "gradient-norm clipping and the gradient log live in the fused training step, which this optimizer wiring does not allow")),
+    "accum": (
+        ("config", "gradient accumulation sums the fused training step's flat gradient buffers: an embedding configuration (loss 'cos' | 'mse' | 'sim_ce' | 'rank') or the softmax configuration (fcn_loss 'cross_entropy', no embedding) only"),
+        ("fused", "gradient accumulation sums the fused training step's flat gradient buffers (fused_step=True)"),
+        ("wiring", "gradient accumulation sums the fused training step's gradients, and this optimizer wiring does not run on that step")),
 }
 
 
@@ -155,6 +159,13 @@ def clip_refused(step_cfg, fused_step=True, wired=True):
     --clip-grad-norm / --grad-stats), or None: the statistics are taken by engine.TrainStep over its flat gradient buffers, so they
     exist only where training runs on that step (ema_refused's step_cfg); the autograd routes and the seen-mask phase have none"""
     return _refused("clip", config=not step_cfg, fused=not fused_step, wiring=not wired)
+
+
+def accum_refused(step_cfg, fused_step=True, wired=True):
+    """why a configuration cannot accumulate gradients over several iterations (accum_steps=, train.py --accum-steps), or None: the sum
+    is kept by engine.TrainStep next to its flat gradient buffers, so it exists only where training runs on that step (ema_refused's
+    step_cfg); the autograd routes and the seen-mask phase step after every backward pass"""
+    return _refused("accum", config=not step_cfg, fused=not fused_step, wiring=not wired)
 
 
 def pseudo_refused(has_unseen, embed_cfg, n_class):
@@ -331,7 +342,7 @@ class Trainer(object):
                  pixel_embeddings=None, loss_func=None, unseen=None, val_unseen=None, label_names=None,
                  forced_unseen=False, embed_arr=None, precision=torch.float32, fused_step=True, rank=0, visualize=0, augment=None,
                  seen_threshold=None, seen_sweep=None, proto=None, support_loader=None, conse=None, conse_sweep=None, seen_gate=None, hub=None,
-                 ema=None, ema_checkpoint=None, clip_grad_norm=None, grad_stats=False, sim_temperature=None, rank_margin=None, rank_hardest=False, bias_loss=None, bias_start_epoch=0, pseudo=None, pseudo_start_epoch=0, ohem=None, ohem_start_epoch=0, calibration=None,
+                 ema=None, ema_checkpoint=None, clip_grad_norm=None, grad_stats=False, accum_steps=None, sim_temperature=None, rank_margin=None, rank_hardest=False, bias_loss=None, bias_start_epoch=0, pseudo=None, pseudo_start_epoch=0, ohem=None, ohem_start_epoch=0, calibration=None,
                  calib_sweep=None, eval_scales=None, eval_flip=False):
         if not cuda:
             raise RuntimeError("this implementation runs on the GPU only (cuda=False has no CPU fallback)")
@@ -582,6 +593,21 @@ class Trainer(object):
                 raise SznError(why)
             self.clip = dict(max_norm=_engine.TrainStep._check_clip(dict(max_norm=float('inf') if clip_grad_norm is None else clip_grad_norm)))
 
+        # gradient accumulation (engine.TrainStep accum=): accum_steps = A >= 1 loader batches per optimizer step.  An iteration stays
+        # one loader batch (one micro-step): train_log.csv, the progress print and self.iteration keep their meaning, a grad_log.csv
+        # row is written for the iterations that ran the optimizer, and a window is carried across the end of an epoch.  The update
+        # uses the mean of the window's gradients, except under the reference's pixel-SUM cross entropy (train.py -c 1), where a larger
+        # batch grows the gradient the same way: there it uses their sum.  Validation and checkpoints in the middle of a window are
+        # fine (they touch neither the gradient buffers nor the accumulators); a resumed run restarts its window
+        self.accum = None
+        if accum_steps is not None:
+            why = accum_refused((bool(pixel_embeddings) and loss_func in _EMBED_LOSSES) or (not pixel_embeddings and loss_func == "cross_entropy"),
+                                fused_step)
+            if why:
+                raise SznError(why)
+            steps, average = _engine.TrainStep._check_accum(dict(steps=accum_steps, average=bool(pixel_embeddings)))
+            self.accum = dict(steps=steps, average=average)
+
         if self.pixel_embeddings:
             arr = np.asarray(embed_arr, dtype=np.float32) if embed_arr is not None else \
                 load_embeddings(dataset, pixel_embeddings)
@@ -743,6 +769,8 @@ class Trainer(object):
             kw.update(ema=self.ema)
         if self.clip is not None:
             kw.update(clip=self.clip)
+        if self.accum is not None:
+            kw.update(accum=self.accum)
         self._step = _engine.TrainStep(self.model, lr=gw['lr'], bias_lr=gb['lr'],
                                        bias_weight_decay=gb.get('weight_decay', 0.0), precision=self.precision,
                                        fused_head=True, keep_grads=os.environ.get("SZN_KEEP_GRADS", "0") == "1", **kw)
@@ -771,6 +799,8 @@ class Trainer(object):
             self._ema_step()
         if self.clip is not None and step is None:
             raise SznError(clip_refused(True, True, False))
+        if self.accum is not None and step is None:
+            raise SznError(accum_refused(True, True, False))
         if self.pseudo is not None:
             if step is None:
                 raise SznError("pseudo labels run inside the fused training step, which this optimizer wiring does not allow")
@@ -808,7 +838,8 @@ class Trainer(object):
                 packed = torch.cat(parts).cpu().numpy()
                 lossv = float(packed[0])
                 gsum = float('nan')                  # not read back on this path (a host sync per iteration for a debug print)
-                if self.clip is not None:            # (before the NaN check: the row of the step that broke is the one to look at)
+                if self.clip is not None and step.last_applied:      # (before the NaN check: the row of the step that broke is the one to
+                    # look at; under accum_steps the iterations that only summed their gradient took no statistics and write no row)
                     gsum = self._grad_log(step, packed[1 + self.n_class * self.n_class:])
                 if np.isnan(lossv):
                     raise ValueError('loss is nan while training')
