@@ -861,6 +861,41 @@ int szn_viz_seenmask(int B, int H, int W, const void* img, int img_kind, const d
 int szn_augment_u8(int B, int Hm, int Wm, const uint8_t* rgb_hwc, const int64_t* label, const int32_t* params,
                    const double* mean_bgr, int Ho, int Wo, float* out_nchw, int64_t* out_label, szn_stream_t stream);
 
+/* szn_augment_affine_u8: szn_augment_u8 with a 2 x 3 affine position map (rotation; the scale, the crop window and the mirror are folded
+ * into it by the host) and a 3 x 4 colour matrix (brightness, contrast, saturation and hue are affine in RGB and collapse into one).
+ * Inputs, outputs, canvas convention, mean_bgr and the error rules are szn_augment_u8's.  params: DEVICE memory, SZN_AUGA_NPARAM int32
+ * per image:
+ *   [0] h  [1] w              the image's own size inside the canvas; clamped to [1, Hm] / [1, Wm] on the device
+ *   [2] mxx [3] mxy [4] tx    source x as a function of the output pixel, 16.16 fixed point
+ *   [5] myx [6] myy [7] ty    source y, likewise
+ *   [8..16] Cm[c][d]          colour matrix, Q16, row-major: output channel c from input channel d, both in RGB order
+ *   [17..19] Co[c]            colour offset, grey levels in Q16
+ * Integer-exact contract, per output pixel (b, yo, xo); all arithmetic is int64, >> is the arithmetic (floor) shift:
+ *   position  X = 2*xo + 1, Y = 2*yo + 1;  sx = ((mxx*X + mxy*Y) >> 1) + tx - 32768,  sy = ((myx*X + myy*Y) >> 1) + ty - 32768
+ *             (szn_augment_u8's pixel-centre convention).
+ *   padding   lx = (sx + 32768) >> 16, ly = (sy + 32768) >> 16.  lx outside [0, w) or ly outside [0, h): the pixel is padding, all three
+ *             planes exactly 0.0f and the label SZN_PAD_LABEL.
+ *   taps      sx clamped to [0, (w-1) << 16]; x0 = sx >> 16, x1 = min(x0 + 1, w - 1), wx = (sx & 0xffff) >> 5; the same in y.  Per source
+ *             byte d: acc_d = (2048-wy) * ((2048-wx)*p00 + wx*p01) + wy * ((2048-wx)*p10 + wx*p11)  (<= 255 * 2^22).
+ *   colour    u_c = sum_d Cm[c][d] * acc_d + ((int64)Co[c] << 22), clamped to [0, 255 << 38] (unit: 2^-38 grey level);
+ *             out plane 2-c = (float)((double)u_c / 2^38 - mean_bgr[2-c]).  u_c < 2^46, so the conversion and the division are exact and
+ *             the only rounding is the double subtraction and the cast: the rounding of szn_image_u8_to_bgr_f32.  Every Cm word is
+ *             clamped to +-2^20 before use, so that no record can overflow int64 (|sum| <= 3 * 2^50 + 2^53).
+ *   label     label[ly][lx], copied as is.
+ * Two identities hold bit for bit:
+ *   identity colour   Cm = 65536 * I, Co = 0 gives u = acc << 16, hence (double)acc / 2^22 - mean: szn_augment_u8's value.
+ *   axis-aligned      the record (h, w, Hs, Ws, step_y, step_x, oy, ox, flip) of szn_augment_u8 becomes  mxx = flip ? -step_x : step_x,
+ *                     mxy = 0, tx = step_x * (ox + (flip ? Wo : 0)),  myx = 0, myy = step_y, ty = step_y * oy:  the source positions
+ *                     are szn_augment_u8's exactly, because (a + 2k) >> 1 == (a >> 1) + k.  The padding rule differs in form (source
+ *                     space here, the scaled grid there); the two agree whenever Ws * Ws < 65536 * w and Hs * Hs < 65536 * h.
+ * The products are exact for Ho, Wo < 2^29; beyond that, as for a garbage record, they wrap modulo 2^64 and every index is still checked
+ * against the image before it is used: no read leaves the canvas.
+ * SZN_ERR_ARG exactly where szn_augment_u8 returns it.  szn_last_kernel(): augment_affine_u8_kernel_v4 when Wo % 4 == 0 and out_nchw,
+ * out_label are 16-byte aligned, else augment_affine_u8_kernel.                                                                   */
+#define SZN_AUGA_NPARAM 20
+int szn_augment_affine_u8(int B, int Hm, int Wm, const uint8_t* rgb_hwc, const int64_t* label, const int32_t* params,
+                          const double* mean_bgr, int Ho, int Wo, float* out_nchw, int64_t* out_label, szn_stream_t stream);
+
 /* ---- multi-scale / mirrored inference (no reference counterpart: the reference evaluates every image once, as stored) -----------
  * szn_resize_flip_f32 makes one view of the network input: in (B,3,H,W) f32 NCHW -> out (B,3,Hs,Ws), bilinear without antialiasing,
  * with the position map and the 11-bit weights of szn_augment_u8.  Per output pixel (b, yo, xo), xo' = flip ? Ws-1-xo : xo:

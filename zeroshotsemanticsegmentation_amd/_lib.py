@@ -55,6 +55,7 @@ class AdamArgs(C.Structure):
 
 MAX_CLASSES = 256           # SZN_MAX_CLASSES
 AUG_NPARAM = 9              # SZN_AUG_NPARAM: int32 words of one image's augmentation record (szn_augment_u8)
+AUGA_NPARAM = 20            # SZN_AUGA_NPARAM: int32 words of one image's affine record (szn_augment_affine_u8)
 
 
 class ClassSet(C.Structure):
@@ -215,6 +216,7 @@ SIGNATURES = {
     "szn_proj_fp8_wgrad": (_I, [_I, _I, _L, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "szn_image_u8_to_bgr_f32": (_I, [_I, _I, _I, _P, C.POINTER(C.c_double), _P, _P]),
     "szn_augment_u8": (_I, [_I, _I, _I, _P, _P, _P, C.POINTER(C.c_double), _I, _I, _P, _P, _P]),
+    "szn_augment_affine_u8": (_I, [_I, _I, _I, _P, _P, _P, C.POINTER(C.c_double), _I, _I, _P, _P, _P]),
     "szn_resize_flip_f32": (_I, [_I, _I, _I, _P, _I, _I, _I, _P, _P]),
     "szn_ms_head_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I, _MV]),
     "szn_ms_head": (_I, [_I] * 8 + [_MV, _P, _CS, _I, _P, _P, _P, _P, _P, _P]),

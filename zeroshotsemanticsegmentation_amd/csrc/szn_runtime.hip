@@ -47,7 +47,7 @@ static thread_local float g_work_fraction = 1.f;
 void szn_note_work_fraction(float f) { g_work_fraction = f; }
 float szn_noted_work_fraction(void) { return g_work_fraction; }
 
-extern "C" int szn_version(void) { return 115; /* 0.1.15: szn_hub_stats, szn_hub_head */ }
+extern "C" int szn_version(void) { return 116; /* 0.1.16: szn_augment_affine_u8 */ }
 extern "C" int szn_device_info(int device, szn_device_info_t* out) {
     if (!out) SZN_FAIL(SZN_ERR_ARG, "device_info: null output");
     hipDeviceProp_t p;

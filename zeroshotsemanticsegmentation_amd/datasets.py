@@ -304,9 +304,20 @@ class Augment(object):
     [0, Hs - H] x [0, Ws - W]; where it is smaller the origin is 0: the image sits top-left and PAD_LABEL padding fills the bottom and
     right, as pad_collate pads.  Every draw is a pure function of (seed, rank, epoch, iteration, index in the batch) -- a Philox
     counter-based generator keyed by (seed, rank) at counter (epoch, iteration, index) -- so a resumed run and every rank of a
-    data-parallel job reproduce their own stream, and ranks differ."""
+    data-parallel job reproduce their own stream, and ranks differ.
 
-    def __init__(self, crop, scale=(0.5, 2.0), flip=True, seed=1337):
+    rotate = R >= 0 degrees and jitter = dict(brightness=B, contrast=C, saturation=S, hue=Hdeg), each >= 0, add a rotation by
+    phi ~ U[-R, R] about the image centre and a photometric chain -- brightness x + 255 b, b ~ U[-B, B]; contrast about the mean colour,
+    alpha ~ U[1-C, 1+C]; saturation about the luma, sigma ~ U[1-S, 1+S]; hue, a rotation by theta ~ U[-Hdeg, Hdeg] about the grey axis --
+    each applied at its drawn strength to every image (no coin flips; a zero range switches a transform off exactly).  With either set,
+    params() returns the 20-word affine record of szn_augment_affine_u8 and apply() launches that kernel; with rotate == 0 and jitter
+    None both do exactly what they did before.  The first four numbers of an image's draw are the same in both modes, so its scale,
+    window draw and mirror do not depend on the options."""
+
+    JITTER_KEYS = ("brightness", "contrast", "saturation", "hue")
+    LUMA = (0.299, 0.587, 0.114)
+
+    def __init__(self, crop, scale=(0.5, 2.0), flip=True, seed=1337, rotate=0.0, jitter=None):
         self.crop = (int(crop[0]), int(crop[1]))
         self.scale = (float(scale[0]), float(scale[1]))
         self.flip = bool(flip)
@@ -315,6 +326,18 @@ class Augment(object):
             raise ValueError("Augment: crop %s must be positive" % (self.crop,))
         if not 0.0 < self.scale[0] <= self.scale[1]:
             raise ValueError("Augment: scale range %s must satisfy 0 < lo <= hi" % (self.scale,))
+        self.rotate = float(rotate)
+        if not 0.0 <= self.rotate < float("inf"):
+            raise ValueError("Augment: rotate %r must be a finite angle >= 0 (degrees)" % (rotate,))
+        self.jitter = None
+        if jitter is not None:
+            unknown = sorted(set(jitter) - set(self.JITTER_KEYS))
+            if unknown:
+                raise ValueError("Augment: jitter knows %s, not %s" % (", ".join(self.JITTER_KEYS), unknown))
+            self.jitter = tuple(float(jitter.get(k, 0.0)) for k in self.JITTER_KEYS)
+            if not all(0.0 <= v < float("inf") for v in self.jitter):
+                raise ValueError("Augment: jitter strengths %s must be finite and >= 0" % (dict(zip(self.JITTER_KEYS, self.jitter)),))
+        self.affine = self.rotate != 0.0 or self.jitter is not None
 
     @staticmethod
     def record(h, w, s, oy_u=0.0, ox_u=0.0, flip=False, crop=None):
@@ -328,15 +351,96 @@ class Augment(object):
         ox = min(int(ox_u * (Ws - crop[1] + 1)), Ws - crop[1]) if crop is not None and Ws > crop[1] else 0
         return [h, w, Hs, Ws, ((h << 16) + Hs // 2) // Hs, ((w << 16) + Ws // 2) // Ws, oy, ox, int(bool(flip))]
 
-    def params(self, sizes, epoch, iteration, rank=0):
-        """sizes (B,2) = (h, w) per image -> int32 numpy (B, AUG_NPARAM)"""
+    @staticmethod
+    def bridge(rec, crop):
+        """the 9-word record of szn_augment_u8 as the 8 geometry words of szn_augment_affine_u8 (include/szn.h, axis-aligned identity):
+        the same source positions, exactly"""
+        h, w, _, _, step_y, step_x, oy, ox, flip = [int(v) for v in rec]
+        return [h, w, -step_x if flip else step_x, 0, step_x * (ox + (int(crop[1]) if flip else 0)), 0, step_y, step_y * oy]
+
+    @staticmethod
+    def color_matrix(b=0.0, alpha=1.0, sigma=1.0, theta=0.0, mean_bgr=utils.MEAN_BGR):
+        """the photometric chain as one affine map of RGB grey levels, float64: brightness x + 255 b; contrast m + alpha (x - m) about the
+        mean colour m; saturation g + sigma (x - g), g = the luma 0.299 R + 0.587 G + 0.114 B; hue, the rotation by theta degrees about
+        the grey axis (1,1,1) -> (M (3,3), o (3,)) with x_out = M x + o.  b = 0, alpha = sigma = 1, theta = 0 give exactly (I, 0)."""
+        m = np.asarray(mean_bgr, dtype=np.float64)[::-1]
+        one = np.ones(3)
+        S = sigma * np.eye(3) + (1.0 - sigma) * np.outer(one, np.asarray(Augment.LUMA))
+        t = np.deg2rad(theta)
+        K = np.array([[0.0, -1.0, 1.0], [1.0, 0.0, -1.0], [-1.0, 1.0, 0.0]])
+        R = np.cos(t) * np.eye(3) + (1.0 - np.cos(t)) / 3.0 * np.outer(one, one) + np.sin(t) / np.sqrt(3.0) * K
+        RS = R @ S
+        return alpha * RS, RS @ (alpha * 255.0 * b * one + (1.0 - alpha) * m)
+
+    @staticmethod
+    def color_words(M, o):
+        """(M, o) of color_matrix -> the 12 Q16 words Cm (row-major), Co of the record; a matrix entry beyond +-16 (the kernel's clamp of
+        +-2^20) or an offset beyond the int32 range is refused"""
+        cm = np.rint(65536.0 * np.asarray(M, dtype=np.float64)).reshape(9)
+        co = np.rint(65536.0 * np.asarray(o, dtype=np.float64)).reshape(3)
+        if not (np.all(np.isfinite(cm)) and np.all(np.isfinite(co))) or np.abs(cm).max() > 1 << 20 or np.abs(co).max() >= 1 << 31:
+            raise ValueError("Augment: colour matrix %s, offset %s outside the Q16 range of the record" % (np.asarray(M).tolist(), np.asarray(o).tolist()))
+        return [int(v) for v in cm] + [int(v) for v in co]
+
+    @staticmethod
+    def affine_record(h, w, s, phi=0.0, oy_u=0.0, ox_u=0.0, flip=False, crop=None, color=None):
+        """the 20-word int32 record of one image (szn_augment_affine_u8, include/szn.h).  The image is scaled to record()'s Hs x Ws and
+        rotated by phi degrees about its centre; the rotated image sits centred in its bounding box Wb = |cos| Ws + |sin| Hs,
+        Hb = |sin| Ws + |cos| Hs; the crop window's origin is u * (Hb - H) for u in [0, 1) where the box exceeds the crop (H, W), else
+        0; the mirror comes last.  The inverse map (output pixel -> source position) is composed in float64 and rounded once to 16.16.
+        phi == 0 takes the bridge of record() instead: exactly the positions of szn_augment_u8.  color = (M, o) of color_matrix, None =
+        the identity.  Two choices differ from the textbook form Rinv / s with an integer window: the inverse scale is
+        diag(w / Ws, h / Hs), the ratios of the ROUNDED sizes, so that the scaled image is exactly Hs x Ws and phi -> 0 meets the bridge;
+        and the window origin over the box is real-valued, because the box's sides are."""
+        h, w = int(h), int(w)
+        if flip and crop is None:
+            raise ValueError("Augment: the mirror is taken about the crop's centre line: flip needs crop=(H, W)")
+        rec9 = Augment.record(h, w, s, oy_u, ox_u, flip, crop)
+        Hs, Ws = rec9[2], rec9[3]
+        if max(h, w, Hs, Ws) >= 1 << 14:
+            raise ValueError("Augment: image %d x %d scaled to %d x %d exceeds the 16.16 fixed-point range of the affine record" % (h, w, Hs, Ws))
+        if phi == 0.0:
+            geo = Augment.bridge(rec9, crop if crop is not None else (0, 0))
+        else:
+            c, sn = np.cos(np.deg2rad(phi)), np.sin(np.deg2rad(phi))
+            c, sn = (0.0 if abs(c) < 1e-15 else c), (0.0 if abs(sn) < 1e-15 else sn)      # quarter turns are exact
+            Wb, Hb = abs(c) * Ws + abs(sn) * Hs, abs(sn) * Ws + abs(c) * Hs
+            Hc, Wc = (crop if crop is not None else (0, 0))
+            oy = oy_u * (Hb - Hc) if crop is not None and Hb > Hc else 0.0
+            ox = ox_u * (Wb - Wc) if crop is not None and Wb > Wc else 0.0
+            # source pixels per pixel of the scaled image, per axis (the rounded sizes, as in record()), times the inverse rotation
+            ax, ay = w / Ws, h / Hs
+            A = np.array([[ax * c, ax * sn], [-ay * sn, ay * c]])
+            org = np.array([ox + (Wc if flip else 0) - Wb / 2.0, oy - Hb / 2.0])
+            t = A @ org + np.array([w / 2.0, h / 2.0])
+            if flip:
+                A[:, 0] = -A[:, 0]
+            geo = [h, w] + [int(v) for v in np.rint(65536.0 * np.array([A[0, 0], A[0, 1], t[0], A[1, 0], A[1, 1], t[1]]))]
+        if max(abs(v) for v in geo) >= 1 << 31:
+            raise ValueError("Augment: the affine map %s of image %d x %d leaves the int32 16.16 range" % (geo[2:], h, w))
+        return geo + (Augment.color_words(*color) if color is not None else [65536, 0, 0, 0, 65536, 0, 0, 0, 65536, 0, 0, 0])
+
+    def draw(self, i, epoch, iteration, rank=0):
+        """image i's nine uniform numbers: scale, window y, window x, mirror, then rotation, brightness, contrast, saturation, hue"""
+        bits = np.random.Philox(key=[self.seed, int(rank)], counter=[int(epoch), int(iteration), i, 0])
+        return np.random.Generator(bits).random(9 if self.affine else 4)
+
+    def params(self, sizes, epoch, iteration, rank=0, mean_bgr=utils.MEAN_BGR):
+        """sizes (B,2) = (h, w) per image -> int32 numpy (B, AUG_NPARAM), or (B, AUGA_NPARAM) with rotate / jitter set (mean_bgr is the
+        pivot of the contrast and only read then)"""
         sizes = np.asarray(sizes).reshape(-1, 2)
-        out = np.empty((len(sizes), utils.L.AUG_NPARAM), dtype=np.int32)
+        out = np.empty((len(sizes), utils.L.AUGA_NPARAM if self.affine else utils.L.AUG_NPARAM), dtype=np.int32)
         lo, hi = self.scale
+        jb, jc, js, jh = self.jitter or (0.0, 0.0, 0.0, 0.0)
         for i, (h, w) in enumerate(sizes):
-            bits = np.random.Philox(key=[self.seed, int(rank)], counter=[int(epoch), int(iteration), i, 0])
-            u = np.random.Generator(bits).random(4)
-            out[i] = self.record(h, w, lo + (hi - lo) * u[0], u[1], u[2], self.flip and u[3] < 0.5, self.crop)
+            u = self.draw(i, epoch, iteration, rank)
+            s, flip = lo + (hi - lo) * u[0], self.flip and u[3] < 0.5
+            if not self.affine:
+                out[i] = self.record(h, w, s, u[1], u[2], flip, self.crop)
+                continue
+            d = 2.0 * u[4:9] - 1.0                                                       # U[-1, 1)
+            color = self.color_matrix(jb * d[1], 1.0 + jc * d[2], 1.0 + js * d[3], jh * d[4], mean_bgr)
+            out[i] = self.affine_record(h, w, s, self.rotate * d[0], u[1], u[2], flip, self.crop, color)
         return out
 
     def apply(self, batch, epoch, iteration, rank=0, device=None, mean_bgr=utils.MEAN_BGR):
@@ -344,6 +448,8 @@ class Augment(object):
         if not isinstance(batch, (tuple, list)) or len(batch) != 3:
             raise ValueError("Augment needs (images, labels, sizes) batches: build the training loaders with collate_fn=datasets.augment_collate")
         img, lbl, sizes = batch
+        if self.affine:
+            return utils.augment_affine_to_device(img, lbl, self.params(sizes, epoch, iteration, rank, mean_bgr), self.crop, device, mean_bgr)
         return utils.augment_to_device(img, lbl, self.params(sizes, epoch, iteration, rank), self.crop, device, mean_bgr)
 
 

@@ -14,6 +14,9 @@ Added for this implementation (none change the reference flags):
                        (vis_utils; 25 = the reference's behaviour, 0 = off)
   --crop-size H W      train on randomly scaled, cropped and mirrored images at a fixed H x W network input (datasets.Augment; one
                        kernel on the GPU, szn_augment_u8); --scale-range LO HI (default 0.5 2.0), --no-flip.  Validation is untouched
+  --rotate DEG         with --crop-size: rotate every training image by an angle from [-DEG, DEG]; --color-jitter B C S H: brightness
+                       (fraction of 255), contrast, saturation, hue (degrees).  Either switches the augmentation to one affine kernel
+                       (szn_augment_affine_u8: a 2 x 3 position map and a 3 x 4 colour matrix per image).  No default strengths
   --conse T            ConSE zero-shot inference for the softmax network (-c 1): validation and -m test_fcn -r <ckpt> mix the class
                        embeddings (--conse-dim E, default 300) of the top T seen classes with their softmax probabilities per pixel and
                        name the nearest class by cosine (szn_conse_head); --conse-gamma G penalises the seen classes, --conse-sweep LO
@@ -141,6 +144,15 @@ def build_parser():
     p.add_argument('--scale-range', type=float, nargs=2, metavar=('LO', 'HI'), default=[0.5, 2.0],
                    help="with --crop-size: the isotropic scale of each image is drawn uniformly from [LO, HI]")
     p.add_argument('--no-flip', action='store_true', help="with --crop-size: never mirror")
+    p.add_argument('--rotate', type=float, default=None, metavar='DEG',
+                   help="with --crop-size: also rotate every training image about its centre by an angle drawn uniformly from "
+                        "[-DEG, DEG] degrees (szn_augment_affine_u8; PSPNet-style pipelines use 10).  No default strength: nobody has "
+                        "tuned one here.  Off by default")
+    p.add_argument('--color-jitter', type=float, nargs=4, metavar=('B', 'C', 'S', 'H'), default=None,
+                   help="with --crop-size: photometric jitter of every training image, each strength >= 0: brightness +-B as a fraction "
+                        "of 255, contrast factor in [1-C, 1+C] about the mean colour, saturation factor in [1-S, 1+S], hue +-H degrees "
+                        "(one colour matrix per image, szn_augment_affine_u8; SSD-style pipelines use about 0.125 0.5 0.5 18).  No "
+                        "default strengths: nobody has tuned them here.  Off by default")
     p.add_argument('--eval-scales', type=float, nargs='+', metavar='S', default=None,
                    help="multi-scale validation (per-epoch validation, -m test_fcn, -m test_all): every image is evaluated at each of "
                         "these scales (1.0 must be among them) and the classes' cosine similarities are summed over the views; "
@@ -675,6 +687,21 @@ def check_accum(steps, cfg):
     return int(steps)
 
 
+def check_affine(rotate, color_jitter, crop_size):
+    """--rotate / --color-jitter: both act inside the augmentation of --crop-size and are an error without it; strengths >= 0 -> the
+    rotate= and jitter= arguments of datasets.Augment (0.0 and None without the flags: the plain scale / crop / flip kernel)"""
+    if rotate is None and color_jitter is None:
+        return 0.0, None
+    if not crop_size:
+        raise Exception("--rotate / --color-jitter act inside the training augmentation: they need --crop-size H W")
+    if rotate is not None and not rotate >= 0:
+        raise Exception("--rotate: DEG must be at least 0 (got %r)" % (rotate,))
+    if color_jitter is not None and not all(v >= 0 for v in color_jitter):
+        raise Exception("--color-jitter: B C S H must each be at least 0 (got %r)" % (list(color_jitter),))
+    jitter = None if color_jitter is None else dict(zip(('brightness', 'contrast', 'saturation', 'hue'), color_jitter))
+    return float(rotate or 0.0), jitter
+
+
 USE_EMA_MISSING = "--use-ema: the checkpoint %s carries no 'ema_state_dict' (it was written without --ema)"
 
 
@@ -727,6 +754,7 @@ def main(argv=None):
     ema = check_ema(args.ema, args.ema_every, args.ema_no_warmup, args.use_ema, cfg)
     clip_grad_norm, grad_stats = check_clip(args.clip_grad_norm, args.grad_stats, cfg)
     accum_steps = check_accum(args.accum_steps, cfg)
+    rotate, jitter = check_affine(args.rotate, args.color_jitter, args.crop_size)
     hide_unseen = args.hide_unseen or args.pseudo_label is not None or args.bias_loss is not None
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -772,7 +800,7 @@ def main(argv=None):
         # the training loaders hand out raw padded batches with their sizes (at every batch size, 1 included); the trainers scale,
         # crop and mirror them on the GPU
         from .datasets import Augment, augment_collate
-        augment = Augment(crop=args.crop_size, scale=args.scale_range, flip=not args.no_flip, seed=1337)
+        augment = Augment(crop=args.crop_size, scale=args.scale_range, flip=not args.no_flip, seed=1337, rotate=rotate, jitter=jitter)
         train_collate = augment_collate
     if args.synthetic:
         n_img, H, W = args.synthetic

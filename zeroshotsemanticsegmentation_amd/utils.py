@@ -61,15 +61,26 @@ def augment_to_device(img_u8, label, params, out_hw, device=None, mean_bgr=MEAN_
     (B,Hm,Wm,3) and labels (B,Hm,Wm) of a padded batch -- host or device -- and one int32 record per image (B, AUG_NPARAM), as
     datasets.Augment.params draws them -> (data (B,3,Ho,Wo) f32 BGR minus mean_bgr, target (B,Ho,Wo) int64), each image randomly
     scaled, cropped to out_hw and mirrored; pixels outside the scaled image are 0.0 / datasets.PAD_LABEL."""
+    return _augment("augment_to_device", "szn_augment_u8", L.AUG_NPARAM, img_u8, label, params, out_hw, device, mean_bgr)
+
+
+def augment_affine_to_device(img_u8, label, params, out_hw, device=None, mean_bgr=MEAN_BGR):
+    """augment_to_device with rotation and colour jitter (szn_augment_affine_u8 in include/szn.h): the same inputs and outputs, the
+    records are the (B, AUGA_NPARAM) int32 affine ones -- a 2 x 3 fixed-point position map and a 3 x 4 fixed-point colour matrix per
+    image, as datasets.Augment.params draws them with rotate / jitter set."""
+    return _augment("augment_affine_to_device", "szn_augment_affine_u8", L.AUGA_NPARAM, img_u8, label, params, out_hw, device, mean_bgr)
+
+
+def _augment(who, entry, nparam, img_u8, label, params, out_hw, device, mean_bgr):
     as_t = lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
     t, lbl, rec = as_t(img_u8), as_t(label), as_t(params)
     if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[-1] != 3:
-        raise L.SznError("augment_to_device expects uint8 (B,Hm,Wm,3) images, got %s %s" % (t.dtype, tuple(t.shape)))
+        raise L.SznError("%s expects uint8 (B,Hm,Wm,3) images, got %s %s" % (who, t.dtype, tuple(t.shape)))
     B, Hm, Wm, _ = t.shape
     if tuple(lbl.shape) != (B, Hm, Wm) or lbl.is_floating_point():
-        raise L.SznError("augment_to_device expects integer (B,Hm,Wm) labels matching the images, got %s %s" % (lbl.dtype, tuple(lbl.shape)))
-    if rec.dtype != torch.int32 or tuple(rec.shape) != (B, L.AUG_NPARAM):
-        raise L.SznError("augment_to_device expects int32 (%d,%d) params, got %s %s" % (B, L.AUG_NPARAM, rec.dtype, tuple(rec.shape)))
+        raise L.SznError("%s expects integer (B,Hm,Wm) labels matching the images, got %s %s" % (who, lbl.dtype, tuple(lbl.shape)))
+    if rec.dtype != torch.int32 or tuple(rec.shape) != (B, nparam):
+        raise L.SznError("%s expects int32 (%d,%d) params, got %s %s" % (who, B, nparam, rec.dtype, tuple(rec.shape)))
     Ho, Wo = int(out_hw[0]), int(out_hw[1])
     dev = torch.device(device) if device is not None else (t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device()))
     t = t.to(dev, non_blocking=True).contiguous()
@@ -78,7 +89,7 @@ def augment_to_device(img_u8, label, params, out_hw, device=None, mean_bgr=MEAN_
     data = torch.empty(B, 3, max(Ho, 0), max(Wo, 0), device=dev, dtype=torch.float32)
     target = torch.empty(B, max(Ho, 0), max(Wo, 0), device=dev, dtype=torch.int64)
     mean = (C.c_double * 3)(*[float(m) for m in mean_bgr])
-    L.call("szn_augment_u8", B, Hm, Wm, L.ptr(t), L.ptr(lbl), L.ptr(rec), mean, Ho, Wo, L.ptr(data), L.ptr(target), L.stream_ptr())
+    L.call(entry, B, Hm, Wm, L.ptr(t), L.ptr(lbl), L.ptr(rec), mean, Ho, Wo, L.ptr(data), L.ptr(target), L.stream_ptr())
     return data, target
 
 
